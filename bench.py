@@ -8,7 +8,7 @@ prefix beam search W=10 (chunk mode: LM unused, reference basecall.py:110-121) -
 Inputs are resident in HBM when the timed region starts.  One process per GPU; ranks shard reads with no
 data-path collective (weak scaling); the only RCCL traffic is the start-up broadcast of the weights.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 With --gpus N > 1 and no WORLD_SIZE in the environment this process is only the LAUNCHER: before anything touches a GPU it
 makes a private rendezvous directory, starts N fresh copies of itself with RANK / LOCAL_RANK / WORLD_SIZE set (one per
@@ -47,6 +47,17 @@ _T0 = time.perf_counter()
 def note(msg):
     """progress line on stderr (stdout carries the one JSON line only)"""
     print(f"[bench {time.perf_counter() - _T0:6.1f}s] {msg}", file=sys.stderr, flush=True)
+
+
+def dump_outputs(directory, labels, lens):
+    """--dump-outputs: what the timed path handed its caller in its last step -- one batch's labels [512][1024] and their lengths
+    [512] -- as float32 .npy files (2 MB).  Label entries past a window's length are not part of the result (the buffer is reused
+    from batch to batch) and are written as -1, so that two builds computing the same labels write the same bytes."""
+    os.makedirs(directory, exist_ok=True)
+    lab = labels.astype(np.float32)
+    lab[np.arange(CHUNK)[None, :] >= lens[:, None]] = -1.0
+    np.save(os.path.join(directory, "labels.npy"), lab)
+    np.save(os.path.join(directory, "label_lengths.npy"), lens.astype(np.float32))
 
 
 def effective_cores():
@@ -608,7 +619,11 @@ def main():
     ap.add_argument("--e2e-reads", type=int, default=32768,
                     help="reads of the raw end-to-end secondary leg (the other driver legs take a half or a sixteenth of it): jobs of a few "
                          "seconds each, so that the fill and drain of the beam-search groups are a few per cent of a leg, as in a real run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the labels and label lengths of the last timed step (rank 0) to DIR/<name>.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -762,6 +777,9 @@ def main():
     for k in range(max(1, args.regions)):
         regions.append(timed(submit_windowed if args.windowed else submit, preheat=(k == 0)))
         regions_per_rank.append(per_rank_ms)
+    if args.dump_outputs and rank == 0:
+        last = out[(args.steps - 1) % len(out)]   # the last timed step's buffers, before the roofline pass below reuses them
+        dump_outputs(args.dump_outputs, *last)
     elapsed = sorted(regions)[(len(regions) - 1) // 2]
     headline_per_rank_ms = regions_per_rank[regions.index(elapsed)]      # every rank's own clock over the REPORTED region
     value_runs = [world * args.steps * reads_per_batch * READ_LEN / e for e in regions]

@@ -19,6 +19,7 @@ import json
 import math
 import os
 import re
+import shutil
 import subprocess
 import sys
 import types
@@ -509,6 +510,7 @@ def gen_fast5_signals():
         ids.append(rid)
         arrays[rid] = vals
     np.savez_compressed(os.path.join(HERE, "reads_fast5_signals.npz"), **arrays)
+    shutil.copyfile(path, os.path.join(HERE, "reads.fast5"))   # the file itself (data fixture): the fast5 readers' real-file case
     with open(os.path.join(HERE, "reads_fast5_ids.json"), "w") as f:
         json.dump({"source": "radian/data/reads.fast5 /read_<id>/Raw/Signal (int16, unscaled DAQ values)",
                    "read_ids": ids, "lengths": [int(arrays[i].shape[0]) for i in ids]}, f, indent=0)

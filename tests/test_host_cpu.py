@@ -193,11 +193,10 @@ def test_fast5_reader_roundtrip_and_reference_file(tmp_path, golden_dir):
     got = [(r.read_id, r.get_raw_data()) for r in fast5.iter_directory(str(tmp_path))]  # recursive like rglob
     assert [g[0] for g in got] == ids
     assert all(a.dtype == np.int16 and np.array_equal(a, sig[r]) for r, a in got)
-    ref = "/root/reference/radian/data/reads.fast5"   # build container only
-    if os.path.exists(ref):
-        got = [(r.read_id, r.get_raw_data()) for r in fast5.iter_reads(ref)]
-        assert [g[0] for g in got] == ids
-        assert all(np.array_equal(a, sig[r]) for r, a in got)
+    ref = os.path.join(golden_dir, "reads.fast5")   # the reference's sample file, stored as a fixture
+    got = [(r.read_id, r.get_raw_data()) for r in fast5.iter_reads(ref)]
+    assert [g[0] for g in got] == ids
+    assert all(np.array_equal(a, sig[r]) for r, a in got)
 
 
 @pytest.mark.skipif(not _have_hdf5(), reason="libhdf5 not available")
@@ -324,10 +323,9 @@ def test_pure_python_hdf5_reader(tmp_path, golden_dir, monkeypatch):
     h5weights.write_keras_weights(q, w)
     monkeypatch.setenv("RADIAN_HDF5_PURE", "1")
     assert np.array_equal(h5weights.read_keras_weights(q), w)
-    ref = "/root/reference/radian/data/reads.fast5"   # build container only: compact link-message groups inside
-    if os.path.exists(ref):
-        got = [(r.read_id, r.get_raw_data()) for r in fast5.iter_reads(ref)]
-        assert [g[0] for g in got] == ids and all(np.array_equal(a, sig[r]) for r, a in got)
+    ref = os.path.join(golden_dir, "reads.fast5")   # the reference's sample file: compact link-message groups inside
+    got = [(r.read_id, r.get_raw_data()) for r in fast5.iter_reads(ref)]
+    assert [g[0] for g in got] == ids and all(np.array_equal(a, sig[r]) for r, a in got)
 
 
 def _label_matrix(frag_lists, chunk_len):
@@ -704,7 +702,7 @@ def test_tile_planner_properties_under_address_sanitizer(tmp_path):
     assert r.returncode == 0 and b"every property holds" in r.stdout, (r.stdout.decode()[-800:], r.stderr.decode()[-3000:])
 
 
-def test_host_budget_placement_rule(tmp_path):
+def test_host_budget_placement_rule(tmp_path, monkeypatch):
     """radian_amd/hostbudget.py: every local rank gets a disjoint, contiguous share of the usable cores -- the cores of
     its GPU's NUMA node when the (fake) sysfs tells -- and sizes its threads from the share: eight chunk-mode ranks on 64 cores start 8 x 6
     stitch threads, not 8 x 16."""
@@ -755,17 +753,10 @@ def test_host_budget_placement_rule(tmp_path):
     plans = [hb.plan(r, 4, usable=range(64), gpu_nodes=[0, 0, 0, 0, 1, 1, 1, 1], devices=[5, 5, 5, 5], sysfs=str(sysfs)) for r in range(4)]
     assert all(p["how"] == "numa" and p["numa_node"] == 1 and len(p["cpus"]) == 8 for p in plans)
     assert sorted(c for p in plans for c in p["cpus"]) == list(range(32, 64))
-    # HIP_VISIBLE_DEVICES re-orders the devices a rank sees
-    import os
-    old = os.environ.get("HIP_VISIBLE_DEVICES")
-    os.environ["HIP_VISIBLE_DEVICES"] = "4,5"
-    try:
-        assert hb._visible_order(8) == [4, 5]
-    finally:
-        if old is None:
-            del os.environ["HIP_VISIBLE_DEVICES"]
-        else:
-            os.environ["HIP_VISIBLE_DEVICES"] = old
+    # HIP_VISIBLE_DEVICES re-orders the devices a rank sees (with no ROCR_VISIBLE_DEVICES narrowing them first: a GPU job's own may be set)
+    monkeypatch.delenv("ROCR_VISIBLE_DEVICES", raising=False)
+    monkeypatch.setenv("HIP_VISIBLE_DEVICES", "4,5")
+    assert hb._visible_order(8) == [4, 5]
 
 
 def test_apply_binds_a_child_rank_to_its_slice():
