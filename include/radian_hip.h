@@ -332,6 +332,39 @@ int rd_fast5_read_batch(rd_fast5* f, int64_t lo, int64_t hi, int16_t* samples, i
 int rd_stitch_chunk(const uint8_t* labels, const int32_t* label_len, int chunk_len, const int32_t* read_win_off, int n_reads,
                     uint8_t* seq_out, const int64_t* seq_off, int32_t* seq_len, int n_threads);
 
+/* ---- read-accuracy evaluation: radian/align.py ------------------------------------------------------------------------ */
+/* pairwise2.align.globalms(ref, seq, match, mismatch, gap_open, gap_extend) + analyse_alignment (radian/align.py:9-57,87-92;
+ * the reference passes 2, -4, -4, -2) for a batch of pairs, on the GPU (align.hip).
+ *   refs / reads   concatenated bytes; pair p is refs[ref_off[p] .. ref_off[p+1]) against reads[read_off[p] .. read_off[p+1])
+ *                  (offsets have n_pairs + 1 entries and start at 0).  Characters are compared as bytes (no U -> T here).
+ *   Affine-gap global alignment (Gotoh), int32 scores: a gap of length L costs gap_open + (L-1) * gap_extend, end gaps are
+ *   penalised.  Of the co-optimal alignments the traceback takes the one of a FIXED tie-break (the reference draws one at
+ *   random, align.py:89): diagonal before deletion (ref base against a read gap) before insertion, and inside a gap run
+ *   extending before closing.
+ *   score[p]       the optimal score
+ *   counts[4p..]   n_match, n_sub, n_ins, n_del after analyse_alignment's soft clip (its return order)
+ *   status[p]      RD_ALIGN_OK, RD_ALIGN_CLIP_INDEX_ERROR (analyse_alignment raises IndexError), RD_ALIGN_EMPTY_AFTER_CLIP
+ *                  (clip_start > clip_end: all counts 0), RD_ALIGN_TOO_LARGE (not aligned, see below)
+ *   ops_out / ops_off / ops_len (all NULL, or all given): pair p's alignment columns go to ops_out + ops_off[p] (capacity
+ *                  n + m), ops_len[p] of them, 'M' match, 'X' mismatch, 'D' deletion, 'I' insertion.
+ *   budget_bytes   device workspace one batch of pairs may take (rd_align_workspace_bytes each); 0 = a quarter of the free
+ *                  device memory.  Pairs are sorted by cells and packed into batches under it.  A pair that alone exceeds it is
+ *                  not aligned: status RD_ALIGN_TOO_LARGE, and the call returns RD_ERR_NOMEM naming it after aligning the others
+ *                  (the check is made before any launch).
+ * Synchronous; uses the context's stream. */
+#define RD_ALIGN_OK 0
+#define RD_ALIGN_CLIP_INDEX_ERROR 1
+#define RD_ALIGN_EMPTY_AFTER_CLIP 2
+#define RD_ALIGN_TOO_LARGE 3
+int rd_align_batch(rd_ctx* ctx, const uint8_t* refs, const int64_t* ref_off, const uint8_t* reads, const int64_t* read_off, int n_pairs,
+                   int match, int mismatch, int gap_open, int gap_extend, int64_t budget_bytes, int32_t* score, int32_t* counts,
+                   int32_t* status, uint8_t* ops_out, const int64_t* ops_off, int32_t* ops_len);
+/* Workspace bytes rd_align_batch needs for one pair of lengths n x m alone (about n * m / 2: four direction bits per cell). */
+int64_t rd_align_workspace_bytes(int64_t n, int64_t m);
+/* Host, no GPU: the soft clip and counts rd_align_batch applies to an alignment -- the same code the device runs.  ops: n_ops
+ * columns of M / X / D / I; ref / read: the characters the D / I columns consume (their order in the alignment). */
+int rd_align_clip_count(const uint8_t* ops, int64_t n_ops, const uint8_t* ref, const uint8_t* read, int32_t* counts, int32_t* status);
+
 /* ---- multi-GPU start-up: one RCCL broadcast of weights + LM table over xGMI ------------------- */
 /* librccl can be loaded in this process (dlopen + symbol lookup; creates nothing).  Ranks other than the one that draws the
  * unique id call this before the collective ncclCommInitRank, so that a rank without a usable librccl is known to everyone first. */

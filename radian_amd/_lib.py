@@ -76,6 +76,9 @@ SIGNATURES = {
     "rd_pipe_set_lanes": (c_i, [c_vp, c_i]),
     "rd_pipe_submit": (c_i, [c_vp, c_vp, c_i, c_i, c_vp, c_i, c_vp, c_vp]),
     "rd_pipe_flush": (c_i, [c_vp]),
+    "rd_align_batch": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rd_align_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "rd_align_clip_count": (c_i, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "rd_rccl_probe": (c_i, []),
     "rd_rccl_unique_id": (c_i, [c_vp]),
     "rd_rccl_init": (c_i, [c_vp, c_i, c_i, c_vp]),

@@ -51,6 +51,51 @@ def device_for_rank(local_rank):
     return local_rank if local_rank < n else local_rank % n
 
 
+# rd_align_batch per-pair status (include/radian_hip.h RD_ALIGN_*)
+ALIGN_OK, ALIGN_CLIP_INDEX_ERROR, ALIGN_EMPTY_AFTER_CLIP, ALIGN_TOO_LARGE = 0, 1, 2, 3
+ALIGN_SCORES = (2, -4, -4, -2)   # radian/align.py:87: globalms(ref, seq, match, mismatch, gap open, gap extend)
+
+
+def _as_bytes(s):
+    return s.encode("latin-1") if isinstance(s, str) else bytes(s)
+
+
+def _concat(seqs):
+    """bytes of a list of str / bytes -> (uint8 buffer, int64 offsets [n + 1])"""
+    bs = [_as_bytes(s) for s in seqs]
+    off = np.zeros(len(bs) + 1, dtype=np.int64)
+    np.cumsum([len(b) for b in bs], out=off[1:])
+    buf = np.frombuffer(b"".join(bs), dtype=np.uint8) if off[-1] else np.zeros(1, dtype=np.uint8)
+    return np.ascontiguousarray(buf), off
+
+
+def align_workspace_bytes(n, m):
+    """device workspace (bytes) rd_align_batch needs for one n x m pair alone (rd_align_workspace_bytes; no GPU)"""
+    return int(_lib.load().rd_align_workspace_bytes(int(n), int(m)))
+
+
+def align_clip_count(ops, ref, read):
+    """analyse_alignment's soft clip and counts (radian/align.py:9-57) of one alignment given as its column ops (M / X / D / I)
+    and the characters its D / I columns consume -- the library's own code (rd_align_clip_count, host; no GPU).
+    Returns ((n_match, n_sub, n_ins, n_del), status)."""
+    L = _lib.load()
+    o, r, q = (np.frombuffer(_as_bytes(x), dtype=np.uint8) if len(x) else np.zeros(1, dtype=np.uint8) for x in (ops, ref, read))
+    cnt = np.zeros(4, dtype=np.int32)
+    st = np.zeros(1, dtype=np.int32)
+    rc = L.rd_align_clip_count(_p(o), len(ops), _p(r), _p(q), _p(cnt), _p(st))
+    if rc != 0:
+        raise RadianHipError(f"[rd error {rc}] " + L.rd_last_error().decode("utf-8", "replace"))
+    return tuple(int(c) for c in cnt), int(st[0])
+
+
+class AlignResult:
+    """Backend.align's per-pair arrays: score int32 [n], counts int32 [n, 4] (n_match, n_sub, n_ins, n_del after the soft clip),
+    status int32 [n] (ALIGN_*), ops (list of bytes of M / X / D / I columns, or None when not asked for)."""
+
+    def __init__(self, score, counts, status, ops):
+        self.score, self.counts, self.status, self.ops = score, counts, status, ops
+
+
 class PipeTicket:
     """One batch queued on a Backend's reads-level pipeline (Backend.pipe_submit_raw).  The arrays the library writes into
     live here until the batch is delivered."""
@@ -597,3 +642,32 @@ class Backend:
         n = ctypes.c_int(0)
         self._check(self._L.rd_rccl_comm_count(self._h, ctypes.byref(n)))
         return n.value
+
+    # ------------------------------------------------------------------ read-accuracy evaluation (radian/align.py)
+    def align(self, refs, reads, scores=ALIGN_SCORES, budget_bytes=0, with_ops=False, allow_too_large=False):
+        """Global affine-gap alignment of reads[p] against refs[p] (str or bytes, compared byte by byte) and analyse_alignment's
+        clip + counts, on the GPU (rd_align_batch).  budget_bytes: device workspace per batch, 0 = a quarter of free memory.
+        A pair that does not fit the budget raises, unless allow_too_large: it then comes back with status ALIGN_TOO_LARGE."""
+        if len(refs) != len(reads):
+            raise ValueError(f"{len(refs)} refs for {len(reads)} reads")
+        n = len(refs)
+        rbuf, roff = _concat(refs)
+        qbuf, qoff = _concat(reads)
+        score = np.zeros(n, dtype=np.int32)
+        counts = np.zeros((n, 4), dtype=np.int32)
+        status = np.zeros(n, dtype=np.int32)
+        ops = ops_off = ops_len = None
+        if with_ops:
+            ops_off = np.zeros(n + 1, dtype=np.int64)
+            np.cumsum((roff[1:] - roff[:-1]) + (qoff[1:] - qoff[:-1]), out=ops_off[1:])
+            ops = np.zeros(max(int(ops_off[-1]), 1), dtype=np.uint8)
+            ops_len = np.zeros(n, dtype=np.int32)
+        m, x, go, ge = (int(v) for v in scores)
+        rc = self._L.rd_align_batch(self._h, _p(rbuf), _p(roff), _p(qbuf), _p(qoff), n, m, x, go, ge, int(budget_bytes), _p(score),
+                                    _p(counts), _p(status), _p(ops), _p(ops_off), _p(ops_len))
+        if rc != 0 and not (allow_too_large and rc == -4 and (status == ALIGN_TOO_LARGE).any()):
+            self._check(rc)
+        ops_list = None
+        if with_ops:
+            ops_list = [ops[ops_off[p]: ops_off[p] + ops_len[p]].tobytes() for p in range(n)]
+        return AlignResult(score, counts, status, ops_list)

@@ -1,4 +1,4 @@
-"""Seeded synthetic inputs of BASELINE.json's configs: Gaussian int16 reads."""
+"""Seeded synthetic inputs of BASELINE.json's configs: Gaussian int16 reads; and the read-accuracy workload (alignment_pairs)."""
 import numpy as np
 
 from .preprocess import mad_normalise, get_windows
@@ -38,3 +38,53 @@ def peaky_probs(n_windows, chunk_len=1024, seed=0, gain=4.0, blank_bias=2.0):
     np.exp(z, out=z)
     z /= z.sum(axis=-1, keepdims=True)
     return z
+
+
+def alignment_pairs(n_pairs, seed=0, median_len=1500, sigma=0.35, p_sub=0.08, p_ins=0.04, p_del=0.04, max_junk=40, p_u=0.25, p_n=0.25,
+                    min_len=1):
+    """Seeded read-accuracy workload (radian_amd.align): (ids, refs, reads) as str.  Reference lengths are log-normal around
+    median_len; each read is its reference with ~p_sub substitutions, p_ins insertions and p_del deletions per base, and 0..max_junk
+    random bases of junk at each end (so the soft clip engages).  A fraction p_u of the reads is written with U for T (the basecaller's
+    alphabet), a fraction p_n of the references carries a few N."""
+    rng = np.random.default_rng(seed)
+    alpha = np.frombuffer(b"ACGT", dtype=np.uint8)
+    lens = np.maximum(np.round(median_len * np.exp(sigma * rng.standard_normal(n_pairs))).astype(np.int64), min_len)
+    ids, refs, reads = [], [], []
+    for k in range(n_pairs):
+        n = int(lens[k])
+        ref = alpha[rng.integers(0, 4, n)]
+        if rng.random() < p_n:
+            ref = ref.copy()
+            ref[rng.integers(0, n, max(1, n // 200))] = ord("N")
+        # per reference base: deleted, substituted or kept, then maybe one inserted base after it
+        ev = rng.random(n)
+        sub = alpha[(np.searchsorted(alpha, ref) % 4 + rng.integers(1, 4, n)) % 4]   # a different base (any base at an N)
+        cols = np.zeros((n, 2), dtype=np.uint8)
+        cols[:, 0] = np.where(ev < p_del, 0, np.where(ev < p_del + p_sub, sub, ref))
+        cols[:, 1] = np.where(rng.random(n) < p_ins, alpha[rng.integers(0, 4, n)], 0)
+        out = cols.reshape(-1)
+        out = out[out != 0]
+        nn = out == ord("N")   # a kept N: the basecaller emits a base
+        out[nn] = alpha[rng.integers(0, 4, int(nn.sum()))]
+        head = alpha[rng.integers(0, 4, int(rng.integers(0, max_junk + 1)))]
+        tail = alpha[rng.integers(0, 4, int(rng.integers(0, max_junk + 1)))]
+        read = bytes(head) + bytes(out) + bytes(tail)
+        if rng.random() < p_u:
+            read = read.replace(b"T", b"U")
+        ids.append(f"read_{seed}_{k}")
+        refs.append(ref.tobytes().decode("ascii"))
+        reads.append(read.decode("ascii"))
+    return ids, refs, reads
+
+
+def write_alignment_inputs(path_fasta, path_tsv, ids, refs, reads, line_width=60):
+    """the FASTA of the reads (wrapped lines) and the reference TSV (header, then id <tab> text <tab> sequence) radian_amd.align reads"""
+    with open(path_fasta, "w") as f:
+        for rid, s in zip(ids, reads):
+            f.write(f">{rid} synthetic\n")
+            for o in range(0, len(s), line_width):
+                f.write(s[o: o + line_width] + "\n")
+    with open(path_tsv, "w") as f:
+        f.write("read_id\ttranscript\tsequence\n")
+        for rid, s in zip(ids, refs):
+            f.write(f"{rid}\tsynthetic\t{s}\n")
