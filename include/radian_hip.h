@@ -35,8 +35,8 @@ extern "C" {
 #define RD_ERR_STATE (-3) /* call order (e.g. forward before weights) */
 #define RD_ERR_NOMEM (-4) /* device allocation failed */
 #define RD_ERR_RCCL (-5)  /* RCCL error / librccl not loadable */
-#define RD_ERR_FORMAT (-6) /* rd_lm_json_* / rd_fast5_*: the input is not of the one shape the fast reader handles (no verdict: use the full parser / libhdf5) */
-#define RD_ERR_IO (-7)     /* rd_fast5_open: the file cannot be opened or mapped */
+#define RD_ERR_FORMAT (-6) /* rd_lm_json_* / rd_fast5_*: the input is not of the one shape the fast reader handles (no verdict: use the full parser / libhdf5); rd_tfrecord_*: the shard is malformed */
+#define RD_ERR_IO (-7)     /* rd_fast5_open / rd_tfrecord_open: the file cannot be opened or mapped */
 /* Not an error code: the value of label_len[i] for a sequence whose beam search looked up a context that a SPARSE RNA model
  * does not hold (rd_load_lm, rows of NaN).  The reference raises KeyError at radian/decode.py:83 on such a read; the caller
  * does the same when it reaches that read (radian_amd/basecall.py).  The sequence's labels are not written. */
@@ -364,6 +364,54 @@ int64_t rd_align_workspace_bytes(int64_t n, int64_t m);
 /* Host, no GPU: the soft clip and counts rd_align_batch applies to an alignment -- the same code the device runs.  ops: n_ops
  * columns of M / X / D / I; ref / read: the characters the D / I columns consume (their order in the alignment). */
 int rd_align_clip_count(const uint8_t* ops, int64_t n_ops, const uint8_t* ref, const uint8_t* read, int32_t* counts, int32_t* status);
+
+/* ---- model evaluation on labelled windows: the reference's val_loss (radian/model.py:77-98, radian/train.py:48-79) ------------
+ * Labelled windows as the reference stores them: TFRecord shards of tf.train.Example records (radian/data.py:9-31), read on the
+ * HOST without TensorFlow (tfrecord.hip).  Framing: u64 length, u32 masked crc32c of it, the data, u32 masked crc32c of the data;
+ * both checksums are verified.  Features: `signal` 1024 floats, `label` a float list (the first label_length values are the labels,
+ * each exactly 0..3), `signal_length` (1..1024) and `label_length` (0..len(label)) one int64 each; repeated fields packed or not.
+ *   rd_tfrecord_open / rd_tfrecord_open_mem (the buffer is parsed at once and may be released after the call) / rd_tfrecord_close
+ *   rd_tfrecord_count   records of the shard and the total of their labels
+ *   rd_tfrecord_read    records [lo, hi): signals [hi - lo][1024] float32, input_len (= signal_length), label_off [hi - lo + 1] into
+ *                       labels (capacity labels_cap, 0..3 each), label_len
+ * Anything else -- a bad checksum, a truncated frame, a missing or malformed feature, a value outside the ranges above -- returns
+ * RD_ERR_FORMAT with a message naming the record's index; rd_tfrecord_open returns RD_ERR_IO when the file cannot be read.
+ * rd_crc32c: the Castagnoli CRC of a buffer (unmasked; crc32c("123456789") = 0xE3069283). */
+typedef struct rd_tfrecord rd_tfrecord;
+int rd_tfrecord_open(const char* path, rd_tfrecord** out);
+int rd_tfrecord_open_mem(const void* buf, size_t n, rd_tfrecord** out);
+void rd_tfrecord_close(rd_tfrecord* f);
+int rd_tfrecord_count(const rd_tfrecord* f, int64_t* n_records, int64_t* n_labels);
+int rd_tfrecord_read(const rd_tfrecord* f, int64_t lo, int64_t hi, float* signals, int32_t* input_len, int64_t* label_off,
+                     int32_t* label_len, uint8_t* labels, int64_t labels_cap);
+uint32_t rd_crc32c(const void* buf, size_t n);
+
+/* The CTC loss of Keras's ctc_batch_cost and a greedy edit distance, per window, on the GPU (ctc.hip).
+ * Window i has RD_CTC_T = 1024 softmax rows y[t][0..4] (A, C, G, T, blank), input_len[i] (1..1024) rows counted, and
+ * label_len[i] (0..RD_CTC_MAX_LABEL) labels 0..3 at labels + label_off[i].
+ *   loss[i]          -log of the summed probability of every path of input_len[i] rows that collapses to the labels, with
+ *                    p[t][k] = (y[t][k] + 1e-7) / sum_j (y[t][j] + 1e-7) (Keras log(y + epsilon), then TF's log-softmax), in fp64;
+ *                    +inf when no path exists
+ *   status[i]        RD_CTC_OK, or RD_CTC_INFEASIBLE: label_len + (adjacent equal labels) > input_len, loss +inf
+ *   greedy_len[i]    labels of the greedy decode: argmax of each counted row (lowest class on a tie), repeats collapsed, blanks dropped
+ *   edit_distance[i] Levenshtein distance (unit costs) between the greedy labels and the window's labels
+ *   greedy_out       nullable: window i's greedy labels at greedy_out + i * 1024
+ * A label_len above RD_CTC_MAX_LABEL, an input_len outside 1..1024 or a label outside 0..3 is RD_ERR_ARG before anything is launched.
+ * One launch per call, over the caller's windows; the context's workspaces are reused.  Synchronous; the context's stream.
+ *   rd_ctc_eval           windows [n][1024] float32 (MAD-normalised) -> the forward (rd_forward, the loaded weights) -> the above
+ *   rd_ctc_probs          caller-supplied rows probs [n][1024][5] float32 (host)
+ *   rd_ctc_probs_resident the same with d_probs in device memory (rd_dev_alloc; e.g. rd_forward_resident's output) */
+#define RD_CTC_T 1024
+#define RD_CTC_MAX_LABEL 255
+#define RD_CTC_OK 0
+#define RD_CTC_INFEASIBLE 1
+int rd_ctc_eval(rd_ctx* ctx, const float* windows, int n_windows, const int32_t* input_len, const uint8_t* labels, const int64_t* label_off,
+                const int32_t* label_len, double* loss, int32_t* status, int32_t* greedy_len, int32_t* edit_distance, uint8_t* greedy_out);
+int rd_ctc_probs(rd_ctx* ctx, const float* probs, int n_windows, const int32_t* input_len, const uint8_t* labels, const int64_t* label_off,
+                 const int32_t* label_len, double* loss, int32_t* status, int32_t* greedy_len, int32_t* edit_distance, uint8_t* greedy_out);
+int rd_ctc_probs_resident(rd_ctx* ctx, const float* d_probs, int n_windows, const int32_t* input_len, const uint8_t* labels,
+                          const int64_t* label_off, const int32_t* label_len, double* loss, int32_t* status, int32_t* greedy_len,
+                          int32_t* edit_distance, uint8_t* greedy_out);
 
 /* ---- multi-GPU start-up: one RCCL broadcast of weights + LM table over xGMI ------------------- */
 /* librccl can be loaded in this process (dlopen + symbol lookup; creates nothing).  Ranks other than the one that draws the

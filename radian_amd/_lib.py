@@ -79,6 +79,15 @@ SIGNATURES = {
     "rd_align_batch": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rd_align_workspace_bytes": (c_i64, [c_i64, c_i64]),
     "rd_align_clip_count": (c_i, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "rd_tfrecord_open": (c_i, [ctypes.c_char_p, ctypes.POINTER(c_vp)]),
+    "rd_tfrecord_open_mem": (c_i, [c_vp, c_sz, ctypes.POINTER(c_vp)]),
+    "rd_tfrecord_close": (None, [c_vp]),
+    "rd_tfrecord_count": (c_i, [c_vp, c_i64p, c_i64p]),
+    "rd_tfrecord_read": (c_i, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64]),
+    "rd_crc32c": (ctypes.c_uint32, [c_vp, c_sz]),
+    "rd_ctc_eval": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rd_ctc_probs": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rd_ctc_probs_resident": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rd_rccl_probe": (c_i, []),
     "rd_rccl_unique_id": (c_i, [c_vp]),
     "rd_rccl_init": (c_i, [c_vp, c_i, c_i, c_vp]),

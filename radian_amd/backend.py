@@ -96,6 +96,42 @@ class AlignResult:
         self.score, self.counts, self.status, self.ops = score, counts, status, ops
 
 
+# rd_ctc_* per-window status (include/radian_hip.h RD_CTC_*)
+CTC_OK, CTC_INFEASIBLE = 0, 1
+CTC_T, CTC_MAX_LABEL = 1024, 255
+
+
+def _pack_labels(labels, label_len, n):
+    """labels: [n, Lmax] array (Keras's dense form) or a list of n sequences, label_len: counted labels of each (None: all of a
+    sequence) -> (uint8 buffer, int64 offsets [n], int32 lengths [n])"""
+    if label_len is None:
+        label_len = [len(l) for l in labels]
+    ll = np.ascontiguousarray(label_len, dtype=np.int32).reshape(-1)
+    if len(labels) != n or ll.size != n:
+        raise ValueError(f"{len(labels)} label rows and {ll.size} lengths for {n} windows")
+    rows = []
+    for i in range(n):
+        row = np.asarray(labels[i]).reshape(-1)
+        if ll[i] < 0 or ll[i] > row.size:
+            raise ValueError(f"window {i}: label_length {int(ll[i])} outside 0..{row.size}")
+        r = row[: ll[i]]
+        if r.size and (np.any(r != np.round(r)) or r.min() < 0 or r.max() > 3):
+            raise ValueError(f"window {i}: labels must be 0..3")
+        rows.append(r.astype(np.uint8))
+    off = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(ll, out=off[1:])
+    buf = np.concatenate(rows) if off[-1] else np.zeros(1, dtype=np.uint8)
+    return np.ascontiguousarray(buf), np.ascontiguousarray(off[:-1]), ll
+
+
+class CtcResult:
+    """Backend.ctc_eval / ctc_probs per-window arrays: loss float64 [n] (+inf when infeasible), status int32 [n] (CTC_*),
+    greedy_len int32 [n], edit_distance int32 [n], greedy (list of uint8 arrays, or None when not asked for)."""
+
+    def __init__(self, loss, status, greedy_len, edit_distance, greedy):
+        self.loss, self.status, self.greedy_len, self.edit_distance, self.greedy = loss, status, greedy_len, edit_distance, greedy
+
+
 class PipeTicket:
     """One batch queued on a Backend's reads-level pipeline (Backend.pipe_submit_raw).  The arrays the library writes into
     live here until the batch is delivered."""
@@ -671,3 +707,39 @@ class Backend:
         if with_ops:
             ops_list = [ops[ops_off[p]: ops_off[p] + ops_len[p]].tobytes() for p in range(n)]
         return AlignResult(score, counts, status, ops_list)
+
+    # ------------------------------------------------------------------ model evaluation on labelled windows (val_loss)
+    def _ctc(self, fn, data, input_len, labels, label_len, with_greedy, n=None):
+        n = data.shape[0] if n is None else n
+        il = np.ascontiguousarray(input_len, dtype=np.int32).reshape(-1)
+        if il.size != n:
+            raise ValueError(f"{il.size} input lengths for {n} windows")
+        lab, off, ll = _pack_labels(labels, label_len, n)
+        loss = np.zeros(n, dtype=np.float64)
+        status = np.zeros(n, dtype=np.int32)
+        glen = np.zeros(n, dtype=np.int32)
+        ed = np.zeros(n, dtype=np.int32)
+        g = np.zeros((n, CTC_T), dtype=np.uint8) if with_greedy else None
+        self._check(fn(self._h, data if isinstance(data, ctypes.c_void_p) else _p(data), n, _p(il), _p(lab), _p(off), _p(ll), _p(loss), _p(status), _p(glen), _p(ed), _p(g)))
+        greedy = [g[i, : glen[i]].copy() for i in range(n)] if with_greedy else None
+        return CtcResult(loss, status, glen, ed, greedy)
+
+    def ctc_eval(self, windows, input_len, labels, label_len=None, with_greedy=False):
+        """Keras ctc_batch_cost on the loaded weights' softmax rows (radian/model.py:77-98) plus a greedy edit distance, on the GPU
+        (rd_ctc_eval: forward -> CTC -> greedy / Levenshtein).  windows [n, 1024] float32; input_len [n]; labels [n, Lmax] or a list
+        of sequences of 0..3 with label_len [n] of them counted (None: all).  Returns a CtcResult."""
+        windows = np.ascontiguousarray(windows, dtype=np.float32)
+        if windows.ndim != 2 or windows.shape[1] != CTC_T:
+            raise ValueError(f"windows must be [n_windows, {CTC_T}]")
+        return self._ctc(self._L.rd_ctc_eval, windows, input_len, labels, label_len, with_greedy)
+
+    def ctc_probs(self, probs, input_len, labels, label_len=None, with_greedy=False):
+        """the same on caller-supplied softmax rows probs [n, 1024, 5] float32 (rd_ctc_probs)"""
+        probs = np.ascontiguousarray(probs, dtype=np.float32)
+        if probs.ndim != 3 or probs.shape[1:] != (CTC_T, 5):
+            raise ValueError(f"probs must be [n_windows, {CTC_T}, 5]")
+        return self._ctc(self._L.rd_ctc_probs, probs, input_len, labels, label_len, with_greedy)
+
+    def ctc_probs_resident(self, d_probs, n, input_len, labels, label_len=None, with_greedy=False):
+        """the same on n windows of rows already in device memory (rd_ctc_probs_resident; d_probs from dev_alloc)"""
+        return self._ctc(self._L.rd_ctc_probs_resident, d_probs, input_len, labels, label_len, with_greedy, n=int(n))

@@ -167,6 +167,7 @@ struct rd_ctx {
     DevBuf ws_queue;                // the work-queue counter of beam_search_queue_kernel (decode.hip)
     DevBuf ws_wide, ws_wide_slot;   // beam widths above 51 (decode_wide.hip): per-sequence scratch block, per-trie-node slot map
     DevBuf ws_align;                // rd_align_batch (align.hip): one batch of pairs, sized exactly to the batch under the caller's budget
+    DevBuf ws_ctc;                  // rd_ctc_* (ctc.hip): window descriptors, labels, per-window results, greedy labels
     int64_t trie_budget = (int64_t)24 << 30;   // bytes of beam-search workspace one launch may ask for (rd_plan_trie_runs; rd_set_trie_budget)
     // pinned host staging
     void* h_stage = nullptr;
