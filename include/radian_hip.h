@@ -232,42 +232,38 @@ int rd_basecall_chunk_resident(rd_ctx* ctx, const float* d_windows, int n_window
 int rd_decode_resident(rd_ctx* ctx, const float* d_probs, int n_windows, int chunk_len, const int32_t* valid_len,
                        int beam_width, uint8_t* labels_out, int32_t* label_len);
 
-/* Software pipeline over chunk-mode batches: the forwards of consecutive submitted batches rotate over a few
- * independent streams ("lanes", default 2, rd_pipe_set_lanes; each lane has its own activation tensors) so that one
- * batch's partially filled last round of workgroups overlaps the next batch's launches; the beam search + label
- * copy-out of a GROUP of submitted batches (default 4, rd_pipe_config) runs on a further, high-priority stream and
- * overlaps the forwards of the next group.  Same contract as rd_basecall_chunk_resident, except that
- * labels_out/label_len of a submitted batch are only valid after rd_pipe_flush (or once a later submit had to
- * recycle its slot); the caller keeps them alive until then (labels of window i at labels_out + i*chunk_len).
- * The input buffers of a submitted batch must stay untouched until then as well. */
-int rd_pipe_config(rd_ctx* ctx, int group_batches);
-int rd_pipe_set_lanes(rd_ctx* ctx, int lanes); /* 1..4; only while the pipeline is empty */
-int rd_pipe_submit(rd_ctx* ctx, const float* d_windows, int n_windows, int chunk_len, const int32_t* valid_len,
-                   int beam_width, uint8_t* labels_out, int32_t* label_len);
-int rd_pipe_flush(rd_ctx* ctx);
 /* reads-level forms with the signal resident in HBM */
 int rd_basecall_reads_chunk_resident(rd_ctx* ctx, const float* d_signal, const int64_t* read_off, int n_reads,
                                      int chunk_len, int step, int beam_width, uint8_t* labels_out, int32_t* label_len);
 int rd_basecall_reads_global_resident(rd_ctx* ctx, const float* d_signal, const int64_t* read_off, int n_reads,
                                       int chunk_len, int step, int beam_width, int use_lm, double s_thr, double r_thr,
                                       uint8_t* labels_out, const int64_t* label_off, int32_t* label_len);
-int rd_pipe_submit_reads(rd_ctx* ctx, const float* d_signal, const int64_t* read_off, int n_reads, int chunk_len,
-                         int step, int beam_width, uint8_t* labels_out, int32_t* label_len);
 
-/* The same pipeline over batches of WHOLE READS, for both decode types and for raw input -- the loop body of
- * radian/basecall.py:77-121 (mad_normalise, get_windows, predict, assemble_matrices, beam_search) for a stream of read
- * batches inside ONE context: on the next forward lane [raw form: H2D of the samples out of the lane's pinned staging block,
- * MAD normalisation] -> streamed forward -> [global: per-read assembly]; on the decode stream, per GROUP of batches, the
- * beam search of every read (global; LM-gated with use_lm) or window (chunk) + labels to the host.  A group closes after
- * rd_pipe_config batches, or -- global mode -- as soon as its forward rows cover the beam search of its longest read (a
- * read's search is one serial chain of a time step per sample, which only the next group's forwards can hide).
- * Contracts as rd_basecall_reads_global / rd_basecall_raw_global / rd_basecall_raw_chunk, except:
+/* Software pipeline over submitted batches inside ONE context -- for a stream of read batches, the loop body of
+ * radian/basecall.py:77-121 (mad_normalise, get_windows, predict, assemble_matrices, beam_search).  A submit only queues its
+ * batch on the next forward lane (a stream with its own activation tensors; default 2, rd_pipe_set_lanes): [raw form: H2D of
+ * the samples out of the lane's pinned staging block, MAD normalisation] -> forward (streamed over whole reads; the windows form:
+ * every window's rows) -> [global: per-read assembly].  Consecutive batches' kernel chains on different lanes fill each other's
+ * last partial round of workgroups.  Batches gather in a GROUP; a closed group's beam search of every read (global; LM-gated
+ * with use_lm) or window (chunk) + labels to the host runs on a high-priority decode stream under the next groups' forwards.
+ * A group closes after rd_pipe_config batches (default 4), or -- global mode -- as soon as its forward rows cover the beam
+ * search of its longest read (a read's search is one serial chain of a time step per sample, which only the next group's
+ * forwards can hide).  rd_pipe_config / rd_pipe_set_lanes only while the pipeline is empty (after rd_pipe_flush).
+ * Contracts as the blocking entry points -- rd_basecall_chunk_resident (rd_pipe_submit), rd_basecall_reads_chunk_resident
+ * (rd_pipe_submit_reads), rd_basecall_reads_global / rd_basecall_raw_global / rd_basecall_raw_chunk -- except:
  *   - labels_out / label_len / status of a submitted batch are valid once rd_pipe_progress reports it delivered (or after
- *     rd_pipe_flush); the caller keeps them alive until then.  raw / read_off / label_off may be reused when the call returns;
- *     d_signal must stay untouched until delivery;
+ *     rd_pipe_flush); the caller keeps them alive until then (chunk mode: labels of window i at labels_out + i*chunk_len).
+ *     raw / read_off / label_off / valid_len may be reused when the call returns; d_signal / d_windows must stay untouched until
+ *     delivery;
  *   - empty reads are rejected (RD_ERR_ARG): basecall.py:77-82 skips them before this point.
  * Batches whose read lengths equal the previous batch's on the same lane reuse its tile descriptors; otherwise the plan
  * is rebuilt on the host and uploaded behind the lane's previous forward -- no stream is drained for it. */
+int rd_pipe_config(rd_ctx* ctx, int group_batches);
+int rd_pipe_set_lanes(rd_ctx* ctx, int lanes); /* 1..4; only while the pipeline is empty */
+int rd_pipe_submit(rd_ctx* ctx, const float* d_windows, int n_windows, int chunk_len, const int32_t* valid_len,
+                   int beam_width, uint8_t* labels_out, int32_t* label_len);
+int rd_pipe_submit_reads(rd_ctx* ctx, const float* d_signal, const int64_t* read_off, int n_reads, int chunk_len,
+                         int step, int beam_width, uint8_t* labels_out, int32_t* label_len);
 int rd_pipe_submit_reads_global(rd_ctx* ctx, const float* d_signal, const int64_t* read_off, int n_reads, int chunk_len,
                                 int step, int beam_width, int use_lm, double s_thr, double r_thr, uint8_t* labels_out,
                                 const int64_t* label_off, int32_t* label_len);
@@ -276,11 +272,12 @@ int rd_pipe_submit_raw_global(rd_ctx* ctx, const int16_t* raw, const int64_t* re
                               uint8_t* labels_out, const int64_t* label_off, int32_t* label_len, int32_t* status);
 int rd_pipe_submit_raw_chunk(rd_ctx* ctx, const int16_t* raw, const int64_t* read_off, int n_reads, int outlier_clip,
                              int chunk_len, int step, int beam_width, uint8_t* labels_out, int32_t* label_len, int32_t* status);
-/* Deliver finished groups of the reads-level pipeline to their callers, in submission order.  Without blocking when
+/* Deliver finished groups of the pipeline to their callers, in submission order.  Without blocking when
  * wait_for <= 0; otherwise returns once at least wait_for of the batches submitted so far (counted since the context was
  * created) have been delivered, closing the open group if what is awaited sits in it.  *delivered = that count. */
 int rd_pipe_progress(rd_ctx* ctx, int64_t wait_for, int64_t* delivered);
-/* Batches submitted to the reads-level pipeline so far: right after a submit, the number rd_pipe_progress must reach for
+int rd_pipe_flush(rd_ctx* ctx);   /* launches the open group and delivers every batch submitted so far */
+/* Batches submitted to the pipeline so far: right after a submit, the number rd_pipe_progress must reach for
  * that batch to have been delivered. */
 int rd_pipe_submitted(rd_ctx* ctx, int64_t* submitted);
 

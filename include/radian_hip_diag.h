@@ -57,7 +57,7 @@ int rd_split3(rd_ctx* ctx, const float* values, size_t n, uint16_t* terms_out);
  * of the longest read). */
 int rd_pipe_policy_read(rd_ctx* ctx, int beam_width, int on_partition, int use_lm, double* ns_per_row, double* us_per_step,
                         int64_t* rows_per_step);
-/* Counters of the reads-level pipeline over the context's life (no reference counterpart; for tools and tests): out[0..n) of
+/* Counters of the pipeline over the context's life (no reference counterpart; for tools and tests): out[0..n) of
  * { batches submitted, batches delivered, groups whose beam search was launched, of those: global-mode groups that held more sequences than
  * their decode partition keeps resident and were searched through the work queue, groups closed at that limit instead }. */
 int rd_pipe_stats(rd_ctx* ctx, int64_t* out, int n);

@@ -133,7 +133,7 @@ class CtcResult:
 
 
 class PipeTicket:
-    """One batch queued on a Backend's reads-level pipeline (Backend.pipe_submit_raw).  The arrays the library writes into
+    """One batch queued on a Backend's pipeline (Backend.pipe_submit_raw).  The arrays the library writes into
     live here until the batch is delivered."""
 
     def __init__(self, be, decode_type, off, n):
@@ -523,11 +523,13 @@ class Backend:
         self._check(self._L.rd_decode_resident(self._h, d_probs, n, T, _p(valid_len), int(beam_width), _p(labels), _p(lens)))
 
     def pipe_submit(self, d_windows, n, T, valid_len, beam_width, labels, lens):
-        """Two-stream pipeline (rd_pipe_submit): labels/lens are filled two submits later or at pipe_flush()."""
+        """Pipelined chunk-mode batch of pre-cut windows resident in HBM (rd_pipe_submit); labels / lens are filled once
+        pipe_progress reports the batch delivered (or at pipe_flush)."""
         self._check(self._L.rd_pipe_submit(self._h, d_windows, n, T, _p(valid_len), int(beam_width), _p(labels), _p(lens)))
 
     def pipe_submit_reads(self, d_signal, read_off, n_reads, chunk_len, step, beam_width, labels, lens):
-        """Pipelined chunk-mode batch of whole reads resident in HBM (rd_pipe_submit_reads)."""
+        """Pipelined chunk-mode batch of whole normalised reads resident in HBM (rd_pipe_submit_reads); labels / lens are filled
+        once pipe_progress reports the batch delivered (or at pipe_flush)."""
         self._check(self._L.rd_pipe_submit_reads(self._h, d_signal, _p(read_off), int(n_reads), int(chunk_len), int(step),
                                                  int(beam_width), _p(labels), _p(lens)))
 
@@ -542,7 +544,7 @@ class Backend:
                                                               int(step), int(beam_width), 1 if use_lm else 0, float(s_threshold),
                                                               float(r_threshold), _p(labels), _p(label_off), _p(lens)))
 
-    # ------------------------------------------------------------------ reads-level pipeline (one context, pipe_reads.hip)
+    # ------------------------------------------------------------------ the context's pipeline (pipe_reads.hip)
     def pipe_submit_reads_global(self, d_signal, read_off, n_reads, chunk_len, step, beam_width, use_lm, s_threshold, r_threshold,
                                  labels, label_off, lens):
         """Pipelined global-mode batch of normalised reads resident in HBM (rd_pipe_submit_reads_global); labels / lens are
@@ -552,7 +554,7 @@ class Backend:
                                                         _p(labels), _p(label_off), _p(lens)))
 
     def pipe_progress(self, wait_for=0):
-        """Deliver finished groups of the reads-level pipeline; blocks until `wait_for` submits (counted over the context's
+        """Deliver finished groups of the pipeline; blocks until `wait_for` submits (counted over the context's
         life) are delivered when wait_for > 0.  -> number of submits delivered so far."""
         n = ctypes.c_int64(0)
         self._check(self._L.rd_pipe_progress(self._h, int(wait_for), ctypes.byref(n)))
@@ -589,13 +591,13 @@ class Backend:
         return t
 
     def pipe_submitted(self):
-        """batches submitted to the reads-level pipeline so far = the pipe_progress count at which the latest one is delivered"""
+        """batches submitted to the pipeline so far = the pipe_progress count at which the latest one is delivered"""
         n = ctypes.c_int64(0)
         self._check(self._L.rd_pipe_submitted(self._h, ctypes.byref(n)))
         return n.value
 
     def pipe_stats(self):
-        """counters of the reads-level pipeline (rd_pipe_stats)"""
+        """counters of the pipeline (rd_pipe_stats)"""
         v = (ctypes.c_int64 * 5)()
         self._check(self._L.rd_pipe_stats(self._h, v, 5))
         return dict(zip(("submitted", "delivered", "launches", "queue_launches", "limit_closes"), (int(x) for x in v)))

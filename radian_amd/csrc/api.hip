@@ -143,8 +143,6 @@ static void timer_free(KernelTimer& t)
 }
 
 extern "C" int rd_rccl_finalize(rd_ctx* ctx);
-void rd_pipe_destroy_internal(rd_ctx* ctx);
-int rd_pipe_drain_decode_internal(rd_ctx* ctx);
 void rd_plan_cache_destroy_internal(rd_ctx* ctx);
 
 extern "C" int rd_destroy(rd_ctx* ctx)
@@ -153,7 +151,6 @@ extern "C" int rd_destroy(rd_ctx* ctx)
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     rd_rccl_finalize(ctx);
-    rd_pipe_destroy_internal(ctx);
     rd_rpipe_destroy(ctx);
     rd_plan_cache_destroy_internal(ctx);
     timer_free(ctx->timer_conv);
@@ -735,10 +732,9 @@ int decode_and_fetch(rd_ctx* ctx, const void* d_probs, int is_f64, const int64_t
     if (n_seq == 0) return RD_OK;
     SeqMeta sm;
     std::vector<int64_t> lab_off;
-    // beam searches still in flight on a pipeline's decode stream use the context's trie workspace: let them finish
-    int rc = rd_pipe_drain_decode_internal(ctx);
+    // beam searches still in flight on the pipeline's decode streams use the context's trie workspace: let them finish
+    int rc = rd_rpipe_drain_decode(ctx);
     if (rc) return rc;
-    if ((rc = rd_rpipe_drain_decode(ctx))) return rc;
     rc = prepare_seq_meta(ctx, seq_off, seq_off2, split, seq_len, n_seq, W, sm, lab_off);
     if (rc) return rc;
     if (ctx->ws_labels.reserve((size_t)sm.total_labels + 16)) return RD_ERR_NOMEM;
@@ -991,297 +987,6 @@ extern "C" int rd_count_windows(int64_t n_samples, int chunk_len, int step)
 {
     if (n_samples < 0 || chunk_len < 1 || step < 1 || step > chunk_len) return -1;
     return count_windows(n_samples, chunk_len, step);
-}
-
-// --------------------------------------------------------------------------------------------- software pipeline
-// Chunk-mode batches flow through several HIP streams.  Forwards (MFMA-bound): consecutive batches rotate over a few
-// forward lanes (FwdLane: a stream + its own activation tensors), so two independent kernel chains are in flight and the
-// partially filled last round of one chain's launch is filled by the other's workgroups.  Beam search (one wave per
-// window, latency-bound): the windows of a GROUP of batches are decoded by one launch on a further, high-priority
-// stream together with their label copy-out, overlapped with the forwards of the next group.  Grouping matters because
-// the decoder's throughput comes from waves per SIMD: 4 x 512 windows decode in about the time of 512.  Two slots of
-// probability / metadata / pinned output buffers; a slot is recycled only after its labels were handed to the caller.
-namespace {
-
-struct PipeSub {
-    int n = 0;          // windows of this submitted batch
-    int win0 = 0;       // first window inside the slot
-    uint8_t* user_labels = nullptr;
-    int32_t* user_lens = nullptr;
-};
-
-struct PipeSlot {
-    DevBuf probs, meta, labels;
-    void* h_meta = nullptr;
-    size_t h_meta_cap = 0;
-    void* h_out = nullptr;
-    size_t h_out_cap = 0;
-    hipEvent_t dec_done = nullptr;
-    bool busy = false;      // decode launched, labels not yet delivered
-    int T = 0, W = 0, nwin = 0;
-    int f16 = 0;            // the slot's probability rows are _Float16 (rd_set_logits)
-    int64_t rows = 0;       // probability rows produced into this slot so far
-    std::vector<PipeSub> subs;
-    std::vector<int64_t> off1, off2;   // per window: source rows (see DecodeArgs)
-    std::vector<int32_t> split, valid;
-    unsigned lane_mask = 0; // forward lanes that produced rows of the open group
-};
-
-struct Pipe {
-    hipStream_t s_dec = nullptr;
-    PipeSlot slot[2];
-    int cur = 0;
-    int group = 4;          // batches per decode launch
-    int lanes = 2;          // forward lanes the submitted batches rotate over
-    int next_lane = 0;
-};
-
-int pipe_get(rd_ctx* ctx, Pipe** out)
-{
-    if (!ctx->pipe) {
-        Pipe* p = new Pipe();
-        int lo = 0, hi = 0;
-        RD_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        RD_HIP(hipStreamCreateWithPriority(&p->s_dec, hipStreamNonBlocking, hi));
-        for (int i = 0; i < 2; i++) {
-            RD_HIP(hipEventCreateWithFlags(&p->slot[i].dec_done, hipEventDisableTiming));
-        }
-        ctx->pipe = p;
-    }
-    *out = (Pipe*)ctx->pipe;
-    return RD_OK;
-}
-
-void pipe_reset(PipeSlot& s)
-{
-    s.subs.clear();
-    s.off1.clear();
-    s.off2.clear();
-    s.split.clear();
-    s.valid.clear();
-    s.nwin = 0;
-    s.rows = 0;
-    s.lane_mask = 0;
-}
-
-int pipe_collect(PipeSlot& s)
-{
-    if (!s.busy) return RD_OK;
-    RD_HIP(hipEventSynchronize(s.dec_done));
-    const size_t nT = (size_t)s.nwin * s.T;
-    const uint8_t* hl = (const uint8_t*)s.h_out;
-    const int32_t* hlen = (const int32_t*)((const char*)s.h_out + align_up(nT, 256));
-    s.busy = false;
-    int rc = RD_OK;
-    for (const PipeSub& sb : s.subs)
-        for (int i = 0; i < sb.n; i++) {
-            const int w = sb.win0 + i;
-            if (hlen[w] < 0 || hlen[w] > s.T) {
-                rd_set_error("pipeline: window %d produced an impossible label length %d", w, hlen[w]);
-                rc = RD_ERR_STATE;
-                continue;
-            }
-            sb.user_lens[i] = hlen[w];
-            if (hlen[w]) memcpy(sb.user_labels + (size_t)i * s.T, hl + (size_t)w * s.T, (size_t)hlen[w]);
-        }
-    pipe_reset(s);
-    return rc;
-}
-
-// launch the beam search + copy-out of everything forwarded into the slot so far
-int pipe_launch_decode(rd_ctx* ctx, Pipe* p, PipeSlot& s)
-{
-    if (s.nwin == 0 || s.busy) return RD_OK;
-    int rc;
-    const size_t n = (size_t)s.nwin, nT = n * s.T;
-    // metadata: [off1 | off2 | node_off | label_off] int64, then [seq_len | split] int32, then label_len int32 (device only)
-    const size_t a8 = align_up(n * 8, 256), a4 = align_up(n * 4, 256);
-    const size_t o_off2 = a8, o_node = 2 * a8, o_lab = 3 * a8, o_len = 4 * a8, o_split = o_len + a4, o_llen = o_split + a4;
-    const size_t meta_bytes = o_llen + a4;
-    if ((rc = pinned_reserve(&s.h_meta, &s.h_meta_cap, meta_bytes))) return rc;
-    if (s.meta.reserve(meta_bytes)) return RD_ERR_NOMEM;
-    char* hm = (char*)s.h_meta;
-    int64_t* h_node = (int64_t*)(hm + o_node);
-    int64_t* h_lab = (int64_t*)(hm + o_lab);
-    memcpy(hm, s.off1.data(), n * 8);
-    memcpy(hm + o_off2, s.off2.data(), n * 8);
-    memcpy(hm + o_len, s.valid.data(), n * 4);
-    memcpy(hm + o_split, s.split.data(), n * 4);
-    for (int i = 0; i < s.nwin; i++) h_lab[i] = (int64_t)i * s.T;
-    std::vector<TrieRun> runs;
-    rd_plan_trie_runs(ctx, s.W, 0, s.nwin, [&](int k) { return (int64_t)s.valid[k]; }, h_node, runs);
-    if (s.labels.reserve(nT + 16)) return RD_ERR_NOMEM;
-    if ((rc = pinned_reserve(&s.h_out, &s.h_out_cap, align_up(nT, 256) + n * 4))) return rc;
-    if ((rc = rd_rpipe_drain_decode(ctx))) return rc;   // (beam searches of the other pipeline use the same trie workspace)
-    for (int l = 0; l < RD_MAX_LANES; l++)   // every forward that wrote into this slot has finished (a lane's event is its latest forward)
-        if (s.lane_mask & (1u << l)) RD_HIP(hipStreamWaitEvent(p->s_dec, ctx->lanes[l].done, 0));
-    RD_HIP(hipMemcpyAsync(s.meta.p, s.h_meta, o_llen, hipMemcpyHostToDevice, p->s_dec));
-    char* dm = (char*)s.meta.p;
-    for (const TrieRun& r : runs) {
-        rc = rd_decode_dev(ctx, s.probs.p, s.f16 ? 2 : 0, (const int64_t*)dm + r.k0, (const int32_t*)(dm + o_len) + r.k0, (const int64_t*)(dm + o_node) + r.k0,
-                           (const int64_t*)(dm + o_lab) + r.k0, r.k1 - r.k0, r.nodes, s.W, 0, 0.0, 0.0, s.labels.as<uint8_t>(),
-                           (int32_t*)(dm + o_llen) + r.k0, nullptr, p->s_dec, (const int64_t*)(dm + o_off2) + r.k0, (const int32_t*)(dm + o_split) + r.k0);
-        if (rc) return rc;
-    }
-    RD_HIP(hipMemcpyAsync(s.h_out, s.labels.p, nT, hipMemcpyDeviceToHost, p->s_dec));
-    RD_HIP(hipMemcpyAsync((char*)s.h_out + align_up(nT, 256), dm + o_llen, n * 4, hipMemcpyDeviceToHost, p->s_dec));
-    RD_HIP(hipEventRecord(s.dec_done, p->s_dec));
-    s.busy = true;
-    return RD_OK;
-}
-
-// slot that can take `rows` more probability rows for windows of T rows decoded at width W; closes / recycles groups
-int pipe_open_slot(rd_ctx* ctx, Pipe* p, int T, int W, int64_t rows, PipeSlot** out, int f16 = 0)
-{
-    int rc;
-    PipeSlot* s = &p->slot[p->cur];
-    // a group is homogeneous in chunk_len, beam width and row type and bounded in size; otherwise close it and move on
-    if (s->nwin > 0 && (s->T != T || s->W != W || s->f16 != f16 || (int)s->subs.size() >= p->group)) {
-        if ((rc = pipe_launch_decode(ctx, p, *s))) return rc;
-        p->cur ^= 1;
-        s = &p->slot[p->cur];
-    }
-    if (s->busy && (rc = pipe_collect(*s))) return rc;   // the slot's previous group goes to its callers first
-    const size_t need = (size_t)(s->rows + rows) * 20;
-    if (need > s->probs.cap) {
-        if (s->nwin > 0) {
-            // growing would move probabilities already produced: close the group instead
-            if ((rc = pipe_launch_decode(ctx, p, *s))) return rc;
-            p->cur ^= 1;
-            s = &p->slot[p->cur];
-            if (s->busy && (rc = pipe_collect(*s))) return rc;
-        }
-        if (s->probs.reserve((size_t)rows * 20 * (size_t)p->group)) return RD_ERR_NOMEM;
-    }
-    s->T = T;
-    s->W = W;
-    s->f16 = f16;
-    *out = s;
-    return RD_OK;
-}
-
-int pipe_close_if_full(rd_ctx* ctx, Pipe* p, PipeSlot* s)
-{
-    if ((int)s->subs.size() >= p->group) {
-        int rc = pipe_launch_decode(ctx, p, *s);
-        if (rc) return rc;
-        p->cur ^= 1;
-    }
-    return RD_OK;
-}
-
-void pipe_destroy(rd_ctx* ctx)
-{
-    Pipe* p = (Pipe*)ctx->pipe;
-    if (!p) return;
-    if (p->s_dec) (void)hipStreamSynchronize(p->s_dec);
-    for (int i = 0; i < 2; i++) {
-        PipeSlot& s = p->slot[i];
-        s.probs.release();
-        s.meta.release();
-        s.labels.release();
-        if (s.h_meta) (void)hipHostFree(s.h_meta);
-        if (s.h_out) (void)hipHostFree(s.h_out);
-        if (s.dec_done) (void)hipEventDestroy(s.dec_done);
-    }
-    if (p->s_dec) (void)hipStreamDestroy(p->s_dec);
-    delete p;
-    ctx->pipe = nullptr;
-}
-
-}  // namespace
-
-void rd_pipe_destroy_internal(rd_ctx* ctx) { pipe_destroy(ctx); }
-
-int rd_pipe_drain_decode_internal(rd_ctx* ctx)
-{
-    Pipe* p = (Pipe*)ctx->pipe;
-    if (p && p->s_dec && (p->slot[0].busy || p->slot[1].busy)) RD_HIP(hipStreamSynchronize(p->s_dec));
-    return RD_OK;
-}
-
-extern "C" int rd_pipe_config(rd_ctx* ctx, int group_batches)
-{
-    RD_REQUIRE(ctx, "rd_pipe_config: null context");
-    RD_REQUIRE(group_batches >= 1 && group_batches <= 64, "rd_pipe_config: group_batches %d out of range [1,64]", group_batches);
-    RD_HIP(hipSetDevice(ctx->device));
-    Pipe* p = nullptr;
-    int rc = pipe_get(ctx, &p);
-    if (rc) return rc;
-    RD_REQUIRE(p->slot[0].nwin == 0 && p->slot[1].nwin == 0 && !p->slot[0].busy && !p->slot[1].busy && rd_rpipe_idle(ctx),
-               "rd_pipe_config: pipeline not empty (call rd_pipe_flush first)");
-    p->group = group_batches;
-    ctx->pipe_group = group_batches;
-    return RD_OK;
-}
-
-extern "C" int rd_pipe_set_lanes(rd_ctx* ctx, int lanes)
-{
-    RD_REQUIRE(ctx, "rd_pipe_set_lanes: null context");
-    RD_REQUIRE(lanes >= 1 && lanes <= RD_MAX_LANES, "rd_pipe_set_lanes: %d out of range [1,%d]", lanes, RD_MAX_LANES);
-    Pipe* p = nullptr;
-    int rc = pipe_get(ctx, &p);
-    if (rc) return rc;
-    RD_REQUIRE(p->slot[0].nwin == 0 && p->slot[1].nwin == 0 && !p->slot[0].busy && !p->slot[1].busy && rd_rpipe_idle(ctx),
-               "rd_pipe_set_lanes: pipeline not empty (call rd_pipe_flush first)");
-    p->lanes = lanes;
-    p->next_lane = 0;
-    ctx->pipe_lanes = lanes;
-    return RD_OK;
-}
-
-extern "C" int rd_pipe_submit(rd_ctx* ctx, const float* d_windows, int n_windows, int chunk_len, const int32_t* valid_len,
-                              int beam_width, uint8_t* labels_out, int32_t* label_len)
-{
-    RD_REQUIRE(ctx && d_windows && valid_len && labels_out && label_len, "rd_pipe_submit: null argument");
-    RD_REQUIRE(n_windows >= 1 && chunk_len >= 1, "rd_pipe_submit: bad shape");
-    RD_REQUIRE(beam_width >= 1 && beam_width <= rd_decode_max_width(), "beam_width %d out of range", beam_width);
-    RD_REQUIRE(rd_decode_len_ok(beam_width, chunk_len), "rd_pipe_submit: chunk_len %d too long for beam width %d (1 + W * rows < 2^29)", chunk_len, beam_width);
-    for (int i = 0; i < n_windows; i++)
-        RD_REQUIRE(valid_len[i] >= 0 && valid_len[i] <= chunk_len, "valid_len[%d]=%d out of range", i, valid_len[i]);
-    RD_HIP(hipSetDevice(ctx->device));
-    Pipe* p = nullptr;
-    int rc = pipe_get(ctx, &p);
-    if (rc) return rc;
-    PipeSlot* s = nullptr;
-    const int64_t rows = (int64_t)n_windows * chunk_len;
-    if ((rc = pipe_open_slot(ctx, p, chunk_len, beam_width, rows, &s))) return rc;
-    const int lane = p->next_lane;
-    p->next_lane = (p->next_lane + 1) % p->lanes;
-    rc = rd_forward_dev(ctx, d_windows, n_windows, chunk_len, s->probs.as<float>() + (size_t)s->rows * 5, lane);
-    if (rc) return rc;
-    s->lane_mask |= 1u << lane;
-    PipeSub sb;
-    sb.n = n_windows;
-    sb.win0 = s->nwin;
-    sb.user_labels = labels_out;
-    sb.user_lens = label_len;
-    s->subs.push_back(sb);
-    for (int i = 0; i < n_windows; i++) {
-        s->off1.push_back(s->rows + (int64_t)i * chunk_len);
-        s->off2.push_back(s->rows + (int64_t)i * chunk_len);
-        s->split.push_back(0);
-        s->valid.push_back(valid_len[i]);
-    }
-    s->nwin += n_windows;
-    s->rows += rows;
-    return pipe_close_if_full(ctx, p, s);
-}
-
-extern "C" int rd_pipe_flush(rd_ctx* ctx)
-{
-    RD_REQUIRE(ctx, "rd_pipe_flush: null context");
-    RD_HIP(hipSetDevice(ctx->device));
-    int rc;
-    if ((rc = rd_rpipe_flush(ctx))) return rc;   // the reads-level pipeline (pipe_reads.hip)
-    Pipe* p = (Pipe*)ctx->pipe;
-    if (!p) return RD_OK;
-    // order of completion on the decode stream: the other slot's group (if any) was launched first
-    PipeSlot& a = p->slot[p->cur ^ 1];
-    PipeSlot& b = p->slot[p->cur];
-    if ((rc = pipe_launch_decode(ctx, p, b))) return rc;
-    if ((rc = pipe_collect(a))) return rc;
-    return pipe_collect(b);
 }
 
 // --------------------------------------------------------------------------------------------- reads-level entry points
@@ -1631,45 +1336,6 @@ extern "C" int rd_basecall_raw_global(rd_ctx* ctx, const int16_t* raw, const int
         RD_REQUIRE(status[r] != 2, "rd_basecall_raw_global: read %d is empty (the caller skips empty reads, basecall.py:77-82)", r);
     return rd_basecall_reads_global_resident(ctx, ctx->ws_in.as<float>(), read_off, n_reads, chunk_len, step, beam_width, use_lm,
                                              s_thr, r_thr, labels_out, label_off, label_len);
-}
-
-// pipelined chunk-mode batches of whole reads (same overlap scheme as rd_pipe_submit)
-extern "C" int rd_pipe_submit_reads(rd_ctx* ctx, const float* d_signal, const int64_t* read_off, int n_reads, int chunk_len,
-                                    int step, int beam_width, uint8_t* labels_out, int32_t* label_len)
-{
-    int rc = check_reads_args(ctx, d_signal, read_off, n_reads, chunk_len, step, beam_width);
-    if (rc) return rc;
-    RD_REQUIRE(labels_out && label_len, "rd_pipe_submit_reads: null output");
-    RD_REQUIRE(rd_decode_len_ok(beam_width, chunk_len), "rd_pipe_submit_reads: chunk_len %d too long for beam width %d (1 + W * rows < 2^29)", chunk_len, beam_width);
-    RD_HIP(hipSetDevice(ctx->device));
-    const ReadsPlan* P = nullptr;
-    const TileLists* tl = nullptr;
-    if ((rc = get_plan(ctx, read_off, n_reads, chunk_len, step, 0, &P, &tl, nullptr))) return rc;
-    Pipe* p = nullptr;
-    if ((rc = pipe_get(ctx, &p))) return rc;
-    PipeSlot* s = nullptr;
-    const int f16 = ctx->logits_f16;
-    if ((rc = pipe_open_slot(ctx, p, chunk_len, beam_width, P->total_rows, &s, f16))) return rc;
-    const int lane = p->next_lane;
-    p->next_lane = (p->next_lane + 1) % p->lanes;
-    rc = rd_forward_tiles_dev(ctx, d_signal, *tl, P->total_rows, (char*)s->probs.p + (size_t)s->rows * 5 * (f16 ? 2 : 4), lane, f16);
-    if (rc) return rc;
-    s->lane_mask |= 1u << lane;
-    PipeSub sb;
-    sb.n = P->n_windows;
-    sb.win0 = s->nwin;
-    sb.user_labels = labels_out;
-    sb.user_lens = label_len;
-    s->subs.push_back(sb);
-    for (int w = 0; w < P->n_windows; w++) {
-        s->off1.push_back(P->off1[w] + s->rows);
-        s->off2.push_back(P->off2[w] + s->rows);
-        s->split.push_back(P->split[w]);
-        s->valid.push_back(P->valid[w]);
-    }
-    s->nwin += P->n_windows;
-    s->rows += P->total_rows;
-    return pipe_close_if_full(ctx, p, s);
 }
 
 // --------------------------------------------------------------------------------------------- device memory

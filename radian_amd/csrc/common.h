@@ -175,8 +175,7 @@ struct rd_ctx {
     bool h_stage_busy = false;   // an async copy out of h_stage was queued and the stream has not been synchronised since
     KernelTimer timer_conv, timer_decode, timer_head, timer_in;
     void* rccl = nullptr;  // RcclState*
-    void* pipe = nullptr;  // Pipe* (two-stream forward/decode software pipeline over chunk-mode batches, api.hip)
-    void* rpipe = nullptr; // ReadsPipe* (the same scheme over batches of whole reads, global mode / raw input, pipe_reads.hip)
+    void* rpipe = nullptr; // ReadsPipe* (the forward / decode software pipeline over submitted batches, pipe_reads.hip)
     int pipe_group = 4;    // batches per beam-search launch (rd_pipe_config)
     int pipe_lanes = 2;    // forward streams the submitted batches rotate over (rd_pipe_set_lanes)
     void* plan_cache[2] = {nullptr, nullptr};  // PlanCache* for chunk / global reads-level plans
@@ -220,10 +219,7 @@ int rd_assemble_dev(rd_ctx* ctx, const void* d_probs, int nW, int T, int pad, in
                     int streamed = 0 /* 1: d_probs is the streamed forward [N][5]; row t is taken from row t */,
                     int in_f16 = 0 /* 1: d_probs rows are _Float16 */);
 
-// api.hip
-int rd_pipe_drain_decode_internal(rd_ctx* ctx);   // wait for the chunk pipeline's beam searches in flight
 // pipe_reads.hip
-int rd_rpipe_flush(rd_ctx* ctx);
 bool rd_rpipe_idle(const rd_ctx* ctx);
 int rd_rpipe_drain_decode(rd_ctx* ctx);   // wait for the pipeline's beam searches in flight (they share the trie workspace)
 void rd_rpipe_destroy(rd_ctx* ctx);

@@ -1,11 +1,12 @@
-// pipe_reads.hip -- software pipeline over batches of WHOLE READS inside one rd_ctx (declared in include/radian_hip.h):
-// rd_pipe_submit_reads_global / rd_pipe_submit_raw_global / rd_pipe_submit_raw_chunk / rd_pipe_progress.
+// pipe_reads.hip -- the context's software pipeline over submitted batches (declared in include/radian_hip.h): rd_pipe_submit (pre-cut
+// windows), rd_pipe_submit_reads / rd_pipe_submit_reads_global (whole reads resident in HBM), rd_pipe_submit_raw_chunk /
+// rd_pipe_submit_raw_global (raw int16 reads), rd_pipe_progress / rd_pipe_flush, rd_pipe_config / rd_pipe_set_lanes.
 //
 // The loop body of radian/basecall.py:77-121 for a stream of read batches.  What runs where:
 //   forward lane (rotating, rd_pipe_set_lanes; each lane owns its activation tensors, staging and tile descriptors):
 //       [raw form: H2D of the int16 samples out of the lane's pinned staging block -> mad_normalise (preprocess.py:24-49)]
-//       -> streamed TCN forward (every time step once) into the open GROUP's probability rows
-//       -> [global mode: per-read assembly (matrix_assembly.py:6-53) of the batch into the group's float64 matrix]
+//       -> streamed TCN forward (every time step once; windows form: every window's rows) into the open GROUP's
+//       probability rows -> [global mode: per-read assembly (matrix_assembly.py:6-53) of the batch into the group's float64 matrix]
 //   decode stream (high priority): per closed group ONE metadata upload, the beam search of every read (global: LM-gated,
 //       decode.py:100-212) or window (chunk) of the group, labels + lengths (+ normalisation status) to pinned host memory.
 // A group closes when it holds rd_pipe_config batches -- or, in global mode, as soon as its forward work covers the beam
@@ -487,7 +488,6 @@ int slot_launch_decode(rd_ctx* ctx, ReadsPipe* p, RSlot& s)
     const size_t ho_len = align_up((size_t)s.labels_total + 16, 256);
     s.status_off = ho_len + align_up(n * 4, 256);
     if ((rc = pinned_reserve(&s.h_out, &s.h_out_cap, s.status_off + (size_t)s.n_reads * 4 + 16))) return rc;
-    if ((rc = rd_pipe_drain_decode_internal(ctx))) return rc;   // (beam searches of the chunk pipeline use the same trie workspace)
     // the group's beam search runs on the decode partition when its forwards kept one clear and its sequences are few
     // enough to run there at chain pace, else on the whole chip; the two streams share the trie workspace, so a launch on
     // one waits for the other's latest
@@ -555,6 +555,20 @@ int close_group(rd_ctx* ctx, ReadsPipe* p)
     if (rc) return rc;
     p->cur = (p->cur + 1) % ReadsPipe::NSLOT;
     return RD_OK;
+}
+
+// the open group is launched, then every launched group delivered, in launch order
+int flush_groups(rd_ctx* ctx, ReadsPipe* p)
+{
+    int rc;
+    if ((rc = slot_launch_decode(ctx, p, p->slot[p->cur]))) return rc;
+    for (;;) {
+        RSlot* first = nullptr;
+        for (RSlot& s : p->slot)
+            if (s.busy && (!first || s.launch_seq < first->launch_seq)) first = &s;
+        if (!first) return RD_OK;
+        if ((rc = slot_collect(p, *first))) return rc;
+    }
 }
 
 // a group that can take `rows` more probability rows with these decode parameters; closes / recycles groups as needed
@@ -662,22 +676,70 @@ int lane_plan_upload(FwdLane* L, RLane& R, char* hs)
     return RD_OK;
 }
 
-int check_args(rd_ctx* ctx, const void* signal, const int64_t* read_off, int n_reads, int chunk_len, int step, int W)
+// window_bound: the beam search's length bound is checked on chunk_len (rd_pipe_submit_reads, which decodes windows), not on every read
+int check_args(rd_ctx* ctx, const void* signal, const int64_t* read_off, int n_reads, int chunk_len, int step, int W, bool window_bound = false)
 {
     RD_REQUIRE(ctx && signal && read_off, "null argument");
     RD_REQUIRE(n_reads >= 1 && chunk_len >= 1, "bad shape");
     RD_REQUIRE(step >= 1 && step <= chunk_len, "step %d must be in [1, chunk_len]", step);
     RD_REQUIRE(W >= 1 && W <= rd_decode_max_width(), "beam_width %d out of range", W);
+    RD_REQUIRE(!window_bound || rd_decode_len_ok(W, chunk_len), "chunk_len %d too long for beam width %d (1 + W * rows < 2^29)", chunk_len, W);
     RD_REQUIRE(read_off[0] == 0, "read_off[0] must be 0");
     for (int r = 0; r < n_reads; r++) {
         RD_REQUIRE(read_off[r + 1] > read_off[r], "read %d is empty (the caller skips empty reads, basecall.py:77-82)", r);
-        RD_REQUIRE(rd_decode_len_ok(W, read_off[r + 1] - read_off[r]), "read %d has %lld samples; beam width %d supports at most %lld (1 + W * rows < 2^29)", r,
+        RD_REQUIRE(window_bound || rd_decode_len_ok(W, read_off[r + 1] - read_off[r]), "read %d has %lld samples; beam width %d supports at most %lld (1 + W * rows < 2^29)", r,
                    (long long)(read_off[r + 1] - read_off[r]), W, (long long)((((int64_t)1 << 29) - 2) / W));
     }
     if (!ctx->model.loaded) {
         rd_set_error("no weights loaded (rd_load_weights)");
         return RD_ERR_STATE;
     }
+    return RD_OK;
+}
+
+// The batch forwarded on lane `plane` is part of group s: its sequences, rows and reads join it (rows64 / labels_total: the group's totals
+// with the batch; steps: its time steps of global-mode search, one per sample of a read), the lanes rotate, and the group closes by the
+// rule of its mode.
+int join_group(rd_ctx* ctx, ReadsPipe* p, RSlot* s, RSub&& sb, const std::vector<RSeq>& seqs, int64_t rows, int64_t rows64, int64_t labels_total,
+               int64_t longest, int64_t steps, int plane)
+{
+    s->seqs.insert(s->seqs.end(), seqs.begin(), seqs.end());
+    s->rows64 = rows64;
+    s->labels_total = labels_total;
+    s->lane_mask |= 1u << plane;
+    s->n_reads += sb.n_reads;
+    s->rows += rows;
+    if (longest > s->longest) s->longest = longest;
+    s->steps_total += steps;
+    s->subs.push_back(std::move(sb));
+    p->next_lane = (plane % RD_MAX_LANES + 1) % ctx->pipe_lanes;
+    p->submitted++;
+    const int W = s->W, part = s->part, use_lm = s->use_lm;
+    bool close;
+    if (s->mode == 1) {
+        // global mode: by coverage of the longest read's chain (see chain_rows), not by a batch count
+        const int limit = part ? part_seq_limit(part, W) : 0;
+        const bool few = part && ((int)s->seqs.size() <= limit || s->oversub);
+        const int m = few ? std::min(3, part_waves_per_simd(part, W, (int64_t)s->seqs.size())) : 0;
+        int64_t need = chain_rows(ctx, p->calib, W, m, use_lm) * s->longest;
+        // An oversubscribed partition (decided by submit when the crossing batch arrived) finishes no sooner than its total work allows: every
+        // resident slot steps at the saturated pace, so the group's forward rows must also cover  steps_total x pace(3) / slots  -- a rate
+        // against a rate, hence WITHOUT the 20 % that chain_rows adds for the one chain that decides a covered group's end (x 5/6): with
+        // the margin a partition at 0.9 of the forward's pace could never "cover" itself and the group grew to its buffer's cap -- 27
+        // batches, half-second searches, 20 M samples/s on 64 x 4096-sample batches at W = 25.  A partition slower than the forward (the
+        // pre-check tolerates 1.25x) covers nothing however long the group: there the group ends with its chain covered and three rounds
+        // of resident sequences gathered.
+        const int resident = part ? queue_resident_seqs(part, W) : 1;
+        const int64_t need_chain = need;
+        if (s->oversub) need = std::max(need, chain_rows(ctx, p->calib, W, 3, use_lm) * 5 / 6 * s->steps_total / resident);
+        close = s->rows >= need || s->rows >= kGroupRowsCap || (s->oversub && s->rows >= need_chain && (int)s->seqs.size() >= 3 * resident);
+        // (the very first group of a context closes with its first batch: nothing is decoding yet, and its chains start one
+        // group's forward time earlier -- a quarter of a second on a job of long reads)
+        close = close || p->launches == 0;
+    } else {
+        close = (int)s->subs.size() >= ctx->pipe_group;
+    }
+    if (close) return close_group(ctx, p);
     return RD_OK;
 }
 
@@ -692,7 +754,6 @@ int submit(rd_ctx* ctx, int mode, const float* d_signal, const int16_t* raw, int
     RD_HIP(hipSetDevice(ctx->device));
     ReadsPipe* p = nullptr;
     if ((rc = rpipe_get(ctx, &p))) return rc;
-    const int n_lanes = ctx->pipe_lanes < 1 ? 1 : ctx->pipe_lanes;
     // global mode, a batch of few reads (long reads, small steps): its forward keeps `part` CUs of every XCD clear and the
     // group's beam search runs there at chain pace; a batch of many reads uses every CU (see chain_rows)
     // (the CU masks are laid out for 8 XCDs x 32 CUs: on any other device there is no partition)
@@ -700,7 +761,7 @@ int submit(rd_ctx* ctx, int mode, const float* d_signal, const int16_t* raw, int
     const int part = part_cus && n_reads <= part_seq_limit(part_cus, W) / 2 ? part_cus : 0;
     if (part && part != p->part_cus) {   // (part_cus of the pipe = the size its masked streams exist for)
         // another partition size (first use, or the beam width's class changed): drain, then new masked streams
-        if ((rc = rd_rpipe_flush(ctx))) return rc;
+        if ((rc = flush_groups(ctx, p))) return rc;
         if (p->s_part) {
             rd_masked_stream_release(p->s_part);
             p->s_part = nullptr;
@@ -710,7 +771,7 @@ int submit(rd_ctx* ctx, int mode, const float* d_signal, const int16_t* raw, int
         if ((rc = rd_masked_stream_acquire(ctx->device, part, false, &p->s_part))) return rc;
         p->part_cus = part;
     }
-    const int lane = p->next_lane % n_lanes;
+    const int lane = p->next_lane % ctx->pipe_lanes;
     const int plane = lane + (part ? RD_MAX_LANES : 0);   // the lane's partitioned twin: same staging, masked stream, own activations
     FwdLane* L = nullptr;
     if ((rc = rd_lane_get(ctx, plane, &L))) return rc;
@@ -718,23 +779,25 @@ int submit(rd_ctx* ctx, int mode, const float* d_signal, const int16_t* raw, int
     const size_t n_samples = (size_t)read_off[n_reads];
     const int f16 = ctx->logits_f16;
 
-    // ---- host side first: the lane's staging block is free again, the plan is known, every buffer is large enough
-    if (R.staged_pending) {
-        RD_HIP(hipEventSynchronize(R.staged));
-        R.staged_pending = false;
-    }
+    // ---- host side first: the plan is known, the lane's staging block is free again, every buffer is large enough
     if (!R.staged) RD_HIP(hipEventCreateWithFlags(&R.staged, hipEventDisableTiming));
     bool miss = false;
     size_t n_desc = 0;
     if ((rc = lane_plan_build(ctx, R, read_off, n_reads, chunk_len, step, mode, &miss, &n_desc))) return rc;
     const ReadsPlan& P = R.plan;
-    // staging block: [read offsets | raw samples] | descriptors (plan miss) | AsmRead records (global mode)
+    // staging block: [read offsets | raw samples] | descriptors (plan miss) | AsmRead records (global mode).  A chunk-mode batch of
+    // resident signal whose plan the lane already holds stages nothing, and does not wait for the block.
+    const bool stages = raw || miss || mode == 1;
     const size_t st_off = align_up((size_t)(n_reads + 1) * 8, 256);
     const size_t st_raw = raw ? align_up(n_samples * 2 + 16, 256) : 0;
     const size_t st_desc = miss ? align_up(n_desc * sizeof(TileDesc), 256) : 0;
     const size_t st_asm = mode == 1 ? align_up((size_t)n_reads * sizeof(AsmRead), 256) : 0;
     const size_t o_raw = st_off, o_desc = raw ? st_off + st_raw : 0, o_asm = o_desc + st_desc;
-    if ((rc = pinned_reserve(&R.h_stage, &R.h_stage_cap, o_asm + st_asm + 256))) return rc;
+    if (stages && R.staged_pending) {
+        RD_HIP(hipEventSynchronize(R.staged));
+        R.staged_pending = false;
+    }
+    if (stages && (rc = pinned_reserve(&R.h_stage, &R.h_stage_cap, o_asm + st_asm + 256))) return rc;
     char* hs = (char*)R.h_stage;
     // device: descriptors | AsmRead records
     const size_t d_asm = align_up(n_desc * sizeof(TileDesc), 256);
@@ -758,7 +821,7 @@ int submit(rd_ctx* ctx, int mode, const float* d_signal, const int16_t* raw, int
 
     // ---- the group this batch joins (may close / deliver earlier groups)
     RSlot* s = nullptr;
-    int64_t expect_rows = 0;
+    int64_t expect_rows = ctx->pipe_group * P.total_rows;   // (chunk mode: the group's batches, from its first one on)
     int64_t longest_b = 0;
     if (mode == 1) {
         for (int r = 0; r < n_reads; r++) longest_b = std::max<int64_t>(longest_b, read_off[r + 1] - read_off[r]);
@@ -904,8 +967,10 @@ int submit(rd_ctx* ctx, int mode, const float* d_signal, const int16_t* raw, int
     }
     AsmRead* d_ar = (AsmRead*)((char*)R.tiles.p + d_asm);
     if (n64 && (rc = copy_on_stream(d_ar, hs + o_asm, (size_t)n64 * sizeof(AsmRead), L->st))) return rc;
-    RD_HIP(hipEventRecord(R.staged, L->st));   // the staging block is free once these copies are done
-    R.staged_pending = true;
+    if (stages) {
+        RD_HIP(hipEventRecord(R.staged, L->st));   // the staging block is free once these copies are done
+        R.staged_pending = true;
+    }
     const size_t rb = f16 ? 10 : 20;
     if ((rc = rd_forward_tiles_dev(ctx, sig, R.lists, P.total_rows, (char*)s->probs.p + (size_t)s->rows * rb, plane, f16))) return rc;
     if (n64 && (rc = rd_assemble_batch_dev(L->st, s->probs.p, d_ar, n64, max_n, chunk_len, step, s->mat.as<double>(), R.streamed ? 1 : 0, f16)))
@@ -921,43 +986,40 @@ int submit(rd_ctx* ctx, int mode, const float* d_signal, const int16_t* raw, int
     }
 
     // ---- the batch is part of the group
-    s->seqs.insert(s->seqs.end(), seqs.begin(), seqs.end());
-    s->rows64 = rows64;
-    s->labels_total = labels_total;
-    s->lane_mask |= 1u << plane;
-    s->n_reads += n_reads;
-    s->rows += P.total_rows;
-    if (longest > s->longest) s->longest = longest;
-    if (mode == 1) s->steps_total += (int64_t)n_samples;     // (a read's search takes one time step per sample)
-    s->subs.push_back(std::move(sb));
-    p->next_lane = (lane + 1) % n_lanes;
-    p->submitted++;
-    bool close;
-    if (mode == 1) {
-        // global mode: by coverage of the longest read's chain (see chain_rows), not by a batch count
-        const int limit = part ? part_seq_limit(part, W) : 0;
-        const bool few = part && ((int)s->seqs.size() <= limit || s->oversub);
-        const int m = few ? std::min(3, part_waves_per_simd(part, W, (int64_t)s->seqs.size())) : 0;
-        int64_t need = chain_rows(ctx, p->calib, W, m, use_lm) * s->longest;
-        // An oversubscribed partition (decided when the crossing batch arrived, above) finishes no sooner than its total work allows: every
-        // resident slot steps at the saturated pace, so the group's forward rows must also cover  steps_total x pace(3) / slots  -- a rate
-        // against a rate, hence WITHOUT the 20 % that chain_rows adds for the one chain that decides a covered group's end (x 5/6): with
-        // the margin a partition at 0.9 of the forward's pace could never "cover" itself and the group grew to its buffer's cap -- 27
-        // batches, half-second searches, 20 M samples/s on 64 x 4096-sample batches at W = 25.  A partition slower than the forward (the
-        // pre-check tolerates 1.25x) covers nothing however long the group: there the group ends with its chain covered and three rounds
-        // of resident sequences gathered.
-        const int resident = part ? queue_resident_seqs(part, W) : 1;
-        const int64_t need_chain = need;
-        if (s->oversub) need = std::max(need, chain_rows(ctx, p->calib, W, 3, use_lm) * 5 / 6 * s->steps_total / resident);
-        close = s->rows >= need || s->rows >= kGroupRowsCap || (s->oversub && s->rows >= need_chain && (int)s->seqs.size() >= 3 * resident);
-        // (the very first group of a context closes with its first batch: nothing is decoding yet, and its chains start one
-        // group's forward time earlier -- a quarter of a second on a job of long reads)
-        close = close || p->launches == 0;
-    } else {
-        close = (int)s->subs.size() >= ctx->pipe_group;
+    return join_group(ctx, p, s, std::move(sb), seqs, P.total_rows, rows64, labels_total, longest, mode == 1 ? (int64_t)n_samples : 0, plane);
+}
+
+// The windows form of a chunk-mode submit (rd_pipe_submit): n pre-cut windows of T samples, valid_len[w] rows of window w decoded, its
+// labels at labels_out + w*T.  No plan and no staging: the forward of every window's rows on the next unpartitioned lane, float32 rows.
+int submit_windows(rd_ctx* ctx, const float* d_windows, int n, int T, const int32_t* valid_len, int W, uint8_t* labels_out, int32_t* label_len)
+{
+    int rc;
+    RD_HIP(hipSetDevice(ctx->device));
+    ReadsPipe* p = nullptr;
+    if ((rc = rpipe_get(ctx, &p))) return rc;
+    const int lane = p->next_lane % ctx->pipe_lanes;
+    const int64_t rows = (int64_t)n * T;
+    RSlot* s = nullptr;
+    if ((rc = open_slot(ctx, p, 0, W, 0, 0, 0.0, 0.0, 0, rows, ctx->pipe_group * rows, &s))) return rc;
+    RSub sb;
+    sb.seq0 = (int)s->seqs.size();
+    sb.read0 = s->n_reads;
+    sb.n_seq = n;
+    sb.user_labels = labels_out;
+    sb.user_lens = label_len;
+    std::vector<RSeq> seqs(n);
+    for (int w = 0; w < n; w++) {
+        RSeq& q = seqs[w];
+        q.off1 = q.off2 = s->rows + (int64_t)w * T;
+        q.split = 0;
+        q.len = valid_len[w];
+        q.is64 = 0;
+        q.label_off = s->labels_total + (int64_t)w * T;
+        sb.user_label_off.push_back((int64_t)w * T);
     }
-    if (close) return close_group(ctx, p);
-    return RD_OK;
+    // (open_slot left room for the batch's rows: s->rows + rows <= s->cap_rows)
+    if ((rc = rd_forward_dev(ctx, d_windows, n, T, s->probs.as<float>() + (size_t)s->rows * 5, lane))) return rc;
+    return join_group(ctx, p, s, std::move(sb), seqs, rows, s->rows64, s->labels_total + rows, 0, 0, lane);
 }
 
 }  // namespace
@@ -1005,21 +1067,6 @@ int rd_rpipe_drain_decode(rd_ctx* ctx)
     return RD_OK;
 }
 
-int rd_rpipe_flush(rd_ctx* ctx)
-{
-    ReadsPipe* p = (ReadsPipe*)ctx->rpipe;
-    if (!p) return RD_OK;
-    int rc;
-    if ((rc = slot_launch_decode(ctx, p, p->slot[p->cur]))) return rc;
-    for (;;) {   // every launched group, in launch order
-        RSlot* first = nullptr;
-        for (RSlot& s : p->slot)
-            if (s.busy && (!first || s.launch_seq < first->launch_seq)) first = &s;
-        if (!first) return RD_OK;
-        if ((rc = slot_collect(p, *first))) return rc;
-    }
-}
-
 void rd_rpipe_destroy(rd_ctx* ctx)
 {
     ReadsPipe* p = (ReadsPipe*)ctx->rpipe;
@@ -1061,6 +1108,55 @@ void rd_rpipe_destroy(rd_ctx* ctx)
 }
 
 // ------------------------------------------------------------------------------------------------ C ABI
+extern "C" int rd_pipe_config(rd_ctx* ctx, int group_batches)
+{
+    RD_REQUIRE(ctx, "rd_pipe_config: null context");
+    RD_REQUIRE(group_batches >= 1 && group_batches <= 64, "rd_pipe_config: group_batches %d out of range [1,64]", group_batches);
+    RD_REQUIRE(rd_rpipe_idle(ctx), "rd_pipe_config: pipeline not empty (call rd_pipe_flush first)");
+    ctx->pipe_group = group_batches;
+    return RD_OK;
+}
+
+extern "C" int rd_pipe_set_lanes(rd_ctx* ctx, int lanes)
+{
+    RD_REQUIRE(ctx, "rd_pipe_set_lanes: null context");
+    RD_REQUIRE(lanes >= 1 && lanes <= RD_MAX_LANES, "rd_pipe_set_lanes: %d out of range [1,%d]", lanes, RD_MAX_LANES);
+    RD_REQUIRE(rd_rpipe_idle(ctx), "rd_pipe_set_lanes: pipeline not empty (call rd_pipe_flush first)");
+    ctx->pipe_lanes = lanes;
+    if (ctx->rpipe) ((ReadsPipe*)ctx->rpipe)->next_lane = 0;
+    return RD_OK;
+}
+
+extern "C" int rd_pipe_flush(rd_ctx* ctx)
+{
+    RD_REQUIRE(ctx, "rd_pipe_flush: null context");
+    if (!ctx->rpipe) return RD_OK;
+    RD_HIP(hipSetDevice(ctx->device));
+    return flush_groups(ctx, (ReadsPipe*)ctx->rpipe);
+}
+
+extern "C" int rd_pipe_submit(rd_ctx* ctx, const float* d_windows, int n_windows, int chunk_len, const int32_t* valid_len,
+                              int beam_width, uint8_t* labels_out, int32_t* label_len)
+{
+    RD_REQUIRE(ctx && d_windows && valid_len && labels_out && label_len, "rd_pipe_submit: null argument");
+    RD_REQUIRE(n_windows >= 1 && chunk_len >= 1, "rd_pipe_submit: bad shape");
+    RD_REQUIRE(beam_width >= 1 && beam_width <= rd_decode_max_width(), "beam_width %d out of range", beam_width);
+    RD_REQUIRE(rd_decode_len_ok(beam_width, chunk_len), "rd_pipe_submit: chunk_len %d too long for beam width %d (1 + W * rows < 2^29)", chunk_len, beam_width);
+    for (int i = 0; i < n_windows; i++)
+        RD_REQUIRE(valid_len[i] >= 0 && valid_len[i] <= chunk_len, "valid_len[%d]=%d out of range", i, valid_len[i]);
+    return submit_windows(ctx, d_windows, n_windows, chunk_len, valid_len, beam_width, labels_out, label_len);
+}
+
+extern "C" int rd_pipe_submit_reads(rd_ctx* ctx, const float* d_signal, const int64_t* read_off, int n_reads, int chunk_len,
+                                    int step, int beam_width, uint8_t* labels_out, int32_t* label_len)
+{
+    int rc = check_args(ctx, d_signal, read_off, n_reads, chunk_len, step, beam_width, true);
+    if (rc) return rc;
+    RD_REQUIRE(labels_out && label_len, "rd_pipe_submit_reads: null output");
+    return submit(ctx, 0, d_signal, nullptr, 0, read_off, n_reads, chunk_len, step, beam_width, 0, 0.0, 0.0, labels_out, nullptr, label_len,
+                  nullptr);
+}
+
 extern "C" int rd_pipe_submit_reads_global(rd_ctx* ctx, const float* d_signal, const int64_t* read_off, int n_reads, int chunk_len, int step,
                                            int beam_width, int use_lm, double s_thr, double r_thr, uint8_t* labels_out,
                                            const int64_t* label_off, int32_t* label_len)

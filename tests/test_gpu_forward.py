@@ -132,7 +132,7 @@ def test_fused_global_equals_separate(be, oracle):
 
 
 def test_pipeline_equals_unpipelined(be):
-    """rd_pipe_submit/flush (two streams, batch i+1 forward overlapping batch i decode) == rd_basecall_chunk."""
+    """rd_pipe_submit/flush (forwards on rotating lanes, a group's beam search under the next group's forwards) == rd_basecall_chunk."""
     rng = np.random.default_rng(8)
     n, T = 24, 1024
     batches = []

@@ -1,5 +1,5 @@
-"""The reads-level pipeline inside one context (rd_pipe_submit_reads_global / rd_pipe_submit_raw_global /
-rd_pipe_submit_raw_chunk / rd_pipe_progress; csrc/pipe_reads.hip): forwards of consecutive batches on rotating lanes,
+"""The pipeline inside one context (rd_pipe_submit_reads_global / rd_pipe_submit_raw_global / rd_pipe_submit_raw_chunk /
+rd_pipe_submit_reads / rd_pipe_submit / rd_pipe_progress; csrc/pipe_reads.hip): forwards of consecutive batches on rotating lanes,
 per-read assembly on the lane, the beam search of a group of batches on the decode stream.
 
 Parity: every submitted batch's labels equal (a) the unpipelined entry point's on the same input and (b) the oracle's --
@@ -137,6 +137,56 @@ def test_pipe_raw_chunk_ragged_equals_unpipelined(dev, step, W):
             bad = [w for w in range(len(got[r])) if not np.array_equal(got[r][w], ref[i][0][r][w])]
             assert not bad, (step, W, i, r, bad[:5])
     dev.pipe_config(4)
+
+
+def test_pipe_chunk_resident_forms_counted_and_delivered_by_progress(dev):
+    """rd_pipe_submit (windows) and rd_pipe_submit_reads (normalised reads) are batches of the same pipeline, mixed in one group:
+    rd_pipe_submitted counts them, rd_pipe_progress delivers them in submission order, and a batch's labels are final once progress
+    reports it delivered -- before any flush"""
+    from radian_amd import synthetic
+    n, W, step = 16, 10, 512
+    raws = synthetic.synthetic_reads(n, READ_LEN, seed=91)
+    norm = np.stack([synthetic.mad_normalise(r, 4) for r in raws]).astype(np.float32)
+    windows, valid, _, _ = synthetic.reads_to_windows(list(raws), CHUNK, step)
+    nw = windows.shape[0]
+    off = np.arange(n + 1, dtype=np.int64) * READ_LEN
+    d_sig, d_win = dev.dev_alloc(norm.nbytes), dev.dev_alloc(windows.nbytes)
+    dev.h2d(d_sig, norm)
+    dev.h2d(d_win, windows)
+
+    def outputs():
+        return np.zeros((nw, CHUNK), dtype=np.uint8), np.full(nw, -1, dtype=np.int32)
+
+    try:
+        ref_reads, ref_win = outputs(), outputs()
+        dev.basecall_reads_chunk_resident(d_sig, off, n, CHUNK, step, W, *ref_reads)
+        dev.basecall_chunk_resident(d_win, nw, CHUNK, valid, W, *ref_win)
+        dev.pipe_flush()
+        dev.pipe_config(2)
+        base = dev.pipe_submitted()
+        assert dev.pipe_progress(0) == base
+        outs = []
+        for i in range(5):
+            lab, ln = outputs()
+            if i % 2:
+                dev.pipe_submit(d_win, nw, CHUNK, valid, W, lab, ln)
+            else:
+                dev.pipe_submit_reads(d_sig, off, n, CHUNK, step, W, lab, ln)
+            assert dev.pipe_submitted() == base + i + 1
+            outs.append((lab, ln, ref_win if i % 2 else ref_reads))
+        seen = []
+        for i, (lab, ln, (rlab, rln)) in enumerate(outs):
+            assert dev.pipe_progress(base + i + 1) >= base + i + 1
+            assert np.array_equal(ln, rln), i
+            assert all(np.array_equal(lab[w, : ln[w]], rlab[w, : rln[w]]) for w in range(nw)), i
+            seen.append((lab.copy(), ln.copy()))
+        assert dev.pipe_progress(0) == base + 5
+        dev.pipe_flush()
+        for (lab, ln, _), (lab0, ln0) in zip(outs, seen):
+            assert np.array_equal(lab, lab0) and np.array_equal(ln, ln0)
+    finally:
+        dev.dev_free(d_sig)
+        dev.dev_free(d_win)
 
 
 def test_pipe_resident_global_and_progress_contract(dev):
@@ -322,8 +372,8 @@ def test_beam_search_workspace_budget_cuts_launches_without_changing_results(dev
     """a launch's trie is W x ALL its rows (20-24 B per node, + decode_wide's scratch per sequence) -- a big group at a
     wide beam asked for hundreds of GB and died with RD_ERR_NOMEM mid-job.  Launches beyond the context's budget now run as several
     runs of sequences that share the workspace (rd_plan_trie_runs).  With a budget of 2 MB -- a handful of sequences per run -- every
-    route gives the labels the default (one run) gives: rd_decode_batch, the blocking raw calls, the chunk pipeline over resident windows and
-    the reads pipeline in both modes (global: float64 and float32 passes, LM on)."""
+    route gives the labels the default (one run) gives: rd_decode_batch, the blocking raw calls, the pipeline over raw reads in
+    both modes (global: float64 and float32 passes, LM on) and over resident windows."""
     from radian_amd import synthetic
     rng = np.random.default_rng(900 + W)
     table = np.random.default_rng(1).dirichlet([0.3] * 4, size=4 ** 3)
