@@ -8,7 +8,7 @@ prefix beam search W=10 (chunk mode: LM unused, reference basecall.py:110-121) -
 Inputs are resident in HBM when the timed region starts.  One process per GPU; ranks shard reads with no
 data-path collective (weak scaling); the only RCCL traffic is the start-up broadcast of the weights.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 With --gpus N > 1 and no WORLD_SIZE in the environment this process is only the LAUNCHER: before anything touches a GPU it
 makes a private rendezvous directory, starts N fresh copies of itself with RANK / LOCAL_RANK / WORLD_SIZE set (one per
@@ -17,12 +17,13 @@ variables itself (e.g. `python -m torch.distributed.run --nproc-per-node N bench
 the ranks find each other through a directory named after that launcher's pid.  No PyTorch in any bench process: the
 128-byte RCCL id travels through the rendezvous directory, barrier and max-over-ranks through RCCL (rd_rccl_*).
 
-The line: `value` = the median of --regions (3) timed regions of K steps each (`value_runs`: all of them); `roofline` = the dominant
-kernel against the fp32-MFMA peak from live HIP events, launch-weighted, with `by_variant`; `cpu_baseline` = the oracle port on the host's
-cores.  N = 1 adds secondary legs (other precisions, forward only, the literal windowed job, peaky decode-only, global + LM, heads of other
-base densities, raw and files -> FASTA end to end); N > 1 adds the files -> FASTA legs through the multi-GPU route inside the ranks
-(files_leg: work queue, native reader, per-rank core slice, rank files, merger process) -- the host feed that SURVEY 8e names as the
-scaling limit, which the HBM-resident headline cannot see.
+The line: `value` = the median of --regions (3) timed regions of K steps each (`value_runs`: all of them).  A plain run stops there: set-up,
+warm-up, the timed regions, --dump-outputs, the line (`roofline` is null).  Everything else the bench measures runs only with --full:
+`roofline` = the dominant kernel against the fp32-MFMA peak from live HIP events, launch-weighted, with `by_variant`; `cpu_baseline` = the
+oracle port on the host's cores.  N = 1 adds secondary legs (other precisions, forward only, the literal windowed job, peaky decode-only,
+global + LM, heads of other base densities, raw and files -> FASTA end to end); N > 1 adds the files -> FASTA legs through the multi-GPU
+route inside the ranks (files_leg: work queue, native reader, per-rank core slice, rank files, merger process) -- the host feed that
+SURVEY 8e names as the scaling limit, which the HBM-resident headline cannot see.  --no-secondary / --no-cpu-baseline drop parts of --full.
 """
 import argparse
 import json
@@ -589,7 +590,9 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--regions", type=int, default=3, help="timed regions of --steps steps each (after --warmup steps each); the line reports the median region")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the roofline pass, the secondary legs (N = 1) or the files -> FASTA legs (N > 1), and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--windowed", action="store_true", help="evaluate all 512 windows per step like the reference (default: streamed forward)")
     ap.add_argument("--precision", choices=["fp32", "f16x3", "bf16x3"], default="fp32",
                     help="matrix-product arithmetic of the forward: exact fp32 MFMA (default), split-f16 products, or the "
@@ -598,7 +601,7 @@ def main():
                     help="untimed steps for this long before the W warm-up steps (GPU clocks after idle); 0 = none")
     ap.add_argument("--decode-math", choices=["glibc", "fast"], default="glibc",
                     help="arithmetic of the beam search in the timed region (default: the library's default, glibc's operation sequence)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary legs (other precision modes, global+LM, raw end to end)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the secondary legs (other precision modes, global+LM, raw end to end)")
     ap.add_argument("--check", action="store_true",
                     help="untimed cross-checks on batch 0: streamed labels == windowed labels == the oracle's; probabilities within 1e-4 of the oracle's")
     ap.add_argument("--decode-group", type=int, default=8, help="batches per beam-search launch in the two-stream pipeline")
@@ -611,10 +614,10 @@ def main():
                     help="fp32 conv workgroup shape: 0 = 128 x 256 tiles, two workgroups per CU (product); 1 = 256 x 256, one per CU (measurement)")
     ap.add_argument("--cpu-reads", type=int, default=0, help="reads in the CPU-baseline sample (0: sized to the usable core count)")
     ap.add_argument("--nrank-files-per-rank", type=int, default=4,
-                    help="N > 1: multi-read fast5 files (4096 reads x 4096 samples each) per rank in the files -> FASTA leg through the multi-GPU "
+                    help="N > 1 with --full: multi-read fast5 files (4096 reads x 4096 samples each) per rank in the files -> FASTA leg through the multi-GPU "
                          "route (secondary_e2e_fast5_to_fasta; ~3 s of basecalling per rank at the default); 0 = no such leg")
     ap.add_argument("--nrank-legs", default="chunk,global",
-                    help="N > 1: which files -> FASTA legs run through the multi-GPU route: chunk (configs[2]), global (configs[3]'s geometry: global decode "
+                    help="N > 1 with --full: which files -> FASTA legs run through the multi-GPU route: chunk (configs[2]), global (configs[3]'s geometry: global decode "
                          "with the 12-mer LM), or both (default)")
     ap.add_argument("--e2e-reads", type=int, default=32768,
                     help="reads of the raw end-to-end secondary leg (the other driver legs take a half or a sixteenth of it): jobs of a few "
@@ -640,7 +643,7 @@ def main():
     from radian_amd import Backend, weights, synthetic
     from radian_amd.backend import RD_TIMER_CONV, RD_TIMER_DECODE, RD_TIMER_HEAD
 
-    secondaries = world == 1 and not args.no_secondary and not args.windowed and args.precision == "fp32"
+    secondaries = args.full and world == 1 and not args.no_secondary and not args.windowed and args.precision == "fp32"
     stitch_pool = None   # (the pipelined driver stitches natively on host threads: no worker processes to start)
 
     from radian_amd.backend import device_for_rank
@@ -790,9 +793,9 @@ def main():
 
     samples_per_step = reads_per_batch * READ_LEN  # input samples basecalled per step per GPU
     value = world * args.steps * samples_per_step / elapsed
-    # ---- roofline of the dominant kernel (dilated conv on fp32 MFMA), HIP events on the launch stream
+    # ---- --full from here on.  Roofline of the dominant kernel (dilated conv on fp32 MFMA), HIP events on the launch stream
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # Conv / head launches: a pipelined region on ONE forward lane directly after the timed region (same clock / thermal
         # state): launches of consecutive batches run back to back on the lane's stream, the beam search of the previous group on
         # the decode stream -- the timed region's regime minus the second lane, whose launches would overlap these and make a
@@ -899,10 +902,10 @@ def main():
             "decode_hbm_frac": float(sum(batches[i % n_batches][1].sum() for i in range(n_dec))) / max(1e-9, td["total_ms"] * 1e-3) * 20.0 / 8.0e12,
             "decode_timesteps_per_s_" + other + "_math": float(sum(batches[i % n_batches][1].sum() for i in range(n_dec))) / max(1e-9, tdg["total_ms"] * 1e-3),
         }
-    # secondaries, reported beside the headline (one GPU, fp32 headline only): the same job in the other matrix-product
+    # secondaries, reported beside the headline (--full, one GPU, fp32 headline only): the same job in the other matrix-product
     # modes; configs[3]'s global + LM geometry; the raw-reads end-to-end driver loop
     sec = {}
-    if world == 1 and args.precision == "fp32" and not args.no_secondary and not args.windowed:
+    if secondaries:
         for mode, key, desc, acc in (
                 ("bf16x3", "secondary_bf16x3",
                  "three-term bf16 split: hi+mid+lo reconstructs every finite fp32 operand exactly; six v_mfma_f32_32x32x16_bf16 per "
@@ -923,7 +926,7 @@ def main():
                 be.set_precision("fp32")
             sec[key] = {"precision": desc, "value": world * args.steps * samples_per_step / el2, "unit": "samples/s",
                         "ms_per_step": el2 / args.steps * 1e3, "accuracy": acc}
-    if world == 1 and args.precision == "fp32" and not args.no_secondary and not args.windowed:
+    if secondaries:
         # BASELINE configs[1] "forward only": the headline's batches through the signal model alone (rd_forward_reads_resident: the
         # streamed evaluation, no beam search), on the same rotating forward lanes.  Beside the headline it splits the step into its
         # forward and what the beam search adds (co-running hides none of the search's SIMD time).
@@ -942,7 +945,7 @@ def main():
                 "beam_search_adds_ms_per_step": elapsed / args.steps * 1e3 - el_f / args.steps * 1e3}
         except Exception as e:
             print(f"[bench] secondary_forward_only failed: {e}", file=sys.stderr)
-    if world == 1 and args.precision == "fp32" and not args.no_secondary and not args.windowed:
+    if secondaries:
         # The literal configs[2] job: ALL 512 windows x 1024 rows through the model, as the reference evaluates them (basecall.py:88-93),
         # rd_pipe_submit on the same lanes and groups.  Bit-identical labels to the headline (bench.py --check); 1.78x the model rows.
         note("secondary_windowed")
@@ -1097,7 +1100,7 @@ def main():
                 print(f"[bench] secondary_e2e_fast5_to_fasta_global_lm failed: {e}", file=sys.stderr)
         del table
     nrank_legs = [x for x in args.nrank_legs.split(",") if x in ("chunk", "global")]
-    if world > 1 and args.precision == "fp32" and not args.no_secondary and not args.windowed and args.nrank_files_per_rank > 0 and nrank_legs:
+    if args.full and world > 1 and args.precision == "fp32" and not args.no_secondary and not args.windowed and args.nrank_files_per_rank > 0 and nrank_legs:
         # The one leg of the N > 1 line: the job from a fast5 directory to FASTA files through the product's multi-GPU
         # route, every rank on its own core slice -- the host feed SURVEY 8e names as the scaling limit.  Every rank takes part; the
         # ranks meet through files (own launcher: its rendezvous directory; foreign launcher: a directory named after its pid).
@@ -1146,7 +1149,7 @@ def main():
 
     cpu = None
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cores = effective_cores()
             nr = args.cpu_reads or max(2, min(reads_per_batch, 4 * cores))   # ~10-20 s of CPU work, all usable cores busy
             note(f"cpu_baseline: oracle on {nr} reads, {cores} threads")

@@ -51,7 +51,7 @@ WORLD = 4
 
 def test_bench_four_ranks_broadcast_through_the_collective_seam(standin_env):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(WORLD), "--steps", "4", "--warmup", "1", "--preheat-ms", "0", "--check",
-                        "--regions", "2", "--nrank-files-per-rank", "1", "--nrank-legs", "chunk"],
+                        "--regions", "2", "--full", "--nrank-files-per-rank", "1", "--nrank-legs", "chunk"],
                        env=standin_env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-4000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip()]
@@ -64,7 +64,7 @@ def test_bench_four_ranks_broadcast_through_the_collective_seam(standin_env):
     assert hb["split"] in ("numa", "even") and (not hb["bound"] or hb["cores"] <= max(1, usable // WORLD + 1)), (hb, usable)
     assert abs(d["ms_per_step"] - max(d["ms_per_step_per_rank"])) < 1e-6        # (the reported region's own per-rank clocks)
     assert d["value"] > 0 and d["scaling"] == "weak" and len(d["value_runs"]) == 2 and min(d["value_runs"]) <= d["value"] <= max(d["value_runs"])
-    # round 6: the N > 1 line carries the files -> FASTA leg through the multi-GPU route (work queue, native reader, per-rank core slice,
+    # the N > 1 --full line carries the files -> FASTA leg through the multi-GPU route (work queue, native reader, per-rank core slice,
     # rank files, merger process), every rank's share and rate in it
     leg = d["secondary_e2e_fast5_to_fasta"]
     assert "skipped" not in leg, leg
@@ -148,14 +148,14 @@ def test_cli_four_ranks_receive_the_artefacts_by_broadcast(tmp_path, standin_env
 
 def test_bench_under_the_drivers_own_launcher(standin_env):
     """the round-end driver's command, rank for rank: `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
-    --master-port P bench.py --gpus N --steps K --warmup W` (a foreign launcher: RANK / LOCAL_RANK / WORLD_SIZE come from it, the rendezvous
-    directory is named after its pid) -- two ranks, the collectives through the stand-in library: ONE JSON line on the job's stdout."""
+    --master-port P bench.py --gpus N --steps K --warmup W`, here with --full (a foreign launcher: RANK / LOCAL_RANK / WORLD_SIZE come from it,
+    the rendezvous directory is named after its pid) -- two ranks, the collectives through the stand-in library: ONE JSON line on the job's stdout."""
     import socket
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--preheat-ms", "0"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--preheat-ms", "0", "--full"]
     r = subprocess.run(cmd, env=standin_env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-4000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip().startswith("{")]
@@ -163,8 +163,8 @@ def test_bench_under_the_drivers_own_launcher(standin_env):
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["startup_comm"] == "rccl" and d["rccl_nranks"] == 2 and len(d["ms_per_step_per_rank"]) == 2
     assert d["config"]["launcher"].startswith("foreign") and d["value"] > 0 and d["steps"] == 4 and d["warmup"] == 1
-    # round 6: under the driver's launcher the line carries BOTH files -> FASTA legs through the multi-GPU route (default flags: 4 files of 4096 reads
-    # per rank): configs[2] (chunk) and configs[3]'s geometry (global decode, 12-mer LM) -- the configuration BASELINE.json quotes its scaling curve on
+    # with --full, under the driver's launcher the line carries BOTH files -> FASTA legs through the multi-GPU route (default flags: 4 files of 4096
+    # reads per rank): configs[2] (chunk) and configs[3]'s geometry (global decode, 12-mer LM) -- the configuration BASELINE.json quotes its scaling curve on
     for key, mode in (("secondary_e2e_fast5_to_fasta", "chunk"), ("secondary_e2e_fast5_to_fasta_global_lm", "global")):
         leg = d[key]
         assert "skipped" not in leg, leg

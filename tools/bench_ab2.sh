@@ -1,5 +1,5 @@
 for a in "--steps 200 --decode-form one" "--steps 200 --decode-form two" "--steps 200 --decode-form one" "--steps 200 --decode-form two" "--steps 200 --decode-form one --decode-math fast" "--steps 200 --decode-form two --decode-math fast"; do
-  echo "== $a"; python bench.py --no-secondary --no-cpu-baseline $a 2>/dev/null | python -c "
+  echo "== $a"; python bench.py --full --no-secondary --no-cpu-baseline $a 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     l=l.strip()

@@ -23,7 +23,7 @@ same = np.array_equal(out[0][0], out[1][0]) and all(np.array_equal(a, b) for x, 
 print("probabilities and labels bit-identical across shapes:", same)
 be.close()
 for shape in (0, 1, 0, 1):
-    r = subprocess.run([sys.executable, os.path.join(R, "bench.py"), "--conv-shape", str(shape), "--no-secondary", "--no-cpu-baseline"], capture_output=True, text=True)
+    r = subprocess.run([sys.executable, os.path.join(R, "bench.py"), "--conv-shape", str(shape), "--full", "--no-secondary", "--no-cpu-baseline"], capture_output=True, text=True)
     d = json.loads(r.stdout.strip().splitlines()[-1])
     rf = d["roofline"]
     print(f"shape {shape}: headline {d['value'] / 1e6:.2f} M samples/s, conv {rf['avg_launch_ms']:.4f} ms per launch = {rf['frac']:.3f} of peak, pipeline_frac {rf['pipeline_frac']:.3f}", flush=True)

@@ -11,7 +11,7 @@ OUT=gpurun_out/power_watch.txt
     sleep 0.5
   done ) &
 W=$!
-timeout -k 10 300 python bench.py --no-secondary --no-cpu-baseline --steps $STEPS --warmup 20 "$@" > gpurun_out/power_watch_bench.json 2> gpurun_out/power_watch_bench.err
+timeout -k 10 300 python bench.py --full --no-secondary --no-cpu-baseline --steps $STEPS --warmup 20 "$@" > $(dirname $OUT)/power_watch_bench.json 2> $(dirname $OUT)/power_watch_bench.err
 RC=$?
 kill $W 2>/dev/null
 wait $W 2>/dev/null

@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/profq_$TAG
 mkdir -p $OUT
 cd $R
-ARGS="bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --lanes 1 --precision $PREC"
+ARGS="bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-secondary --lanes 1 --precision $PREC"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ARGS > $OUT/trace_bench.json 2> $OUT/trace_err.log
 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_WAIT_INST_LDS --output-format csv -d $OUT/pmc_lds -- python3 $ARGS > $OUT/pmc_lds_bench.json 2> $OUT/pmc_lds_err.log
 python3 - <<PY
