@@ -410,6 +410,45 @@ int rd_ctc_probs_resident(rd_ctx* ctx, const float* d_probs, int n_windows, cons
                           const int64_t* label_off, const int32_t* label_len, double* loss, int32_t* status, int32_t* greedy_len,
                           int32_t* edit_distance, uint8_t* greedy_out);
 
+/* Training of the signal model on labelled windows (train.hip): radian/train.py's model.fit with
+ * Keras's ctc_batch_cost (the batch mean of the per-window losses above) and TF 2.4's Adam.  Exact fp32 only: a context set to
+ * another precision is refused (RD_ERR_ARG).  The windows, input_len, labels and their checks are those of rd_ctc_eval
+ * (all RD_ERR_ARG before anything is launched).  A window without a CTC path (RD_CTC_INFEASIBLE) contributes zero loss and
+ * zero gradient; the mean still divides by n_windows (Keras would turn the whole step into inf / NaN).
+ *   loss[i], status[i]   per window, from the weights before the update (loss +inf when infeasible)
+ *   rd_train_grad        the gradient of the batch's mean loss, in load_weights order (rd_get_weights' layout); no update
+ *   rd_train_step        the same gradient, then one Adam update of the context's weights, in place:
+ *                          t += 1;  m += (g - m)(1 - beta1);  v += (g^2 - v)(1 - beta2);
+ *                          w -= m alpha / (sqrt(v) + epsilon),  alpha = lr sqrt(1 - beta2^t) / (1 - beta1^t)   (fp32)
+ *                        every later forward, rd_clone_artifacts and rd_rccl_bcast_model sees the new weights, in every packing
+ *   rd_train_step_resident  d_windows [n][1024] in device memory (rd_dev_alloc)
+ *   rd_train_reset       Adam's moments and t to zero (rd_load_weights does this too: Keras restores weights, not the optimiser)
+ *   rd_get_weights       the context's current weights, n = the model's parameter count (2 200 581 for sig2seq.yaml)
+ * Training workspaces (saved activations: about 19 x 1 KiB x 1024 per window) are allocated by the first training call and
+ * only grow; a context that never trains allocates none.  Synchronous; the context's stream. */
+typedef struct rd_adam {
+    float lr;        /* 1e-4 in sig2seq.yaml */
+    float beta1;     /* 0.9 */
+    float beta2;     /* 0.999 */
+    float epsilon;   /* 1e-7 */
+} rd_adam;
+int rd_train_grad(rd_ctx* ctx, const float* windows, int n_windows, const int32_t* input_len, const uint8_t* labels, const int64_t* label_off,
+                  const int32_t* label_len, float* grad, double* loss, int32_t* status);
+int rd_train_step(rd_ctx* ctx, const float* windows, int n_windows, const int32_t* input_len, const uint8_t* labels, const int64_t* label_off,
+                  const int32_t* label_len, const rd_adam* opt, double* loss, int32_t* status);
+int rd_train_step_resident(rd_ctx* ctx, const float* d_windows, int n_windows, const int32_t* input_len, const uint8_t* labels,
+                           const int64_t* label_off, const int32_t* label_len, const rd_adam* opt, double* loss, int32_t* status);
+int rd_train_reset(rd_ctx* ctx);
+int rd_get_weights(rd_ctx* ctx, float* flat, size_t n);
+/* The loaded model's parameter count (the size of rd_get_weights' and rd_train_grad's arrays). */
+int rd_model_params(rd_ctx* ctx, int64_t* n);
+/* The CTC part of rd_train_grad alone, on caller-supplied softmax rows probs [n][1024][5] float32 (host): grad_z [n][1024][5] is
+ * dL/dz of the batch's mean loss with respect to the last Dense's output z (y = softmax(z)), through Keras's chain
+ * dL/du = p - gamma (u = log(y + eps)), dL/dy = (p - gamma)/(y + eps), dL/dz_j = y_j (dL/dy_j - sum_k y_k dL/dy_k); zero on rows
+ * t >= input_len and on infeasible windows.  Accumulated in fp64, written as fp32.  Any precision setting. */
+int rd_train_ctc_grad(rd_ctx* ctx, const float* probs, int n_windows, const int32_t* input_len, const uint8_t* labels,
+                      const int64_t* label_off, const int32_t* label_len, float* grad_z, double* loss, int32_t* status);
+
 /* ---- multi-GPU start-up: one RCCL broadcast of weights + LM table over xGMI ------------------- */
 /* librccl can be loaded in this process (dlopen + symbol lookup; creates nothing).  Ranks other than the one that draws the
  * unique id call this before the collective ncclCommInitRank, so that a rank without a usable librccl is known to everyone first. */

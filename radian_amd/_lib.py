@@ -88,6 +88,13 @@ SIGNATURES = {
     "rd_ctc_eval": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rd_ctc_probs": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rd_ctc_probs_resident": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rd_train_grad": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rd_train_step": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rd_train_step_resident": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rd_train_reset": (c_i, [c_vp]),
+    "rd_get_weights": (c_i, [c_vp, c_vp, c_sz]),
+    "rd_model_params": (c_i, [c_vp, c_i64p]),
+    "rd_train_ctc_grad": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rd_rccl_probe": (c_i, []),
     "rd_rccl_unique_id": (c_i, [c_vp]),
     "rd_rccl_init": (c_i, [c_vp, c_i, c_i, c_vp]),

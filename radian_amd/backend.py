@@ -745,3 +745,77 @@ class Backend:
     def ctc_probs_resident(self, d_probs, n, input_len, labels, label_len=None, with_greedy=False):
         """the same on n windows of rows already in device memory (rd_ctc_probs_resident; d_probs from dev_alloc)"""
         return self._ctc(self._L.rd_ctc_probs_resident, d_probs, input_len, labels, label_len, with_greedy, n=int(n))
+
+    # ------------------------------------------------------------------ training (radian/train.py: model.fit with ctc_batch_cost and Adam)
+    def _train_args(self, n, input_len, labels, label_len):
+        il = np.ascontiguousarray(input_len, dtype=np.int32).reshape(-1)
+        if il.size != n:
+            raise ValueError(f"{il.size} input lengths for {n} windows")
+        lab, off, ll = _pack_labels(labels, label_len, n)
+        return il, lab, off, ll, np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.int32)
+
+    @staticmethod
+    def _windows(windows):
+        windows = np.ascontiguousarray(windows, dtype=np.float32)
+        if windows.ndim != 2 or windows.shape[1] != CTC_T:
+            raise ValueError(f"windows must be [n_windows, {CTC_T}]")
+        return windows
+
+    def train_grad(self, windows, input_len, labels, label_len=None):
+        """(grad float32 [n_params] in load_weights order, loss float64 [n], status int32 [n]): the gradient of the batch's mean
+        Keras ctc_batch_cost on the loaded weights (rd_train_grad; infeasible windows give zero loss and gradient, the mean divides by n)"""
+        windows = self._windows(windows)
+        n = windows.shape[0]
+        il, lab, off, ll, loss, status = self._train_args(n, input_len, labels, label_len)
+        grad = np.zeros(self._param_count(), dtype=np.float32)
+        self._check(self._L.rd_train_grad(self._h, _p(windows), n, _p(il), _p(lab), _p(off), _p(ll), _p(grad), _p(loss), _p(status)))
+        return grad, loss, status
+
+    def train_step(self, windows, input_len, labels, label_len=None, lr=1e-4, beta1=0.9, beta2=0.999, epsilon=1e-7, resident_n=None):
+        """One Adam step on the batch, in place on the context's weights (rd_train_step; rd_train_step_resident when windows is a
+        device pointer and resident_n its window count).  Returns (loss float64 [n], status int32 [n]) before the update."""
+        opt = _Adam(lr, beta1, beta2, epsilon)
+        if resident_n is not None:
+            n = int(resident_n)
+            il, lab, off, ll, loss, status = self._train_args(n, input_len, labels, label_len)
+            self._check(self._L.rd_train_step_resident(self._h, windows, n, _p(il), _p(lab), _p(off), _p(ll), ctypes.byref(opt), _p(loss),
+                                                       _p(status)))
+            return loss, status
+        windows = self._windows(windows)
+        n = windows.shape[0]
+        il, lab, off, ll, loss, status = self._train_args(n, input_len, labels, label_len)
+        self._check(self._L.rd_train_step(self._h, _p(windows), n, _p(il), _p(lab), _p(off), _p(ll), ctypes.byref(opt), _p(loss), _p(status)))
+        return loss, status
+
+    def train_reset(self):
+        """Adam's moments and step count to zero (rd_train_reset)"""
+        self._check(self._L.rd_train_reset(self._h))
+
+    def get_weights(self):
+        """the context's current weights, flat float32 in load_weights order (rd_get_weights)"""
+        out = np.zeros(self._param_count(), dtype=np.float32)
+        self._check(self._L.rd_get_weights(self._h, _p(out), out.size))
+        return out
+
+    def _param_count(self):
+        """the loaded model's parameter count, from the library (weights may have arrived by rd_clone_artifacts / rd_rccl_bcast_model)"""
+        n = ctypes.c_int64(0)
+        self._check(self._L.rd_model_params(self._h, ctypes.byref(n)))
+        return n.value
+
+    def train_ctc_grad(self, probs, input_len, labels, label_len=None):
+        """(grad_z float32 [n, 1024, 5], loss float64 [n], status int32 [n]): dL/dz of the batch's mean loss on caller-supplied softmax
+        rows probs [n, 1024, 5] (rd_train_ctc_grad: the CTC part of train_grad alone)"""
+        probs = np.ascontiguousarray(probs, dtype=np.float32)
+        if probs.ndim != 3 or probs.shape[1:] != (CTC_T, 5):
+            raise ValueError(f"probs must be [n_windows, {CTC_T}, 5]")
+        n = probs.shape[0]
+        il, lab, off, ll, loss, status = self._train_args(n, input_len, labels, label_len)
+        gz = np.zeros_like(probs)
+        self._check(self._L.rd_train_ctc_grad(self._h, _p(probs), n, _p(il), _p(lab), _p(off), _p(ll), _p(gz), _p(loss), _p(status)))
+        return gz, loss, status
+
+
+class _Adam(ctypes.Structure):
+    """rd_adam (include/radian_hip.h)"""
+    _fields_ = [("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("epsilon", ctypes.c_float)]

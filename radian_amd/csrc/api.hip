@@ -153,6 +153,7 @@ extern "C" int rd_destroy(rd_ctx* ctx)
     rd_rccl_finalize(ctx);
     rd_rpipe_destroy(ctx);
     rd_plan_cache_destroy_internal(ctx);
+    rd_train_destroy(ctx);
     timer_free(ctx->timer_conv);
     timer_free(ctx->timer_decode);
     timer_free(ctx->timer_head);
@@ -395,37 +396,11 @@ void pack_dense_bf3(const float* k, uint16_t* dst)
     }
 }
 
-}  // namespace
-
-extern "C" int rd_load_weights(rd_ctx* ctx, const void* blob, size_t nbytes)
+// every packed image of the flat weights w (load_weights order) into host (model_layout(nb).total floats); sets the split
+// scales of m; returns the floats of w consumed
+size_t model_image(const float* w, int nb, const ModelLayout& L, Model& m, std::vector<float>& host)
 {
-    RD_REQUIRE(ctx && blob, "rd_load_weights: null argument");
-    RD_REQUIRE(nbytes >= sizeof(rd_weights_header), "rd_load_weights: blob too small (%zu bytes)", nbytes);
-    rd_weights_header h;
-    memcpy(&h, blob, sizeof(h));
-    RD_REQUIRE(h.magic == 0x574e4452u, "rd_load_weights: bad magic 0x%08x", h.magic);
-    RD_REQUIRE(h.version == 1, "rd_load_weights: unsupported version %u", h.version);
-    RD_REQUIRE(h.nb_filters == RD_C && h.kernel_size == RD_K && h.relu_units == RD_H && h.n_classes == RD_NCLS,
-               "rd_load_weights: geometry (%u filters, k=%u, %u relu units, %u classes) is not sig2seq.yaml's (256,3,128,5)",
-               h.nb_filters, h.kernel_size, h.relu_units, h.n_classes);
-    RD_REQUIRE(h.n_blocks >= 1 && h.n_blocks <= RD_MAX_BLOCKS, "rd_load_weights: n_blocks %u out of range", h.n_blocks);
-    const int nb = (int)h.n_blocks;
-    size_t expect = (size_t)RD_K * RD_C + RD_C + CONV_PK + RD_C + RD_C + RD_C;
-    expect += (size_t)(nb - 1) * 2 * (CONV_PK + RD_C);
-    expect += D1_PK + RD_H + (size_t)RD_H * RD_NCLS + RD_NCLS;
-    RD_REQUIRE(h.n_floats == expect, "rd_load_weights: header says %u floats, geometry needs %zu", h.n_floats, expect);
-    RD_REQUIRE(nbytes == sizeof(h) + expect * sizeof(float), "rd_load_weights: blob is %zu bytes, expected %zu", nbytes,
-               sizeof(h) + expect * sizeof(float));
-    for (int b = 0; b < nb; b++) RD_REQUIRE(h.dilations[b] >= 1 && h.dilations[b] <= 4096, "rd_load_weights: bad dilation");
-    const float* w = (const float*)((const char*)blob + sizeof(h));
-
-    RD_HIP(hipSetDevice(ctx->device));
-    Model& m = ctx->model;
-    m.loaded = false;
-    m.nblocks = nb;
-    for (int b = 0; b < nb; b++) m.dil[b] = (int)h.dilations[b];
-    ModelLayout L = model_layout(nb);
-    std::vector<float> host(L.total, 0.f);
+    host.assign(L.total, 0.f);
     size_t off = 0;
     for (int b = 0; b < nb; b++) {
         if (b == 0) {
@@ -464,6 +439,41 @@ extern "C" int rd_load_weights(rd_ctx* ctx, const void* blob, size_t nbytes)
     off += RD_H * RD_NCLS;
     memcpy(&host[L.b_d2], w + off, sizeof(float) * RD_NCLS);
     off += RD_NCLS;
+    return off;
+}
+
+}  // namespace
+
+extern "C" int rd_load_weights(rd_ctx* ctx, const void* blob, size_t nbytes)
+{
+    RD_REQUIRE(ctx && blob, "rd_load_weights: null argument");
+    RD_REQUIRE(nbytes >= sizeof(rd_weights_header), "rd_load_weights: blob too small (%zu bytes)", nbytes);
+    rd_weights_header h;
+    memcpy(&h, blob, sizeof(h));
+    RD_REQUIRE(h.magic == 0x574e4452u, "rd_load_weights: bad magic 0x%08x", h.magic);
+    RD_REQUIRE(h.version == 1, "rd_load_weights: unsupported version %u", h.version);
+    RD_REQUIRE(h.nb_filters == RD_C && h.kernel_size == RD_K && h.relu_units == RD_H && h.n_classes == RD_NCLS,
+               "rd_load_weights: geometry (%u filters, k=%u, %u relu units, %u classes) is not sig2seq.yaml's (256,3,128,5)",
+               h.nb_filters, h.kernel_size, h.relu_units, h.n_classes);
+    RD_REQUIRE(h.n_blocks >= 1 && h.n_blocks <= RD_MAX_BLOCKS, "rd_load_weights: n_blocks %u out of range", h.n_blocks);
+    const int nb = (int)h.n_blocks;
+    size_t expect = (size_t)RD_K * RD_C + RD_C + CONV_PK + RD_C + RD_C + RD_C;
+    expect += (size_t)(nb - 1) * 2 * (CONV_PK + RD_C);
+    expect += D1_PK + RD_H + (size_t)RD_H * RD_NCLS + RD_NCLS;
+    RD_REQUIRE(h.n_floats == expect, "rd_load_weights: header says %u floats, geometry needs %zu", h.n_floats, expect);
+    RD_REQUIRE(nbytes == sizeof(h) + expect * sizeof(float), "rd_load_weights: blob is %zu bytes, expected %zu", nbytes,
+               sizeof(h) + expect * sizeof(float));
+    for (int b = 0; b < nb; b++) RD_REQUIRE(h.dilations[b] >= 1 && h.dilations[b] <= 4096, "rd_load_weights: bad dilation");
+    const float* w = (const float*)((const char*)blob + sizeof(h));
+
+    RD_HIP(hipSetDevice(ctx->device));
+    Model& m = ctx->model;
+    m.loaded = false;
+    m.nblocks = nb;
+    for (int b = 0; b < nb; b++) m.dil[b] = (int)h.dilations[b];
+    ModelLayout L = model_layout(nb);
+    std::vector<float> host;
+    const size_t off = model_image(w, nb, L, m, host);
     if (off != expect) {
         rd_set_error("rd_load_weights: internal size mismatch");
         return RD_ERR_ARG;
@@ -471,7 +481,26 @@ extern "C" int rd_load_weights(rd_ctx* ctx, const void* blob, size_t nbytes)
     if (m.storage.reserve(L.total * sizeof(float))) return RD_ERR_NOMEM;
     RD_HIP(hipMemcpy(m.storage.p, host.data(), L.total * sizeof(float), hipMemcpyHostToDevice));
     model_bind(m, L);
+    m.split_stale = false;
+    rd_train_invalidate(ctx);   // Keras restores weights into a fresh optimiser
     m.loaded = true;
+    return RD_OK;
+}
+
+// After training steps (train.hip) only the fp32 images are current: rebuild every image from the trained weights on the host,
+// with rd_load_weights' packers, so that each packing equals a fresh load of the same weights.
+int rd_model_refresh_split(rd_ctx* ctx)
+{
+    Model& m = ctx->model;
+    if (!m.split_stale) return RD_OK;
+    std::vector<float> flat;
+    if (int rc = rd_train_weights_host(ctx, flat)) return rc;
+    const ModelLayout L = model_layout(m.nblocks);
+    std::vector<float> host;
+    model_image(flat.data(), m.nblocks, L, m, host);
+    if (int rc = rd_sync_lanes(ctx)) return rc;
+    RD_HIP(hipMemcpy(m.storage.p, host.data(), L.total * sizeof(float), hipMemcpyHostToDevice));
+    m.split_stale = false;
     return RD_OK;
 }
 
@@ -1626,6 +1655,8 @@ static int artifacts_prepare(rd_ctx* ctx, const BcastHeader& hd)
 
 static void artifacts_arrived(rd_ctx* ctx, const BcastHeader& hd)
 {
+    ctx->model.split_stale = false;
+    rd_train_invalidate(ctx);
     ctx->model.loaded = true;
     if (hd.lm_loaded) ctx->lm.loaded = true;
 }
@@ -1639,6 +1670,7 @@ extern "C" int rd_rccl_bcast_model(rd_ctx* ctx, int root)
     BcastHeader hd = {};
     if (st->rank == root) {
         RD_REQUIRE(ctx->model.loaded, "rd_rccl_bcast_model: root has no weights loaded");
+        if (int rc = rd_model_refresh_split(ctx)) return rc;
         artifacts_header(ctx, hd);
     }
     if (st->scratch.reserve(sizeof(BcastHeader))) return RD_ERR_NOMEM;
@@ -1670,8 +1702,9 @@ extern "C" int rd_clone_artifacts(rd_ctx* dst, rd_ctx* src)
     RD_REQUIRE(dst && src && dst != src, "rd_clone_artifacts: two distinct contexts are needed");
     RD_REQUIRE(src->model.loaded, "rd_clone_artifacts: the source context has no weights loaded");
     BcastHeader hd;
-    artifacts_header(src, hd);
     RD_HIP(hipSetDevice(src->device));
+    if (int rc = rd_model_refresh_split(src)) return rc;
+    artifacts_header(src, hd);
     RD_HIP(hipStreamSynchronize(src->stream));
     RD_HIP(hipSetDevice(dst->device));
     int rc = artifacts_prepare(dst, hd);

@@ -73,6 +73,7 @@ struct Model {
     float* w_d2 = nullptr;      // [128][5] (Keras layout)
     float* b_d2 = nullptr;      // [5]
     DevBuf storage;
+    bool split_stale = false;   // training rewrote the fp32 images (train.hip): the f16x3 / bf16x3 images are rebuilt before their next use
 };
 
 struct LM {
@@ -179,6 +180,7 @@ struct rd_ctx {
     int pipe_group = 4;    // batches per beam-search launch (rd_pipe_config)
     int pipe_lanes = 2;    // forward streams the submitted batches rotate over (rd_pipe_set_lanes)
     void* plan_cache[2] = {nullptr, nullptr};  // PlanCache* for chunk / global reads-level plans
+    void* train = nullptr; // TrainState* (train.hip): created by the first training call, never by inference
 };
 
 // forward.hip
@@ -218,6 +220,13 @@ int rd_gather_windows_dev(hipStream_t st, const float* d_rows, const int64_t* d_
 int rd_assemble_dev(rd_ctx* ctx, const void* d_probs, int nW, int T, int pad, int step, double* d_out, int64_t N,
                     int streamed = 0 /* 1: d_probs is the streamed forward [N][5]; row t is taken from row t */,
                     int in_f16 = 0 /* 1: d_probs rows are _Float16 */);
+
+// train.hip
+void rd_train_invalidate(rd_ctx* ctx);   // new weights arrived: the next training call re-reads them and zeroes the Adam moments
+void rd_train_destroy(rd_ctx* ctx);
+int rd_train_weights_host(rd_ctx* ctx, std::vector<float>& flat);
+// api.hip: rebuilds every packed image from the trained weights when split_stale is set
+int rd_model_refresh_split(rd_ctx* ctx);
 
 // pipe_reads.hip
 bool rd_rpipe_idle(const rd_ctx* ctx);

@@ -1686,6 +1686,7 @@ int rd_forward_tiles_dev(rd_ctx* ctx, const float* d_signal, const TileLists& tl
     }
     if (total_rows == 0) return RD_OK;
     int rc = RD_OK;
+    if (m.split_stale && ctx->precision != 0 && (rc = rd_model_refresh_split(ctx))) return rc;   // trained weights (train.hip)
     FwdLane* L = nullptr;
     if ((rc = rd_lane_get(ctx, lane, &L))) return rc;
     if (total_rows >= INT32_MAX) {

@@ -54,6 +54,34 @@ def synthetic_weights(seed=1234, dilations=DEFAULT_DILATIONS, bias_scale=0.05, h
     return np.concatenate(parts)
 
 
+def keras_init_weights(seed=0, dilations=DEFAULT_DILATIONS):
+    """The distributions of the initial weights Keras gives this graph (model.py:52-89, sig2seq.yaml), drawn from a seeded numpy
+    generator.  Flat float32 in load_weights order.
+      TCN kernels, the matching conv included: he_normal = a normal of stddev sqrt(2 / fan_in) / 0.87962566103423978 truncated
+        at two standard deviations (fan_in = kernel_size * input channels; sig2seq.yaml's kernel_initializer, which keras-tcn
+        hands to its convs);
+      both Dense kernels: glorot_uniform, U(-l, l) with l = sqrt(6 / (fan_in + fan_out));
+      every bias: zeros.
+    TensorFlow's random stream is not reproduced: the same seed gives the same weights here, not TensorFlow's."""
+    rng = np.random.default_rng(seed)
+    parts = []
+    for name, shape in tensor_shapes(dilations):
+        if name.endswith("bias"):
+            w = np.zeros(shape)
+        elif name.startswith("dense"):
+            lim = np.sqrt(6.0 / (shape[0] + shape[1]))
+            w = rng.uniform(-lim, lim, size=shape)
+        else:
+            sd = np.sqrt(2.0 / int(np.prod(shape[:-1]))) / 0.87962566103423978
+            w = rng.normal(0.0, sd, size=shape)
+            bad = np.abs(w) > 2 * sd
+            while bad.any():
+                w[bad] = rng.normal(0.0, sd, size=int(bad.sum()))
+                bad = np.abs(w) > 2 * sd
+        parts.append(w.astype(np.float32).ravel())
+    return np.concatenate(parts)
+
+
 def pack_blob(flat, dilations=DEFAULT_DILATIONS):
     flat = np.ascontiguousarray(flat, dtype=np.float32)
     if flat.size != n_params(dilations):
