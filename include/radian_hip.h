@@ -294,6 +294,41 @@ int rd_pipe_submitted(rd_ctx* ctx, int64_t* submitted);
  * converted correctly rounded and locale-independently (the double Python's float() gives).  No GPU is touched, no context is needed. */
 int rd_lm_json_probe(const char* buf, size_t n, int* k_out);
 int rd_lm_json_fill(const char* buf, size_t n, int k, double* table, int64_t* n_entries, int64_t* n_contexts);
+/* The way back: table [4^k][4] -> that text, in one pass, keys in row order, every number with the shortest digits that convert back to
+ * the same double -- rd_lm_json_fill and json.load (the reference) both return the table bit for bit.  Rows of NaN (absent contexts) are
+ * left out.  RD_ERR_ARG: a row mixes NaN with numbers, or holds an infinity or a negative value; RD_ERR_IO: the file cannot be written. */
+int rd_lm_json_write(const char* path, const double* table, int k, int64_t* n_rows, int64_t* n_bytes);
+
+/* ---- making the RNA model.  The reference ships one model (human protein-coding mRNA) and nothing that builds one.
+ * What a row means is fixed by the reference's lookup (radian/decode.py:42-49,77-96,152-158): labelings are in decode order, 3'->5'
+ * (basecall.py:130 writes the FASTA line reversed), the row of a context is the distribution of the label after it.
+ *
+ * rd_fasta_scan: host only.  One pass over a FASTA text: `>` lines are headers; in sequence lines ACGT, U = T and their lower case are
+ *   codes 0..3, any other letter, `*` and `-` are code 255 (a break: no counted window spans it), white space is skipped and any other
+ *   byte is RD_ERR_FORMAT with record and line in rd_last_error().  field >= 0 keeps only the records whose header (the text after `>`),
+ *   split on `|`, has `value` as field `field` (0-based).  counts = {records read, records kept, codes of the kept records}.  Call once with
+ *   codes = offsets = NULL for the sizes, then with codes[counts[2]] and offsets[counts[1] + 1].
+ *
+ * rd_lm_build: counts every window of k + 1 labels over ACGT of every record -- in decode order, i.e. of the record reversed, unless
+ *   as_written -- then the lower orders as exact marginals, and fills row c from the largest order j <= k whose row of c's last j labels
+ *   has a positive sum s: p[b] = (count[b] + alpha) / (s + 4 alpha), float64, each operation rounded once.  unseen: 0 = that back-off;
+ *   1 = a context without a count at order k gets 0.25 four times; 2 = it gets a row of NaN (a sparse model).  k in 1..13.  The table becomes
+ *   the context's RNA model exactly as if rd_load_lm had been called with it, and is copied to table_out [4^k][4] when that is not NULL
+ *   (counts_out [4^k][4], the order-k counts, likewise).  cut: bytes of input per launch (0: the default); no effect on the result.
+ *   Counters are 32-bit: an input of more than 2^32 - 1 codes is refused (RD_ERR_ARG), as is one without any window to count.
+ *   stats[32]: [0] windows counted, [1] contexts with a count at order k, [2] contexts whose gate opens at r_thr (entropy < r_thr,
+ *   decode.py:90), [3] counted windows whose context is one of those, [4] absent rows, [5] uniform rows, [6] launches of the count,
+ *   [8 + j] rows filled from order j, [24..28] microseconds of the call's stages: host staging, upload, count, marginals + table +
+ *   entropies, download.
+ *
+ * rd_lm_score: the records' windows against the context's RNA model (built or loaded; not a hashed one).  stats[8]: [0] windows,
+ *   [1] those with p(next | context) > 0, [2] with p = 0, [3] whose context the model does not hold, [4] whose context's gate opens at
+ *   r_thr; *nll_sum = sum of -ln p over [1], glibc's ln, added in a fixed order. */
+int rd_fasta_scan(const char* buf, size_t n, int field, const char* value, uint8_t* codes, int64_t* offsets, int64_t* counts);
+int rd_lm_build(rd_ctx* ctx, const uint8_t* codes, const int64_t* offsets, int64_t n_records, int k, int as_written, int unseen, double alpha,
+                double r_thr, int64_t cut, double* table_out, uint32_t* counts_out, int64_t* stats);
+int rd_lm_score(rd_ctx* ctx, const uint8_t* codes, const int64_t* offsets, int64_t n_records, int as_written, double r_thr, int64_t cut,
+                int64_t* stats, double* nll_sum);
 
 /* ---- the step before the hot path, on the HOST's cores: raw signals out of fast5 files, in batches --
  * radian/basecall.py:7,70-76: `get_fast5_file(path).get_reads()`, `read.read_id`, `read.get_raw_data()` (int16 DAQ values, unscaled).

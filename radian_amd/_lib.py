@@ -62,6 +62,10 @@ SIGNATURES = {
     "rd_fast5_read_batch": (c_i, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_i]),
     "rd_lm_json_probe": (c_i, [c_vp, ctypes.c_size_t, ctypes.POINTER(c_i)]),
     "rd_lm_json_fill": (c_i, [c_vp, ctypes.c_size_t, c_i, c_vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    "rd_lm_json_write": (c_i, [ctypes.c_char_p, c_vp, c_i, c_i64p, c_i64p]),
+    "rd_fasta_scan": (c_i, [c_vp, c_sz, c_i, ctypes.c_char_p, c_vp, c_vp, c_vp]),
+    "rd_lm_build": (c_i, [c_vp, c_vp, c_vp, c_i64, c_i, c_i, c_i, c_d, c_d, c_i64, c_vp, c_vp, c_vp]),
+    "rd_lm_score": (c_i, [c_vp, c_vp, c_vp, c_i64, c_i, c_d, c_i64, c_vp, c_dp]),
     "rd_dev_alloc": (c_i, [c_vp, c_sz, ctypes.POINTER(c_vp)]),
     "rd_mem_info": (c_i, [c_vp, ctypes.POINTER(c_sz), ctypes.POINTER(c_sz)]),
     "rd_dev_free": (c_i, [c_vp, c_vp]),

@@ -253,6 +253,51 @@ class Backend:
         self._check(self._L.rd_load_lm(self._h, _p(table), int(k)))
         self.lm_k = k
 
+    UNSEEN = {"backoff": 0, "uniform": 1, "absent": 2}
+
+    @staticmethod
+    def _records(codes, offsets):
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offsets.ndim != 1 or len(offsets) < 1 or codes.ndim != 1 or int(offsets[-1]) != len(codes):
+            raise ValueError("offsets must be [records + 1] and end at len(codes)")
+        return (codes if len(codes) else np.zeros(1, dtype=np.uint8)), offsets
+
+    def build_lm(self, codes, offsets, k, as_written=False, unseen="backoff", pseudocount=0.0, r_threshold=0.5, cut=0,
+                 want_table=True, want_counts=False):
+        """The RNA model of the transcripts in codes / offsets (lm.read_fasta), built on the device and left there as this
+        context's LM, as load_lm would leave it (rd_lm_build; the contract is in include/radian_hip.h).  Returns (table [4^k,4] or
+        None, stats); with want_counts stats["counts"] holds the order-k counts [4^k,4] uint32.  cut: input bytes per launch."""
+        codes, offsets = self._records(codes, offsets)
+        if unseen not in self.UNSEEN:
+            raise ValueError(f"unseen must be one of {sorted(self.UNSEEN)}")
+        big = 1 <= k <= 13
+        table = np.empty((4 ** k, 4), dtype=np.float64) if want_table and big else None
+        counts = np.empty((4 ** k, 4), dtype=np.uint32) if want_counts and big else None
+        st = np.zeros(32, dtype=np.int64)
+        self._check(self._L.rd_lm_build(self._h, _p(codes), _p(offsets), len(offsets) - 1, int(k), 1 if as_written else 0, self.UNSEEN[unseen],
+                                        float(pseudocount), float(r_threshold), int(cut), _p(table), _p(counts), _p(st)))
+        self.lm_k = k
+        stats = {"windows": int(st[0]), "contexts": 4 ** k, "contexts_seen": int(st[1]), "gate_contexts": int(st[2]), "gate_windows": int(st[3]),
+                 "absent_rows": int(st[4]), "uniform_rows": int(st[5]), "launches": int(st[6]),
+                 "stage_us": {name: int(st[24 + i]) for i, name in enumerate(("staging", "upload", "count", "table", "download"))},
+                 "rows_per_order": {j: int(st[8 + j]) for j in range(k, -1, -1) if st[8 + j]}}
+        if counts is not None:
+            stats["counts"] = counts
+        return table, stats
+
+    def score_lm(self, codes, offsets, as_written=False, r_threshold=0.5, cut=0):
+        """Another set of transcripts against this context's LM (rd_lm_score): windows, how many have p > 0 / p = 0 / an absent
+        context / an open gate, and the mean -ln p(next | context) over those with p > 0."""
+        codes, offsets = self._records(codes, offsets)
+        st = np.zeros(8, dtype=np.int64)
+        total = ctypes.c_double(0.0)
+        self._check(self._L.rd_lm_score(self._h, _p(codes), _p(offsets), len(offsets) - 1, 1 if as_written else 0, float(r_threshold), int(cut),
+                                        _p(st), ctypes.byref(total)))
+        n = int(st[1])
+        return {"windows": int(st[0]), "scored": n, "zero": int(st[2]), "absent": int(st[3]), "gate_windows": int(st[4]),
+                "nll_sum": total.value, "mean_nll": total.value / n if n else float("nan")}
+
     def load_lm_absent(self, k):
         """--context-len k with an RNA model whose keys have another length (rd_load_lm_absent): every lookup is the reference's KeyError."""
         self._check(self._L.rd_load_lm_absent(self._h, int(k)))

@@ -513,13 +513,13 @@ int rd_model_halo(const rd_ctx* ctx)
 
 // --------------------------------------------------------------------------------------------- LM
 // doubles of the LM image: table [n][4], entropies [n], then one bit per context ("absent from a sparse model"), padded to doubles
-static size_t lm_image_doubles(int table_order)
+size_t rd_lm_image_doubles(int table_order)
 {
     const size_t n = (size_t)1 << (2 * table_order);
     return n * 5 + (n + 63) / 64;
 }
 
-static void lm_bind(LM& lm)
+void rd_lm_bind(LM& lm)
 {
     const size_t n = (size_t)1 << (2 * lm.table_order);
     lm.table = lm.storage.as<double>();
@@ -527,6 +527,10 @@ static void lm_bind(LM& lm)
     lm.d_missing = (uint32_t*)(lm.table + n * 5);
 }
 
+// The table goes up as it is; what the search needs beside it -- per-context entropy (decode.py:73-76,85-90), and for a row of NaNs (a
+// context that the sparse model does not hold: the reference's dict lookup raises KeyError when the search reaches it, decode.py:83) a
+// zeroed row, a closed gate (entropy +inf) and its bit in the "absent" mask, which the beam search checks for every labeling that enters
+// the beam -- is derived on the device by the pass a model built there goes through as well (rd_lm_finish_device, lmbuild.hip).
 static int load_lm_table(rd_ctx* ctx, const double* table, int table_order, int context_len, int hashed)
 {
     LM& lm = ctx->lm;
@@ -535,46 +539,11 @@ static int load_lm_table(rd_ctx* ctx, const double* table, int table_order, int 
     if (!table) return RD_OK;
     RD_HIP(hipSetDevice(ctx->device));
     const size_t n = (size_t)1 << (2 * table_order);
-    // per-context entropy, decode.py:73-76,85-90 (math.log == glibc log; python sum is left-assoc)
-    // A row of NaNs marks a context that the (sparse) model does not hold: the reference's dict lookup raises KeyError when the
-    // search reaches it (decode.py:83).  Such rows are zeroed on the device, their gate stays closed (entropy +inf) and their bit
-    // is set in the "absent" mask, which the beam search checks for every labeling that enters the beam.
-    std::vector<double> ent(n);
-    std::vector<uint32_t> missing(((n + 63) / 64) * 2, 0u);
-    std::vector<double> patched;
-    size_t n_missing = 0;
-    for (size_t c = 0; c < n && !hashed; c++)
-        if (table[c * 4] != table[c * 4]) {
-            if (patched.empty()) patched.assign(table, table + n * 4);
-            for (int i = 0; i < 4; i++) patched[c * 4 + i] = 0.0;
-            missing[c >> 5] |= 1u << (c & 31);
-            n_missing++;
-        }
-    if (n_missing) table = patched.data();
-    for (size_t c = 0; c < n; c++) {
-        const double* d = table + c * 4;
-        double s = 0.0;
-        bool any = false;
-        for (int i = 0; i < 4; i++)
-            if (d[i] > 0) {
-                double v = d[i] * log(d[i]);
-                s = any ? s + v : v;
-                any = true;
-            }
-        ent[c] = any ? -s : 0.0;
-        if (n_missing && ((missing[c >> 5] >> (c & 31)) & 1u)) ent[c] = INFINITY;
-    }
-    lm.k = context_len;
+    if (lm.storage.reserve(rd_lm_image_doubles(table_order) * sizeof(double))) return RD_ERR_NOMEM;
     lm.table_order = table_order;
-    lm.hashed = hashed;
-    lm.sparse = n_missing ? 1 : 0;
-    if (lm.storage.reserve(lm_image_doubles(table_order) * sizeof(double))) return RD_ERR_NOMEM;
-    lm_bind(lm);
-    RD_HIP(hipMemcpy(lm.table, table, n * 4 * sizeof(double), hipMemcpyHostToDevice));
-    RD_HIP(hipMemcpy(lm.d_entropy, ent.data(), n * sizeof(double), hipMemcpyHostToDevice));
-    RD_HIP(hipMemcpy(lm.d_missing, missing.data(), missing.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    lm.loaded = true;
-    return RD_OK;
+    rd_lm_bind(lm);
+    RD_HIP(hipMemcpyAsync(lm.table, table, n * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    return rd_lm_finish_device(ctx, table_order, context_len, hashed);
 }
 
 extern "C" int rd_load_lm(rd_ctx* ctx, const double* table, int k)
@@ -600,8 +569,8 @@ extern "C" int rd_load_lm_absent(rd_ctx* ctx, int k)
     lm.table_order = k;
     lm.hashed = 0;
     lm.sparse = 1;
-    if (lm.storage.reserve(lm_image_doubles(k) * sizeof(double))) return RD_ERR_NOMEM;
-    lm_bind(lm);
+    if (lm.storage.reserve(rd_lm_image_doubles(k) * sizeof(double))) return RD_ERR_NOMEM;
+    rd_lm_bind(lm);
     RD_HIP(hipMemset(lm.table, 0, n * 4 * sizeof(double)));
     RD_HIP(hipMemset(lm.d_entropy, 0xff, n * sizeof(double)));                  // NaN: `entropy < r_threshold` is false
     RD_HIP(hipMemset(lm.d_missing, 0xff, ((n + 63) / 64) * sizeof(double)));
@@ -1621,7 +1590,7 @@ static void artifacts_header(const rd_ctx* ctx, BcastHeader& hd)
     hd.lm_order = ctx->lm.table_order;
     hd.lm_hashed = ctx->lm.hashed;
     hd.lm_sparse = ctx->lm.sparse;
-    hd.lm_doubles = ctx->lm.loaded ? (int64_t)lm_image_doubles(ctx->lm.table_order) : 0;
+    hd.lm_doubles = ctx->lm.loaded ? (int64_t)rd_lm_image_doubles(ctx->lm.table_order) : 0;
 }
 
 // The receiver's side: geometry and scales from the header, storage reserved and bound; the images are not there yet
@@ -1641,14 +1610,14 @@ static int artifacts_prepare(rd_ctx* ctx, const BcastHeader& hd)
     ctx->lm.loaded = false;
     ctx->lm.gate_valid = false;
     if (hd.lm_loaded) {
-        RD_REQUIRE(hd.lm_order >= 1 && hd.lm_order <= 13 && hd.lm_doubles == (int64_t)lm_image_doubles(hd.lm_order),
+        RD_REQUIRE(hd.lm_order >= 1 && hd.lm_order <= 13 && hd.lm_doubles == (int64_t)rd_lm_image_doubles(hd.lm_order),
                    "artefact header: LM table of order %d with %lld doubles", hd.lm_order, (long long)hd.lm_doubles);
         ctx->lm.k = hd.lm_k;
         ctx->lm.table_order = hd.lm_order;
         ctx->lm.hashed = hd.lm_hashed;
         ctx->lm.sparse = hd.lm_sparse;
         if (ctx->lm.storage.reserve((size_t)hd.lm_doubles * 8)) return RD_ERR_NOMEM;
-        lm_bind(ctx->lm);
+        rd_lm_bind(ctx->lm);
     }
     return RD_OK;
 }

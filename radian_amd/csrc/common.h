@@ -183,6 +183,11 @@ struct rd_ctx {
     void* train = nullptr; // TrainState* (train.hip): created by the first training call, never by inference
 };
 
+// the LM image (api.hip): table [n][4], entropies [n], then one bit per context ("absent from a sparse model"), padded to doubles
+size_t rd_lm_image_doubles(int table_order);
+void rd_lm_bind(LM& lm);   // the pointers of lm into lm.storage, by lm.table_order
+// lmbuild.hip: entropies and absent mask of the table in lm.table (rows of NaN = absent contexts), on the device; marks the model loaded
+int rd_lm_finish_device(rd_ctx* ctx, int table_order, int context_len, int hashed);
 // forward.hip
 int rd_forward_dev(rd_ctx* ctx, const float* d_windows, int nW, int T, float* d_probs, int lane = 0);
 int rd_forward_tiles_dev(rd_ctx* ctx, const float* d_signal, const TileLists& tiles, int64_t total_rows, void* d_probs, int lane = 0,

@@ -16,6 +16,8 @@
 
 #include <charconv>
 #include <cmath>
+#include <cstdio>
+#include <vector>
 
 namespace {
 
@@ -134,5 +136,75 @@ extern "C" int rd_lm_json_fill(const char* buf, size_t n, int k, double* table, 
     }
     *n_entries = entries;
     *n_contexts = distinct;
+    return RD_OK;
+}
+
+// The writer: table [4^k][4] -> the text the reader above (and json.load) takes, one pass, keys in row order.  Every number is written with the
+// shortest digits that convert back to the same double (std::to_chars), so both readers return the table bit for bit.  Rows of NaN -- contexts
+// a sparse model does not hold -- are left out; a NaN beside numbers, an infinity or a negative value is no probability and is refused.
+// *n_rows = keys written, *n_bytes = size of the text.
+extern "C" int rd_lm_json_write(const char* path, const double* table, int k, int64_t* n_rows, int64_t* n_bytes)
+{
+    RD_REQUIRE(path && table && n_rows && n_bytes, "rd_lm_json_write: null argument");
+    RD_REQUIRE(k >= 1 && k <= 13, "rd_lm_json_write: context length %d out of range [1,13]", k);
+    const size_t n = (size_t)1 << (2 * k);
+    for (size_t c = 0; c < n; c++) {
+        const double* d = table + c * 4;
+        const int nan = (int)std::isnan(d[0]) + (int)std::isnan(d[1]) + (int)std::isnan(d[2]) + (int)std::isnan(d[3]);
+        RD_REQUIRE(nan == 0 || nan == 4, "rd_lm_json_write: context %zu mixes NaN with numbers", c);
+        for (int i = 0; i < 4 && !nan; i++)
+            RD_REQUIRE(std::isfinite(d[i]) && !std::signbit(d[i]), "rd_lm_json_write: context %zu holds %g, which is no probability", c, d[i]);
+    }
+    FILE* f = fopen(path, "wb");
+    if (!f) {
+        rd_set_error("rd_lm_json_write: cannot open %s for writing", path);
+        return RD_ERR_IO;
+    }
+    constexpr size_t kEntryMax = 13 + 8 + 4 * 26 + 8;     // key, punctuation, four numbers of at most 24 characters
+    std::vector<char> buf((size_t)1 << 20);
+    size_t fill = 0;
+    int64_t rows = 0, bytes = 0;
+    bool ok = true;
+    buf[fill++] = '{';
+    for (size_t c = 0; c < n && ok; c++) {
+        const double* d = table + c * 4;
+        if (std::isnan(d[0])) continue;
+        if (fill + kEntryMax > buf.size()) {
+            ok = fwrite(buf.data(), 1, fill, f) == fill;
+            bytes += (int64_t)fill;
+            fill = 0;
+        }
+        char* p = buf.data() + fill;
+        if (rows) {
+            *p++ = ',';
+            *p++ = ' ';
+        }
+        *p++ = '"';
+        for (int i = k - 1; i >= 0; i--) *p++ = "ACGT"[(c >> (2 * i)) & 3];
+        *p++ = '"';
+        *p++ = ':';
+        *p++ = ' ';
+        *p++ = '[';
+        for (int i = 0; i < 4; i++) {
+            if (i) {
+                *p++ = ',';
+                *p++ = ' ';
+            }
+            p = std::to_chars(p, p + 26, d[i]).ptr;
+        }
+        *p++ = ']';
+        fill = (size_t)(p - buf.data());
+        rows++;
+    }
+    buf[fill++] = '}';
+    ok = ok && fwrite(buf.data(), 1, fill, f) == fill;
+    bytes += (int64_t)fill;
+    ok = (fclose(f) == 0) && ok;
+    if (!ok) {
+        rd_set_error("rd_lm_json_write: writing %s failed", path);
+        return RD_ERR_IO;
+    }
+    *n_rows = rows;
+    *n_bytes = bytes;
     return RD_OK;
 }

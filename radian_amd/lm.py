@@ -124,3 +124,51 @@ def load_json(path, native=True):
     with open(path, "r") as f:
         raw = json.load(f)
     return table_from_dict(raw)
+
+
+def read_fasta(path, field=None, value=None):
+    """Transcripts for radian_amd.lm_build: FASTA (plain or .gz, by its first two bytes) -> (codes uint8, offsets int64 [kept + 1],
+    info).  The library's scanner does the work (rd_fasta_scan: count pass, fill pass; its rules are in include/radian_hip.h): codes are
+    0..3 for ACGT (U = T, either case) and 255 for anything that breaks a sequence; field / value keep only the records whose header,
+    split on `|`, has `value` in field `field`.  A byte that cannot be part of a sequence raises ValueError naming record and line."""
+    import ctypes
+    import gzip
+    from . import _lib
+    L = _lib.load()
+    with open(path, "rb") as f:
+        raw = f.read()
+    if raw[:2] == b"\x1f\x8b":
+        raw = gzip.decompress(raw)
+    if (field is None) != (value is None):
+        raise ValueError("a header field to match and its value go together")
+    fld = -1 if field is None else int(field)
+    if field is not None and fld < 0:
+        raise ValueError("header fields count from 0")
+    val = None if value is None else str(value).encode()
+    buf = np.frombuffer(raw, dtype=np.uint8) if raw else np.zeros(1, dtype=np.uint8)
+    ptr = ctypes.c_void_p(buf.ctypes.data)
+    counts = np.zeros(3, dtype=np.int64)
+    cp = counts.ctypes.data_as(ctypes.c_void_p)
+    if L.rd_fasta_scan(ptr, len(raw), fld, val, None, None, cp) != 0:
+        raise ValueError(f"{path}: {L.rd_last_error().decode()}")
+    codes = np.empty(max(int(counts[2]), 1), dtype=np.uint8)
+    offsets = np.zeros(int(counts[1]) + 1, dtype=np.int64)
+    if L.rd_fasta_scan(ptr, len(raw), fld, val, codes.ctypes.data_as(ctypes.c_void_p), offsets.ctypes.data_as(ctypes.c_void_p), cp) != 0:
+        raise ValueError(f"{path}: {L.rd_last_error().decode()}")
+    return codes[: int(counts[2])], offsets, {"records": int(counts[0]), "kept": int(counts[1]), "bases": int(counts[2])}
+
+
+def write_json(path, table, k):
+    """table [4^k, 4] float64 -> the reference's model file (rd_lm_json_write: one pass, shortest digits that read back to the same
+    bits, rows of NaN left out).  Returns (keys written, bytes)."""
+    import ctypes
+    import os
+    from . import _lib
+    L = _lib.load()
+    table = np.ascontiguousarray(table, dtype=np.float64)
+    if table.shape != (4 ** k, 4):
+        raise ValueError(f"LM table must be [4^{k},4], got {table.shape}")
+    rows, nbytes = ctypes.c_int64(0), ctypes.c_int64(0)
+    if L.rd_lm_json_write(os.fsencode(path), table.ctypes.data_as(ctypes.c_void_p), int(k), ctypes.byref(rows), ctypes.byref(nbytes)) != 0:
+        raise ValueError(L.rd_last_error().decode())
+    return rows.value, nbytes.value
