@@ -11,12 +11,11 @@
 
 namespace {
 
+// assembled row t of a read whose forward rows start at probs (streamed: row t of the read; windowed: window i at row i*T)
 template <typename IT>
-__global__ __launch_bounds__(256) void assemble_kernel(const IT* __restrict__ probs, int nW, int T, int pad, int step,
-                                                        double* __restrict__ out, int64_t N, int streamed)
+__device__ __forceinline__ void assemble_row(const IT* __restrict__ probs, int64_t t, int nW, int T, int pad, int step, int streamed,
+                                             double* __restrict__ o)
 {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= N) return;
     // windows i with i*step <= t < i*step + rows_i ; rows_i = T except the last (T - pad)
     int64_t lo = t - T + 1;
     int i_min = lo <= 0 ? 0 : (int)((lo + step - 1) / step);
@@ -36,7 +35,15 @@ __global__ __launch_bounds__(256) void assemble_kernel(const IT* __restrict__ pr
         for (int c = 0; c < 5; c++) x[c] = x[c] / norm;
     }
 #pragma unroll
-    for (int c = 0; c < 5; c++) out[t * 5 + c] = x[c];
+    for (int c = 0; c < 5; c++) o[c] = x[c];
+}
+
+template <typename IT>
+__global__ __launch_bounds__(256) void assemble_kernel(const IT* __restrict__ probs, int nW, int T, int pad, int step,
+                                                        double* __restrict__ out, int64_t N, int streamed)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < N) assemble_row(probs, t, nW, T, pad, step, streamed, out + t * 5);
 }
 
 // The same gather for a BATCH of reads in one launch (the pipelined global path): blockIdx.y = read, one record per read.
@@ -46,28 +53,7 @@ __global__ __launch_bounds__(256) void assemble_batch_kernel(const IT* __restric
 {
     const AsmRead rd = reads[blockIdx.y];
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= rd.N) return;
-    const int nW = rd.nW, pad = rd.pad;
-    int64_t lo = t - T + 1;
-    int i_min = lo <= 0 ? 0 : (int)((lo + step - 1) / step);
-    int i_max = (int)(t / step);
-    if (i_max > nW - 1) i_max = nW - 1;
-    if (i_max == nW - 1 && t >= (int64_t)(nW - 1) * step + (T - pad)) i_max--;
-    if (i_min > i_max) i_min = i_max;
-    const IT* base = probs + (size_t)rd.src_row * 5;
-    const IT* r = streamed ? base + (size_t)t * 5 : base + ((size_t)i_min * T + (size_t)(t - (int64_t)i_min * step)) * 5;
-    double x[5];
-#pragma unroll
-    for (int c = 0; c < 5; c++) x[c] = (double)r[c];
-    if (i_max > i_min) {
-        double norm = (((fabs(x[0]) + fabs(x[1])) + fabs(x[2])) + fabs(x[3])) + fabs(x[4]);
-        if (norm == 0.0) norm = 1.0;
-#pragma unroll
-        for (int c = 0; c < 5; c++) x[c] = x[c] / norm;
-    }
-    double* o = out + (size_t)(rd.out_row + t) * 5;
-#pragma unroll
-    for (int c = 0; c < 5; c++) o[c] = x[c];
+    if (t < rd.N) assemble_row(probs + (size_t)rd.src_row * 5, t, rd.nW, T, rd.pad, step, streamed, out + (size_t)(rd.out_row + t) * 5);
 }
 
 }  // namespace

@@ -183,7 +183,12 @@ struct rd_ctx {
     void* train = nullptr; // TrainState* (train.hip): created by the first training call, never by inference
 };
 
-// the LM image (api.hip): table [n][4], entropies [n], then one bit per context ("absent from a sparse model"), padded to doubles
+// model.hip
+size_t rd_model_image_floats(int nblocks);   // floats of a model's device storage: every packed image of every precision
+void rd_model_bind(Model& m);                // the pointers of m into m.storage, by m.nblocks
+int rd_model_refresh_split(rd_ctx* ctx);     // rebuilds every packed image from the trained weights when split_stale is set
+int rd_model_halo(const rd_ctx* ctx);        // receptive field - 1 = (K-1) * 2 * sum(dilations)
+// the LM image: table [n][4], entropies [n], then one bit per context ("absent from a sparse model"), padded to doubles
 size_t rd_lm_image_doubles(int table_order);
 void rd_lm_bind(LM& lm);   // the pointers of lm into lm.storage, by lm.table_order
 // lmbuild.hip: entropies and absent mask of the table in lm.table (rows of NaN = absent contexts), on the device; marks the model loaded
@@ -200,7 +205,6 @@ int rd_masked_stream_acquire(int device, int cus_per_xcd, bool complement, hipSt
 void rd_masked_stream_release(hipStream_t st);   // waits for the stream, then hands it back (never destroyed)
 int rd_sync_lanes(rd_ctx* ctx);                          // every forward stream idle
 int rd_split3_dev(rd_ctx* ctx, const float* d_in, size_t n, uint16_t* d_out);   // fp32 -> [3][n] bf16 bit patterns (hi, mid, lo)
-int rd_model_halo(const rd_ctx* ctx);  // receptive field - 1 = (K-1) * 2 * sum(dilations)
 // decode.hip
 int rd_decode_dev(rd_ctx* ctx, const void* d_probs, int ptype /* 0 f32, 1 f64, 2 f16 rows */, const int64_t* d_seq_off, const int32_t* d_seq_len,
                   const int64_t* d_node_off, const int64_t* d_label_off, int n_seq, int64_t total_nodes, int W, int use_lm,
@@ -230,8 +234,8 @@ int rd_assemble_dev(rd_ctx* ctx, const void* d_probs, int nW, int T, int pad, in
 void rd_train_invalidate(rd_ctx* ctx);   // new weights arrived: the next training call re-reads them and zeroes the Adam moments
 void rd_train_destroy(rd_ctx* ctx);
 int rd_train_weights_host(rd_ctx* ctx, std::vector<float>& flat);
-// api.hip: rebuilds every packed image from the trained weights when split_stale is set
-int rd_model_refresh_split(rd_ctx* ctx);
+// api.hip
+void rd_plan_cache_destroy_internal(rd_ctx* ctx);   // the cached reads-level plans of the synchronous entry points
 
 // pipe_reads.hip
 bool rd_rpipe_idle(const rd_ctx* ctx);

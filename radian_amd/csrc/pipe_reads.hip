@@ -343,10 +343,7 @@ struct RLane {                // per forward lane: staging + descriptors of the 
     hipEvent_t staged = nullptr;
     bool staged_pending = false;
     // the plan the descriptors on the device were built from
-    bool valid = false;
-    int chunk = -1, step = -1, mode = -1, nblocks = -1;
-    int dil[RD_MAX_BLOCKS] = {0};
-    std::vector<int64_t> lens;
+    PlanKey key;
     ReadsPlan plan;
     bool streamed = false;
     TileLists lists;
@@ -618,27 +615,10 @@ int open_slot(rd_ctx* ctx, ReadsPipe* p, int mode, int W, int f16, int use_lm, d
 int lane_plan_build(rd_ctx* ctx, RLane& R, const int64_t* read_off, int n_reads, int chunk, int step, int mode, bool* miss, size_t* n_desc)
 {
     const int halo = rd_model_halo(ctx);
-    std::vector<int64_t> lens(n_reads);
-    for (int r = 0; r < n_reads; r++) lens[r] = read_off[r + 1] - read_off[r];
-    bool hit = R.valid && R.chunk == chunk && R.step == step && R.mode == mode && R.nblocks == ctx->model.nblocks && R.lens == lens;
-    for (int b = 0; hit && b < ctx->model.nblocks; b++) hit = R.dil[b] == ctx->model.dil[b];
-    *miss = !hit;
+    *miss = !R.key.matches(ctx->model, read_off, n_reads, chunk, step, mode, halo);
+    int rc = *miss ? R.key.rebuild(ctx->model, read_off, n_reads, chunk, step, mode, halo, R.plan, &R.streamed, &R.n_desc) : RD_OK;
     *n_desc = R.n_desc;
-    if (hit) return RD_OK;
-    R.valid = false;
-    R.plan = ReadsPlan();
-    int rc = mode == 0 ? plan_reads_chunk(ctx->model, read_off, n_reads, chunk, step, halo, R.plan)
-                       : plan_reads_global(ctx->model, read_off, n_reads, chunk, step, halo, R.plan, &R.streamed);
-    if (rc) return rc;
-    R.n_desc = plan_pad_tiles(R.plan);
-    *n_desc = R.n_desc;
-    R.chunk = chunk;
-    R.step = step;
-    R.mode = mode;
-    R.nblocks = ctx->model.nblocks;
-    for (int b = 0; b < RD_MAX_BLOCKS; b++) R.dil[b] = b < ctx->model.nblocks ? ctx->model.dil[b] : 0;
-    R.lens.swap(lens);
-    return RD_OK;
+    return rc;
 }
 
 // descriptors of a rebuilt plan: into the staging block at hs, one copy to the lane's descriptor buffer on the lane's
@@ -646,43 +626,23 @@ int lane_plan_build(rd_ctx* ctx, RLane& R, const int64_t* read_off, int n_reads,
 int lane_plan_upload(FwdLane* L, RLane& R, char* hs)
 {
     ReadsPlan& P = R.plan;
-    size_t off = 0;
-    for (int li = 0; li < RD_MAX_LAYERS; li++) {
-        R.lists.d[li] = nullptr;
-        R.lists.n[li] = 0;
-        R.lists.rows[li] = 0;
-    }
-    for (int li = 0; li < P.n_layers; li++) {
-        if (P.per_layer || li == 0) {
-            const std::vector<TileDesc>& v = P.tiles[li];
-            if (!v.empty()) memcpy(hs + off * sizeof(TileDesc), v.data(), v.size() * sizeof(TileDesc));
-            R.lists.d[li] = R.tiles.as<TileDesc>() + off;
-            R.lists.n[li] = (int)(v.size() / 4);
-            R.lists.rows[li] = P.rows[li];
-            off += v.size();
-        } else {
-            R.lists.d[li] = R.lists.d[0];
-            R.lists.n[li] = R.lists.n[0];
-            R.lists.rows[li] = R.lists.rows[0];
-        }
-    }
+    const size_t off = plan_fill_lists(P, R.tiles.as<TileDesc>(), (TileDesc*)hs, R.lists);
     if (off) {
         int rc_ = copy_on_stream(R.tiles.p, hs, off * sizeof(TileDesc), L->st);
         if (rc_) return rc_;
     }
     // the host copies of the descriptors are not needed again (the per-sequence vectors of the plan are)
     for (int li = 0; li < RD_MAX_LAYERS; li++) std::vector<TileDesc>().swap(P.tiles[li]);
-    R.valid = true;
+    R.key.valid = true;
     return RD_OK;
 }
 
 // window_bound: the beam search's length bound is checked on chunk_len (rd_pipe_submit_reads, which decodes windows), not on every read
 int check_args(rd_ctx* ctx, const void* signal, const int64_t* read_off, int n_reads, int chunk_len, int step, int W, bool window_bound = false)
 {
-    RD_REQUIRE(ctx && signal && read_off, "null argument");
-    RD_REQUIRE(n_reads >= 1 && chunk_len >= 1, "bad shape");
-    RD_REQUIRE(step >= 1 && step <= chunk_len, "step %d must be in [1, chunk_len]", step);
-    RD_REQUIRE(W >= 1 && W <= rd_decode_max_width(), "beam_width %d out of range", W);
+    // the pipeline's own rules come before the base check's "no weights loaded" (RD_ERR_STATE, its message kept when they hold)
+    const int rc = rd_check_reads_args(ctx, signal, read_off, n_reads, chunk_len, step, W);
+    if (rc == RD_ERR_ARG) return rc;
     RD_REQUIRE(!window_bound || rd_decode_len_ok(W, chunk_len), "chunk_len %d too long for beam width %d (1 + W * rows < 2^29)", chunk_len, W);
     RD_REQUIRE(read_off[0] == 0, "read_off[0] must be 0");
     for (int r = 0; r < n_reads; r++) {
@@ -690,11 +650,7 @@ int check_args(rd_ctx* ctx, const void* signal, const int64_t* read_off, int n_r
         RD_REQUIRE(window_bound || rd_decode_len_ok(W, read_off[r + 1] - read_off[r]), "read %d has %lld samples; beam width %d supports at most %lld (1 + W * rows < 2^29)", r,
                    (long long)(read_off[r + 1] - read_off[r]), W, (long long)((((int64_t)1 << 29) - 2) / W));
     }
-    if (!ctx->model.loaded) {
-        rd_set_error("no weights loaded (rd_load_weights)");
-        return RD_ERR_STATE;
-    }
-    return RD_OK;
+    return rc;
 }
 
 // The batch forwarded on lane `plane` is part of group s: its sequences, rows and reads join it (rows64 / labels_total: the group's totals
@@ -808,7 +764,7 @@ int submit(rd_ctx* ctx, int mode, const float* d_signal, const int16_t* raw, int
             return RD_ERR_STATE;
         }
         if (R.tiles.reserve(d_asm + st_asm + (d_asm + st_asm) / 4 + 256)) {
-            R.valid = false;
+            R.key.invalidate();
             return RD_ERR_NOMEM;
         }
     }
@@ -878,26 +834,25 @@ int submit(rd_ctx* ctx, int mode, const float* d_signal, const int16_t* raw, int
     int n64 = 0;
     if (mode == 1) {
         AsmRead* ar = (AsmRead*)(hs + o_asm);
+        std::vector<ReadRows> rr;
+        rows64 = classify_reads(P.read_win_off.data(), P.valid.data(), n_reads, chunk_len, step, rows64, rr);   // float64 rows go behind the group's previous ones
         for (int r = 0; r < n_reads; r++) {
-            const int nW = P.read_win_off[r + 1] - P.read_win_off[r];
-            const int pad = P.valid[r];
-            const int64_t N = assembled_rows(nW, chunk_len, pad, step);
+            const int64_t N = rr[r].N;
             RD_REQUIRE(N == read_off[r + 1] - read_off[r], "internal: assembled length mismatch for read %d", r);
             RSeq q;
             q.split = 0;
             q.len = (int32_t)N;
-            q.is64 = assembled_is_f64(nW, chunk_len, pad, step);
+            q.is64 = rr[r].is64;
             q.label_off = labels_total;
             if (q.is64) {
                 AsmRead& a = ar[n64++];
                 a.src_row = s->rows + P.read_row[r];
-                a.out_row = rows64;
+                a.out_row = rr[r].row64;
                 a.N = (int32_t)N;
-                a.nW = nW;
-                a.pad = pad;
+                a.nW = P.read_win_off[r + 1] - P.read_win_off[r];
+                a.pad = P.valid[r];
                 a.pad_ = 0;
-                q.off1 = q.off2 = rows64;   // float64 rows go behind the group's previous ones
-                rows64 += N;
+                q.off1 = q.off2 = rr[r].row64;
                 if (N > max_n) max_n = N;
             } else {
                 q.off1 = q.off2 = s->rows + P.read_row[r];   // single coverage: the forward's rows are consecutive time steps
@@ -962,7 +917,7 @@ int submit(rd_ctx* ctx, int mode, const float* d_signal, const int16_t* raw, int
         sig = R.sig.as<float>();
     }
     if (miss && (rc = lane_plan_upload(L, R, hs + o_desc))) {
-        R.valid = false;
+        R.key.invalidate();
         return rc;
     }
     AsmRead* d_ar = (AsmRead*)((char*)R.tiles.p + d_asm);

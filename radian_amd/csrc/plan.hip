@@ -1,6 +1,8 @@
 // plan.hip -- host-side geometry of the reads-level paths: see plan.h.
 #include "plan.h"
 
+#include <string.h>
+
 namespace rdi {
 
 int64_t assembled_rows(int nW, int T, int pad, int step)
@@ -23,6 +25,18 @@ int assembled_is_f64(int nW, int T, int pad, int step)
     return 0;
 }
 
+int64_t classify_reads(const int32_t* win_off, const int32_t* pad, int n_reads, int T, int step, int64_t rows64, std::vector<ReadRows>& out)
+{
+    out.resize(n_reads);
+    for (int r = 0; r < n_reads; r++) {
+        const int nW = win_off[r + 1] - win_off[r];
+        out[r].N = assembled_rows(nW, T, pad[r], step);
+        out[r].is64 = assembled_is_f64(nW, T, pad[r], step);
+        out[r].row64 = rows64;
+        if (out[r].is64) rows64 += out[r].N;
+    }
+    return rows64;
+}
 
 void add_segment(std::vector<TileDesc>& list, int64_t& rows, int64_t seg_row, int64_t src_row, int len, int in_len,
                  int64_t alt_row = 0, int alt_in = INT32_MAX, int alt_res = INT32_MAX)
@@ -156,6 +170,62 @@ size_t plan_pad_tiles(ReadsPlan& P)
             total += v.size();
         }
     return total;
+}
+
+bool PlanKey::matches(const Model& m, const int64_t* read_off, int n_reads, int chunk_, int step_, int mode_, int halo_) const
+{
+    if (!valid || chunk != chunk_ || step != step_ || mode != mode_ || halo != halo_ || nblocks != m.nblocks || read_off[0] != 0 ||
+        lens.size() != (size_t)n_reads)
+        return false;
+    for (int b = 0; b < m.nblocks; b++)
+        if (dil[b] != m.dil[b]) return false;
+    for (int r = 0; r < n_reads; r++)
+        if (lens[r] != read_off[r + 1] - read_off[r]) return false;
+    return true;
+}
+
+int PlanKey::rebuild(const Model& m, const int64_t* read_off, int n_reads, int chunk_, int step_, int mode_, int halo_, ReadsPlan& P, bool* streamed,
+                     size_t* n_desc)
+{
+    invalidate();
+    P = ReadsPlan();
+    int rc = mode_ == 0 ? plan_reads_chunk(m, read_off, n_reads, chunk_, step_, halo_, P) : plan_reads_global(m, read_off, n_reads, chunk_, step_, halo_, P, streamed);
+    if (rc) return rc;
+    *n_desc = plan_pad_tiles(P);
+    chunk = chunk_;
+    step = step_;
+    mode = mode_;
+    halo = halo_;
+    nblocks = m.nblocks;
+    for (int b = 0; b < RD_MAX_BLOCKS; b++) dil[b] = b < m.nblocks ? m.dil[b] : 0;
+    lens.resize(n_reads);
+    for (int r = 0; r < n_reads; r++) lens[r] = read_off[r + 1] - read_off[r];
+    return RD_OK;
+}
+
+size_t plan_fill_lists(const ReadsPlan& P, const TileDesc* d_base, TileDesc* h_dst, TileLists& lists)
+{
+    size_t off = 0;
+    for (int li = 0; li < RD_MAX_LAYERS; li++) {
+        lists.d[li] = nullptr;
+        lists.n[li] = 0;
+        lists.rows[li] = 0;
+    }
+    for (int li = 0; li < P.n_layers; li++) {
+        if (P.per_layer || li == 0) {
+            const std::vector<TileDesc>& v = P.tiles[li];
+            if (!v.empty()) memcpy(h_dst + off, v.data(), v.size() * sizeof(TileDesc));
+            lists.d[li] = d_base + off;
+            lists.n[li] = (int)(v.size() / 4);
+            lists.rows[li] = P.rows[li];
+            off += v.size();
+        } else {
+            lists.d[li] = lists.d[0];
+            lists.n[li] = lists.n[0];
+            lists.rows[li] = lists.rows[0];
+        }
+    }
+    return off;
 }
 
 int pinned_reserve(void** p, size_t* cap, size_t bytes)

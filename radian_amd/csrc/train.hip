@@ -20,6 +20,7 @@
 //   Adam      TF 2.4 ApplyAdam on the flat fp32 master weights (load_weights order), then the fp32 LDS images of the inference
 //             kernels are rewritten on the device; the f16x3 / bf16x3 images are rebuilt on the host when next needed.
 #include "common.h"
+#include "model_params.h"
 #include "../../include/radian_hip.h"
 
 #include <algorithm>
@@ -31,48 +32,10 @@ namespace {
 constexpr int TT = RD_CTC_T;               // rows per window
 constexpr int MAXL = RD_CTC_MAX_LABEL;
 constexpr double EPS = 1e-7;               // Keras backend epsilon()
-constexpr size_t CONV_N = (size_t)RD_K * RD_C * RD_C;
-
-// ------------------------------------------------------------------------------------------------ parameter map (load_weights order)
-struct ParamMap {
-    size_t w0[RD_MAX_BLOCKS], b0[RD_MAX_BLOCKS], w1[RD_MAX_BLOCKS], b1[RD_MAX_BLOCKS], wm, bm, wd1, bd1, wd2, bd2, total;
-};
-
-ParamMap param_map(int nb)
-{
-    ParamMap p = {};
-    size_t o = 0;
-    for (int b = 0; b < nb; b++) {
-        p.w0[b] = o;
-        o += b == 0 ? (size_t)RD_K * RD_C : CONV_N;
-        p.b0[b] = o;
-        o += RD_C;
-        p.w1[b] = o;
-        o += CONV_N;
-        p.b1[b] = o;
-        o += RD_C;
-        if (b == 0) {
-            p.wm = o;
-            o += RD_C;
-            p.bm = o;
-            o += RD_C;
-        }
-    }
-    p.wd1 = o;
-    o += (size_t)RD_C * RD_H;
-    p.bd1 = o;
-    o += RD_H;
-    p.wd2 = o;
-    o += (size_t)RD_H * RD_NCLS;
-    p.bd2 = o;
-    o += RD_NCLS;
-    p.total = o;
-    return p;
-}
 
 // ------------------------------------------------------------------------------------------------ fp32 image <-> flat weights
 // kind 0: raw copy; 1: conv kernel [j][ci][co] <-> [chunk = (ci/16)*3 + j][co][swizzled ci%16]; 2: dense kernel [ci][h] <-> [ci/16][h][swz]
-// (api.hip pack_conv / pack_dense: the same permutation, so an image written here equals rd_load_weights' bit for bit)
+// (the index functions of model.hip's pack_conv / pack_dense, model_params.h: an image written here equals rd_load_weights' bit for bit)
 struct PackSeg {
     int64_t src;
     float* dst;
@@ -83,8 +46,6 @@ struct PackTable {
     PackSeg s[MAX_SEGS];
 };
 
-__device__ __forceinline__ int swz(int row, int k) { return ((((k >> 2) ^ ((row >> 2) & 3)) << 2) | (k & 3)); }
-
 __global__ __launch_bounds__(256) void pack_kernel(float* __restrict__ flat, PackTable tb, int to_flat)
 {
     const PackSeg sg = tb.s[blockIdx.y];
@@ -93,10 +54,10 @@ __global__ __launch_bounds__(256) void pack_kernel(float* __restrict__ flat, Pac
     int64_t d = i;
     if (sg.kind == 1) {
         const int j = i / (RD_C * RD_C), ci = (i / RD_C) % RD_C, co = i % RD_C;
-        d = (int64_t)((ci / 16) * RD_K + j) * RD_C * 16 + co * 16 + swz(co, ci % 16);
+        d = (int64_t)rd_conv_image_row(j, ci, co) * 16 + rd_swz_f32(co, ci % 16);
     } else if (sg.kind == 2) {
         const int ci = i / RD_H, h = i % RD_H;
-        d = (int64_t)(ci / 16) * RD_H * 16 + h * 16 + swz(h, ci % 16);
+        d = (int64_t)rd_dense_image_row(ci, h) * 16 + rd_swz_f32(h, ci % 16);
     }
     if (to_flat) flat[sg.src + i] = sg.dst[d];
     else sg.dst[d] = flat[sg.src + i];
@@ -552,10 +513,10 @@ PackTable pack_table(const Model& m, const ParamMap& pm, int* nseg)
             add(pm.w0[0], m.w_in, RD_K * RD_C, 0);
             add(pm.b0[0], m.b_in, RD_C, 0);
         } else {
-            add(pm.w0[b], m.w_conv[2 * b], (int)CONV_N, 1);
+            add(pm.w0[b], m.w_conv[2 * b], (int)RD_CONV_N, 1);
             add(pm.b0[b], m.b_conv[2 * b], RD_C, 0);
         }
-        add(pm.w1[b], m.w_conv[2 * b + 1], (int)CONV_N, 1);
+        add(pm.w1[b], m.w_conv[2 * b + 1], (int)RD_CONV_N, 1);
         add(pm.b1[b], m.b_conv[2 * b + 1], RD_C, 0);
     }
     add(pm.wm, m.w_match, RD_C, 0);
@@ -572,7 +533,7 @@ int run_pack(rd_ctx* ctx, TrainState* st, int to_flat)
 {
     int nseg = 0;
     PackTable tb = pack_table(ctx->model, st->pm, &nseg);
-    hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((CONV_N + 255) / 256), nseg), dim3(256), 0, ctx->stream, st->master.as<float>(), tb, to_flat);
+    hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((RD_CONV_N + 255) / 256), nseg), dim3(256), 0, ctx->stream, st->master.as<float>(), tb, to_flat);
     RD_HIP(hipGetLastError());
     return RD_OK;
 }

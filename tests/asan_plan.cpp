@@ -6,12 +6,17 @@
 //   * what a sub-tile READS exists: samples src_row .. src_row + in_len inside the batch's signal, rows taken from the stream
 //     (alt_row + t for t >= alt_in / alt_res) inside the tensor;
 //   * per decoded sequence, the rows the decoder will read (off1 / off2 / split / valid) lie inside the tensor.
+// For the plan key and the descriptor layout both reads-level paths share (PlanKey, plan_fill_lists): every TileLists entry lies inside the
+// descriptor block, the lists of a plan do not overlap and hold the plan's descriptors; a key hits only once its owner has validated it, an
+// unchanged batch is a hit, a changed length, dilation, chunk, step, mode, halo or first offset is a miss, and so is everything after
+// invalidate() or a failed rebuild.
 // A violated property is what would be an out-of-bounds access on the GPU.
 #include "../radian_amd/csrc/plan.h"
 
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
+#include <cstring>
 #include <random>
 
 void rd_set_error(const char* fmt, ...) { (void)fmt; }
@@ -65,6 +70,73 @@ static int check_plan(const rdi::ReadsPlan& P, int64_t n_samples, bool chunk_mod
         }
     }
     CHECK((int)P.read_win_off.size() >= 1 && P.read_win_off.back() == P.n_windows, "it %d window offsets", it);
+    return 0;
+}
+
+static int check_key_and_fill(const Model& m, const std::vector<int64_t>& off, int n_reads, int chunk, int step, int halo, int mode, std::mt19937_64& rng, int it)
+{
+    using namespace rdi;
+    PlanKey key;
+    ReadsPlan P;
+    bool streamed = false;
+    size_t n_desc = 0;
+    CHECK(!key.matches(m, off.data(), n_reads, chunk, step, mode, halo), "it %d mode %d: a fresh key hits", it, mode);
+    CHECK(key.rebuild(m, off.data(), n_reads, chunk, step, mode, halo, P, &streamed, &n_desc) == 0, "it %d mode %d: rebuild failed", it, mode);
+    CHECK(!key.matches(m, off.data(), n_reads, chunk, step, mode, halo), "it %d mode %d: a rebuilt key hits before its owner has the descriptors", it, mode);
+    if (check_plan(P, off[n_reads], mode == 0, it)) return 1;
+    // the "device" block and the host destination: n_desc descriptors each, one more behind the destination that must stay untouched
+    std::vector<TileDesc> dev(n_desc + 1), host(n_desc + 1);
+    memset((void*)&host[n_desc], 0x5a, sizeof(TileDesc));
+    const TileDesc guard = host[n_desc];
+    TileLists tl;
+    CHECK(plan_fill_lists(P, dev.data(), host.data(), tl) == n_desc, "it %d mode %d: descriptors written != %zu", it, mode, n_desc);
+    CHECK(memcmp(&host[n_desc], &guard, sizeof(TileDesc)) == 0, "it %d mode %d: written beyond the descriptor block", it, mode);
+    size_t next = 0;
+    for (int li = 0; li < RD_MAX_LAYERS; li++) {
+        if (li >= P.n_layers) {
+            CHECK(tl.d[li] == nullptr && tl.n[li] == 0 && tl.rows[li] == 0, "it %d mode %d layer %d: a list beyond the model's layers", it, mode, li);
+        } else if (P.per_layer || li == 0) {
+            const size_t n = P.tiles[li].size();
+            CHECK(tl.d[li] >= dev.data() && (size_t)(tl.d[li] - dev.data()) + n <= n_desc, "it %d mode %d layer %d: list outside the descriptor block", it, mode, li);
+            const size_t o = (size_t)(tl.d[li] - dev.data());
+            CHECK(o >= next, "it %d mode %d layer %d: list overlaps the one before", it, mode, li);
+            CHECK(n % 8 == 0 && (size_t)tl.n[li] * 4 == n && tl.rows[li] == P.rows[li], "it %d mode %d layer %d: %d workgroup tiles of %zu descriptors", it, mode, li, tl.n[li], n);
+            CHECK(n == 0 || memcmp(&host[o], P.tiles[li].data(), n * sizeof(TileDesc)) == 0, "it %d mode %d layer %d: descriptors differ from the plan's", it, mode, li);
+            next = o + n;
+        } else {
+            CHECK(tl.d[li] == tl.d[0] && tl.n[li] == tl.n[0] && tl.rows[li] == tl.rows[0], "it %d mode %d layer %d: not list 0", it, mode, li);
+        }
+    }
+    CHECK(next == n_desc, "it %d mode %d: lists cover %zu of %zu descriptors", it, mode, next, n_desc);
+    key.valid = true;
+    CHECK(key.matches(m, off.data(), n_reads, chunk, step, mode, halo), "it %d mode %d: the unchanged batch misses", it, mode);
+    std::vector<int64_t> off2 = off;
+    const int r = (int)(rng() % n_reads);
+    for (int q = r + 1; q <= n_reads; q++) off2[q] += 1;   // read r one sample longer
+    CHECK(!key.matches(m, off2.data(), n_reads, chunk, step, mode, halo), "it %d mode %d: a changed length hits", it, mode);
+    off2 = off;
+    off2.push_back(off2.back() + 5);                       // one read more
+    CHECK(!key.matches(m, off2.data(), n_reads + 1, chunk, step, mode, halo), "it %d mode %d: a longer batch hits", it, mode);
+    off2 = off;
+    off2[0] = 1;
+    CHECK(!key.matches(m, off2.data(), n_reads, chunk, step, mode, halo), "it %d mode %d: read_off[0] != 0 hits", it, mode);
+    Model m2 = m;
+    m2.dil[rng() % m.nblocks] += 1;                        // (with the same halo passed: the key holds every dilation)
+    CHECK(!key.matches(m2, off.data(), n_reads, chunk, step, mode, halo), "it %d mode %d: a changed dilation hits", it, mode);
+    m2 = m;
+    m2.nblocks += 1;
+    CHECK(!key.matches(m2, off.data(), n_reads, chunk, step, mode, halo), "it %d mode %d: a changed block count hits", it, mode);
+    CHECK(!key.matches(m, off.data(), n_reads, chunk + 1, step, mode, halo) && !key.matches(m, off.data(), n_reads, chunk, step + 1, mode, halo) &&
+              !key.matches(m, off.data(), n_reads, chunk, step, 1 - mode, halo) && !key.matches(m, off.data(), n_reads, chunk, step, mode, halo + 4),
+          "it %d mode %d: a changed chunk / step / mode / halo hits", it, mode);
+    if (it % 2) {
+        key.invalidate();
+    } else {
+        off2 = off;
+        for (int q = r + 1; q <= n_reads; q++) off2[q] -= off[r + 1] - off[r];   // read r empty: the planner refuses it
+        CHECK(key.rebuild(m, off2.data(), n_reads, chunk, step, mode, halo, P, &streamed, &n_desc) != 0, "it %d mode %d: an empty read was planned", it, mode);
+    }
+    CHECK(!key.matches(m, off.data(), n_reads, chunk, step, mode, halo), "it %d mode %d: a voided key hits", it, mode);
     return 0;
 }
 
@@ -146,6 +218,8 @@ int main(int argc, char** argv)
             if (rdi::plan_reads_global(m, off.data(), n_reads, chunk, step, halo, P, &streamed) != 0) { printf("plan_reads_global failed at %d\n", it); return 1; }
             if (check_plan(P, off[n_reads], false, it)) return 1;
         }
+        for (int mode = 0; mode < 2; mode++)
+            if (check_key_and_fill(m, off, n_reads, chunk, step, halo, mode, rng, it)) return 1;
     }
     printf("%d geometries, %ld tile descriptors, every property holds, no sanitizer report\n", iters, tiles);
     return 0;

@@ -3,7 +3,7 @@
 // rd_rccl_comm_count, the launcher, the transport agreement -- runs with N > 1 on a one-GPU box.  Real RCCL refuses two ranks on one
 // device ("Duplicate GPU detected"); on the 8-GPU node the real library is used and this file plays no part.
 //
-// It implements the seven entry points the product resolves with dlsym (csrc/api.hip rccl_load) with the signatures of
+// It implements the seven entry points the product resolves with dlsym (csrc/rccl.hip rccl_load) with the signatures of
 // /opt/rocm/include/rccl/rccl.h, over a POSIX shared-memory segment named after the unique id: a collective synchronises the caller's
 // stream, stages the data through the segment in chunks with hipMemcpy, and meets the other ranks at a counting barrier.  Semantics
 // (element counts, data types, root, in-place buffers, max-reduction of doubles) are RCCL's; performance is irrelevant.
