@@ -408,7 +408,13 @@ int rd_align_clip_count(const uint8_t* ops, int64_t n_ops, const uint8_t* ref, c
  *                       labels (capacity labels_cap, 0..3 each), label_len
  * Anything else -- a bad checksum, a truncated frame, a missing or malformed feature, a value outside the ranges above -- returns
  * RD_ERR_FORMAT with a message naming the record's index; rd_tfrecord_open returns RD_ERR_IO when the file cannot be read.
- * rd_crc32c: the Castagnoli CRC of a buffer (unmasked; crc32c("123456789") = 0xE3069283). */
+ * rd_crc32c: the Castagnoli CRC of a buffer (unmasked; crc32c("123456789") = 0xE3069283).
+ *   rd_tfrecord_write   the writer of the same shards: n records to path (created or truncated; append != 0: added at its end), record i
+ *                       with signals[i][1024], signal_length input_len[i] (1..1024) and the label_len[i] labels (0..3 each) at
+ *                       labels + label_off[i].  `signal` and `label` are packed float lists, the lengths one int64 each, map entries
+ *                       in key order, both checksums per frame: the bytes depend on the arguments only, and rd_tfrecord_read returns
+ *                       exactly what was written.  RD_ERR_ARG for a value outside those ranges (nothing is written), RD_ERR_IO when
+ *                       the file cannot be written. */
 typedef struct rd_tfrecord rd_tfrecord;
 int rd_tfrecord_open(const char* path, rd_tfrecord** out);
 int rd_tfrecord_open_mem(const void* buf, size_t n, rd_tfrecord** out);
@@ -417,6 +423,40 @@ int rd_tfrecord_count(const rd_tfrecord* f, int64_t* n_records, int64_t* n_label
 int rd_tfrecord_read(const rd_tfrecord* f, int64_t lo, int64_t hi, float* signals, int32_t* input_len, int64_t* label_off,
                      int32_t* label_len, uint8_t* labels, int64_t labels_cap);
 uint32_t rd_crc32c(const void* buf, size_t n);
+int rd_tfrecord_write(const char* path, const float* signals, const int32_t* input_len, const uint8_t* labels, const int64_t* label_off,
+                      const int32_t* label_len, int64_t n, int append);
+
+/* ---- label windows for training shards: fitting alignment of window calls against reference sequences (fit.hip, DESIGN.md
+ * section 14; radian_amd/label_build.py) ------------------------------------------------------------------------------------
+ * Query p = queries[query_off[p] .. query_off[p+1]) (codes 0..3, m <= 1024 of them) is fitted into reference query_ref[p] =
+ * refs[ref_off[r] .. ref_off[r+1]) (codes 0..4; code 4, any letter that is not A C G T, matches nothing, itself included): the
+ * whole query is aligned, the reference before and after the span it covers is free.  Offsets have count + 1 entries and start
+ * at 0.  Many queries may name one reference; it is uploaded once per batch, not once per query.
+ *   Gotoh's three states, int32, reference = rows i, query = columns j, a gap of length L costs gap_open + (L-1) * gap_extend:
+ *     H(i,0) = 0;  H(0,j) = F(0,j) = gap_open + (j-1) * gap_extend (j >= 1);  E(i,0) = F(i,0) = E(0,j) = -inf
+ *     E(i,j) = max(H(i-1,j) + open, E(i-1,j) + extend)      deletion: consumes a reference base
+ *     F(i,j) = max(H(i,j-1) + open, F(i,j-1) + extend)      insertion: consumes a query base
+ *     H(i,j) = max(H(i-1,j-1) + s(r[i-1], q[j-1]), E(i,j), F(i,j))
+ *   score[p]       max over i of H(i,m)
+ *   ref_end[p]     the smallest i that attains it
+ *   ref_start[p]   the row in which the traceback from (ref_end, m) reaches column 0; the traceback has rd_align_batch's fixed
+ *                  preference: diagonal, then E, then F, and inside a gap run extending before closing.  The query's label is
+ *                  the reference's [ref_start, ref_end)
+ *   counts[4p..]   n_match, n_sub, n_ins, n_del of the traced columns (no soft clip)
+ *   status[p]      RD_FIT_OK; RD_FIT_EMPTY (m = 0: nothing to fit, outputs 0); RD_FIT_TOO_LARGE (see budget_bytes)
+ *   budget_bytes   the kernel keeps no per-cell state (what the traceback would find is carried through the recurrence), so the
+ *                  budget caps the call's own device buffer: the references, queries, descriptors and results of one batch.
+ *                  0 = a quarter of the free device memory.  Queries are packed into batches under it in reference order; one
+ *                  whose reference and query alone exceed it is not aligned: status RD_FIT_TOO_LARGE, and the call returns
+ *                  RD_ERR_NOMEM naming it after aligning the others.  Results do not depend on the batches.
+ * A code outside its range, a query longer than 1024 or a reference index outside 0..n_refs-1 is RD_ERR_ARG before anything is
+ * launched.  Synchronous; uses the context's stream. */
+#define RD_FIT_OK 0
+#define RD_FIT_EMPTY 1
+#define RD_FIT_TOO_LARGE 2
+int rd_fit_batch(rd_ctx* ctx, const uint8_t* refs, const int64_t* ref_off, int64_t n_refs, const uint8_t* queries, const int64_t* query_off,
+                 const int32_t* query_ref, int64_t n_queries, int match, int mismatch, int gap_open, int gap_extend, int64_t budget_bytes,
+                 int32_t* score, int32_t* ref_start, int32_t* ref_end, int32_t* counts, int32_t* status);
 
 /* The CTC loss of Keras's ctc_batch_cost and a greedy edit distance, per window, on the GPU (ctc.hip).
  * Window i has RD_CTC_T = 1024 softmax rows y[t][0..4] (A, C, G, T, blank), input_len[i] (1..1024) rows counted, and

@@ -89,6 +89,8 @@ SIGNATURES = {
     "rd_tfrecord_count": (c_i, [c_vp, c_i64p, c_i64p]),
     "rd_tfrecord_read": (c_i, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64]),
     "rd_crc32c": (ctypes.c_uint32, [c_vp, c_sz]),
+    "rd_tfrecord_write": (c_i, [ctypes.c_char_p, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i]),
+    "rd_fit_batch": (c_i, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i, c_i, c_i, c_i, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rd_ctc_eval": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rd_ctc_probs": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rd_ctc_probs_resident": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -56,6 +56,44 @@ ALIGN_OK, ALIGN_CLIP_INDEX_ERROR, ALIGN_EMPTY_AFTER_CLIP, ALIGN_TOO_LARGE = 0, 1
 ALIGN_SCORES = (2, -4, -4, -2)   # radian/align.py:87: globalms(ref, seq, match, mismatch, gap open, gap extend)
 
 
+# rd_fit_batch per-query status (include/radian_hip.h RD_FIT_*)
+FIT_OK, FIT_EMPTY, FIT_TOO_LARGE = 0, 1, 2
+
+
+class FitResult:
+    """Backend.fit_batch's per-query arrays: score, ref_start, ref_end int32 [n], counts int32 [n, 4] (n_match, n_sub, n_ins, n_del of
+    the traced columns), status int32 [n] (FIT_*)."""
+
+    def __init__(self, score, ref_start, ref_end, counts, status):
+        self.score, self.ref_start, self.ref_end, self.counts, self.status = score, ref_start, ref_end, counts, status
+
+
+def _concat_codes(seqs):
+    """list of code sequences (uint8 arrays / bytes / lists) -> (uint8 buffer, int64 offsets [n + 1])"""
+    arrs = [np.ascontiguousarray(np.frombuffer(s, dtype=np.uint8) if isinstance(s, (bytes, bytearray)) else s, dtype=np.uint8).reshape(-1) for s in seqs]
+    off = np.zeros(len(arrs) + 1, dtype=np.int64)
+    np.cumsum([a.size for a in arrs], out=off[1:])
+    buf = np.concatenate(arrs) if off[-1] else np.zeros(1, dtype=np.uint8)
+    return np.ascontiguousarray(buf), off
+
+
+def tfrecord_write(path, signals, input_len, labels, label_len=None, append=False):
+    """Write labelled windows as a TFRecord shard of tf.train.Example records (radian/data.py:9-15), the library's rd_tfrecord_write
+    (host; no GPU).  signals float32 [n, 1024], input_len [n] (signal_length, 1..1024), labels as Backend.ctc_eval takes them."""
+    L = _lib.load()
+    sig = np.ascontiguousarray(signals, dtype=np.float32)
+    n = len(input_len)
+    if sig.size != n * CTC_T:
+        raise ValueError(f"signals must be [{n}, {CTC_T}] float32")
+    il = np.ascontiguousarray(input_len, dtype=np.int32).reshape(-1)
+    buf, off, ll = _pack_labels(labels, label_len, n)
+    rc = L.rd_tfrecord_write(str(path).encode(), _p(sig), _p(il), _p(buf), _p(off), _p(ll), n, 1 if append else 0)
+    if rc == -7:
+        raise OSError(L.rd_last_error().decode("utf-8", "replace"))
+    if rc != 0:
+        raise RadianHipError(f"[rd error {rc}] " + L.rd_last_error().decode("utf-8", "replace"))
+
+
 def _as_bytes(s):
     return s.encode("latin-1") if isinstance(s, str) else bytes(s)
 
@@ -754,6 +792,39 @@ class Backend:
         if with_ops:
             ops_list = [ops[ops_off[p]: ops_off[p] + ops_len[p]].tobytes() for p in range(n)]
         return AlignResult(score, counts, status, ops_list)
+
+    # ------------------------------------------------------------------ label windows: fitting alignment (radian_amd/label_build.py)
+    def fit_batch(self, refs, queries, query_ref, scores=ALIGN_SCORES, budget_bytes=0, allow_too_large=False):
+        """Fit queries[p] (codes 0..3) into refs[query_ref[p]] (codes 0..4, 4 matching nothing): the whole query aligned, the
+        reference free before and after the span, on the GPU (rd_fit_batch).  budget_bytes: device buffer per batch, 0 = a quarter of
+        free memory.  A query that does not fit the budget raises, unless allow_too_large: it then comes back with FIT_TOO_LARGE."""
+        if len(query_ref) != len(queries):
+            raise ValueError(f"{len(query_ref)} reference indices for {len(queries)} queries")
+        rbuf, roff = _concat_codes(refs)
+        qbuf, qoff = _concat_codes(queries)
+        return self.fit_batch_flat(rbuf, roff, qbuf, qoff, query_ref, scores, budget_bytes, allow_too_large)
+
+    def fit_batch_flat(self, rbuf, roff, qbuf, qoff, query_ref, scores=ALIGN_SCORES, budget_bytes=0, allow_too_large=False):
+        """fit_batch on the C ABI's own layout: codes back to back (uint8) and int64 offsets with count + 1 entries"""
+        roff, qoff = np.ascontiguousarray(roff, dtype=np.int64), np.ascontiguousarray(qoff, dtype=np.int64)
+        rbuf, qbuf = np.ascontiguousarray(rbuf, dtype=np.uint8), np.ascontiguousarray(qbuf, dtype=np.uint8)
+        n = len(qoff) - 1
+        if len(query_ref) != n or rbuf.size < roff[-1] or qbuf.size < qoff[-1]:
+            raise ValueError("fit_batch_flat: buffers, offsets and reference indices do not agree")
+        qref = np.ascontiguousarray(query_ref, dtype=np.int32).reshape(-1) if n else np.zeros(1, dtype=np.int32)
+        score, start, end, status = (np.zeros(max(n, 1), dtype=np.int32) for _ in range(4))
+        counts = np.zeros((max(n, 1), 4), dtype=np.int32)
+        m, x, go, ge = (int(v) for v in scores)
+        rc = self._L.rd_fit_batch(self._h, _p(rbuf), _p(roff), len(roff) - 1, _p(qbuf), _p(qoff), _p(qref), n, m, x, go, ge, int(budget_bytes),
+                                  _p(score), _p(start), _p(end), _p(counts), _p(status))
+        if rc != 0 and not (allow_too_large and rc == -4 and (status[:n] == FIT_TOO_LARGE).any()):
+            self._check(rc)
+        return FitResult(score[:n], start[:n], end[:n], counts[:n], status[:n])
+
+    @staticmethod
+    def tfrecord_write(path, signals, input_len, labels, label_len=None, append=False):
+        """rd_tfrecord_write (host): see backend.tfrecord_write"""
+        tfrecord_write(path, signals, input_len, labels, label_len, append)
 
     # ------------------------------------------------------------------ model evaluation on labelled windows (val_loss)
     def _ctc(self, fn, data, input_len, labels, label_len, with_greedy, n=None):

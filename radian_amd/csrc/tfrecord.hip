@@ -18,6 +18,9 @@
 // 1..1024, label_length outside 0..len(label), and a counted label (the first label_length values) that is not exactly
 // 0, 1, 2 or 3.  Values past label_length are padding and are not read (ctc_batch_cost takes the first label_length).
 //
+// The writer (rd_tfrecord_write, radian_amd/label_build.py) emits the same four features -- `signal` and `label` as packed float lists,
+// the two lengths as one int64 each, map entries in key order -- framed with both masked checksums; a shard it wrote reads back exactly.
+//
 // Every access is bounds-checked (tests/asan_tfrecord.cpp feeds truncated and corrupted shards in exact-size buffers).
 // No GPU is touched; the file is part of libradian_hip.so so that the host side stays one ctypes binding.
 #include "common.h"
@@ -292,6 +295,63 @@ void index_shard(const uint8_t* p, size_t n, rd_tfrecord* out)
     }
 }
 
+// ---- writer: one serialised tf.train.Example, built inside out ----
+void put_varint(std::string& o, uint64_t v)
+{
+    while (v >= 0x80) {
+        o.push_back((char)(v | 0x80));
+        v >>= 7;
+    }
+    o.push_back((char)v);
+}
+
+void put_delimited(std::string& o, int field, const std::string& body)
+{
+    put_varint(o, (uint64_t)field << 3 | 2);
+    put_varint(o, body.size());
+    o += body;
+}
+
+// map entry {key = 1, value = 2: Feature {kind_field: list {value = 1, packed}}}; an empty list is an empty list message
+void put_feature(std::string& feats, const char* key, int kind_field, const std::string& packed)
+{
+    std::string list, feature, entry;
+    if (!packed.empty()) put_delimited(list, 1, packed);
+    put_delimited(feature, kind_field, list);
+    put_delimited(entry, 1, key);
+    put_delimited(entry, 2, feature);
+    put_delimited(feats, 1, entry);
+}
+
+void put_example(std::string& out, const float* signal, int64_t signal_length, const uint8_t* label, int64_t label_length)
+{
+    std::string feats, pk;
+    pk.resize((size_t)label_length * 4);
+    for (int64_t k = 0; k < label_length; k++) {
+        const float v = (float)label[k];
+        memcpy(&pk[(size_t)k * 4], &v, 4);
+    }
+    put_feature(feats, kNames[F_LABEL], 2, pk);
+    pk.clear();
+    put_varint(pk, (uint64_t)label_length);
+    put_feature(feats, kNames[F_LABLEN], 3, pk);
+    pk.assign((const char*)signal, (size_t)TF_WIN * 4);
+    put_feature(feats, kNames[F_SIGNAL], 2, pk);
+    pk.clear();
+    put_varint(pk, (uint64_t)signal_length);
+    put_feature(feats, kNames[F_SIGLEN], 3, pk);
+    std::string ex;
+    put_delimited(ex, 1, feats);
+    const uint64_t len = ex.size();
+    char head[12];
+    memcpy(head, &len, 8);
+    const uint32_t lcrc = masked(crc32c((const uint8_t*)head, 8)), dcrc = masked(crc32c((const uint8_t*)ex.data(), ex.size()));
+    memcpy(head + 8, &lcrc, 4);
+    out.append(head, 12);
+    out += ex;
+    out.append((const char*)&dcrc, 4);
+}
+
 template <typename F>
 int guarded(const char* fn, F&& body)
 {
@@ -391,4 +451,41 @@ extern "C" int rd_tfrecord_read(const rd_tfrecord* f, int64_t lo, int64_t hi, fl
     for (int64_t r = lo; r < hi; r++) label_len[r - lo] = (int32_t)(f->label_off[(size_t)r + 1] - f->label_off[(size_t)r]);
     if (nl) memcpy(labels, f->labels.data() + l0, (size_t)nl);
     return RD_OK;
+}
+
+extern "C" int rd_tfrecord_write(const char* path, const float* signals, const int32_t* input_len, const uint8_t* labels, const int64_t* label_off,
+                                 const int32_t* label_len, int64_t n, int append)
+{
+    RD_REQUIRE(path && n >= 0 && (n == 0 || (signals && input_len && label_off && label_len)), "rd_tfrecord_write: bad argument");
+    for (int64_t r = 0; r < n; r++) {
+        RD_REQUIRE(input_len[r] >= 1 && input_len[r] <= TF_WIN, "rd_tfrecord_write: record %lld: signal_length %d is outside 1..%d", (long long)r,
+                   input_len[r], TF_WIN);
+        RD_REQUIRE(label_len[r] >= 0 && label_off[r] >= 0 && (label_len[r] == 0 || labels), "rd_tfrecord_write: record %lld: label_length %d at offset %lld",
+                   (long long)r, label_len[r], (long long)label_off[r]);
+        for (int k = 0; k < label_len[r]; k++)
+            RD_REQUIRE(labels[label_off[r] + k] <= 3, "rd_tfrecord_write: record %lld: label %d is %d, not one of 0, 1, 2, 3", (long long)r, k,
+                       labels[label_off[r] + k]);
+    }
+    return guarded("rd_tfrecord_write", [&]() {
+        FILE* f = fopen(path, append ? "ab" : "wb");
+        if (!f) {
+            rd_set_error("rd_tfrecord_write: cannot open %s: %s", path, strerror(errno));
+            return RD_ERR_IO;
+        }
+        std::string buf;
+        bool ok = true;
+        for (int64_t r = 0; r < n && ok; r++) {
+            put_example(buf, signals + (size_t)r * TF_WIN, input_len[r], labels ? labels + label_off[r] : nullptr, label_len[r]);
+            if (buf.size() >= (4u << 20) || r + 1 == n) {
+                ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
+                buf.clear();
+            }
+        }
+        if (fclose(f) != 0) ok = false;
+        if (!ok) {
+            rd_set_error("rd_tfrecord_write: writing %s failed: %s", path, strerror(errno));
+            return RD_ERR_IO;
+        }
+        return RD_OK;
+    });
 }
