@@ -458,6 +458,60 @@ int rd_fit_batch(rd_ctx* ctx, const uint8_t* refs, const int64_t* ref_off, int64
                  const int32_t* query_ref, int64_t n_queries, int match, int mismatch, int gap_open, int gap_extend, int64_t budget_bytes,
                  int32_t* score, int32_t* ref_start, int32_t* ref_end, int32_t* counts, int32_t* status);
 
+/* ---- reads onto transcripts: minimizer seeds, chains, the best transcript of every read (map.hip, DESIGN.md section 15;
+ * radian_amd/map.py writes align's and label_build's read_ref.tsv with it).  The reference makes that file outside its own tree with
+ * minimap2 (radian/align.py:62,87; radian/accuracy.py parses its SAM).  Forward strand only.  Everything below is integer arithmetic:
+ * results are exact and depend on neither the budget nor the way reads are grouped into calls.
+ * Records (transcripts, reads) are codes back to back with count + 1 offsets that start at 0; codes 0..3 are A C G T, any other value
+ * (rd_fasta_scan's 255, an N) is a break.
+ *   Seeds      a k-mer (RD_MAP_MIN_K <= k <= RD_MAP_MAX_K) exists where k consecutive codes are 0..3; packed 2 bits per base, first base
+ *              highest, into x < 2^2k.  Its hash: x = x * RD_MAP_HASH_C1 mod 2^2k; x ^= x >> k; x = x * RD_MAP_HASH_C2 mod 2^2k; x ^= x >> k
+ *              (both constants odd: the map is invertible on 2k bits).  A segment is a maximal run of codes 0..3 within one record.  In
+ *              every window of w (1..64) consecutive k-mers of one segment the k-mer with the smallest (hash, position) is a minimizer; a
+ *              segment with fewer than w k-mers gives its single minimum.  The minimizers of a record are the distinct positions chosen.
+ *   Index      rd_map_index: for every minimizer of every transcript, hash -> (transcript t, position r); the entries of one hash are in
+ *              ascending (t, r).  Built on the device, kept in the context (a second call replaces it).  A hash with more than max_occ
+ *              entries is not used for seeding.  Fewer than 2^24 transcripts of fewer than 2^24 codes each, fewer than 2^31 codes and
+ *              records together: RD_ERR_ARG otherwise.  stats[8] (nullable): [0] entries, [1] distinct hashes, [2] hashes over max_occ,
+ *              [3] [4] microseconds of the seeding and of the sort.
+ *   Anchors    for every minimizer of a read at q whose hash is usable, one anchor (t, r, q) per index entry; a read's anchors are
+ *              ordered by (t, r, q), and those of one t are a segment.
+ *   Chains     over a segment's anchors in that order, with dq = q_i - q_j, dr = r_i - r_j:
+ *                f(i) = max(k, max_j f(j) + min(dq, dr, k) - gap(|dr - dq|)),   gap(0) = 0, gap(d) = (d * k >> 6) + (floor(log2 d) >> 1)
+ *              j over the RD_MAP_LOOKBACK anchors before i in the segment with 0 < dq <= max_gap, 0 < dr <= max_gap and
+ *              |dr - dq| <= bandwidth.  Anchor i extends the best j when that candidate is greater than k, and of equal candidates the
+ *              nearest j; otherwise it starts a chain of its own.  The chain's first anchor and anchor count travel with f (no
+ *              back-pointer pass).  The segment's chain ends at the smallest i with the largest f; it qualifies with at least
+ *              min_anchors anchors and a score of at least min_score.
+ *   rd_map_batch  per read: status[p] and hits[8p..] = t, score, score2, n_anchors, q0, r0, q1, r1: the transcript of the qualifying
+ *              chain with the largest score (of equal scores the smallest t), the best qualifying score on any other transcript or 0,
+ *              the chain's anchor count, and its first (q0, r0) and last (q1, r1) anchors.  status: RD_MAP_OK; RD_MAP_NO_SEED (no
+ *              anchor: hits 0); RD_MAP_NO_CHAIN (anchors, but no qualifying chain: hits 0); RD_MAP_TOO_LARGE (see budget_bytes).
+ *              RD_MAP_EMPTY_SPAN is never returned here: radian_amd/map.py gives it to a read whose fitted span is empty.
+ *   budget_bytes  bounds the anchor workspace (64 bytes per anchor of a launch + 1 MiB); 0 = a quarter of the free device memory.  A
+ *              count pass and a scan give every read's anchors before anything is allocated; consecutive reads are packed into
+ *              launches under the budget (at most 65535 reads each), a fill pass writes the anchors.  A read that alone exceeds the
+ *              budget is not mapped: status RD_MAP_TOO_LARGE, and the call returns RD_ERR_NOMEM naming it after mapping the others.
+ *              stats[16] (nullable): [0] launches, [1] read minimizers, [2] anchors, [3] segments, [8..13] microseconds of seeds,
+ *              count + scan, fill, sort, segments + chains, best-of-read (asking for them synchronises between the stages).
+ *   rd_map_minimizers  host, no context: the minimizer positions (ascending) and hashes of one record, from the same code the
+ *              device runs.  *n_out is their number; at most cap are written (pos, hash nullable).
+ * RD_ERR_STATE for rd_map_batch without an index.  Synchronous; the context's stream. */
+#define RD_MAP_HASH_C1 0x9E3779B1u
+#define RD_MAP_HASH_C2 0x85EBCA6Bu
+#define RD_MAP_MIN_K 8
+#define RD_MAP_MAX_K 15
+#define RD_MAP_LOOKBACK 64
+#define RD_MAP_OK 0
+#define RD_MAP_NO_SEED 1
+#define RD_MAP_NO_CHAIN 2
+#define RD_MAP_TOO_LARGE 3
+#define RD_MAP_EMPTY_SPAN 4
+int rd_map_minimizers(const uint8_t* codes, int64_t n, int k, int w, int32_t* pos, uint32_t* hash, int64_t cap, int64_t* n_out);
+int rd_map_index(rd_ctx* ctx, const uint8_t* codes, const int64_t* offsets, int64_t n_records, int k, int w, int max_occ, int64_t* stats);
+int rd_map_batch(rd_ctx* ctx, const uint8_t* reads, const int64_t* read_off, int64_t n_reads, int min_anchors, int min_score, int max_gap,
+                 int bandwidth, int64_t budget_bytes, int32_t* status, int32_t* hits, int64_t* stats);
+
 /* The CTC loss of Keras's ctc_batch_cost and a greedy edit distance, per window, on the GPU (ctc.hip).
  * Window i has RD_CTC_T = 1024 softmax rows y[t][0..4] (A, C, G, T, blank), input_len[i] (1..1024) rows counted, and
  * label_len[i] (0..RD_CTC_MAX_LABEL) labels 0..3 at labels + label_off[i].

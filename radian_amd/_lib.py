@@ -91,6 +91,9 @@ SIGNATURES = {
     "rd_crc32c": (ctypes.c_uint32, [c_vp, c_sz]),
     "rd_tfrecord_write": (c_i, [ctypes.c_char_p, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i]),
     "rd_fit_batch": (c_i, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i, c_i, c_i, c_i, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rd_map_minimizers": (c_i, [c_vp, c_i64, c_i, c_i, c_vp, c_vp, c_i64, c_i64p]),
+    "rd_map_index": (c_i, [c_vp, c_vp, c_vp, c_i64, c_i, c_i, c_i, c_vp]),
+    "rd_map_batch": (c_i, [c_vp, c_vp, c_vp, c_i64, c_i, c_i, c_i, c_i, c_i64, c_vp, c_vp, c_vp]),
     "rd_ctc_eval": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rd_ctc_probs": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rd_ctc_probs_resident": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

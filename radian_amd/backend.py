@@ -77,6 +77,38 @@ def _concat_codes(seqs):
     return np.ascontiguousarray(buf), off
 
 
+# rd_map_batch per-read status (include/radian_hip.h RD_MAP_*); MAP_EMPTY_SPAN is given by radian_amd.map, never by the library
+MAP_OK, MAP_NO_SEED, MAP_NO_CHAIN, MAP_TOO_LARGE, MAP_EMPTY_SPAN = 0, 1, 2, 3, 4
+
+
+class MapResult:
+    """Backend.map_batch's per-read arrays, int32 [n] each: status (MAP_*), t, score, score2, n_anchors, q0, r0, q1, r1; stats: the
+    call's counters (launches, minimizers, anchors, segments, stage_us) when asked for."""
+
+    FIELDS = ("t", "score", "score2", "n_anchors", "q0", "r0", "q1", "r1")
+
+    def __init__(self, status, hits, stats=None):
+        self.status, self.hits, self.stats = status, hits, stats
+        for c, name in enumerate(self.FIELDS):
+            setattr(self, name, hits[:, c])
+
+
+def map_minimizers(codes, k, w):
+    """(positions int32, hashes uint32) of the (w,k)-minimizers of one record of codes (0..3; anything else a break): the library's
+    own seed code on the host (rd_map_minimizers; no GPU)."""
+    L = _lib.load()
+    c = np.ascontiguousarray(codes, dtype=np.uint8).reshape(-1)
+    n = c.size
+    buf = c if n else np.zeros(1, dtype=np.uint8)
+    pos = np.zeros(max(n, 1), dtype=np.int32)
+    hs = np.zeros(max(n, 1), dtype=np.uint32)
+    got = ctypes.c_int64(0)
+    rc = L.rd_map_minimizers(_p(buf), n, int(k), int(w), _p(pos), _p(hs), pos.size, ctypes.byref(got))
+    if rc != 0:
+        raise RadianHipError(f"[rd error {rc}] " + L.rd_last_error().decode("utf-8", "replace"))
+    return pos[: got.value].copy(), hs[: got.value].copy()
+
+
 def tfrecord_write(path, signals, input_len, labels, label_len=None, append=False):
     """Write labelled windows as a TFRecord shard of tf.train.Example records (radian/data.py:9-15), the library's rd_tfrecord_write
     (host; no GPU).  signals float32 [n, 1024], input_len [n] (signal_length, 1..1024), labels as Backend.ctc_eval takes them."""
@@ -820,6 +852,49 @@ class Backend:
         if rc != 0 and not (allow_too_large and rc == -4 and (status[:n] == FIT_TOO_LARGE).any()):
             self._check(rc)
         return FitResult(score[:n], start[:n], end[:n], counts[:n], status[:n])
+
+    # ------------------------------------------------------------------ reads onto transcripts (radian_amd/map.py)
+    def map_index(self, codes, offsets, k=14, w=8, max_occ=500):
+        """The seed index of the transcripts in codes / offsets (lm.read_fasta's arrays), built on the device and kept in this context
+        (rd_map_index).  Returns {entries, keys, keys_dropped, stage_us}."""
+        codes, offsets = self._records(codes, offsets)
+        st = np.zeros(8, dtype=np.int64)
+        self._check(self._L.rd_map_index(self._h, _p(codes), _p(offsets), len(offsets) - 1, int(k), int(w), int(max_occ), _p(st)))
+        return {"entries": int(st[0]), "keys": int(st[1]), "keys_dropped": int(st[2]), "stage_us": {"seeds": int(st[3]), "sort": int(st[4])}}
+
+    def map_batch(self, reads, min_anchors=3, min_score=40, max_gap=1000, bandwidth=500, budget_bytes=0, allow_too_large=False, with_stats=False):
+        """Map reads (code sequences 0..3, anything else a break) against the context's index (rd_map_batch): seeds, anchors, chains, the
+        best and second-best transcript of every read.  budget_bytes: the anchor workspace of one launch, 0 = a quarter of free memory.  A
+        read that does not fit it raises, unless allow_too_large: it then comes back with MAP_TOO_LARGE."""
+        buf, off = _concat_codes(reads) if len(reads) else (np.zeros(1, dtype=np.uint8), np.zeros(1, dtype=np.int64))
+        return self.map_batch_flat(buf, off, min_anchors, min_score, max_gap, bandwidth, budget_bytes, allow_too_large, with_stats)
+
+    def map_batch_flat(self, buf, off, min_anchors=3, min_score=40, max_gap=1000, bandwidth=500, budget_bytes=0, allow_too_large=False, with_stats=False):
+        """map_batch on the C ABI's own layout: codes back to back (uint8) and int64 offsets with count + 1 entries"""
+        buf, off = np.ascontiguousarray(buf, dtype=np.uint8), np.ascontiguousarray(off, dtype=np.int64)
+        n = len(off) - 1
+        if buf.size < off[-1]:
+            raise ValueError("map_batch_flat: the offsets end beyond the buffer")
+        if buf.size == 0:
+            buf = np.zeros(1, dtype=np.uint8)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        hits = np.zeros((max(n, 1), 8), dtype=np.int32)
+        st = np.zeros(16, dtype=np.int64) if with_stats else None
+        rc = self._L.rd_map_batch(self._h, _p(buf), _p(off), n, int(min_anchors), int(min_score), int(max_gap), int(bandwidth), int(budget_bytes),
+                                  _p(status), _p(hits), _p(st))
+        if rc != 0 and not (allow_too_large and rc == -4 and (status[:n] == MAP_TOO_LARGE).any()):
+            self._check(rc)
+        stats = None
+        if with_stats:
+            names = ("seeds", "lookup", "fill", "sort", "chain", "best")
+            stats = {"launches": int(st[0]), "minimizers": int(st[1]), "anchors": int(st[2]), "segments": int(st[3]),
+                     "stage_us": {nm: int(st[8 + i]) for i, nm in enumerate(names)}}
+        return MapResult(status[:n], hits[:n], stats)
+
+    @staticmethod
+    def map_minimizers(codes, k, w):
+        """rd_map_minimizers (host): see backend.map_minimizers"""
+        return map_minimizers(codes, k, w)
 
     @staticmethod
     def tfrecord_write(path, signals, input_len, labels, label_len=None, append=False):

@@ -181,6 +181,7 @@ struct rd_ctx {
     int pipe_lanes = 2;    // forward streams the submitted batches rotate over (rd_pipe_set_lanes)
     void* plan_cache[2] = {nullptr, nullptr};  // PlanCache* for chunk / global reads-level plans
     void* train = nullptr; // TrainState* (train.hip): created by the first training call, never by inference
+    void* map = nullptr;   // MapState* (map.hip): the seed index of rd_map_index and the buffers of rd_map_batch
 };
 
 // model.hip
@@ -234,6 +235,8 @@ int rd_assemble_dev(rd_ctx* ctx, const void* d_probs, int nW, int T, int pad, in
 void rd_train_invalidate(rd_ctx* ctx);   // new weights arrived: the next training call re-reads them and zeroes the Adam moments
 void rd_train_destroy(rd_ctx* ctx);
 int rd_train_weights_host(rd_ctx* ctx, std::vector<float>& flat);
+// map.hip
+void rd_map_destroy(rd_ctx* ctx);
 // api.hip
 void rd_plan_cache_destroy_internal(rd_ctx* ctx);   // the cached reads-level plans of the synchronous entry points
 

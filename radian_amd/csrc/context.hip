@@ -141,6 +141,7 @@ extern "C" int rd_destroy(rd_ctx* ctx)
     rd_rpipe_destroy(ctx);
     rd_plan_cache_destroy_internal(ctx);
     rd_train_destroy(ctx);
+    rd_map_destroy(ctx);
     timer_free(ctx->timer_conv);
     timer_free(ctx->timer_decode);
     timer_free(ctx->timer_head);
