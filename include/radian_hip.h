@@ -397,6 +397,51 @@ int64_t rd_align_workspace_bytes(int64_t n, int64_t m);
  * columns of M / X / D / I; ref / read: the characters the D / I columns consume (their order in the alignment). */
 int rd_align_clip_count(const uint8_t* ops, int64_t n_ops, const uint8_t* ref, const uint8_t* read, int32_t* counts, int32_t* status);
 
+/* ---- forced CTC alignment: per-base qualities and signal positions (ctcalign.hip) -------------------------
+ * NO reference behaviour: the reference writes bare FASTA.  The Viterbi alignment of a GIVEN label sequence (labels 0..3 as the
+ * decode returns them; blank is class 4) against the [T,5] probability rows of a sequence; rows and sequences as rd_decode_batch
+ * (seq_off / seq_len in rows, n_seq sequences, float32 or float64 rows), labels of sequence i at labels + label_off[i],
+ * label_len[i] of them.  Per sequence with T rows and L labels c_0 .. c_{L-1}, met EXACTLY (bit for bit), not to a tolerance:
+ *   states    s = 0 .. 2L; even states are blank, odd state 2i+1 is label i
+ *   lp[t][c]  = log((double)P[t][c]) as glibc's log evaluates it (csrc/glibc_math.h, whatever rd_set_decode_math says); log 0 = -inf
+ *   start     V[0][0] = lp[0][4], V[0][1] = lp[0][c_0], every other state -inf
+ *   step      V[t][s] = lp[t][cls(s)] + max(V[t-1][s], V[t-1][s-1], V[t-1][s-2]); the third term only for odd s >= 3 with
+ *             c_i != c_{i-1}.  fp64, one max and one add per cell.  Tie-break: a predecessor replaces the best so far only if
+ *             it is STRICTLY greater, tried in the order s, s-1, s-2
+ *   end       state 2L, or 2L-1 if V[T-1][2L-1] is strictly greater; score[i] = that value
+ *   status[i] RD_CTCALIGN_OK; RD_CTCALIGN_NO_PATH when the score is -inf (L > T, repeats without room for the blank between them,
+ *             zero-probability rows): the per-base outputs are then -1, -1, 0; RD_CTCALIGN_TOO_LARGE (see budget_bytes; same outputs)
+ *   L = 0 is valid (the score of the all-blank path); T = 0 is RD_ERR_ARG
+ *   first_step / last_step [label_off[i] + k]   the first and the last row the traced path spends in state 2k+1 (every row between
+ *             them is in that state)
+ *   qual [label_off[i] + k]   p = max over those rows of (double)P[t][c_k], e = 1 - p; the number of q in 1..50 with
+ *             e <= 10^(-q/10), i.e. min(50, floor(-10 log10 e)) by comparison with a table of 50 doubles (e = 0 gives 50).
+ *             This is the model's own confidence in the base where it was emitted -- NOT calibrated against observed error rates
+ *   budget_bytes   device workspace one launch may take (rd_ctc_align_workspace_bytes per sequence; the 2-bit back-pointers are
+ *             nearly all of it); 0 = a quarter of the free device memory.  Sequences are packed into launches under it in the
+ *             caller's order.  A sequence that alone exceeds it is not aligned: status RD_CTCALIGN_TOO_LARGE, and the call returns
+ *             RD_ERR_NOMEM naming it after aligning the others.  Results do not depend on the launches.
+ * Synchronous; uses the context's stream. */
+#define RD_CTCALIGN_OK 0
+#define RD_CTCALIGN_NO_PATH 1
+#define RD_CTCALIGN_TOO_LARGE 2
+int rd_ctc_align_batch(rd_ctx* ctx, const void* probs, int prob_is_f64, const int64_t* seq_off, const int32_t* seq_len, int n_seq,
+                       const uint8_t* labels, const int64_t* label_off, const int32_t* label_len, int64_t budget_bytes,
+                       int32_t* first_step, int32_t* last_step, uint8_t* qual, double* score, int32_t* status);
+/* Workspace bytes of one sequence of n_rows rows and n_labels labels, each term rounded up to 256:
+ *   64 n_rows (log rows) + 4 n_rows ceil((2 n_labels + 1) / 16) (back-pointers) + 16 n_rows (band columns) */
+int64_t rd_ctc_align_workspace_bytes(int64_t n_rows, int64_t n_labels);
+/* rd_basecall_raw_global plus the forced alignment of every read's labels against the very rows its beam search read (the
+ * assembled float64 rows, or the forward's float32 / f16 rows of a single-coverage read), while they are on the device.  Labels,
+ * label_len and status exactly as rd_basecall_raw_global.  qual_out / first_step_out / last_step_out are indexed as labels_out
+ * (label_off); one row is one raw sample, so the steps are sample indices into the read.  score_out / align_status per read
+ * (a read that came back RD_LEN_MISSING_CONTEXT: RD_CTCALIGN_NO_PATH).  budget_bytes and RD_ERR_NOMEM as rd_ctc_align_batch:
+ * every read is basecalled and every read under the budget aligned before the call returns it. */
+int rd_basecall_raw_global_q(rd_ctx* ctx, const int16_t* raw, const int64_t* read_off, int n_reads, int outlier_clip, int chunk_len,
+                             int step, int beam_width, int use_lm, double s_thr, double r_thr, uint8_t* labels_out,
+                             const int64_t* label_off, int32_t* label_len, int32_t* status, int64_t budget_bytes, uint8_t* qual_out,
+                             int32_t* first_step_out, int32_t* last_step_out, double* score_out, int32_t* align_status);
+
 /* ---- model evaluation on labelled windows: the reference's val_loss (radian/model.py:77-98, radian/train.py:48-79) ------------
  * Labelled windows as the reference stores them: TFRecord shards of tf.train.Example records (radian/data.py:9-31), read on the
  * HOST without TensorFlow (tfrecord.hip).  Framing: u64 length, u32 masked crc32c of it, the data, u32 masked crc32c of the data;

@@ -56,6 +56,24 @@ ALIGN_OK, ALIGN_CLIP_INDEX_ERROR, ALIGN_EMPTY_AFTER_CLIP, ALIGN_TOO_LARGE = 0, 1
 ALIGN_SCORES = (2, -4, -4, -2)   # radian/align.py:87: globalms(ref, seq, match, mismatch, gap open, gap extend)
 
 
+# rd_ctc_align_batch per-sequence status (include/radian_hip.h RD_CTCALIGN_*)
+CTCALIGN_OK, CTCALIGN_NO_PATH, CTCALIGN_TOO_LARGE = 0, 1, 2
+CTCALIGN_STATUS_NAMES = ("ok", "no-path", "too-large")
+
+
+def ctc_align_workspace_bytes(n_rows, n_labels):
+    """device workspace Backend.ctc_align needs for one sequence of n_rows rows and n_labels labels (rd_ctc_align_workspace_bytes)"""
+    return int(_lib.load().rd_ctc_align_workspace_bytes(int(n_rows), int(n_labels)))
+
+
+class CtcAlignResult:
+    """per sequence: first_step / last_step (int32 arrays, one entry per label), qual (uint8 array), score (float), status"""
+    __slots__ = ("first_step", "last_step", "qual", "score", "status")
+
+    def __init__(self, first_step, last_step, qual, score, status):
+        self.first_step, self.last_step, self.qual, self.score, self.status = first_step, last_step, qual, score, status
+
+
 # rd_fit_batch per-query status (include/radian_hip.h RD_FIT_*)
 FIT_OK, FIT_EMPTY, FIT_TOO_LARGE = 0, 1, 2
 
@@ -599,6 +617,34 @@ class Backend:
                                                    _p(labels), _p(label_off), _p(lens), _p(status)))
         return [_labels_of(labels, off[r], lens[r]) for r in range(n)], status
 
+    def basecall_raw_global_q(self, raws, outlier_clip, chunk_len, step, beam_width, use_lm, s_threshold=0.0, r_threshold=0.0,
+                              budget_bytes=0, allow_too_large=False):
+        """basecall_raw_global plus the forced alignment of every read's labels against the rows its beam search read
+        (rd_basecall_raw_global_q): -> (labels per read, status per read, CtcAlignResult with one entry per read; the steps are
+        sample indices into the read).  A read over the alignment budget raises, unless allow_too_large: it then comes back with
+        status CTCALIGN_TOO_LARGE."""
+        flat, off = self._pack_raw(raws)
+        n = len(raws)
+        cap = int(off[-1]) + 1
+        labels = np.zeros(cap, dtype=np.uint8)
+        qual = np.zeros(cap, dtype=np.uint8)
+        first = np.full(cap, -1, dtype=np.int32)
+        last = np.full(cap, -1, dtype=np.int32)
+        lens = np.zeros(n, dtype=np.int32)
+        status = np.zeros(n, dtype=np.int32)
+        score = np.zeros(n, dtype=np.float64)
+        ast = np.zeros(n, dtype=np.int32)
+        label_off = np.ascontiguousarray(off[:-1])
+        rc = self._L.rd_basecall_raw_global_q(self._h, _p(flat), _p(off), n, int(outlier_clip), int(chunk_len), int(step), int(beam_width),
+                                              1 if use_lm else 0, float(s_threshold), float(r_threshold), _p(labels), _p(label_off), _p(lens),
+                                              _p(status), int(budget_bytes), _p(qual), _p(first), _p(last), _p(score), _p(ast))
+        if rc != 0 and not (allow_too_large and rc == -4 and (ast == CTCALIGN_TOO_LARGE).any()):
+            self._check(rc)
+        ln = [max(int(x), 0) for x in lens]
+        res = CtcAlignResult([first[off[r]: off[r] + ln[r]].copy() for r in range(n)], [last[off[r]: off[r] + ln[r]].copy() for r in range(n)],
+                             [qual[off[r]: off[r] + ln[r]].copy() for r in range(n)], score, ast)
+        return [_labels_of(labels, off[r], lens[r]) for r in range(n)], status, res
+
     # ------------------------------------------------------------------ device-resident (bench)
     def dev_alloc(self, nbytes):
         p = ctypes.c_void_p()
@@ -824,6 +870,43 @@ class Backend:
         if with_ops:
             ops_list = [ops[ops_off[p]: ops_off[p] + ops_len[p]].tobytes() for p in range(n)]
         return AlignResult(score, counts, status, ops_list)
+
+    # ------------------------------------------------------------------ forced CTC alignment
+    def ctc_align(self, mats, seq_off, seq_len, labels, budget_bytes=0, allow_too_large=False):
+        """Forced (Viterbi) CTC alignment of labels[i] (codes 0..3) against rows seq_off[i] .. + seq_len[i] of mats ([rows,5] float32 or
+        float64), on the GPU (rd_ctc_align_batch; the contract is in include/radian_hip.h).  budget_bytes: device workspace per launch,
+        0 = a quarter of free memory.  A sequence that does not fit it raises, unless allow_too_large: status CTCALIGN_TOO_LARGE."""
+        mats = np.ascontiguousarray(mats)
+        if mats.dtype not in (np.float32, np.float64):
+            raise TypeError("probabilities must be float32 or float64")
+        seq_off = np.ascontiguousarray(seq_off, dtype=np.int64)
+        seq_len = np.ascontiguousarray(seq_len, dtype=np.int32)
+        n = int(seq_len.shape[0])
+        if len(labels) != n:
+            raise ValueError(f"{len(labels)} label sequences for {n} sequences")
+        if n and int((seq_off + seq_len).max()) > mats.reshape(-1, 5).shape[0]:
+            raise ValueError("a sequence reaches past the rows given")
+        labs = [np.ascontiguousarray(x, dtype=np.uint8).ravel() for x in labels]
+        label_len = np.array([x.shape[0] for x in labs], dtype=np.int32)
+        label_off = np.zeros(n, dtype=np.int64)
+        if n:
+            label_off[1:] = np.cumsum(label_len[:-1].astype(np.int64))
+        tot = int(label_len.astype(np.int64).sum())
+        lbuf = np.zeros(tot + 1, dtype=np.uint8)
+        if tot:
+            lbuf[:tot] = np.concatenate(labs)
+        first = np.full(tot + 1, -1, dtype=np.int32)
+        last = np.full(tot + 1, -1, dtype=np.int32)
+        qual = np.zeros(tot + 1, dtype=np.uint8)
+        score = np.zeros(n, dtype=np.float64)
+        status = np.zeros(n, dtype=np.int32)
+        rc = self._L.rd_ctc_align_batch(self._h, _p(mats), 1 if mats.dtype == np.float64 else 0, _p(seq_off), _p(seq_len), n, _p(lbuf),
+                                        _p(label_off), _p(label_len), int(budget_bytes), _p(first), _p(last), _p(qual), _p(score), _p(status))
+        if rc != 0 and not (allow_too_large and rc == -4 and (status == CTCALIGN_TOO_LARGE).any()):
+            self._check(rc)
+        cut = [(int(label_off[i]), int(label_off[i] + label_len[i])) for i in range(n)]
+        return CtcAlignResult([first[a:b].copy() for a, b in cut], [last[a:b].copy() for a, b in cut], [qual[a:b].copy() for a, b in cut],
+                              score, status)
 
     # ------------------------------------------------------------------ label windows: fitting alignment (radian_amd/label_build.py)
     def fit_batch(self, refs, queries, query_ref, scores=ALIGN_SCORES, budget_bytes=0, allow_too_large=False):

@@ -4,6 +4,7 @@
 #include "plan.h"
 #include "../../include/radian_hip.h"
 
+#include <math.h>
 #include <string.h>
 
 using namespace rdi;
@@ -85,10 +86,22 @@ int prepare_seq_meta(rd_ctx* ctx, const int64_t* seq_off, const int64_t* seq_off
     return RD_OK;
 }
 
+// the forced alignment of every decoded sequence against the rows its beam search read (ctcalign.hip): per-base outputs indexed as
+// labels_out (label_off), score and status per sequence
+struct AlignOut {
+    int64_t budget;
+    int32_t *first, *last;
+    uint8_t* qual;
+    double* score;
+    int32_t* status;
+    bool too_large = false;   // some sequence came back RD_CTCALIGN_TOO_LARGE (the call goes on and returns RD_ERR_NOMEM at its end)
+};
+
 // decode sequences over device rows and deliver labels to host buffers
 int decode_and_fetch(rd_ctx* ctx, const void* d_probs, int is_f64, const int64_t* seq_off, const int32_t* seq_len, int n_seq,
                      int W, int use_lm, double s_thr, double r_thr, uint8_t* labels_out, const int64_t* label_off,
-                     int32_t* label_len, double* best_score, const int64_t* seq_off2 = nullptr, const int32_t* split = nullptr)
+                     int32_t* label_len, double* best_score, const int64_t* seq_off2 = nullptr, const int32_t* split = nullptr,
+                     AlignOut* ao = nullptr)
 {
     if (n_seq == 0) return RD_OK;
     SeqMeta sm;
@@ -124,6 +137,24 @@ int decode_and_fetch(rd_ctx* ctx, const void* d_probs, int is_f64, const int64_t
             return RD_ERR_STATE;
         }
         if (label_len[i]) memcpy(labels_out + label_off[i], hl.data() + lab_off[i], (size_t)label_len[i]);
+    }
+    if (ao) {
+        // the rows and the labels are still where the search left them
+        RD_REQUIRE(!seq_off2, "internal: no forced alignment of sequences with two source regions");
+        std::vector<int32_t> al(n_seq);
+        for (int i = 0; i < n_seq; i++) al[i] = label_len[i] < 0 ? 0 : label_len[i];
+        rc = rd_ctc_align_dev(ctx, ds, d_probs, is_f64, seq_off, seq_len, n_seq, d_labels, lab_off.data(), al.data(), ao->budget, ao->first, ao->last,
+                              ao->qual, label_off, ao->score, ao->status);
+        bool tl = false;
+        for (int i = 0; i < n_seq; i++) {
+            tl |= ao->status[i] == RD_CTCALIGN_TOO_LARGE;
+            if (label_len[i] < 0) {   // no labels (RD_LEN_MISSING_CONTEXT): nothing was aligned
+                ao->status[i] = RD_CTCALIGN_NO_PATH;
+                ao->score[i] = -INFINITY;
+            }
+        }
+        if (rc == RD_ERR_NOMEM && tl) ao->too_large = true;
+        else if (rc) return rc;
     }
     return RD_OK;
 }
@@ -263,7 +294,7 @@ extern "C" int rd_forward_resident(rd_ctx* ctx, const float* d_windows, int n_wi
 // read_off (nullable): the reads' samples, which the assembled lengths must equal.
 static int global_finish(rd_ctx* ctx, const void* d_probs, int f16, bool streamed, const int32_t* win_off, const int32_t* pad, const int64_t* src_row,
                          const int64_t* read_off, int n_reads, int chunk_len, int step, int beam_width, int use_lm, double s_thr, double r_thr,
-                         uint8_t* labels_out, const int64_t* label_off, int32_t* label_len)
+                         uint8_t* labels_out, const int64_t* label_off, int32_t* label_len, AlignOut* ao = nullptr /* per read, as label_len */)
 {
     std::vector<ReadRows> rr;
     const int64_t rows64 = classify_reads(win_off, pad, n_reads, chunk_len, step, 0, rr);
@@ -290,11 +321,26 @@ static int global_finish(rd_ctx* ctx, const void* d_probs, int f16, bool streame
                 idx.push_back(r);
             }
         if (idx.empty()) continue;
-        std::vector<int32_t> ll(idx.size());
+        std::vector<int32_t> ll(idx.size()), ast(idx.size());
+        std::vector<double> asc(idx.size());
+        AlignOut pa;
+        if (ao) {
+            pa = *ao;
+            pa.score = asc.data();
+            pa.status = ast.data();
+        }
         rc = decode_and_fetch(ctx, pass == 0 ? (const void*)ctx->ws_mat.p : d_probs, pass == 0 ? 1 : (f16 ? 2 : 0), so.data(), sl.data(),
-                              (int)idx.size(), beam_width, use_lm, s_thr, r_thr, labels_out, lo.data(), ll.data(), nullptr);
+                              (int)idx.size(), beam_width, use_lm, s_thr, r_thr, labels_out, lo.data(), ll.data(), nullptr, nullptr, nullptr,
+                              ao ? &pa : nullptr);
         if (rc) return rc;
-        for (size_t i = 0; i < idx.size(); i++) label_len[idx[i]] = ll[i];
+        for (size_t i = 0; i < idx.size(); i++) {
+            label_len[idx[i]] = ll[i];
+            if (ao) {
+                ao->score[idx[i]] = asc[i];
+                ao->status[idx[i]] = ast[i];
+                ao->too_large |= pa.too_large;
+            }
+        }
     }
     return RD_OK;
 }
@@ -495,9 +541,9 @@ extern "C" int rd_basecall_reads_chunk(rd_ctx* ctx, const float* signal, const i
                                             label_len);
 }
 
-extern "C" int rd_basecall_reads_global_resident(rd_ctx* ctx, const float* d_signal, const int64_t* read_off, int n_reads,
-                                                 int chunk_len, int step, int beam_width, int use_lm, double s_thr, double r_thr,
-                                                 uint8_t* labels_out, const int64_t* label_off, int32_t* label_len)
+static int reads_global_resident(rd_ctx* ctx, const float* d_signal, const int64_t* read_off, int n_reads, int chunk_len, int step, int beam_width,
+                                 int use_lm, double s_thr, double r_thr, uint8_t* labels_out, const int64_t* label_off, int32_t* label_len,
+                                 AlignOut* ao)
 {
     int rc = rd_check_reads_args(ctx, d_signal, read_off, n_reads, chunk_len, step, beam_width);
     if (rc) return rc;
@@ -513,7 +559,15 @@ extern "C" int rd_basecall_reads_global_resident(rd_ctx* ctx, const float* d_sig
     rc = rd_forward_tiles_dev(ctx, d_signal, *tl, P->total_rows, ctx->ws_probs.p, 0, f16);
     if (rc) return rc;
     return global_finish(ctx, ctx->ws_probs.p, f16, streamed, P->read_win_off.data(), P->valid.data(), P->read_row.data(), read_off, n_reads, chunk_len,
-                         step, beam_width, use_lm, s_thr, r_thr, labels_out, label_off, label_len);
+                         step, beam_width, use_lm, s_thr, r_thr, labels_out, label_off, label_len, ao);
+}
+
+extern "C" int rd_basecall_reads_global_resident(rd_ctx* ctx, const float* d_signal, const int64_t* read_off, int n_reads,
+                                                 int chunk_len, int step, int beam_width, int use_lm, double s_thr, double r_thr,
+                                                 uint8_t* labels_out, const int64_t* label_off, int32_t* label_len)
+{
+    return reads_global_resident(ctx, d_signal, read_off, n_reads, chunk_len, step, beam_width, use_lm, s_thr, r_thr, labels_out, label_off, label_len,
+                                 nullptr);
 }
 
 extern "C" int rd_basecall_reads_global(rd_ctx* ctx, const float* signal, const int64_t* read_off, int n_reads, int chunk_len,
@@ -591,4 +645,23 @@ extern "C" int rd_basecall_raw_global(rd_ctx* ctx, const int16_t* raw, const int
         RD_REQUIRE(status[r] != 2, "rd_basecall_raw_global: read %d is empty (the caller skips empty reads, basecall.py:77-82)", r);
     return rd_basecall_reads_global_resident(ctx, ctx->ws_in.as<float>(), read_off, n_reads, chunk_len, step, beam_width, use_lm,
                                              s_thr, r_thr, labels_out, label_off, label_len);
+}
+
+// rd_basecall_raw_global plus, per read, the forced alignment of its labels against the rows its beam search read (ctcalign.hip)
+extern "C" int rd_basecall_raw_global_q(rd_ctx* ctx, const int16_t* raw, const int64_t* read_off, int n_reads, int outlier_clip,
+                                        int chunk_len, int step, int beam_width, int use_lm, double s_thr, double r_thr,
+                                        uint8_t* labels_out, const int64_t* label_off, int32_t* label_len, int32_t* status, int64_t budget_bytes,
+                                        uint8_t* qual_out, int32_t* first_step_out, int32_t* last_step_out, double* score_out, int32_t* align_status)
+{
+    RD_REQUIRE(qual_out && first_step_out && last_step_out && score_out && align_status, "rd_basecall_raw_global_q: null output");
+    RD_REQUIRE(budget_bytes >= 0, "rd_basecall_raw_global_q: negative budget");
+    int rc = normalise_upload(ctx, raw, read_off, n_reads, outlier_clip, status);
+    if (rc) return rc;
+    for (int r = 0; r < n_reads; r++)
+        RD_REQUIRE(status[r] != 2, "rd_basecall_raw_global_q: read %d is empty (the caller skips empty reads, basecall.py:77-82)", r);
+    AlignOut ao{budget_bytes, first_step_out, last_step_out, qual_out, score_out, align_status};
+    rc = reads_global_resident(ctx, ctx->ws_in.as<float>(), read_off, n_reads, chunk_len, step, beam_width, use_lm, s_thr, r_thr, labels_out, label_off,
+                               label_len, &ao);
+    if (rc) return rc;
+    return ao.too_large ? RD_ERR_NOMEM : RD_OK;   // (rd_last_error names the first read over the budget)
 }

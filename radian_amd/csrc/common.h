@@ -169,6 +169,7 @@ struct rd_ctx {
     DevBuf ws_wide, ws_wide_slot;   // beam widths above 51 (decode_wide.hip): per-sequence scratch block, per-trie-node slot map
     DevBuf ws_align;                // rd_align_batch (align.hip): one batch of pairs, sized exactly to the batch under the caller's budget
     DevBuf ws_ctc;                  // rd_ctc_* (ctc.hip): window descriptors, labels, per-window results, greedy labels
+    DevBuf ws_calign;               // rd_ctc_align_* (ctcalign.hip): a launch's descriptors and results (its DP workspace is ws_align, under the budget)
     int64_t trie_budget = (int64_t)24 << 30;   // bytes of beam-search workspace one launch may ask for (rd_plan_trie_runs; rd_set_trie_budget)
     // pinned host staging
     void* h_stage = nullptr;
@@ -231,6 +232,13 @@ int rd_assemble_dev(rd_ctx* ctx, const void* d_probs, int nW, int T, int pad, in
                     int streamed = 0 /* 1: d_probs is the streamed forward [N][5]; row t is taken from row t */,
                     int in_f16 = 0 /* 1: d_probs rows are _Float16 */);
 
+// ctcalign.hip: forced CTC alignment of sequences whose rows (ptype 0 f32, 1 f64, 2 f16) and labels are on the device already; every
+// array argument but d_probs / d_labels is a host array.  Sequence i: rows seq_off[i] .. + seq_len[i] of d_probs, label_len[i] labels at
+// d_labels + dlab_off[i]; its per-base results go to first_step / last_step / qual + out_off[i].  Launches on st and waits for it.
+// Contract, budget and return value as rd_ctc_align_batch (include/radian_hip.h).
+int rd_ctc_align_dev(rd_ctx* ctx, hipStream_t st, const void* d_probs, int ptype, const int64_t* seq_off, const int32_t* seq_len, int n_seq,
+                     const uint8_t* d_labels, const int64_t* dlab_off, const int32_t* label_len, int64_t budget_bytes, int32_t* first_step,
+                     int32_t* last_step, uint8_t* qual, const int64_t* out_off, double* score, int32_t* status);
 // train.hip
 void rd_train_invalidate(rd_ctx* ctx);   // new weights arrived: the next training call re-reads them and zeroes the Adam moments
 void rd_train_destroy(rd_ctx* ctx);
