@@ -127,6 +127,16 @@ int rd_set_decode_partition(rd_ctx* ctx, int cus_per_xcd);
  * and labelings are identical unless two labelings tie within that distance; the beam search runs 10 % (peaked rows,
  * thousands of sequences) to 35 % (flat rows, few sequences) faster). */
 int rd_set_decode_math(rd_ctx* ctx, int mode);
+/* Window heads of the chunk-mode reads paths (the rows of windows i >= 1 that see their window's zero left-padding): 1 (default) =
+ * evaluated as packed classes of rows that leave out the conv taps lying wholly in the padding, 0 = as tiles of their own that
+ * multiply the padding's zeros.  No effect on results (equal under IEEE comparison: a left-out product is fma(0, w, acc); the sign
+ * of a zero may differ).  Packing applies to the exact-fp32 mode with weights whose conv kernels are finite and whose conv biases
+ * are not -0.0, as rd_load_weights saw them: after a training step (rd_train_*) the context runs head tiles until weights are
+ * loaded again.  rd_head_pack_active says whether the context's next chunk-mode forward will pack (1 / 0); rd_head_pack_tiles how
+ * many packed workgroup tiles the context's latest forward launched (0: it ran head tiles, or had no heads). */
+int rd_set_head_pack(rd_ctx* ctx, int on);
+int rd_head_pack_active(rd_ctx* ctx);
+int64_t rd_head_pack_tiles(rd_ctx* ctx);
 
 /* ---- the five seams, host-pointer form ----------------------------------------------------- */
 /* sig_model.predict(windows) -- radian/basecall.py:91,93.

@@ -413,6 +413,19 @@ class Backend:
         """block 0's first conv inside its second conv's kernel (default) or as a kernel of its own (rd_set_conv_fuse); same bits"""
         self._check(self._L.rd_set_conv_fuse(self._h, 1 if on else 0))
 
+    def set_head_pack(self, on):
+        """window heads of the chunk-mode reads paths as packed row classes without their zero-padding taps (default) or as head tiles
+        (rd_set_head_pack); same bits"""
+        self._check(self._L.rd_set_head_pack(self._h, 1 if on else 0))
+
+    def head_pack_active(self):
+        """whether the next chunk-mode forward packs its window heads (rd_head_pack_active): exact fp32, finite conv kernels, no -0.0 conv bias"""
+        return bool(self._L.rd_head_pack_active(self._h))
+
+    def head_pack_tiles(self):
+        """packed window-head workgroup tiles the context's latest forward launched (rd_head_pack_tiles)"""
+        return int(self._L.rd_head_pack_tiles(self._h))
+
     def set_decode_form(self, form):
         """'auto' (default); 'waves' / 'lanes': launch shape for widths above 12; 'two' / 'one': widths up to 12 always / never as
         two sequences per wave; 'queue': every launch through the work-queue kernel with few resident workgroups (rd_set_decode_form)."""

@@ -395,6 +395,7 @@ struct PlanCache {
     bool streamed = false;
     DevBuf d_tiles;
     TileLists lists;
+    bool has_pack = false;   // the packed heads' block was uploaded with the descriptors (only for a context that packs: rd_pack_heads)
 };
 
 int get_plan(rd_ctx* ctx, const int64_t* read_off, int n_reads, int chunk, int step, int mode, const ReadsPlan** out,
@@ -406,16 +407,21 @@ int get_plan(rd_ctx* ctx, const int64_t* read_off, int n_reads, int chunk, int s
         ctx->plan_cache[mode] = pc;
     }
     const int halo = rd_model_halo(ctx);
-    if (!(pc->d_tiles.p && pc->key.matches(ctx->model, read_off, n_reads, chunk, step, mode, halo))) {
+    const bool pack = mode == 0 && rd_pack_heads(ctx);
+    if (!(pc->d_tiles.p && pc->key.matches(ctx->model, read_off, n_reads, chunk, step, mode, halo)) || (pack && !pc->has_pack)) {
         RD_REQUIRE(read_off[0] == 0, "read_off[0] must be 0");
         size_t total = 0;
         int rc = pc->key.rebuild(ctx->model, read_off, n_reads, chunk, step, mode, halo, pc->plan, &pc->streamed, &total);
         if (rc) return rc;
+        const size_t n_desc = total;
+        if (pack) total += plan_packed_descs(pc->plan);   // the packed heads' block, behind the descriptors
         if (pc->d_tiles.reserve(total * sizeof(TileDesc) + 16)) return RD_ERR_NOMEM;
         // make sure no forward still reads the previous descriptors
         if ((rc = rd_sync_lanes(ctx))) return rc;
         std::vector<TileDesc> host(total);
         plan_fill_lists(pc->plan, pc->d_tiles.as<TileDesc>(), host.data(), pc->lists);
+        if (pack) plan_fill_packed(pc->plan, pc->d_tiles.as<TileDesc>() + n_desc, host.data() + n_desc, pc->lists);
+        pc->has_pack = pack;
         if (total) RD_HIP(hipMemcpy(pc->d_tiles.p, host.data(), total * sizeof(TileDesc), hipMemcpyHostToDevice));
         pc->key.valid = true;
     }

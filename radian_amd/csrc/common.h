@@ -73,6 +73,10 @@ struct Model {
     float* w_d2 = nullptr;      // [128][5] (Keras layout)
     float* b_d2 = nullptr;      // [5]
     DevBuf storage;
+    // rd_load_weights: every conv kernel weight is finite and no conv bias is -0.0, so leaving out a product with a zero-padding row gives results
+    // equal under IEEE comparison (an accumulator that reaches -0.0 by underflow may keep its sign)
+    // and the packed window heads (forward.hip) may skip it.  False for weights the host has not seen (after training, on a broadcast's receiver).
+    bool pack_ok = false;
     bool split_stale = false;   // training rewrote the fp32 images (train.hip): the f16x3 / bf16x3 images are rebuilt before their next use
 };
 
@@ -111,10 +115,31 @@ struct TileDesc {
 // per-layer tile lists: index 0 = block-0 first conv (C_in = 1); 2b = first conv of block b >= 1; 2b+1 = second conv of
 // block b; 2*nblocks = dense head.  Uniform windows and streams use one list for every layer.
 constexpr int RD_MAX_LAYERS = 2 * 16 + 1;
+
+// Packed window heads (chunk-mode plans, exact-fp32 conv kernel only).  The head rows of a layer of dilation d and head
+// length h, sorted by what they read of their window's zero left-padding: class A = time steps [0, d) (only tap 2, shift 0, is live),
+// B = [d, 2d) (taps 1 and 2), C = [2d, h) (all taps).  Packed row p of a class is time step t_lo + p % L of head p / L (a TileDesc of
+// the layer's head_segs: the head's t0 == 0 descriptor); a class is padded to whole 128-row workgroup tiles, rows past the last head or
+// past a head's seg_len are inert.  A launch runs the list's stream prefix, then C, B, A.
+struct PackClass {
+    int32_t t_lo, L, tap_lo;
+    int32_t first_tile, n_tiles;   // workgroup tiles of the launch (first_tile counts from the launch's first workgroup)
+};
+struct PackLayer {
+    PackClass cls[3];          // C, B, A
+    int32_t n_heads;
+    int32_t n_stream_tiles;    // workgroup tiles of the list's stream prefix
+    int32_t n_tiles;           // workgroup tiles of the packed launch: stream prefix + classes (0: the layer is not packed)
+    int32_t mixed;             // 1: the stream prefix ends inside a workgroup tile; that tile's four descriptors, its head sub-tiles
+                               //    emptied, follow the layer's head_segs
+};
 struct TileLists {
     const TileDesc* d[RD_MAX_LAYERS];
     int n[RD_MAX_LAYERS];          // workgroup tiles = descriptors / 4
     int64_t rows[RD_MAX_LAYERS];   // time steps the layer evaluates (for the FLOP / byte accounting of the timers)
+    // packed heads (plan_fill_packed; plan_fill_lists leaves them off)
+    const TileDesc* head_segs[RD_MAX_LAYERS];
+    PackLayer pack[RD_MAX_LAYERS];
 };
 
 struct KernelTimer {
@@ -145,6 +170,8 @@ struct rd_ctx {
     int decode_form = 0; // rd_set_decode_form
     int decode_math = 1; // rd_set_decode_math (default: glibc's operation sequence -- scores bit-identical to the reference's)
     int conv_fuse = 1;   // rd_set_conv_fuse: 1 = block 0's first conv is computed inside its second (forward.hip, FIN), 0 = its own kernel
+    int64_t packed_tiles = 0;   // packed window-head workgroup tiles the latest forward launched (rd_head_pack_tiles)
+    int head_pack = 1;   // rd_set_head_pack: 1 = chunk-mode window heads run as packed classes that skip the zero-padding taps (exact fp32 only), 0 = as head tiles
     int conv_shape = 0;  // rd_set_conv_shape: 0 = 128-row tiles, two 256-thread workgroups per CU; 1 = 256-row tiles, one 512-thread workgroup
     int logits_f16 = 0;  // 1: the reads-level paths keep the softmax rows as f16 in HBM (10 B per time step), the decoder widens them
     hipStream_t stream = nullptr;
@@ -196,6 +223,7 @@ void rd_lm_bind(LM& lm);   // the pointers of lm into lm.storage, by lm.table_or
 // lmbuild.hip: entropies and absent mask of the table in lm.table (rows of NaN = absent contexts), on the device; marks the model loaded
 int rd_lm_finish_device(rd_ctx* ctx, int table_order, int context_len, int hashed);
 // forward.hip
+bool rd_pack_heads(const rd_ctx* ctx);   // the context runs chunk-mode window heads as packed classes (rd_set_head_pack, exact fp32, product shape, Model::pack_ok)
 int rd_forward_dev(rd_ctx* ctx, const float* d_windows, int nW, int T, float* d_probs, int lane = 0);
 int rd_forward_tiles_dev(rd_ctx* ctx, const float* d_signal, const TileLists& tiles, int64_t total_rows, void* d_probs, int lane = 0,
                          int probs_f16 = 0 /* 1: d_probs is _Float16 [rows][5] */);

@@ -226,6 +226,22 @@ extern "C" int rd_set_conv_fuse(rd_ctx* ctx, int on)
     return RD_OK;
 }
 
+extern "C" int rd_set_head_pack(rd_ctx* ctx, int on)
+{
+    RD_REQUIRE(ctx, "rd_set_head_pack: null context");
+    RD_REQUIRE(on == 0 || on == 1, "rd_set_head_pack: %d (1 = window heads as packed classes without their zero-padding taps, 0 = as head tiles)", on);
+    ctx->head_pack = on;
+    return RD_OK;
+}
+
+extern "C" int rd_head_pack_active(rd_ctx* ctx)
+{
+    if (!ctx) return 0;
+    return rd_pack_heads(ctx) ? 1 : 0;
+}
+
+extern "C" int64_t rd_head_pack_tiles(rd_ctx* ctx) { return ctx ? ctx->packed_tiles : 0; }
+
 extern "C" int rd_set_decode_partition(rd_ctx* ctx, int cus_per_xcd)
 {
     RD_REQUIRE(ctx, "rd_set_decode_partition: null context");

@@ -82,6 +82,13 @@ struct ConvArgs {
     const float* w_in;    // [3][256]
     const float* b_in;    // [256]
     ZeroRows zr;
+    // packed window heads (PackLayer, common.h; the <4, 3, EPI_RELU | EPI_RES_IDENT, 2, false> instantiations): workgroups from n_stream on
+    // take their rows from (cls, head_segs) instead of tile descriptors.  n_stream = INT32_MAX: a launch without packed tiles
+    const TileDesc* head_segs;
+    const TileDesc* mixed;   // the four descriptors of workgroup n_stream - 1 where the stream prefix ends inside it (else null)
+    PackClass cls[3];
+    int n_heads;
+    int n_stream;
 };
 
 // block 0, first conv, one output: relu(b + w0 x[t - 2d] + w1 x[t - d] + w2 x[t]) as ONE fma chain in this order -- written out so that
@@ -235,10 +242,23 @@ __device__ __forceinline__ void head_dense5_softmax(const float* hs, const float
 // 0, dil, 2 dil.  Only the weight tiles travel by LDS-DMA.  Values are tcn_in_kernel's bit for bit (conv_in_value), so the layer's
 // output is too (tests/test_gpu_forward.py::test_first_conv_fused_is_bit_identical).
 constexpr int FIN_DMAX = 2;               // dilations of block 0 the FIN variant is built for (sig2seq.yaml: 1)
-template <int NT, int TAPS, int EPI, int WM = 2, bool FIN = false>
-__global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void tcn_gemm_kernel(ConvArgs a)
+// LDS floats of tcn_gemm_kernel: 3 x 24 KiB (conv, WM = 2) / 3 x 32 KiB (WM = 4) / 67 KiB (head) / 70 KiB (FIN)
+template <int NT, int TAPS, int EPI, int WM, bool FIN> constexpr int conv_smem_floats()
+{
+    constexpr int BM = 64 * WM, BN = 2 * NT * 32;
+    constexpr int STAGE_FLOATS = (FIN ? 0 : BM * BK) + BN * BK;
+    constexpr int HEAD_FLOATS = BM * (RD_H + 1) + RD_H * 5 + 8 + BM * 5;
+    constexpr int FIN_FLOATS = FIN ? 2 * 4 * (32 + 2 * FIN_DMAX) * BK + 4 * RD_C : 0;
+    return (EPI == EPI_HEAD && HEAD_FLOATS > 3 * STAGE_FLOATS) ? HEAD_FLOATS : 3 * STAGE_FLOATS + FIN_FLOATS;
+}
+// One workgroup tile of tcn_gemm_kernel.  PACKED: a tile of packed window-head rows of class TAP_LO (ConvArgs; PackLayer, common.h) --
+// the A rows and the epilogue's rows come from (class header, head_segs) per row instead of four sub-tile descriptors, and the K loop
+// runs the taps from TAP_LO on.  The class is a template parameter so that the tap of every chunk stays a literal, as on the stream path.
+template <int NT, int TAPS, int EPI, int WM, bool FIN, bool PACKED, int TAP_LO = 0>
+__device__ __forceinline__ void tcn_gemm_tile(const ConvArgs& a, float* const smem)
 {
     static_assert(!FIN || (EPI == EPI_RES_MATCH && WM == 2 && TAPS == 3 && NT == 4), "FIN: block 0's second conv, product shape");
+    static_assert(!PACKED || (NT == 4 && TAPS == 3 && (EPI == EPI_RELU || EPI == EPI_RES_IDENT) && WM == 2 && !FIN), "PACKED: the product shape's conv launches behind block 0");
     constexpr int BM = 64 * WM;           // time steps per workgroup tile (shadows the file-scope 128)
     constexpr int NWAVE = 2 * WM;
     constexpr int BN = 2 * NT * 32;       // output channels per workgroup (2 waves along N)
@@ -249,9 +269,8 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void tcn_gemm_kernel(Con
     constexpr int NSTAGE = 3;
     constexpr int MIDROWS = 4 * (32 + 2 * FIN_DMAX);                      // rows of a slice's A region
     constexpr int FIN_FLOATS = FIN ? 2 * MIDROWS * BK + 4 * RD_C : 0;     // two regions + the first conv's [w0 | w1 | w2 | b] x 256
-    constexpr int SMEM_FLOATS = (EPI == EPI_HEAD && HEAD_FLOATS > NSTAGE * STAGE_FLOATS) ? HEAD_FLOATS : NSTAGE * STAGE_FLOATS + FIN_FLOATS;
-
-    __shared__ __attribute__((aligned(1024))) float smem[SMEM_FLOATS];  // 3 x 24 KiB (conv, WM = 2) / 3 x 32 KiB (WM = 4) / 67 KiB (head) / 70 KiB (FIN)
+    static_assert(conv_smem_floats<NT, TAPS, EPI, WM, FIN>() == ((EPI == EPI_HEAD && HEAD_FLOATS > NSTAGE * STAGE_FLOATS) ? HEAD_FLOATS : NSTAGE * STAGE_FLOATS + FIN_FLOATS),
+                  "the kernel's LDS block");
 
     if constexpr (FIN) clear_zero_rows(a.zr);   // (this kernel is then the forward's first)
     const int tid = threadIdx.x;
@@ -263,9 +282,22 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void tcn_gemm_kernel(Con
     // step, the segment length.  A segment is a window, a whole read, or the first rows of a window.
     // A workgroup tile is four independent 32-row sub-tiles (rows 32s .. 32s+31), each with its own descriptor: stream
     // tiles use four consecutive sub-tiles of one segment, short head segments are packed four to a tile.
-    const TileDesc* __restrict__ tds = a.tiles + (size_t)blockIdx.x * NWAVE;   // one 32-row sub-tile descriptor per wave
+    // PACKABLE: the launches that may carry packed window-head tiles behind their stream tiles (see ConvArgs)
+    constexpr bool PACKABLE = NT == 4 && TAPS == 3 && (EPI == EPI_RELU || EPI == EPI_RES_IDENT) && WM == 2 && !FIN;
+    const TileDesc* __restrict__ tds = a.tiles + (size_t)(PACKED ? 0 : blockIdx.x) * NWAVE;   // one 32-row sub-tile descriptor per wave
+    if constexpr (PACKABLE && !PACKED) {
+        if (a.mixed && (int)blockIdx.x == a.n_stream - 1) tds = a.mixed;
+    }
     const TileDesc sdm[2] = {tds[wm * 2], tds[wm * 2 + 1]};           // this wave's two sub-tiles
-    const bool mval[2] = {sdm[0].seg_len > sdm[0].t0, sdm[1].seg_len > sdm[1].t0};
+    // packed tile: class header and the tile's first packed row (wave-uniform); pk_rows = packed rows of the class that belong to a head
+    const PackClass pkc = a.cls[TAP_LO];
+    unsigned pk_p0 = 0, pk_rows = 0;
+    if constexpr (PACKED) {
+        pk_p0 = (unsigned)((int)blockIdx.x - pkc.first_tile) * BM;
+        pk_rows = (unsigned)a.n_heads * (unsigned)pkc.L;
+    }
+    const bool mval[2] = {PACKED ? pk_p0 + wm * 64 < pk_rows : sdm[0].seg_len > sdm[0].t0,
+                          PACKED ? pk_p0 + wm * 64 + 32 < pk_rows : sdm[1].seg_len > sdm[1].t0};
 
     // DMA roles, fixed for the whole tile: a wave-instruction moves 16 rows x 64 B; lane -> (row-in-piece, physical
     // 16-B slot).  Wave w stages sub-tile w (two pieces), so the descriptor fields it needs are wave-uniform scalars.
@@ -280,13 +312,34 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void tcn_gemm_kernel(Con
     // zero row where the time step lies before the segment (causal padding) or in an empty sub-tile.  Per chunk the
     // address is then one multiply-add on a per-chunk base.
     int arow[TAPS][2];
+    if constexpr (!PACKED) {
 #pragma unroll
-    for (int tap = 0; tap < TAPS; tap++)
+        for (int tap = 0; tap < TAPS; tap++)
+#pragma unroll
+            for (int pc = 0; pc < 2; pc++) {
+                const int t = d_t0 + pc * 16 + dma_r - (TAPS - 1 - tap) * a.dil;
+                arow[tap][pc] = (t >= 0 && t < d_len) ? (int)((t < d_ain ? d_seg : d_alt) + t) : a.zero_row;
+            }
+    } else {
+        // packed tile: the A operand is a per-lane gather anyway -- tile row R is time step t_lo + p % L of head p / L (p = its packed row),
+        // so a 16-row piece may straddle heads.  Taps below tap_lo, rows past the last head and rows past a head's seg_len read the zero row.
 #pragma unroll
         for (int pc = 0; pc < 2; pc++) {
-            const int t = d_t0 + pc * 16 + dma_r - (TAPS - 1 - tap) * a.dil;
-            arow[tap][pc] = (t >= 0 && t < d_len) ? (int)((t < d_ain ? d_seg : d_alt) + t) : a.zero_row;
+            const unsigned p = pk_p0 + wave * 32 + pc * 16 + dma_r;
+            const unsigned w = p / (unsigned)pkc.L;
+            const int t = pkc.t_lo + (int)(p - w * (unsigned)pkc.L);
+            const bool has = w < (unsigned)a.n_heads;
+            const TileDesc* __restrict__ hd = a.head_segs + (has ? w : 0u);
+            const int64_t h_seg = hd->seg_row, h_alt = hd->alt_row;
+            const int h_len = hd->seg_len, h_in = hd->in_len, h_ain = hd->alt_in;
+            const bool live = has && t < h_len;
+#pragma unroll
+            for (int tap = 0; tap < TAPS; tap++) {
+                const int u = t - (TAPS - 1 - tap) * a.dil;
+                arow[tap][pc] = (live && tap >= TAP_LO && u >= 0 && u < h_in) ? (int)((u < h_ain ? h_seg : h_alt) + u) : a.zero_row;
+            }
         }
+    }
     const char* lanebase = (const char*)(a.in + lane_slot);
     const unsigned lane_off = lane * 16;
 
@@ -295,11 +348,10 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void tcn_gemm_kernel(Con
     constexpr int PB = BN / (16 * NWAVE);   // 1-KiB pieces (16 rows) of B per wave
     constexpr int NA = FIN ? 0 : 2;         // A pieces per wave (FIN: the A tiles are computed, not loaded)
     constexpr int NPIECE = NA + PB;
-    auto stage_piece = [&](int chunk, int tap, float* st, int pc) {
-        // chunk order: input-channel slice outer, tap inner -> the three shifted reads of the same rows are adjacent in time
+    // (chunk = the weight chunk, cc = its input-channel slice, ar = this lane's A row of piece pc)
+    auto stage_piece_at = [&](int chunk, int cc, int ar, float* st, int pc) {
         if (pc < NA) {
-            const int cc = chunk / TAPS;
-            const char* src = lanebase + (size_t)cc * (BK * 4) + (uint64_t)(unsigned)arow[tap][pc] * (RD_C * 4);
+            const char* src = lanebase + (size_t)cc * (BK * 4) + (uint64_t)(unsigned)ar * (RD_C * 4);
             glds16_uncounted((const float*)src, st + (wave * 2 + pc) * 256);   // 1 KiB piece = tile rows 16*piece .. 16*piece+15
         } else {
             const float* wb = a.wpk + (size_t)chunk * BN * BK + wave * PB * 256;   // pre-swizzled on the host: linear copy
@@ -311,9 +363,15 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void tcn_gemm_kernel(Con
             else glds16_uncounted_saddr<3072>(lane_off, wb, dst);
         }
     };
+    // chunk order: input-channel slice outer, tap inner -> the three shifted reads of the same rows are adjacent in time
+    auto stage_piece = [&](int chunk, int tap, float* st, int pc) { stage_piece_at(chunk, chunk / TAPS, arow[tap][pc & 1], st, pc); };
     auto stage = [&](int chunk, int tap, float* st) {
 #pragma unroll
         for (int pc = 0; pc < NPIECE; pc++) stage_piece(chunk, tap, st, pc);
+    };
+    auto stage_piece_all = [&](int chunk, int cc, int tap, float* st) {   // (PACKED: weight chunk `chunk` of slice cc, tap `tap`)
+#pragma unroll
+        for (int pc = 0; pc < NPIECE; pc++) stage_piece_at(chunk, cc, arow[tap][pc & 1], st, pc);
     };
 
     // ---- FIN: the A tiles computed from the raw samples.  Wave w computes sub-tile w's region rows i = 0 .. 31 + 2 dil (time step
@@ -402,7 +460,8 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void tcn_gemm_kernel(Con
             }
     }
     // (cur = this chunk's index, cur_tap = its tap: literals at every call site)
-    auto chunk_step = [&](const float* st, int cur, int cur_tap, int next, int next_tap, float* nst) {
+    // (st_ok: a chunk follows two chunks on -- weight chunk next of slice next_cc, this lane's A rows next_ar0 / next_ar1 -- and is staged into nst)
+    auto chunk_step = [&](const float* st, int cur, int cur_tap, const bool st_ok, int next, int next_cc, int next_ar0, int next_ar1, float* nst) {
         // MFMA order: k-group g, then N tile n, then (kr, m): 8 MFMAs per (g, n) step on two accumulators.  A step needs
         // the A fragments of its k-group (8 registers) and ONE B fragment (4): the next step's B fragment and, during the
         // last step of a group, the next group's A fragments are requested before the step's MFMAs, so 24 fragment
@@ -421,7 +480,6 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void tcn_gemm_kernel(Con
             }
         };
         auto rdB = [&](int sidx) { bq[sidx & 1] = *(const float4*)(Bb + (sidx % NT) * 32 * BK + koff[sidx / NT]); };
-        const bool st_ok = next < NCHUNK;
         if (work) {
             rdA(0);
             rdB(0);
@@ -447,7 +505,7 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void tcn_gemm_kernel(Con
                 __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (st_ok && sidx < NPIECE) stage_piece(next, next_tap, nst, sidx);
+            if (st_ok && sidx < NPIECE) stage_piece_at(next, next_cc, sidx == 0 ? next_ar0 : next_ar1, nst, sidx);
             if constexpr (FIN) {
                 // pass cur_tap of the NEXT slice's region, behind the weight pieces: its ~20 vector instructions issue in the shadow
                 // of the matrix pipe like the DMA's address arithmetic (the region it writes was last read two slices ago)
@@ -466,16 +524,40 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void tcn_gemm_kernel(Con
     float* st2 = smem + 2 * STAGE_FLOATS;
     constexpr bool T3 = TAPS == 3;   // chunk % 3 is the tap; the loop below advances by the 3 stages
     static_assert(TAPS == 3 || TAPS == 1, "tap of a chunk is a literal in the unrolled loop");
-    stage(0, 0, st0);
-    stage(1, T3 ? 1 : 0, st1);
     auto step = [&](int c, int tap, const float* st, int tap2, float* nst) {
         if (c + 1 < NCHUNK) wait_dma_and_barrier<NPIECE, FIN>(); else wait_dma_and_barrier<0, FIN>();
-        chunk_step(st, c, tap, c + 2, tap2, nst);
+        chunk_step(st, c, tap, c + 2 < NCHUNK, c + 2, (c + 2) / TAPS, arow[tap2][0], arow[tap2][1], nst);
     };
-    for (int chunk = 0; chunk < NCHUNK; chunk += 3) {
-        step(chunk, 0, st0, T3 ? 2 : 0, st2);
-        if (chunk + 1 < NCHUNK) step(chunk + 1, T3 ? 1 : 0, st1, 0, st0);
-        if (chunk + 2 < NCHUNK) step(chunk + 2, T3 ? 2 : 0, st2, T3 ? 1 : 0, st1);
+    auto stream_loop = [&]() {
+        stage(0, 0, st0);
+        stage(1, T3 ? 1 : 0, st1);
+        for (int chunk = 0; chunk < NCHUNK; chunk += 3) {
+            step(chunk, 0, st0, T3 ? 2 : 0, st2);
+            if (chunk + 1 < NCHUNK) step(chunk + 1, T3 ? 1 : 0, st1, 0, st0);
+            if (chunk + 2 < NCHUNK) step(chunk + 2, T3 ? 2 : 0, st2, T3 ? 1 : 0, st1);
+        }
+    };
+    if constexpr (PACKED) {
+        // A packed tile's K loop runs the class's live taps only: NCH = 16 (3 - TAP_LO) chunks, chunk i = slice i / NTP, tap TAP_LO + i % NTP,
+        // i.e. the surviving chunks of the full loop in its order (weight chunk slice * 3 + tap).  Staging, counting and the stage rotation
+        // are the full loop's; the loop advances by a common period of the three stages and the class's taps, so tap and stage are literals.
+        constexpr int NTP = TAPS - TAP_LO, NCH = (RD_C / BK) * NTP, PERIOD = NTP == 2 ? 6 : 3;
+        stage_piece_all(TAP_LO, 0, TAP_LO, st0);
+        stage_piece_all((1 / NTP) * TAPS + TAP_LO + 1 % NTP, 1 / NTP, TAP_LO + 1 % NTP, st1);
+        for (int base = 0; base < NCH; base += PERIOD) {
+#pragma unroll
+            for (int j = 0; j < PERIOD; j++) {
+                const int i = base + j;
+                if (i < NCH) {
+                    if (i + 1 < NCH) wait_dma_and_barrier<NPIECE>(); else wait_dma_and_barrier<0>();
+                    const int tap2 = TAP_LO + (j + 2) % NTP, sl2 = base / NTP + (j + 2) / NTP;
+                    chunk_step(j % 3 == 0 ? st0 : j % 3 == 1 ? st1 : st2, 0, 0, i + 2 < NCH, sl2 * TAPS + tap2, sl2, arow[tap2][0], arow[tap2][1],
+                               j % 3 == 0 ? st2 : j % 3 == 1 ? st0 : st1);
+                }
+            }
+        }
+    } else {
+        stream_loop();
     }
     __syncthreads();   // every wave is done with the staging LDS: the epilogues reuse it
 
@@ -494,6 +576,70 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void tcn_gemm_kernel(Con
         float4* sink4 = (float4*)a.sink + (threadIdx.x & 255);   // (1024 floats; two lanes of a 512-thread workgroup may share a slot: nobody reads it)
         const int rrow = lane >> 4;                    // 0..3: row inside a 4-row store group
         const int c4 = (lane & 15) * 4;                // channel offset inside the 64-channel patch
+        // this lane's accumulators of N tiles 2 np, 2 np + 1 of sub-tile m (ReLU) -> the wave's LDS patch
+        auto to_patch = [&](int m, int np) {
+#pragma unroll
+            for (int j = 0; j < 2; j++) {
+                const int n = 2 * np + j;
+#pragma unroll
+                for (int e = 0; e < 16; e++) {
+                    const int rl = (e & 3) + 8 * (e >> 2) + 4 * fh;
+                    ts[rl * TSTR + j * 32 + fr] = relu_raw(acc[m][n][e]);   // bias included since the start
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        };
+        if constexpr (PACKED) {
+            // Packed tile: the general per-row path with the row's own head.  128 threads first work out, for one tile row each, the row it
+            // stores (-1: inert -> the sink) and the row its residual comes from, into LDS behind the waves' patches.
+            {
+                int2* rowinfo = (int2*)(smem + NWAVE * 32 * TSTR);
+                if (tid < BM) {
+                    const unsigned p = pk_p0 + tid;
+                    const unsigned w = p / (unsigned)pkc.L;
+                    const int t = pkc.t_lo + (int)(p - w * (unsigned)pkc.L);
+                    const bool has = w < (unsigned)a.n_heads;
+                    const TileDesc* __restrict__ hd = a.head_segs + (has ? w : 0u);
+                    const int64_t h_seg = hd->seg_row, h_alt = hd->alt_row;
+                    const bool live = has && t < hd->seg_len;
+                    rowinfo[tid] = make_int2(live ? (int)(h_seg + t) : -1, live ? (int)((t < hd->alt_res ? h_seg : h_alt) + t) : a.zero_row);
+                }
+                __syncthreads();
+#pragma unroll
+                for (int m = 0; m < 2; m++) {
+                    if (!mval[m]) continue;
+#pragma unroll
+                    for (int np = 0; np < NT / 2; np++) {
+                        to_patch(m, np);
+                        const int ch = wn * NT * 32 + np * 64 + c4;
+#pragma unroll
+                        for (int ih = 0; ih < 8; ih += 2) {   // (two rows at a time: the kernel's register count stays the stream path's)
+                            float4 rv[2];
+                            int orow[2];
+#pragma unroll
+                            for (int i = 0; i < 2; i++) {
+                                const int2 ri = rowinfo[wm * 64 + m * 32 + (ih + i) * 4 + rrow];
+                                orow[i] = ri.x;
+                                if constexpr (EPI == EPI_RES_IDENT) rv[i] = *(const float4*)(a.resid + (size_t)(unsigned)ri.y * RD_C + ch);
+                            }
+#pragma unroll
+                            for (int i = 0; i < 2; i++) {
+                                float4 v = *(const float4*)(ts + ((ih + i) * 4 + rrow) * TSTR + c4);
+                                if constexpr (EPI == EPI_RES_IDENT) {
+                                    v.x += rv[i].x; v.y += rv[i].y; v.z += rv[i].z; v.w += rv[i].w;   // (>= +0: see the fast path)
+                                }
+                                float4* dst = orow[i] >= 0 ? (float4*)(a.out + (size_t)(unsigned)orow[i] * RD_C + ch) : sink4;
+                                *dst = v;
+                            }
+                        }
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                        __builtin_amdgcn_wave_barrier();
+                    }
+                }
+                return;
+            }
+        }
 #pragma unroll
         for (int m = 0; m < 2; m++) {
             if (!mval[m]) continue;
@@ -503,20 +649,6 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void tcn_gemm_kernel(Con
             const float* __restrict__ resw = a.resid + (size_t)sd.seg_row * RD_C;      // block input (separate tensor)
             const float* __restrict__ resalt = a.resid + (size_t)sd.alt_row * RD_C;
             const bool interior = sd.t0 + 32 <= T;
-            // this lane's accumulators of N tiles 2 np, 2 np + 1 (ReLU) -> the wave's LDS patch
-            auto to_patch = [&](int np) {
-#pragma unroll
-                for (int j = 0; j < 2; j++) {
-                    const int n = 2 * np + j;
-#pragma unroll
-                    for (int e = 0; e < 16; e++) {
-                        const int rl = (e & 3) + 8 * (e >> 2) + 4 * fh;
-                        ts[rl * TSTR + j * 32 + fr] = relu_raw(acc[m][n][e]);   // bias included since the start
-                    }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-            };
             // Fast path (every stream tile but a segment's last): the 32 rows are all inside the segment and on one side of the
             // residual switch, so every address is a wave-uniform base + one per-lane offset -- no per-row selects or 64-bit
             // vector adds.  That matters more than it looks: beside the CU partner's MFMA stream a vector instruction of this
@@ -530,7 +662,7 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void tcn_gemm_kernel(Con
                 const float* __restrict__ rb = (sd.t0 < sd.alt_res ? resw : resalt) + (size_t)sd.t0 * RD_C + wn * (NT * 32);
 #pragma unroll
                 for (int np = 0; np < NT / 2; np++) {
-                    to_patch(np);
+                    to_patch(m, np);
 #pragma unroll
                     for (int ih = 0; ih < 8; ih += 4) {   // (four rows at a time: 16 residual registers live, not 32)
                         float4 rv[4];
@@ -554,7 +686,7 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void tcn_gemm_kernel(Con
             }
 #pragma unroll
             for (int np = 0; np < NT / 2; np++) {
-                to_patch(np);
+                to_patch(m, np);
                 // ---- LDS patch -> (residual) -> global, 16 B per lane
                 const int ch = wn * NT * 32 + np * 64 + c4;
                 float4 wm4 = make_float4(0.f, 0.f, 0.f, 0.f), bm4 = wm4;
@@ -562,12 +694,15 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void tcn_gemm_kernel(Con
                     wm4 = *(const float4*)(a.wmatch + ch);
                     bm4 = *(const float4*)(a.bmatch + ch);
                 }
+                // four rows at a time (registers: see the fast path); two in the kernel that also holds the packed-head paths, whose
+                // allocation otherwise passes the 208 registers of chunk_step's note at this point (a segment's last tile only comes here)
+                constexpr int GR = (PACKABLE && EPI == EPI_RES_IDENT) ? 2 : 4;
 #pragma unroll
-                for (int ih = 0; ih < 8; ih += 4) {   // four rows at a time (registers: see the fast path)
-                    float4 rv[4];
-                    int tt[4];
+                for (int ih = 0; ih < 8; ih += GR) {
+                    float4 rv[GR];
+                    int tt[GR];
 #pragma unroll
-                    for (int i = 0; i < 4; i++) {
+                    for (int i = 0; i < GR; i++) {
                         const int t = sd.t0 + (ih + i) * 4 + rrow;
                         tt[i] = t;
                         if constexpr (EPI == EPI_RES_IDENT) {
@@ -576,7 +711,7 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void tcn_gemm_kernel(Con
                         }
                     }
 #pragma unroll
-                    for (int i = 0; i < 4; i++) {
+                    for (int i = 0; i < GR; i++) {
                         float4 v = *(const float4*)(ts + ((ih + i) * 4 + rrow) * TSTR + c4);
                         const int t = tt[i];
                         const bool inb = interior || t < T;
@@ -620,6 +755,44 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void tcn_gemm_kernel(Con
         static_assert(64 * NWAVE == 2 * BM, "head epilogue: two threads per row");
         head_dense5_softmax<BM>(hs, w2s, w2s + RD_H * 5 + 8, tds, a, tid);
     }
+}
+
+// What a workgroup of tcn_gemm_kernel runs: the launches that may carry packed window-head tiles (ConvArgs) send the workgroups behind
+// the stream tiles to their class's path.
+template <int NT, int TAPS, int EPI, int WM, bool FIN>
+__device__ __forceinline__ void tcn_gemm_workgroup(const ConvArgs& a, float* const smem)
+{
+    if constexpr (NT == 4 && TAPS == 3 && (EPI == EPI_RELU || EPI == EPI_RES_IDENT) && WM == 2 && !FIN) {
+        // one launch per layer: the list's stream tiles first, then the packed window-head classes (longest K loop first)
+        const int bx = (int)blockIdx.x;
+        if (bx >= a.n_stream) {   // (an empty class shares its first tile with the next)
+            if (bx >= a.cls[2].first_tile) tcn_gemm_tile<NT, TAPS, EPI, WM, FIN, true, 2>(a, smem);
+            else if (bx >= a.cls[1].first_tile) tcn_gemm_tile<NT, TAPS, EPI, WM, FIN, true, 1>(a, smem);
+            else tcn_gemm_tile<NT, TAPS, EPI, WM, FIN, true, 0>(a, smem);
+            return;
+        }
+    }
+    tcn_gemm_tile<NT, TAPS, EPI, WM, FIN, false>(a, smem);
+}
+template <int NT, int TAPS, int EPI, int WM = 2, bool FIN = false>
+__global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void tcn_gemm_kernel(ConvArgs a)
+{
+    __shared__ __attribute__((aligned(1024))) float smem[conv_smem_floats<NT, TAPS, EPI, WM, FIN>()];
+    tcn_gemm_workgroup<NT, TAPS, EPI, WM, FIN>(a, smem);
+}
+// The two launches with packed tiles hold four tile paths (stream + three classes).  Each path alone stays within the stream path's
+// register count, but allocated together they came out at 183 / 220 vector registers: bound to the stream path's allocation (176 /
+// 208), which is what leaves room for a beam-search wave beside two of these waves on a SIMD (chunk_step).  (The attribute takes a
+// literal only, hence the two specialisations.)
+template <> __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(92))) void tcn_gemm_kernel<4, 3, EPI_RELU, 2, false>(ConvArgs a)
+{
+    __shared__ __attribute__((aligned(1024))) float smem[conv_smem_floats<4, 3, EPI_RELU, 2, false>()];
+    tcn_gemm_workgroup<4, 3, EPI_RELU, 2, false>(a, smem);
+}
+template <> __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(104))) void tcn_gemm_kernel<4, 3, EPI_RES_IDENT, 2, false>(ConvArgs a)
+{
+    __shared__ __attribute__((aligned(1024))) float smem[conv_smem_floats<4, 3, EPI_RES_IDENT, 2, false>()];
+    tcn_gemm_workgroup<4, 3, EPI_RES_IDENT, 2, false>(a, smem);
 }
 
 // Block 0, first conv: C_in = 1 (VALU; memory-bound 1 KiB write per time step), fused bias + ReLU.
@@ -1403,8 +1576,10 @@ bool fuse_first_conv(const rd_ctx* ctx)
            ctx->model.dil[0] <= FIN_DMAX;
 }
 
+// (pk / head_segs: the layer's packed heads, null where the plan has none for it)
 int launch_layer(rd_ctx* ctx, hipStream_t st, int b, int kind /*0 in, 1 conv0, 2 conv1, 3 head*/, const TileDesc* tiles, int n,
-                double rows, int zero_row, const float* d_signal, float* Xin, float* Xout, float* MID, float* d_probs, int probs_f16)
+                double rows, int zero_row, const float* d_signal, float* Xin, float* Xout, float* MID, float* d_probs, int probs_f16,
+                const PackLayer* pk, const TileDesc* head_segs)
 {
     if (n <= 0) return RD_OK;
     Model& m = ctx->model;
@@ -1522,6 +1697,17 @@ int launch_layer(rd_ctx* ctx, hipStream_t st, int b, int kind /*0 in, 1 conv0, 2
     a.tiles = tiles;
     a.wpk = m.w_conv[wi];
     a.bias = m.b_conv[wi];
+    a.n_stream = INT32_MAX;
+    if (b > 0 && pk && head_segs && pk->n_tiles > 0 && rd_pack_heads(ctx)) {
+        // one launch, as before: the list's stream tiles, then the packed classes C, B, A in place of its head tiles
+        a.head_segs = head_segs;
+        a.mixed = pk->mixed ? head_segs + pk->n_heads : nullptr;
+        for (int c = 0; c < 3; c++) a.cls[c] = pk->cls[c];
+        a.n_heads = pk->n_heads;
+        a.n_stream = pk->n_stream_tiles;
+        n = pk->n_tiles;
+        ctx->packed_tiles += pk->n_tiles - pk->n_stream_tiles;
+    }
     SplitArgs sa = {};
     sa.zero_row = zero_row;
     sa.sink = m.sink;
@@ -1575,6 +1761,11 @@ int launch_layer(rd_ctx* ctx, hipStream_t st, int b, int kind /*0 in, 1 conv0, 2
 }
 
 }  // namespace
+
+bool rd_pack_heads(const rd_ctx* ctx)
+{
+    return ctx->head_pack && ctx->precision == 0 && ctx->conv_shape == 0 && ctx->model.loaded && ctx->model.pack_ok;
+}
 
 int rd_split3_dev(rd_ctx* ctx, const float* d_in, size_t n, uint16_t* d_out)
 {
@@ -1703,10 +1894,13 @@ int rd_forward_tiles_dev(rd_ctx* ctx, const float* d_signal, const TileLists& tl
     const int zero_row = (int)total_rows;
     // (the three tensors' zero rows are cleared by the forward's first kernel: clear_zero_rows)
     const int nl = 2 * m.nblocks + 1;
+    ctx->packed_tiles = 0;
     for (int li = 0; li < nl; li++) {
         const int b = li == nl - 1 ? m.nblocks : li / 2;
         const int kind = li == nl - 1 ? 3 : (li == 0 ? 0 : (li & 1 ? 2 : 1));
-        if ((rc = launch_layer(ctx, L->st, b, kind, tl.d[li], tl.n[li], (double)tl.rows[li], zero_row, d_signal, Xin, Xout, MID, (float*)d_probs, probs_f16))) return rc;
+        if ((rc = launch_layer(ctx, L->st, b, kind, tl.d[li], tl.n[li], (double)tl.rows[li], zero_row, d_signal, Xin, Xout, MID, (float*)d_probs, probs_f16,
+                               &tl.pack[li], tl.head_segs[li])))
+            return rc;
         if (kind == 2) {   // block finished: its output becomes the next block's input
             float* t = Xin;
             Xin = Xout;
@@ -1751,6 +1945,8 @@ int rd_uniform_tiles(rd_ctx* ctx, int nW, int T, TileLists* out)
         out->d[li] = li < nl ? ctx->ws_tiles.as<TileDesc>() : nullptr;
         out->n[li] = li < nl ? (int)n : 0;
         out->rows[li] = li < nl ? (int64_t)nW * T : 0;
+        out->head_segs[li] = nullptr;
+        out->pack[li] = PackLayer();
     }
     return RD_OK;
 }

@@ -203,6 +203,27 @@ void model_image(const float* w, int nb, const ModelLayout& L, Model& m, std::ve
     copy(L.b_d2, pm.bd2, RD_NCLS);
 }
 
+// Model::pack_ok of the flat weights w: every weight of the conv kernels the packed heads run (blocks >= 1) is finite, none of their
+// biases is -0.0.  Then leaving out a product with a zero-padding row gives results equal under IEEE comparison: fma(0, w, acc) == acc
+// unless w is non-finite (NaN); an accumulator of -0.0 becomes +0.0, which compares equal -- the bias check keeps the common way to one out.
+bool weights_allow_packing(const float* w, int nb)
+{
+    const ParamMap pm = param_map(nb);
+    auto finite = [&](size_t at, size_t n) {
+        for (size_t i = 0; i < n; i++)
+            if (!std::isfinite(w[at + i])) return false;
+        return true;
+    };
+    auto no_neg_zero = [&](size_t at, size_t n) {
+        for (size_t i = 0; i < n; i++)
+            if (w[at + i] == 0.f && std::signbit(w[at + i])) return false;
+        return true;
+    };
+    for (int b = 1; b < nb; b++)
+        if (!finite(pm.w0[b], RD_CONV_N) || !finite(pm.w1[b], RD_CONV_N) || !no_neg_zero(pm.b0[b], RD_C) || !no_neg_zero(pm.b1[b], RD_C)) return false;
+    return true;
+}
+
 }  // namespace
 
 size_t rd_model_image_floats(int nblocks) { return model_layout(nblocks).total; }
@@ -240,6 +261,7 @@ extern "C" int rd_load_weights(rd_ctx* ctx, const void* blob, size_t nbytes)
     RD_HIP(hipMemcpy(m.storage.p, host.data(), L.total * sizeof(float), hipMemcpyHostToDevice));
     model_bind(m, L);
     m.split_stale = false;
+    m.pack_ok = weights_allow_packing(w, nb);
     rd_train_invalidate(ctx);   // Keras restores weights into a fresh optimiser
     m.loaded = true;
     return RD_OK;
@@ -259,6 +281,7 @@ int rd_model_refresh_split(rd_ctx* ctx)
     if (int rc = rd_sync_lanes(ctx)) return rc;
     RD_HIP(hipMemcpy(m.storage.p, host.data(), L.total * sizeof(float), hipMemcpyHostToDevice));
     m.split_stale = false;
+    m.pack_ok = weights_allow_packing(flat.data(), m.nblocks);
     return RD_OK;
 }
 

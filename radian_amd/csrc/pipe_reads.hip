@@ -347,7 +347,8 @@ struct RLane {                // per forward lane: staging + descriptors of the 
     ReadsPlan plan;
     bool streamed = false;
     TileLists lists;
-    size_t n_desc = 0;
+    size_t n_desc = 0;        // descriptors of the tile lists and, where has_pack, of the packed heads' block behind them
+    bool has_pack = false;    // (only for a context that packs: rd_pack_heads)
 };
 
 struct ReadsPipe {
@@ -615,8 +616,15 @@ int open_slot(rd_ctx* ctx, ReadsPipe* p, int mode, int W, int f16, int use_lm, d
 int lane_plan_build(rd_ctx* ctx, RLane& R, const int64_t* read_off, int n_reads, int chunk, int step, int mode, bool* miss, size_t* n_desc)
 {
     const int halo = rd_model_halo(ctx);
-    *miss = !R.key.matches(ctx->model, read_off, n_reads, chunk, step, mode, halo);
-    int rc = *miss ? R.key.rebuild(ctx->model, read_off, n_reads, chunk, step, mode, halo, R.plan, &R.streamed, &R.n_desc) : RD_OK;
+    const bool pack = mode == 0 && rd_pack_heads(ctx);
+    *miss = !R.key.matches(ctx->model, read_off, n_reads, chunk, step, mode, halo) || (pack && !R.has_pack);
+    int rc = RD_OK;
+    if (*miss) {
+        size_t n_list = 0;
+        rc = R.key.rebuild(ctx->model, read_off, n_reads, chunk, step, mode, halo, R.plan, &R.streamed, &n_list);
+        R.has_pack = pack;
+        R.n_desc = n_list + (pack ? plan_packed_descs(R.plan) : 0);   // the packed heads' block travels behind the lists
+    }
     *n_desc = R.n_desc;
     return rc;
 }
@@ -626,13 +634,17 @@ int lane_plan_build(rd_ctx* ctx, RLane& R, const int64_t* read_off, int n_reads,
 int lane_plan_upload(FwdLane* L, RLane& R, char* hs)
 {
     ReadsPlan& P = R.plan;
-    const size_t off = plan_fill_lists(P, R.tiles.as<TileDesc>(), (TileDesc*)hs, R.lists);
+    size_t off = plan_fill_lists(P, R.tiles.as<TileDesc>(), (TileDesc*)hs, R.lists);
+    if (R.has_pack) off += plan_fill_packed(P, R.tiles.as<TileDesc>() + off, (TileDesc*)hs + off, R.lists);
     if (off) {
         int rc_ = copy_on_stream(R.tiles.p, hs, off * sizeof(TileDesc), L->st);
         if (rc_) return rc_;
     }
     // the host copies of the descriptors are not needed again (the per-sequence vectors of the plan are)
-    for (int li = 0; li < RD_MAX_LAYERS; li++) std::vector<TileDesc>().swap(P.tiles[li]);
+    for (int li = 0; li < RD_MAX_LAYERS; li++) {
+        std::vector<TileDesc>().swap(P.tiles[li]);
+        std::vector<TileDesc>().swap(P.head_segs[li]);
+    }
     R.key.valid = true;
     return RD_OK;
 }

@@ -45,6 +45,11 @@ struct ReadsPlan {
     std::vector<int64_t> read_row;       // first stream row of each read
     int64_t total_rows = 0;
     int n_windows = 0;
+    // Packed window heads (chunk mode; PackLayer, common.h) of every conv layer behind block 0, beside the head sub-tiles of `tiles`
+    // (which stay complete: the f16x3 / bf16x3 kernels and rd_set_head_pack 0 run them).  head_segs[li]: one descriptor per head of the
+    // layer -- its t0 == 0 sub-tile's -- then, where pack[li].mixed, the four descriptors of the workgroup tile the stream prefix ends in.
+    std::vector<TileDesc> head_segs[RD_MAX_LAYERS];
+    PackLayer pack[RD_MAX_LAYERS] = {};
 };
 
 // chunk mode: one stream per read + one head per window i >= 1; per-layer head lengths
@@ -71,6 +76,12 @@ struct PlanKey {
 // The descriptors of a padded plan, list after list, to h_dst, and `lists` pointing at the same places from d_base (layers
 // without a list of their own share list 0); -> descriptors written
 size_t plan_fill_lists(const ReadsPlan& P, const TileDesc* d_base, TileDesc* h_dst, TileLists& lists);
+
+// The packed block of a plan: plan_packed_descs(P) descriptors, which plan_fill_packed writes to h_dst and points `lists` at from d_base
+// (the device address of h_dst[0]: the owners put the block behind the descriptor block plan_fill_lists filled, in the same upload);
+// -> descriptors written.  Call it after plan_fill_lists, which marks every layer of `lists` unpacked.
+size_t plan_packed_descs(const ReadsPlan& P);
+size_t plan_fill_packed(const ReadsPlan& P, const TileDesc* d_base, TileDesc* h_dst, TileLists& lists);
 
 // api.hip: what every reads-level entry point requires of its arguments (RD_ERR_ARG), then loaded weights (RD_ERR_STATE)
 int rd_check_reads_args(rd_ctx* ctx, const void* signal, const int64_t* read_off, int n_reads, int chunk_len, int step, int W);

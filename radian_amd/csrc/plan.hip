@@ -73,6 +73,45 @@ void layer_halos(const Model& m, LayerHalo* lh)
     lh[2 * m.nblocks] = {H, H, H};                   // dense head
 }
 
+// The packed form of a layer's heads (PackLayer, common.h): n_stream sub-tiles of streams are in `list` so far, `heads` are the head
+// sub-tiles that will follow them.  d = the layer's dilation, h = its head length (capped at the chunk length: no head is longer).
+void pack_layer_heads(const std::vector<TileDesc>& list, const std::vector<TileDesc>& heads, int d, int h, std::vector<TileDesc>& segs, PackLayer& pk)
+{
+    pk = PackLayer();
+    segs.clear();
+    for (const TileDesc& td : heads)
+        if (td.t0 == 0) segs.push_back(td);
+    const int64_t nH = (int64_t)segs.size();
+    if (nH == 0 || nH * h >= ((int64_t)1 << 30)) {   // (packed rows are indexed with 32 bits; such a batch does not fit the row space anyway)
+        segs.clear();
+        return;
+    }
+    const size_t nS = list.size();
+    pk.n_heads = (int32_t)nH;
+    pk.n_stream_tiles = (int32_t)((nS + 3) / 4);
+    pk.mixed = nS % 4 ? 1 : 0;
+    if (pk.mixed) {
+        for (size_t j = nS / 4 * 4; j < nS / 4 * 4 + 4; j++) {
+            TileDesc e = {};
+            e.alt_in = e.alt_res = INT32_MAX;
+            segs.push_back(j < nS ? list[j] : e);
+        }
+    }
+    const int t1 = d < h ? d : h, t2 = 2 * d < h ? 2 * d : h;
+    const int lo[3] = {t2, t1, 0}, hi[3] = {h, t2, t1};   // C, B, A: longest K loop first
+    int32_t tile = pk.n_stream_tiles;
+    for (int c = 0; c < 3; c++) {
+        PackClass& pc = pk.cls[c];
+        pc.t_lo = lo[c];
+        pc.L = hi[c] - lo[c];
+        pc.tap_lo = c;
+        pc.first_tile = tile;
+        pc.n_tiles = (int32_t)((nH * pc.L + 127) / 128);
+        tile += pc.n_tiles;
+    }
+    pk.n_tiles = tile;
+}
+
 // chunk mode: one stream per read + one head per window i >= 1; per-layer head lengths
 int plan_reads_chunk(const Model& m, const int64_t* read_off, int n_reads, int chunk, int step, int halo, ReadsPlan& P)
 {
@@ -118,6 +157,8 @@ int plan_reads_chunk(const Model& m, const int64_t* read_off, int n_reads, int c
         P.n_windows += g.nW;
         P.read_win_off.push_back(P.n_windows);
     }
+    for (int li = 2; li < P.n_layers - 1; li++)   // (block 0's pair -- the fused first-conv launch -- and the dense head keep their head tiles)
+        pack_layer_heads(P.tiles[li], heads[li], m.dil[li / 2], lh[li].h_out < chunk ? lh[li].h_out : chunk, P.head_segs[li], P.pack[li]);
     for (int li = 0; li < P.n_layers; li++) P.tiles[li].insert(P.tiles[li].end(), heads[li].begin(), heads[li].end());
     P.total_rows = row;
     return RD_OK;
@@ -210,6 +251,8 @@ size_t plan_fill_lists(const ReadsPlan& P, const TileDesc* d_base, TileDesc* h_d
         lists.d[li] = nullptr;
         lists.n[li] = 0;
         lists.rows[li] = 0;
+        lists.head_segs[li] = nullptr;
+        lists.pack[li] = PackLayer();
     }
     for (int li = 0; li < P.n_layers; li++) {
         if (P.per_layer || li == 0) {
@@ -224,6 +267,29 @@ size_t plan_fill_lists(const ReadsPlan& P, const TileDesc* d_base, TileDesc* h_d
             lists.n[li] = lists.n[0];
             lists.rows[li] = lists.rows[0];
         }
+    }
+    return off;
+}
+
+size_t plan_packed_descs(const ReadsPlan& P)
+{
+    size_t n = 0;
+    for (int li = 0; li < RD_MAX_LAYERS; li++) n += P.head_segs[li].size();
+    return n;
+}
+
+size_t plan_fill_packed(const ReadsPlan& P, const TileDesc* d_base, TileDesc* h_dst, TileLists& lists)
+{
+    size_t off = 0;
+    for (int li = 0; li < RD_MAX_LAYERS; li++) {
+        const std::vector<TileDesc>& v = P.head_segs[li];
+        lists.head_segs[li] = nullptr;
+        lists.pack[li] = PackLayer();
+        if (v.empty() || P.pack[li].n_tiles == 0) continue;
+        memcpy(h_dst + off, v.data(), v.size() * sizeof(TileDesc));
+        lists.head_segs[li] = d_base + off;
+        lists.pack[li] = P.pack[li];
+        off += v.size();
     }
     return off;
 }

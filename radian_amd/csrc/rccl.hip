@@ -74,6 +74,7 @@ struct BcastHeader {
     int32_t lm_loaded, lm_k, lm_order, lm_hashed, lm_sparse;
     int64_t model_floats, lm_doubles;
     float inv_scale[2 * RD_MAX_BLOCKS], inv_scale_d1;
+    int32_t pack_ok;   // Model::pack_ok of the sender: the images are its images
 };
 
 }  // namespace
@@ -136,6 +137,7 @@ static void artifacts_header(const rd_ctx* ctx, BcastHeader& hd)
     hd.model_floats = (int64_t)rd_model_image_floats(ctx->model.nblocks);
     for (int i = 0; i < 2 * RD_MAX_BLOCKS; i++) hd.inv_scale[i] = ctx->model.inv_scale[i];
     hd.inv_scale_d1 = ctx->model.inv_scale_d1;
+    hd.pack_ok = ctx->model.pack_ok ? 1 : 0;
     hd.lm_loaded = ctx->lm.loaded ? 1 : 0;
     hd.lm_k = ctx->lm.k;
     hd.lm_order = ctx->lm.table_order;
@@ -156,6 +158,7 @@ static int artifacts_prepare(rd_ctx* ctx, const BcastHeader& hd)
     for (int i = 0; i < RD_MAX_BLOCKS; i++) m.dil[i] = hd.dil[i];
     for (int i = 0; i < 2 * RD_MAX_BLOCKS; i++) m.inv_scale[i] = hd.inv_scale[i];
     m.inv_scale_d1 = hd.inv_scale_d1;
+    m.pack_ok = hd.pack_ok == 1;
     if (m.storage.reserve((size_t)hd.model_floats * 4)) return RD_ERR_NOMEM;
     rd_model_bind(m);
     ctx->lm.loaded = false;

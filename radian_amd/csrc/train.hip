@@ -842,6 +842,7 @@ int train_run(rd_ctx* ctx, const char* fn, const float* windows, bool resident, 
         RD_HIP(hipGetLastError());
         if (int rc = run_pack(ctx, st, 0)) return rc;
         ctx->model.split_stale = true;
+        ctx->model.pack_ok = false;   // (the host has not seen the updated weights: window heads run unpacked)
     }
     if (grad_out) RD_HIP(hipMemcpyAsync(grad_out, G, pm.total * 4, hipMemcpyDeviceToHost, s));
     return ctc_finish(s, cd, n, status, loss);
