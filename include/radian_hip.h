@@ -452,6 +452,42 @@ int rd_basecall_raw_global_q(rd_ctx* ctx, const int16_t* raw, const int64_t* rea
                              const int64_t* label_off, int32_t* label_len, int32_t* status, int64_t budget_bytes, uint8_t* qual_out,
                              int32_t* first_step_out, int32_t* last_step_out, double* score_out, int32_t* align_status);
 
+/* ---- signal-to-reference alignment: the per-base event table (events.hip) -------------------------------
+ * NO reference behaviour.  Given a forced alignment (rd_ctc_align_batch, or the fused route below) of label_len[r] labels against
+ * read r -- samples raw + read_off[r] .. read_off[r+1], steps at first_step / last_step + label_off[r], one row = one raw sample --
+ * the samples every label sits on and what the current was there.  Integer arithmetic only; met exactly.  Per read with T samples,
+ * L >= 1 labels and align_status[r] == RD_CTCALIGN_OK:
+ *   event k   covers samples [start_k, end_k): start_k = first_step[k]; end_k = first_step[k+1] for k < L-1 and last_step[L-1] + 1
+ *             for the last one (a base owns the blank rows after it, as a moves table does).  Events are non-empty and back to back;
+ *             the samples before first_step[0] and after last_step[L-1] belong to no event
+ *   ev_start / ev_end [label_off[r] + k]   start_k, end_k
+ *   ev_sum / ev_sumsq   the sum and the sum of squares of the raw int16 samples of the event (int64: 2^30 * 2^31 < 2^63)
+ *   ev_min / ev_max     their minimum and maximum
+ * A read whose align_status is not OK gets start = end = -1 and 0 everywhere else for each of its labels; its neighbours are
+ * unaffected.  RD_ERR_ARG before anything is launched: a null pointer, offsets that are not monotone (read_off non-decreasing;
+ * label_off[r+1] >= label_off[r] + label_len[r]), and for an OK read any step outside 0 <= first_step[k] <= last_step[k] < T or
+ * last_step[k] >= first_step[k+1].  A result does not depend on what else is in the call or on the order of the reads.
+ *   rd_event_stats        on the GPU; synchronous, uses the context's stream
+ *   rd_event_stats_host   host, no GPU: the same boundary code and a plain loop */
+int rd_event_stats(rd_ctx* ctx, const int16_t* raw, const int64_t* read_off, int n_reads, const int32_t* first_step,
+                   const int32_t* last_step, const int64_t* label_off, const int32_t* label_len, const int32_t* align_status,
+                   int32_t* ev_start, int32_t* ev_end, int64_t* ev_sum, int64_t* ev_sumsq, int16_t* ev_min, int16_t* ev_max);
+int rd_event_stats_host(const int16_t* raw, const int64_t* read_off, int n_reads, const int32_t* first_step, const int32_t* last_step,
+                        const int64_t* label_off, const int32_t* label_len, const int32_t* align_status, int32_t* ev_start,
+                        int32_t* ev_end, int64_t* ev_sum, int64_t* ev_sumsq, int16_t* ev_min, int16_t* ev_max);
+/* "Resquiggle": the sibling of rd_basecall_raw_global_q that aligns GIVEN labels -- a reference span in decode order, codes 0..3,
+ * ref_len[r] of them at ref_labels + ref_off[r] (0 is valid, a code above 3 is RD_ERR_ARG) -- instead of the read's own call.
+ * Normalisation, forward and assembly as rd_basecall_raw_global (the rows are the ones its beam search would read: the assembled
+ * float64 rows, or a single-coverage read's float32 / f16 rows); NO beam search; then rd_ctc_align_batch's alignment of the labels
+ * against those rows and rd_event_stats on the raw samples, while both are on the device.  Per-base outputs are indexed by ref_off,
+ * score / align_status / read_status per read.  read_status as rd_basecall_raw_global (an empty read is RD_ERR_ARG); a read that
+ * normalisation refuses (read_status 1) is not aligned: RD_CTCALIGN_NO_PATH, score -inf, "no path" outputs.  budget_bytes,
+ * RD_CTCALIGN_TOO_LARGE and RD_ERR_NOMEM as rd_ctc_align_batch. */
+int rd_resquiggle_raw(rd_ctx* ctx, const int16_t* raw, const int64_t* read_off, int n_reads, int outlier_clip, int chunk_len, int step,
+                      const uint8_t* ref_labels, const int64_t* ref_off, const int32_t* ref_len, int64_t budget_bytes,
+                      int32_t* first_step, int32_t* last_step, uint8_t* qual, double* score, int32_t* align_status, int32_t* read_status,
+                      int32_t* ev_start, int32_t* ev_end, int64_t* ev_sum, int64_t* ev_sumsq, int16_t* ev_min, int16_t* ev_max);
+
 /* ---- model evaluation on labelled windows: the reference's val_loss (radian/model.py:77-98, radian/train.py:48-79) ------------
  * Labelled windows as the reference stores them: TFRecord shards of tf.train.Example records (radian/data.py:9-31), read on the
  * HOST without TensorFlow (tfrecord.hip).  Framing: u64 length, u32 masked crc32c of it, the data, u32 masked crc32c of the data;

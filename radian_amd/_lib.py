@@ -89,6 +89,9 @@ SIGNATURES = {
     "rd_ctc_align_batch": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rd_ctc_align_workspace_bytes": (c_i64, [c_i64, c_i64]),
     "rd_basecall_raw_global_q": (c_i, [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_d, c_d, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rd_event_stats": (c_i, [c_vp, c_vp, c_vp, c_i] + [c_vp] * 11),
+    "rd_event_stats_host": (c_i, [c_vp, c_vp, c_i] + [c_vp] * 11),
+    "rd_resquiggle_raw": (c_i, [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_i64] + [c_vp] * 12),
     "rd_tfrecord_open": (c_i, [ctypes.c_char_p, ctypes.POINTER(c_vp)]),
     "rd_tfrecord_open_mem": (c_i, [c_vp, c_sz, ctypes.POINTER(c_vp)]),
     "rd_tfrecord_close": (None, [c_vp]),

@@ -74,6 +74,57 @@ class CtcAlignResult:
         self.first_step, self.last_step, self.qual, self.score, self.status = first_step, last_step, qual, score, status
 
 
+class EventsResult:
+    """per read, one entry per label: start / end (int32: the event's samples [start, end)), n = end - start, sum / sumsq (int64, over the raw
+    int16 samples), min / max (int16).  A read without a path: start = end = -1 and zeros (rd_event_stats)"""
+    __slots__ = ("start", "end", "n", "sum", "sumsq", "min", "max")
+
+    def __init__(self, start, end, sum_, sumsq, min_, max_):
+        self.start, self.end, self.sum, self.sumsq, self.min, self.max = start, end, sum_, sumsq, min_, max_
+        self.n = [e - s for s, e in zip(start, end)]
+
+
+def _event_buffers(tot):
+    return (np.full(tot + 1, -1, dtype=np.int32), np.full(tot + 1, -1, dtype=np.int32), np.zeros(tot + 1, dtype=np.int64),
+            np.zeros(tot + 1, dtype=np.int64), np.zeros(tot + 1, dtype=np.int16), np.zeros(tot + 1, dtype=np.int16))
+
+
+def _events_of(bufs, cut):
+    return EventsResult(*[[b[a:e].copy() for a, e in cut] for b in bufs])
+
+
+def _event_args(raws, aln):
+    flat, off = Backend._pack_raw(raws)
+    n = len(raws)
+    if not (len(aln.first_step) == len(aln.last_step) == len(aln.status) == n):
+        raise ValueError(f"an alignment of {len(aln.status)} sequences for {n} reads")
+    first = [np.ascontiguousarray(x, dtype=np.int32).ravel() for x in aln.first_step]
+    last = [np.ascontiguousarray(x, dtype=np.int32).ravel() for x in aln.last_step]
+    if any(a.shape != b.shape for a, b in zip(first, last)):
+        raise ValueError("first_step and last_step differ in length")
+    label_len = np.array([x.shape[0] for x in first], dtype=np.int32)
+    label_off = np.zeros(n, dtype=np.int64)
+    if n:
+        label_off[1:] = np.cumsum(label_len[:-1].astype(np.int64))
+    tot = int(label_len.astype(np.int64).sum())
+    fbuf, lbuf = np.full(tot + 1, -1, dtype=np.int32), np.full(tot + 1, -1, dtype=np.int32)
+    if tot:
+        fbuf[:tot], lbuf[:tot] = np.concatenate(first), np.concatenate(last)
+    status = np.ascontiguousarray(aln.status, dtype=np.int32)
+    cut = [(int(label_off[i]), int(label_off[i] + label_len[i])) for i in range(n)]
+    return flat, off, n, fbuf, lbuf, label_off, label_len, status, tot, cut
+
+
+def event_stats_host(raws, aln):
+    """Backend.event_stats on the host (rd_event_stats_host: the same boundary code and a plain loop; no GPU, no context)"""
+    L = _lib.load()
+    flat, off, n, fbuf, lbuf, label_off, label_len, status, tot, cut = _event_args(raws, aln)
+    bufs = _event_buffers(tot)
+    if L.rd_event_stats_host(_p(flat), _p(off), n, _p(fbuf), _p(lbuf), _p(label_off), _p(label_len), _p(status), *[_p(b) for b in bufs]) != 0:
+        raise RadianHipError(L.rd_last_error().decode())
+    return _events_of(bufs, cut)
+
+
 # rd_fit_batch per-query status (include/radian_hip.h RD_FIT_*)
 FIT_OK, FIT_EMPTY, FIT_TOO_LARGE = 0, 1, 2
 
@@ -920,6 +971,52 @@ class Backend:
         cut = [(int(label_off[i]), int(label_off[i] + label_len[i])) for i in range(n)]
         return CtcAlignResult([first[a:b].copy() for a, b in cut], [last[a:b].copy() for a, b in cut], [qual[a:b].copy() for a, b in cut],
                               score, status)
+
+    # ------------------------------------------------------------------ signal-to-reference alignment
+    def event_stats(self, raws, aln):
+        """The event table of an alignment whose rows are the reads' samples (rd_event_stats, on the GPU): raws -- one int16 array per read;
+        aln -- a CtcAlignResult with one entry per read (first_step / last_step as sample indices, status).  -> EventsResult."""
+        flat, off, n, fbuf, lbuf, label_off, label_len, status, tot, cut = _event_args(raws, aln)
+        bufs = _event_buffers(tot)
+        self._check(self._L.rd_event_stats(self._h, _p(flat), _p(off), n, _p(fbuf), _p(lbuf), _p(label_off), _p(label_len), _p(status),
+                                           *[_p(b) for b in bufs]))
+        return _events_of(bufs, cut)
+
+    event_stats_host = staticmethod(event_stats_host)
+
+    def resquiggle_raw(self, raws, ref_labels, outlier_clip, chunk_len, step, budget_bytes=0, allow_too_large=False):
+        """Signal-to-reference alignment (rd_resquiggle_raw): raw int16 reads and, per read, the labels to put on its signal (codes 0..3 in
+        decode order) -> (CtcAlignResult, EventsResult, read status), one entry per read; steps and events are sample indices into the read.
+        No beam search.  A read over the alignment budget raises, unless allow_too_large: status CTCALIGN_TOO_LARGE."""
+        flat, off = self._pack_raw(raws)
+        n = len(raws)
+        if len(ref_labels) != n:
+            raise ValueError(f"{len(ref_labels)} label sequences for {n} reads")
+        labs = [np.ascontiguousarray(x, dtype=np.uint8).ravel() for x in ref_labels]
+        ref_len = np.array([x.shape[0] for x in labs], dtype=np.int32)
+        ref_off = np.zeros(n, dtype=np.int64)
+        if n:
+            ref_off[1:] = np.cumsum(ref_len[:-1].astype(np.int64))
+        tot = int(ref_len.astype(np.int64).sum())
+        lbuf = np.zeros(tot + 1, dtype=np.uint8)
+        if tot:
+            lbuf[:tot] = np.concatenate(labs)
+        first = np.full(tot + 1, -1, dtype=np.int32)
+        last = np.full(tot + 1, -1, dtype=np.int32)
+        qual = np.zeros(tot + 1, dtype=np.uint8)
+        score = np.zeros(n, dtype=np.float64)
+        ast = np.zeros(n, dtype=np.int32)
+        rst = np.zeros(n, dtype=np.int32)
+        bufs = _event_buffers(tot)
+        rc = self._L.rd_resquiggle_raw(self._h, _p(flat), _p(off), n, int(outlier_clip), int(chunk_len), int(step), _p(lbuf), _p(ref_off),
+                                       _p(ref_len), int(budget_bytes), _p(first), _p(last), _p(qual), _p(score), _p(ast), _p(rst),
+                                       *[_p(b) for b in bufs])
+        if rc != 0 and not (allow_too_large and rc == -4 and (ast == CTCALIGN_TOO_LARGE).any()):
+            self._check(rc)
+        cut = [(int(ref_off[i]), int(ref_off[i] + ref_len[i])) for i in range(n)]
+        aln = CtcAlignResult([first[a:b].copy() for a, b in cut], [last[a:b].copy() for a, b in cut], [qual[a:b].copy() for a, b in cut],
+                             score, ast)
+        return aln, _events_of(bufs, cut), rst
 
     # ------------------------------------------------------------------ label windows: fitting alignment (radian_amd/label_build.py)
     def fit_batch(self, refs, queries, query_ref, scores=ALIGN_SCORES, budget_bytes=0, allow_too_large=False):

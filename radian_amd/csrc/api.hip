@@ -292,11 +292,10 @@ extern "C" int rd_forward_resident(rd_ctx* ctx, const float* d_windows, int n_wi
 // src_row[r].  Reads some time step of which is covered twice are assembled into one concatenated float64 matrix; the others
 // (single coverage: the forward's rows are consecutive time steps) are decoded straight from their float32 / f16 rows.
 // read_off (nullable): the reads' samples, which the assembled lengths must equal.
-static int global_finish(rd_ctx* ctx, const void* d_probs, int f16, bool streamed, const int32_t* win_off, const int32_t* pad, const int64_t* src_row,
-                         const int64_t* read_off, int n_reads, int chunk_len, int step, int beam_width, int use_lm, double s_thr, double r_thr,
-                         uint8_t* labels_out, const int64_t* label_off, int32_t* label_len, AlignOut* ao = nullptr /* per read, as label_len */)
+// the rows of every read of the batch: classification, and the float64 matrix of the assembled ones in ctx->ws_mat
+static int global_rows(rd_ctx* ctx, const void* d_probs, int f16, bool streamed, const int32_t* win_off, const int32_t* pad, const int64_t* src_row,
+                       const int64_t* read_off, int n_reads, int chunk_len, int step, std::vector<ReadRows>& rr)
 {
-    std::vector<ReadRows> rr;
     const int64_t rows64 = classify_reads(win_off, pad, n_reads, chunk_len, step, 0, rr);
     for (int r = 0; read_off && r < n_reads; r++)
         RD_REQUIRE(rr[r].N == read_off[r + 1] - read_off[r], "internal: assembled length mismatch for read %d", r);
@@ -308,6 +307,16 @@ static int global_finish(rd_ctx* ctx, const void* d_probs, int f16, bool streame
                              ctx->ws_mat.as<double>() + rr[r].row64 * 5, rr[r].N, streamed ? 1 : 0, f16);
         if (rc) return rc;
     }
+    return RD_OK;
+}
+
+static int global_finish(rd_ctx* ctx, const void* d_probs, int f16, bool streamed, const int32_t* win_off, const int32_t* pad, const int64_t* src_row,
+                         const int64_t* read_off, int n_reads, int chunk_len, int step, int beam_width, int use_lm, double s_thr, double r_thr,
+                         uint8_t* labels_out, const int64_t* label_off, int32_t* label_len, AlignOut* ao = nullptr /* per read, as label_len */)
+{
+    std::vector<ReadRows> rr;
+    int rc = global_rows(ctx, d_probs, f16, streamed, win_off, pad, src_row, read_off, n_reads, chunk_len, step, rr);
+    if (rc) return rc;
     // two decode launches: float64 (assembled) reads and float32 (single-coverage) reads
     for (int pass = 0; pass < 2; pass++) {
         std::vector<int64_t> so, lo;
@@ -670,4 +679,96 @@ extern "C" int rd_basecall_raw_global_q(rd_ctx* ctx, const int16_t* raw, const i
                                label_len, &ao);
     if (rc) return rc;
     return ao.too_large ? RD_ERR_NOMEM : RD_OK;   // (rd_last_error names the first read over the budget)
+}
+
+// "Resquiggle": rd_basecall_raw_global_q's rows, GIVEN labels instead of a beam search, and the event table of the alignment
+// (events.hip) from the raw samples normalise_upload left on the device
+extern "C" int rd_resquiggle_raw(rd_ctx* ctx, const int16_t* raw, const int64_t* read_off, int n_reads, int outlier_clip, int chunk_len, int step,
+                                 const uint8_t* ref_labels, const int64_t* ref_off, const int32_t* ref_len, int64_t budget_bytes,
+                                 int32_t* first_step, int32_t* last_step, uint8_t* qual, double* score, int32_t* align_status, int32_t* read_status,
+                                 int32_t* ev_start, int32_t* ev_end, int64_t* ev_sum, int64_t* ev_sumsq, int16_t* ev_min, int16_t* ev_max)
+{
+    RD_REQUIRE(ctx && ref_off && ref_len && score && align_status && read_status, "rd_resquiggle_raw: null argument");
+    RD_REQUIRE(n_reads >= 1, "rd_resquiggle_raw: bad shape");
+    RD_REQUIRE(budget_bytes >= 0, "rd_resquiggle_raw: negative budget");
+    int64_t labs = 0, labs_end = 0;
+    std::vector<int64_t> dlab(n_reads);
+    for (int r = 0; r < n_reads; r++) {
+        RD_REQUIRE(ref_len[r] >= 0 && ref_len[r] < (1 << 29), "rd_resquiggle_raw: read %d has %d labels", r, ref_len[r]);
+        RD_REQUIRE(ref_off[r] >= labs_end, "rd_resquiggle_raw: label offsets must be non-decreasing and the reads' labels must not overlap (read %d)", r);
+        labs_end = ref_off[r] + ref_len[r];
+        dlab[r] = labs;
+        labs += ref_len[r];
+    }
+    RD_REQUIRE(labs == 0 || (ref_labels && first_step && last_step && qual && ev_start && ev_end && ev_sum && ev_sumsq && ev_min && ev_max),
+               "rd_resquiggle_raw: null label or per-base buffer");
+    for (int r = 0; r < n_reads; r++)
+        for (int k = 0; k < ref_len[r]; k++)
+            RD_REQUIRE(ref_labels[ref_off[r] + k] < 4, "rd_resquiggle_raw: label %d of read %d is %d, not in 0..3", k, r, ref_labels[ref_off[r] + k]);
+    int rc = normalise_upload(ctx, raw, read_off, n_reads, outlier_clip, read_status);
+    if (rc) return rc;
+    for (int r = 0; r < n_reads; r++)
+        RD_REQUIRE(read_status[r] != 2, "rd_resquiggle_raw: read %d is empty (the caller skips empty reads, basecall.py:77-82)", r);
+    if ((rc = rd_check_reads_args(ctx, ctx->ws_in.p, read_off, n_reads, chunk_len, step, 1))) return rc;
+    const ReadsPlan* P = nullptr;
+    const TileLists* tl = nullptr;
+    bool streamed = false;
+    if ((rc = get_plan(ctx, read_off, n_reads, chunk_len, step, 1, &P, &tl, &streamed))) return rc;
+    if (ctx->ws_probs.reserve((size_t)P->total_rows * 20)) return RD_ERR_NOMEM;
+    const int f16 = ctx->logits_f16;
+    if ((rc = rd_forward_tiles_dev(ctx, ctx->ws_in.as<float>(), *tl, P->total_rows, ctx->ws_probs.p, 0, f16))) return rc;
+    std::vector<ReadRows> rr;
+    if ((rc = global_rows(ctx, ctx->ws_probs.p, f16, streamed, P->read_win_off.data(), P->valid.data(), P->read_row.data(), read_off, n_reads, chunk_len,
+                          step, rr)))
+        return rc;
+    // the labels, packed
+    if (ctx->ws_labels.reserve((size_t)labs + 16)) return RD_ERR_NOMEM;
+    std::vector<uint8_t> hl((size_t)labs + 16);
+    for (int r = 0; r < n_reads; r++)
+        if (ref_len[r]) memcpy(hl.data() + dlab[r], ref_labels + ref_off[r], (size_t)ref_len[r]);
+    if (labs) RD_HIP(hipMemcpyAsync(ctx->ws_labels.p, hl.data(), (size_t)labs, hipMemcpyHostToDevice, ctx->stream));
+    // two alignment calls: float64 (assembled) reads and float32 / f16 (single-coverage) reads
+    bool too_large = false;
+    for (int r = 0; r < n_reads; r++) {
+        if (read_status[r] == 0) continue;
+        align_status[r] = RD_CTCALIGN_NO_PATH;   // normalisation refused the read: nothing is aligned
+        score[r] = -INFINITY;
+        for (int k = 0; k < ref_len[r]; k++) {
+            first_step[ref_off[r] + k] = last_step[ref_off[r] + k] = -1;
+            qual[ref_off[r] + k] = 0;
+        }
+    }
+    for (int pass = 0; pass < 2; pass++) {
+        std::vector<int64_t> so, lo, oo;
+        std::vector<int32_t> sl, ll;
+        std::vector<int> idx;
+        for (int r = 0; r < n_reads; r++)
+            if (rr[r].is64 == (pass == 0) && read_status[r] == 0) {
+                so.push_back(pass == 0 ? rr[r].row64 : P->read_row[r]);
+                sl.push_back((int32_t)rr[r].N);
+                lo.push_back(dlab[r]);
+                ll.push_back(ref_len[r]);
+                oo.push_back(ref_off[r]);
+                idx.push_back(r);
+            }
+        if (idx.empty()) continue;
+        std::vector<int32_t> ast(idx.size());
+        std::vector<double> asc(idx.size());
+        rc = rd_ctc_align_dev(ctx, ctx->stream, pass == 0 ? (const void*)ctx->ws_mat.p : ctx->ws_probs.p, pass == 0 ? 1 : (f16 ? 2 : 0), so.data(),
+                              sl.data(), (int)idx.size(), ctx->ws_labels.as<uint8_t>(), lo.data(), ll.data(), budget_bytes, first_step, last_step, qual,
+                              oo.data(), asc.data(), ast.data());
+        bool tl_here = false;
+        for (size_t i = 0; i < idx.size(); i++) tl_here |= ast[i] == RD_CTCALIGN_TOO_LARGE;
+        if (rc == RD_ERR_NOMEM && tl_here) too_large = true;
+        else if (rc) return rc;
+        for (size_t i = 0; i < idx.size(); i++) {
+            score[idx[i]] = asc[i];
+            align_status[idx[i]] = ast[i];
+        }
+    }
+    RD_HIP(hipStreamSynchronize(ctx->stream));   // (hl is read by the label upload when nothing was launched)
+    rc = rd_event_stats_steps(ctx, ctx->stream, (const int16_t*)ctx->ws_raw.p, read_off, n_reads, first_step, last_step, ref_off, ref_len, align_status,
+                              labs_end, ev_start, ev_end, ev_sum, ev_sumsq, ev_min, ev_max);
+    if (rc) return rc;
+    return too_large ? RD_ERR_NOMEM : RD_OK;   // (rd_last_error names the first read over the budget)
 }

@@ -197,6 +197,7 @@ struct rd_ctx {
     DevBuf ws_align;                // rd_align_batch (align.hip): one batch of pairs, sized exactly to the batch under the caller's budget
     DevBuf ws_ctc;                  // rd_ctc_* (ctc.hip): window descriptors, labels, per-window results, greedy labels
     DevBuf ws_calign;               // rd_ctc_align_* (ctcalign.hip): a launch's descriptors and results (its DP workspace is ws_align, under the budget)
+    DevBuf ws_events, ws_events_io; // rd_event_stats* (events.hip): a launch's group descriptors; the step and event arrays of a host-pointer call
     int64_t trie_budget = (int64_t)24 << 30;   // bytes of beam-search workspace one launch may ask for (rd_plan_trie_runs; rd_set_trie_budget)
     // pinned host staging
     void* h_stage = nullptr;
@@ -267,6 +268,17 @@ int rd_assemble_dev(rd_ctx* ctx, const void* d_probs, int nW, int T, int pad, in
 int rd_ctc_align_dev(rd_ctx* ctx, hipStream_t st, const void* d_probs, int ptype, const int64_t* seq_off, const int32_t* seq_len, int n_seq,
                      const uint8_t* d_labels, const int64_t* dlab_off, const int32_t* label_len, int64_t budget_bytes, int32_t* first_step,
                      int32_t* last_step, uint8_t* qual, const int64_t* out_off, double* score, int32_t* status);
+// events.hip: the event table of reads whose raw samples and steps are on the device already; read_off, label_off,
+// label_len and align_status are host arrays, every other array is a device pointer indexed as in rd_event_stats.  No argument check: the
+// kernel stays inside the read and inside its own labels whatever the steps say.  Launches on st and waits for it.
+int rd_event_stats_dev(rd_ctx* ctx, hipStream_t st, const int16_t* d_raw, const int64_t* read_off, int n_reads, const int32_t* d_first,
+                       const int32_t* d_last, const int64_t* label_off, const int32_t* label_len, const int32_t* align_status, int32_t* d_start,
+                       int32_t* d_end, int64_t* d_sum, int64_t* d_sumsq, int16_t* d_min, int16_t* d_max);
+// ... with the steps and the event arrays on the host (n_labels: the extent of the label offsets): uploads the steps, runs
+// rd_event_stats_dev and fetches every read's events
+int rd_event_stats_steps(rd_ctx* ctx, hipStream_t st, const int16_t* d_raw, const int64_t* read_off, int n_reads, const int32_t* first_step,
+                         const int32_t* last_step, const int64_t* label_off, const int32_t* label_len, const int32_t* align_status, int64_t n_labels,
+                         int32_t* ev_start, int32_t* ev_end, int64_t* ev_sum, int64_t* ev_sumsq, int16_t* ev_min, int16_t* ev_max);
 // train.hip
 void rd_train_invalidate(rd_ctx* ctx);   // new weights arrived: the next training call re-reads them and zeroes the Adam moments
 void rd_train_destroy(rd_ctx* ctx);
