@@ -43,6 +43,98 @@ def test_ctc_loss_matches_brute_force_over_all_paths():
     assert np.all(g[1] == 0)
 
 
+MUT_DIL = (1, 3)
+MUT_N = 17
+
+
+@pytest.fixture(scope="module")
+def mutation_case():
+    """dilations (1, 3), 17 windows of mixed lengths (one without a label, one with 255, one without a CTC path): the fp64
+    gradient, the yardstick over the batch orders (the one-thread variant apart) and the all-fp32 restatement, each computed once"""
+    torch = pytest.importorskip("torch")
+    from radian_amd import weights
+    w = weights.synthetic_weights(seed=31, head_gain=0.3, dilations=MUT_DIL)
+    x, il, labs = ref.batch_case(32, MUT_N, special=True)
+    assert min(len(l) for l in labs) == 0 and max(len(l) for l in labs) == 255 and len(set(il)) > 2
+    _, _, R = ref.loss_and_grad(w, x, il, labs, MUT_DIL)
+    variants = ref.summation_variants(MUT_N, one_thread=False, flip=ref.relu_candidates(w, x, MUT_DIL))
+    yard = ref.gradient_yardstick(w, x, il, labs, MUT_DIL, variants, ref_grads=R)
+    _, _, R32 = ref.loss_and_grad(w, x, il, labs, MUT_DIL, dtype=torch.float32)
+    old = {k: ref.rel_l2(R32[k], R[k]) for k in R}
+    return dict(w=w, x=x, il=il, labs=labs, R=R, yard=yard, old=old)
+
+
+def _rejected(grads, case, which):
+    """the tensors whose error against fp64 is beyond 4x the yardstick `which`"""
+    return [k for k in case["R"] if ref.rel_l2(grads[k], case["R"][k]) > ref.bound(case[which][k])]
+
+
+def test_the_gradient_bound_has_teeth(mutation_case, capsys):
+    """The fp32-network restatement stands in for a kernel.  Summed in an order the yardstick has not seen it passes 4x the yardstick
+    in every tensor; with one row's dL/dz dropped, with the batch mean taken over n + 1, or with one input_length one short it
+    fails in at least one.  The dropped row passes the bound this project used before (4x the all-fp32 restatement's error, whose
+    fp32 CTC is a hundred times noisier than the fp32 network): that is why the yardstick changed."""
+    c = mutation_case
+    n = MUT_N
+    run = lambda il=c["il"], **kw: ref.loss_and_grad_kernel_arithmetic(c["w"], c["x"], il, c["labs"], MUT_DIL, **kw)[2]
+    right = run(order=[int(i) for i in np.random.default_rng(77).permutation(n)], threads=2)
+    assert _rejected(right, c, "yard") == []
+    k = next(i for i in range(1, n - 1) if c["il"][i] >= 512 and i != n // 2 and len(c["labs"][i]))
+
+    def drop_row(g):
+        g = g.clone()
+        g[k, 200] = 0
+        return g
+
+    short = list(c["il"])
+    short[k] -= 1
+    wrong = {"dropped row": run(z_hook=drop_row), "mean over n + 1": run(z_hook=lambda g: g * (n / (n + 1.0))), "input_length - 1": run(il=short)}
+    counts = {name: (len(_rejected(g, c, "yard")), len(_rejected(g, c, "old"))) for name, g in wrong.items()}
+    with capsys.disabled():
+        print("\n[train] tensors rejected of %d (new bound, old bound): " % len(c["R"]) + ", ".join(f"{k} {a}/{b}" for k, (a, b) in counts.items()))
+    for name, (new, _) in counts.items():
+        assert new >= 1, (name, counts)
+    assert counts["dropped row"][1] == 0, counts
+
+
+def test_the_yardstick_holds_against_itself(mutation_case):
+    """the one-thread run, whose reductions are split differently from every multi-thread run, is inside 4x the yardstick taken
+    without it"""
+    c = mutation_case
+    one = ref.loss_and_grad_kernel_arithmetic(c["w"], c["x"], c["il"], c["labs"], MUT_DIL, threads=1)[2]
+    assert _rejected(one, c, "yard") == []
+
+
+def test_threads_are_restored_and_order_is_only_an_order():
+    torch = pytest.importorskip("torch")
+    from radian_amd import weights
+    w = weights.synthetic_weights(seed=33, head_gain=0.3, dilations=(3,))
+    x, il, labs = ref.batch_case(34, 3)
+    before = torch.get_num_threads()
+    l0, g0, _ = ref.loss_and_grad(w, x, il, labs, (3,))
+    l1, g1, _ = ref.loss_and_grad(w, x, il, labs, (3,), order=[2, 0, 1], threads=1)
+    assert torch.get_num_threads() == before
+    assert l1 == pytest.approx(l0, rel=1e-12) and ref.rel_l2(g1, g0) < 1e-12
+    seen = []
+    ref.loss_and_grad(w, x, il, labs, (3,), order=[2, 0, 1], z_hook=lambda g: (seen.append(g.clone()), g)[1])
+    _, gz = ref.ctc_grad_z(ref.logits(w, x, (3,)), il, labs)
+    assert np.abs(seen[0].numpy() - gz).max() <= 1e-12 * np.abs(gz).max()   # the hook sees rows in the caller's order
+
+
+@pytest.mark.parametrize("dilations", [(3,), (1, 512, 5), (2, 1024, 7), (1, 2, 4, 8) * 4], ids=lambda d: "-".join(map(str, d)))
+def test_reference_probs_against_the_oracle(oracle, dilations):
+    """ref.probs (torch fp64), on which the GPU gradient tests rest, against the C oracle's fp64-accumulating forward on graphs that
+    no other test puts through it: one block, a dilation whose taps lie partly and wholly in the padding, 16 blocks.  The oracle
+    rounds its rows to float32, so 1e-6 is output rounding (rows are at most 1) with room for an ulp or two"""
+    pytest.importorskip("torch")
+    from radian_amd import weights
+    w = weights.synthetic_weights(seed=35, head_gain=0.3, dilations=dilations)
+    x = np.random.default_rng(36).normal(size=(2, 1024)).astype(np.float32)
+    got = ref.probs(w, x, dilations)
+    exp = oracle.tcn_forward(w, x, dilations=dilations, acc64=True)
+    assert np.abs(got - exp).max() <= 1e-6, float(np.abs(got - exp).max())
+
+
 def test_keras_adam_by_hand():
     w, g = np.float32(0.5), np.float32(-0.02)
     m, v = np.float32(0.0), np.float32(0.0)
