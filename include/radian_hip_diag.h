@@ -62,6 +62,22 @@ int rd_pipe_policy_read(rd_ctx* ctx, int beam_width, int on_partition, int use_l
  * their decode partition keeps resident and were searched through the work queue, groups closed at that limit instead }. */
 int rd_pipe_stats(rd_ctx* ctx, int64_t* out, int n);
 
+/* ---- read mapping, stage by stage (map.hip; for tests) -------------------------------------- */
+/* The seed stage of rd_map_index / rd_map_batch alone, through their own kernels: the records (codes 0..3, anything else a break;
+ * offsets[0..n_records] as for rd_map_index) are laid back to back with one break code after each -- record r starts at flat position
+ * offsets[r] + r --, the minimizer kernel flags the (w,k)-minimizers of that image and the compaction returns their flat positions in
+ * ascending order: pos_out[0..min(*n_out, cap)).  Needs no index and leaves the context's index as it is. */
+int rd_map_diag_minimizers(rd_ctx* ctx, const uint8_t* codes, const int64_t* offsets, int64_t n_records, int k, int w, uint32_t* pos_out,
+                           int64_t cap, int64_t* n_out);
+/* The chain stage of rd_map_batch alone, through its own kernels: n anchors (t[i], r[i], q[i]) in strictly ascending (t, r, q) order, every
+ * value below 2^24 (anything else is RD_ERR_ARG), taken as the sorted anchors of read 0 of one launch (key t << 24 | r, value q).  Segment
+ * heads, their compaction and the chain kernel run as in a launch, on a workspace of the same size and layout.  seg_out[5 * s ..] of the
+ * first min(*n_seg_out, cap_seg) segments = { first anchor of the segment (index into the input), score, the chain's first anchor,
+ * its anchor count, its last anchor }, the two anchors as indices within the segment; a segment of fewer than min_anchors anchors has
+ * score = count = 0 (and 0 for both anchors).  n = 0 gives no segment. */
+int rd_map_diag_chain(rd_ctx* ctx, const uint32_t* t, const uint32_t* r, const uint32_t* q, int64_t n, int k, int min_anchors, int max_gap,
+                      int bandwidth, int32_t* seg_out, int64_t cap_seg, int64_t* n_seg_out);
+
 /* ---- kernel timing on the launch stream (HIP events) --------------------------------------- */
 #define RD_TIMER_CONV 0   /* dilated conv 256->256 (MFMA), the dominant kernel */
 #define RD_TIMER_DECODE 1 /* beam search */

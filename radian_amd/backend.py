@@ -1084,6 +1084,29 @@ class Backend:
                      "stage_us": {nm: int(st[8 + i]) for i, nm in enumerate(names)}}
         return MapResult(status[:n], hits[:n], stats)
 
+    def map_diag_minimizers(self, codes, offsets, k, w):
+        """rd_map_diag_minimizers (tests): the device's seed stage alone.  Ascending positions (uint32) of the minimizers in the flat image
+        of the records, where record r starts at offsets[r] + r."""
+        codes, offsets = self._records(codes, offsets)
+        cap = int(offsets[-1]) + len(offsets)
+        pos = np.zeros(cap, dtype=np.uint32)
+        got = ctypes.c_int64(0)
+        self._check(self._L.rd_map_diag_minimizers(self._h, _p(codes), _p(offsets), len(offsets) - 1, int(k), int(w), _p(pos), cap, ctypes.byref(got)))
+        return pos[: got.value].copy()
+
+    def map_diag_chain(self, t, r, q, k, min_anchors=3, max_gap=1000, bandwidth=500):
+        """rd_map_diag_chain (tests): the device's chain stage alone on anchors in strictly ascending (t, r, q) order.  int32 [segments, 5]:
+        the segment's first anchor, score, and the chain's first anchor, anchor count and last anchor (indices within the segment)."""
+        t, r, q = (np.ascontiguousarray(a, dtype=np.uint32).reshape(-1) for a in (t, r, q))
+        n = t.size
+        if r.size != n or q.size != n:
+            raise ValueError("map_diag_chain: t, r and q differ in length")
+        seg = np.zeros((max(n, 1), 5), dtype=np.int32)
+        got = ctypes.c_int64(0)
+        self._check(self._L.rd_map_diag_chain(self._h, _p(t), _p(r), _p(q), n, int(k), int(min_anchors), int(max_gap), int(bandwidth), _p(seg), seg.shape[0],
+                                              ctypes.byref(got)))
+        return seg[: got.value].copy()
+
     @staticmethod
     def map_minimizers(codes, k, w):
         """rd_map_minimizers (host): see backend.map_minimizers"""

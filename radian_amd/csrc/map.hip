@@ -441,6 +441,87 @@ int check_records(const char* who, const uint8_t* codes, const int64_t* off, int
     return RD_OK;
 }
 
+// ---- the anchor workspace of one launch, and the part of a launch that follows the sort (rd_map_batch; rd_map_diag_chain) ---------------
+// layout: keys a | keys b | q a | q b | segment starts | segment results | head flags | block counts | block offsets | the sort's temporary
+struct LaunchWs {
+    uint64_t *ka, *kb;
+    uint32_t *qa, *qb, *seg_start;
+    int4* seg_res;
+    uint8_t* head;
+    uint32_t nb, *bcnt, *boff;
+    void* tmp;
+    size_t sort_bytes, scan_bytes;
+};
+
+// ctx->ws_align for launches of at most max_anchors anchors: exactly that size (DevBuf::reserve would add headroom beyond the budget)
+int reserve_launch_ws(rd_ctx* ctx, const char* who, int64_t max_anchors)
+{
+    const size_t need = (size_t)(max_anchors * MAP_ANCHOR_BYTES + MAP_LAUNCH_BYTES);
+    if (ctx->ws_align.cap >= need) return RD_OK;
+    ctx->ws_align.release();
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, need);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        rd_set_error("%s: hipMalloc(%zu bytes) of the anchor workspace failed: %s", who, need, hipGetErrorString(e));
+        return RD_ERR_NOMEM;
+    }
+    ctx->ws_align.p = p;
+    ctx->ws_align.cap = need;
+    return RD_OK;
+}
+
+int carve_launch_ws(rd_ctx* ctx, const char* who, int64_t A, int end_bit, LaunchWs& W)
+{
+    uint8_t* base = ctx->ws_align.as<uint8_t>();
+    size_t at = 0;
+    auto take = [&](size_t bytes) {
+        uint8_t* p = base + at;
+        at += align_up(bytes, 256);
+        return p;
+    };
+    W.ka = (uint64_t*)take((size_t)A * 8);
+    W.kb = (uint64_t*)take((size_t)A * 8);
+    W.qa = (uint32_t*)take((size_t)A * 4);
+    W.qb = (uint32_t*)take((size_t)A * 4);
+    W.seg_start = (uint32_t*)take((size_t)A * 4);
+    W.seg_res = (int4*)take((size_t)A * 16);
+    W.head = take((size_t)A);
+    W.nb = (uint32_t)((A + CP_PER - 1) / CP_PER);
+    W.bcnt = (uint32_t*)take((size_t)(W.nb + 1) * 4);
+    W.boff = (uint32_t*)take((size_t)(W.nb + 1) * 4);
+    rocprim::double_buffer<uint64_t> dk(W.ka, W.kb);
+    rocprim::double_buffer<uint32_t> dq(W.qa, W.qb);
+    W.sort_bytes = W.scan_bytes = 0;
+    RD_HIP(rocprim::radix_sort_pairs(nullptr, W.sort_bytes, dk, dq, (size_t)A, 0u, (unsigned)end_bit, ctx->stream));
+    RD_HIP(rocprim::exclusive_scan(nullptr, W.scan_bytes, W.bcnt, W.boff, 0u, (size_t)W.nb + 1, rocprim::plus<uint32_t>(), ctx->stream));
+    W.tmp = take(std::max(W.sort_bytes, W.scan_bytes));
+    if (at > ctx->ws_align.cap) {
+        rd_set_error("%s: internal workspace accounting (%zu > %zu for %lld anchors)", who, at, ctx->ws_align.cap, (long long)A);
+        return RD_ERR_STATE;
+    }
+    return RD_OK;
+}
+
+// sorted anchors (keys, qs) -> segment starts and one chain result per segment in W; *n_seg on the host
+int chain_launch(rd_ctx* ctx, const LaunchWs& W, const uint64_t* keys, const uint32_t* qs, int64_t A, int k, int min_anchors, int max_gap, int bandwidth,
+                 uint32_t* n_seg)
+{
+    hipLaunchKernelGGL(segment_flag_kernel, dim3((unsigned)((A + 255) / 256)), dim3(256), 0, ctx->stream, keys, (uint32_t)A, W.head);
+    hipLaunchKernelGGL(compact_count_kernel, dim3(W.nb), dim3(256), 0, ctx->stream, W.head, A, W.bcnt, W.nb);
+    size_t scan_bytes = W.scan_bytes;
+    RD_HIP(rocprim::exclusive_scan(W.tmp, scan_bytes, W.bcnt, W.boff, 0u, (size_t)W.nb + 1, rocprim::plus<uint32_t>(), ctx->stream));
+    hipLaunchKernelGGL(compact_write_kernel, dim3(W.nb), dim3(256), 0, ctx->stream, W.head, A, W.boff, W.seg_start);
+    RD_HIP(hipGetLastError());
+    *n_seg = 0;
+    RD_HIP(hipMemcpyAsync(n_seg, W.boff + W.nb, 4, hipMemcpyDeviceToHost, ctx->stream));
+    RD_HIP(hipStreamSynchronize(ctx->stream));
+    hipLaunchKernelGGL(map_chain_kernel, dim3((*n_seg + 3) / 4), dim3(256), 0, ctx->stream, keys, qs, W.seg_start, *n_seg, (uint32_t)A, k, min_anchors, max_gap,
+                       bandwidth, W.seg_res);
+    RD_HIP(hipGetLastError());
+    return RD_OK;
+}
+
 }   // namespace
 
 void rd_map_destroy(rd_ctx* ctx)
@@ -650,65 +731,29 @@ extern "C" int rd_map_batch(rd_ctx* ctx, const uint8_t* reads, const int64_t* re
         acc += a;
         max_anchors = std::max(max_anchors, acc);
     }
-    const size_t need = (size_t)(max_anchors * MAP_ANCHOR_BYTES + MAP_LAUNCH_BYTES);
-    if (!launches.empty() && ctx->ws_align.cap < need) {
-        ctx->ws_align.release();   // exactly the largest launch (DevBuf::reserve would add headroom beyond the budget)
-        void* p = nullptr;
-        const hipError_t e = hipMalloc(&p, need);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            rd_set_error("rd_map_batch: hipMalloc(%zu bytes) of the anchor workspace failed: %s", need, hipGetErrorString(e));
-            return RD_ERR_NOMEM;
-        }
-        ctx->ws_align.p = p;
-        ctx->ws_align.cap = need;
-    }
+    if (!launches.empty())
+        if (int rc = reserve_launch_ws(ctx, "rd_map_batch", max_anchors)) return rc;
     RD_HIP(hipMemsetAsync(st->out.p, 0, (size_t)n_reads * 9 * 4, ctx->stream));
     int64_t total_anchors = 0, total_segments = 0;
     for (const Launch& L : launches) {
         const int64_t m0 = read_m[L.r0], m1 = read_m[L.r1], a0 = read_a[L.r0], A = read_a[L.r1] - a0;
         const int n_local = (int)(L.r1 - L.r0);
-        // layout: keys a | keys b | q a | q b | segment starts | segment results | head flags | block counts | block offsets | the sort's temporary
-        uint8_t* base = ctx->ws_align.as<uint8_t>();
-        size_t at = 0;
-        auto take = [&](size_t bytes) {
-            uint8_t* p = base + at;
-            at += align_up(bytes, 256);
-            return p;
-        };
-        uint64_t* ka = (uint64_t*)take((size_t)A * 8);
-        uint64_t* kb = (uint64_t*)take((size_t)A * 8);
-        uint32_t* qa = (uint32_t*)take((size_t)A * 4);
-        uint32_t* qb = (uint32_t*)take((size_t)A * 4);
-        uint32_t* seg_start = (uint32_t*)take((size_t)A * 4);
-        int4* seg_res = (int4*)take((size_t)A * 16);
-        uint8_t* head = take((size_t)A);
-        const uint32_t nb = (uint32_t)((A + CP_PER - 1) / CP_PER);
-        uint32_t* bcnt = (uint32_t*)take((size_t)(nb + 1) * 4);
-        uint32_t* boff = (uint32_t*)take((size_t)(nb + 1) * 4);
         int end_bit = 48;
         while (end_bit < 64 && (n_local - 1) >> (end_bit - 48)) end_bit++;
-        rocprim::double_buffer<uint64_t> dk(ka, kb);
-        rocprim::double_buffer<uint32_t> dq(qa, qb);
-        size_t sort_bytes = 0, scan_bytes = 0;
-        RD_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, dk, dq, (size_t)A, 0u, (unsigned)end_bit, ctx->stream));
-        RD_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, bcnt, boff, 0u, (size_t)nb + 1, rocprim::plus<uint32_t>(), ctx->stream));
-        size_t tmp_bytes = std::max(sort_bytes, scan_bytes);
-        void* tmp = take(tmp_bytes);
-        if (at > ctx->ws_align.cap) {
-            rd_set_error("rd_map_batch: internal workspace accounting (%zu > %zu for %lld anchors)", at, ctx->ws_align.cap, (long long)A);
-            return RD_ERR_STATE;
-        }
+        LaunchWs W;
+        if (int rc = carve_launch_ws(ctx, "rd_map_batch", A, end_bit, W)) return rc;
+        rocprim::double_buffer<uint64_t> dk(W.ka, W.kb);
+        rocprim::double_buffer<uint32_t> dq(W.qa, W.qb);
         t0 = now_us();
         hipLaunchKernelGGL(anchor_fill_kernel, dim3((unsigned)((m1 - m0 + 255) / 256)), dim3(256), 0, ctx->stream, st->hit.as<MzHit>(), st->cnt.as<uint64_t>(),
-                           st->scan.as<uint64_t>(), m0, m1, (uint64_t)a0, (uint32_t)L.r0, st->vals.as<uint64_t>(), ka, qa);
+                           st->scan.as<uint64_t>(), m0, m1, (uint64_t)a0, (uint32_t)L.r0, st->vals.as<uint64_t>(), W.ka, W.qa);
         RD_HIP(hipGetLastError());
         if (stats) {
             RD_HIP(hipStreamSynchronize(ctx->stream));
             t_stage[2] += now_us() - t0;
             t0 = now_us();
         }
-        RD_HIP(rocprim::radix_sort_pairs(tmp, sort_bytes, dk, dq, (size_t)A, 0u, (unsigned)end_bit, ctx->stream));
+        RD_HIP(rocprim::radix_sort_pairs(W.tmp, W.sort_bytes, dk, dq, (size_t)A, 0u, (unsigned)end_bit, ctx->stream));
         const uint64_t* keys = dk.current();
         const uint32_t* qs = dq.current();
         if (stats) {
@@ -716,23 +761,14 @@ extern "C" int rd_map_batch(rd_ctx* ctx, const uint8_t* reads, const int64_t* re
             t_stage[3] += now_us() - t0;
             t0 = now_us();
         }
-        hipLaunchKernelGGL(segment_flag_kernel, dim3((unsigned)((A + 255) / 256)), dim3(256), 0, ctx->stream, keys, (uint32_t)A, head);
-        hipLaunchKernelGGL(compact_count_kernel, dim3(nb), dim3(256), 0, ctx->stream, head, A, bcnt, nb);
-        RD_HIP(rocprim::exclusive_scan(tmp, scan_bytes, bcnt, boff, 0u, (size_t)nb + 1, rocprim::plus<uint32_t>(), ctx->stream));
-        hipLaunchKernelGGL(compact_write_kernel, dim3(nb), dim3(256), 0, ctx->stream, head, A, boff, seg_start);
-        RD_HIP(hipGetLastError());
         uint32_t n_seg = 0;
-        RD_HIP(hipMemcpyAsync(&n_seg, boff + nb, 4, hipMemcpyDeviceToHost, ctx->stream));
-        RD_HIP(hipStreamSynchronize(ctx->stream));
-        hipLaunchKernelGGL(map_chain_kernel, dim3((n_seg + 3) / 4), dim3(256), 0, ctx->stream, keys, qs, seg_start, n_seg, (uint32_t)A, k, min_anchors, max_gap,
-                           bandwidth, seg_res);
-        RD_HIP(hipGetLastError());
+        if (int rc = chain_launch(ctx, W, keys, qs, A, k, min_anchors, max_gap, bandwidth, &n_seg)) return rc;
         if (stats) {
             RD_HIP(hipStreamSynchronize(ctx->stream));
             t_stage[4] += now_us() - t0;
             t0 = now_us();
         }
-        hipLaunchKernelGGL(map_best_kernel, dim3((unsigned)((n_local + 255) / 256)), dim3(256), 0, ctx->stream, keys, qs, seg_start, n_seg, seg_res, n_local,
+        hipLaunchKernelGGL(map_best_kernel, dim3((unsigned)((n_local + 255) / 256)), dim3(256), 0, ctx->stream, keys, qs, W.seg_start, n_seg, W.seg_res, n_local,
                            min_anchors, min_score, st->out.as<int32_t>() + L.r0 * 9);
         RD_HIP(hipGetLastError());
         RD_HIP(hipStreamSynchronize(ctx->stream));   // the next launch reuses the workspace
@@ -763,6 +799,81 @@ extern "C" int rd_map_batch(rd_ctx* ctx, const uint8_t* reads, const int64_t* re
                      (long long)((read_a[r + 1] - read_a[r]) * MAP_ANCHOR_BYTES + MAP_LAUNCH_BYTES), (long long)budget_bytes, (long long)too_large,
                      too_large == 1 ? "" : "s");
         return RD_ERR_NOMEM;
+    }
+    return RD_OK;
+}
+
+// ---- diagnostic seams (include/radian_hip_diag.h): the stages above, one at a time, through the same kernels ----------------------------
+extern "C" int rd_map_diag_minimizers(rd_ctx* ctx, const uint8_t* codes, const int64_t* offsets, int64_t n_records, int k, int w, uint32_t* pos_out,
+                                      int64_t cap, int64_t* n_out)
+{
+    RD_REQUIRE(ctx != nullptr && n_out != nullptr && cap >= 0 && (cap == 0 || pos_out != nullptr), "rd_map_diag_minimizers: null argument");
+    RD_REQUIRE(k >= RD_MAP_MIN_K && k <= RD_MAP_MAX_K, "rd_map_diag_minimizers: k = %d (%d..%d)", k, RD_MAP_MIN_K, RD_MAP_MAX_K);
+    RD_REQUIRE(w >= 1 && w <= MAP_MAX_W, "rd_map_diag_minimizers: w = %d (1..%d)", w, MAP_MAX_W);
+    if (int rc = check_records("rd_map_diag_minimizers", codes, offsets, n_records)) return rc;
+    *n_out = 0;
+    if (n_records == 0) return RD_OK;
+    RD_HIP(hipSetDevice(ctx->device));
+    if (!ctx->map) ctx->map = new MapState();   // k = 0: no index; an index that exists keeps its keys and values
+    MapState* st = (MapState*)ctx->map;
+    std::vector<uint8_t> flat;
+    std::vector<int64_t> flat_off;
+    flatten(codes, offsets, n_records, flat, flat_off);
+    int64_t M = 0;
+    if (int rc = minimizers_dev(ctx, st, flat, flat_off, k, w, &M)) return rc;
+    *n_out = M;
+    const int64_t n = std::min(M, cap);
+    if (n > 0) {
+        RD_HIP(hipMemcpyAsync(pos_out, st->pos.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        RD_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return RD_OK;
+}
+
+extern "C" int rd_map_diag_chain(rd_ctx* ctx, const uint32_t* t, const uint32_t* r, const uint32_t* q, int64_t n, int k, int min_anchors, int max_gap,
+                                 int bandwidth, int32_t* seg_out, int64_t cap_seg, int64_t* n_seg_out)
+{
+    RD_REQUIRE(ctx != nullptr && n_seg_out != nullptr && n >= 0 && cap_seg >= 0 && (cap_seg == 0 || seg_out != nullptr), "rd_map_diag_chain: null argument");
+    RD_REQUIRE(n == 0 || (t != nullptr && r != nullptr && q != nullptr), "rd_map_diag_chain: null anchors");
+    RD_REQUIRE(k >= RD_MAP_MIN_K && k <= RD_MAP_MAX_K, "rd_map_diag_chain: k = %d (%d..%d)", k, RD_MAP_MIN_K, RD_MAP_MAX_K);
+    RD_REQUIRE(min_anchors >= 1, "rd_map_diag_chain: min_anchors = %d (at least 1)", min_anchors);
+    RD_REQUIRE(max_gap >= 1 && max_gap < (1 << 24), "rd_map_diag_chain: max_gap = %d (1 .. 2^24 - 1)", max_gap);
+    RD_REQUIRE(bandwidth >= 0 && bandwidth < (1 << 24), "rd_map_diag_chain: bandwidth = %d (0 .. 2^24 - 1)", bandwidth);
+    RD_REQUIRE(n < ((int64_t)1 << 31), "rd_map_diag_chain: %lld anchors (fewer than 2^31)", (long long)n);
+    for (int64_t i = 0; i < n; i++) {
+        RD_REQUIRE(t[i] < (1u << 24) && r[i] < (1u << 24) && q[i] < (1u << 24), "rd_map_diag_chain: anchor %lld is (%u, %u, %u): every value is below 2^24",
+                   (long long)i, t[i], r[i], q[i]);
+        if (i == 0) continue;
+        const bool up = t[i] != t[i - 1] ? t[i] > t[i - 1] : r[i] != r[i - 1] ? r[i] > r[i - 1] : q[i] > q[i - 1];
+        RD_REQUIRE(up, "rd_map_diag_chain: anchor %lld is not above anchor %lld in (t, r, q) order: the anchors come strictly ascending", (long long)i,
+                   (long long)(i - 1));
+    }
+    *n_seg_out = 0;
+    if (n == 0) return RD_OK;
+    RD_HIP(hipSetDevice(ctx->device));
+    if (int rc = reserve_launch_ws(ctx, "rd_map_diag_chain", n)) return rc;
+    LaunchWs W;
+    if (int rc = carve_launch_ws(ctx, "rd_map_diag_chain", n, 48, W)) return rc;   // read 0 of one launch: no bit above 48 in use
+    std::vector<uint64_t> keys((size_t)n);
+    for (int64_t i = 0; i < n; i++) keys[(size_t)i] = ((uint64_t)t[i] << 24) | (uint64_t)r[i];
+    RD_HIP(hipMemcpyAsync(W.ka, keys.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    RD_HIP(hipMemcpyAsync(W.qa, q, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    uint32_t n_seg = 0;
+    if (int rc = chain_launch(ctx, W, W.ka, W.qa, n, k, min_anchors, max_gap, bandwidth, &n_seg)) return rc;
+    std::vector<uint32_t> start(n_seg);
+    std::vector<int32_t> res((size_t)n_seg * 4);
+    RD_HIP(hipMemcpyAsync(start.data(), W.seg_start, (size_t)n_seg * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RD_HIP(hipMemcpyAsync(res.data(), W.seg_res, (size_t)n_seg * 16, hipMemcpyDeviceToHost, ctx->stream));
+    RD_HIP(hipStreamSynchronize(ctx->stream));
+    *n_seg_out = n_seg;
+    for (int64_t s = 0; s < std::min<int64_t>(n_seg, cap_seg); s++) {
+        const int32_t a0 = (int32_t)start[(size_t)s], *v = res.data() + 4 * s;
+        int32_t* o = seg_out + 5 * s;
+        o[0] = a0;
+        o[1] = v[0];
+        o[2] = v[1] - a0;
+        o[3] = v[2];
+        o[4] = v[3] - a0;
     }
     return RD_OK;
 }

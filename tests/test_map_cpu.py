@@ -1,6 +1,6 @@
 """No-GPU checks of read-to-transcript mapping: the library's seed code (rd_map_minimizers, the host twin of the device's) against the
 restatement of the contract (tests/_map_ref.py); the restatement itself against ground truth on the simulated set; the writers and the
-argument checks of radian_amd.map."""
+argument checks of radian_amd.map; what the shared cases of tests/_map_cases.py (the inputs of tests/test_gpu_map_kernels.py) have to contain."""
 import os
 
 import numpy as np
@@ -197,3 +197,112 @@ def test_map_needs_the_gpu_library_only(lib):
     src = open(os.path.join(ROOT, "radian_amd", "map.py")).read()
     for call in ("be.map_index(", "be.map_batch(", "be.fit_batch(", "be.align("):
         assert call in src
+
+
+# ---- the shared cases of tests/_map_cases.py: what they have to contain, from the restatement alone ---------------------------------------
+def test_chain_cases_meet_their_conditions():
+    """The chain set of tests/test_gpu_map_kernels.py is built to make the chain kernel's rarely taken paths common.  These are conditions on
+    the generators, counted with an instrumented copy of _map_ref.chain's loop (_map_cases.steps): an edit that empties a case fails here."""
+    import collections
+    import _map_cases as mc
+    calls = mc.chain_calls()
+    assert sum(len(s) for c in calls for s in c["segs"]) <= 50000
+    assert {c["k"] for c in calls} == {8, 15} and {1, 3, 65} <= {c["min_anchors"] for c in calls}
+    limits = {(c["max_gap"], c["bandwidth"]) for c in calls}
+    assert {(50, 10), (50, 0), (mr.DEFAULTS["max_gap"], mr.DEFAULTS["bandwidth"])} == limits
+    lattices = [c for c in calls if c["name"].startswith("lattice x")]
+    assert [len(c["segs"]) for c in lattices] == list(mc.SEGMENT_COUNTS)
+    assert {len(s) for c in lattices for s in c["segs"]} == set(mc.LENGTHS)
+    assert all({len(s) for s in c["segs"]} == set(mc.LENGTHS) for c in calls if c["min_anchors"] == 65)
+    win, kinds, dds = collections.Counter(), collections.Counter(), set()
+    tied = wrapped = beyond = equal_k = negative = 0
+    for c in calls:
+        k, G, B = c["k"], c["max_gap"], c["bandwidth"]
+        for seg in c["segs"]:
+            assert seg == sorted(set(seg)) and all(0 <= v < 1 << 24 for a in seg for v in a)
+            st, res = mc.steps(seg, k, G, B)
+            assert res == mr.chain(seg, k, G, B)   # the instrumented loop is the restatement's
+            for s in st:
+                li = s["i"] % 64
+                if s["win"] is not None:
+                    win[s["win"]] += 1
+                if len(s["tied"]) >= 2:
+                    tied += 1
+                    wrapped += any(j % 64 > li for j in s["tied"]) and any(j % 64 < li for j in s["tied"])
+                beyond += s["beyond"]
+                equal_k += s["best"] == k
+                negative += s["best"] is not None and s["best"] < 0
+                for dr, dq, ok in s["pairs"]:   # a pair counts at a limit when that limit alone decides it
+                    if ok:
+                        dds.add(abs(dr - dq))
+                    kinds["dq == max_gap"] += dq == G and ok
+                    kinds["dr == max_gap"] += dr == G and ok
+                    kinds["dq == max_gap + 1"] += dq == G + 1 and 0 < dr <= G and abs(dr - dq) <= B
+                    kinds["dr == max_gap + 1"] += dr == G + 1 and 0 < dq <= G and abs(dr - dq) <= B
+                    kinds["|dr - dq| == bandwidth"] += abs(dr - dq) == B and ok
+                    kinds["|dr - dq| == bandwidth + 1"] += abs(dr - dq) == B + 1 and 0 < dq <= G and 0 < dr <= G
+    assert all(win[d] >= 20 for d in range(1, 65)), {d: win[d] for d in range(1, 65) if win[d] < 20}
+    assert max(win) == 64
+    assert tied >= 100 and wrapped >= 30 and beyond >= 100 and equal_k >= 20 and negative >= 20, (tied, wrapped, beyond, equal_k, negative)
+    assert len(kinds) == 6 and all(n >= 20 for n in kinds.values()), kinds
+    assert set(range(1, 11)) <= dds
+
+
+@pytest.mark.parametrize("d", [1, 2, 31, 32, 33, 62, 63, 64, 65, 66])
+def test_planted_far_winners_are_what_they_claim(d):
+    """the probe's only valid predecessor lies exactly d anchors back, the probes fall on every i mod 64, and beyond the look-back (65, 66)
+    the probe starts a chain of its own although its target would have extended it"""
+    import _map_cases as mc
+    (call,) = [c for c in mc.chain_calls() if c["name"] == f"planted d{d}"]
+    seg, probes = mc.planted(d)
+    assert call["segs"] == [seg] and (call["max_gap"], call["bandwidth"]) == (50, 10) and d in mc.PLANTED_D
+    assert sorted(i % 64 for i in probes) == list(range(64))
+    st, (score, first, count, end) = mc.steps(seg, call["k"], 50, 10)
+    for i in probes:
+        assert all(dq <= 0 for dr, dq, ok in st[i]["pairs"][: d - 1])   # the decoys between the probe and its target
+        if d <= 64:
+            assert st[i]["pairs"][d - 1][2] and st[i]["win"] == d and st[i]["valid"] == 1
+        else:
+            assert st[i]["win"] is None and st[i]["valid"] == 0 and st[i]["beyond"]
+    if d <= 64:   # one chain through every target and probe: a probe that misses its target shows in the segment's result
+        assert (first, count, end) == (0, 2 * len(probes), probes[-1])
+    else:
+        assert (first, count, end) == (probes[0], 2, probes[0] + 1 + (d % 2))   # the next target, past the block's extra decoy where it has one
+
+
+@pytest.mark.parametrize("k, w", [(8, 1), (8, 64), (15, 1), (15, 8), (15, 64)])
+def test_minimizer_images_meet_their_conditions(lib, k, w):
+    """sizes, tile edges and whole images as tests/test_gpu_map_kernels.py needs them, and on every image the library's host seed code
+    equals the restatement (record by record, and the restatement on the flat image: a record's end is a break)"""
+    import _map_cases as mc
+    assert (k, w) in mc.SEEDS and len(mc.SEEDS) == 5
+    images = dict(mc.minimizer_images(k, w))
+    flats = {name: mc.flat_image(recs) for name, recs in images.items()}
+    sizes = {len(f) for f, _ in flats.values()}
+    assert {1, k - 1, k, 1023, 1024, 1025, 2047, 2048, 2049, 3072} <= sizes
+    kmer_at = lambda f, p: p + k <= len(f) and (f[p: p + k] <= 3).all()
+    for edge in (1024, 2048):
+        for p in (edge - 1, edge, edge + 1):
+            f, starts = flats[f"segment starts at {p}"]
+            assert starts[1] == p and f[p - 1] == 255 and kmer_at(f, p)
+        for p in (edge - 1, edge):
+            f, _ = flats[f"break at {p}"]
+            assert f[p] == 255 and kmer_at(f, p - k) and kmer_at(f, p + 1)
+        if w > 1:
+            f, _ = flats[f"{w - 1} k-mers across {edge}"]
+            (seg,) = [s for s in mr.kmers(f, k) if s[0][0] < edge <= s[-1][0] + k - 1 and len(s) < w]
+            assert len(seg) == w - 1 and seg[0][0] < edge < seg[-1][0] + k
+        f, _ = flats[f"homopolymer across {edge}"]
+        run = f[edge - (w + k): edge + (w + k)]
+        assert (run == run[0]).all() and run[0] <= 3
+        picked = [p for p, _ in mr.minimizers(f, k, w) if edge - (w + k) <= p < edge + w]
+        assert edge - 1 in picked and edge in picked   # equal hashes: every window's smallest position, on both sides of the edge
+    assert (flats["all breaks"][0] == 255).all() and mr.minimizers(flats["all breaks"][0], k, w) == []
+    if w == 1:
+        f, _ = flats["every k-mer flagged"]
+        assert len(mr.minimizers(f, k, w)) == len(f) - k > 4096
+    for name, recs in images.items():
+        f, starts = flats[name]
+        assert len(f) <= 5001
+        twin = [(s + p, h) for s, rec in zip(starts, recs) for p, h in _twin(rec, k, w)]
+        assert twin == mr.minimizers(f, k, w), (name, k, w)
