@@ -488,6 +488,57 @@ int rd_resquiggle_raw(rd_ctx* ctx, const int16_t* raw, const int64_t* read_off, 
                       int32_t* first_step, int32_t* last_step, uint8_t* qual, double* score, int32_t* align_status, int32_t* read_status,
                       int32_t* ev_start, int32_t* ev_end, int64_t* ev_sum, int64_t* ev_sumsq, int16_t* ev_min, int16_t* ev_max);
 
+/* ---- poly(A) tail estimation: the longest flat stretch of a read's raw samples (polya.hip) ----------------
+ * NO reference behaviour.  A homopolymer of 30..250 A collapses in any CTC decode, so the tail is measured on the raw samples: the
+ * longest run of windows whose spread is small against the read's own MAD.  Integer arithmetic only; met exactly.  Read r is samples
+ * raw + read_off[r] .. read_off[r+1] (T of them).  Parameters (anything outside its range is RD_ERR_ARG):
+ *   win 8..256 (window length); flat_q 1..32767 (spread threshold); use_level 0/1; -2^20 <= lo_q <= hi_q <= 2^20 (level band);
+ *   max_gap 0..1024 (non-flat windows tolerated inside a segment); min_samples >= win; search_limit >= 0 (0: the whole read).
+ *   The _q values are in units of MAD / 256: a threshold of z in mad_normalise's units is q = round(z * 1.4826 * 256).
+ * Per read:
+ *   scale     m2 = the sum of the two middle order statistics of the samples (ranks (T-1)/2 and T/2: twice the median); d4 = the sum
+ *             of the two middle order statistics of |2x - m2| (four times the MAD) -- the order statistics of rd_normalise_reads.
+ *             status, in this order: T == 0 RD_POLYA_EMPTY; d4 == 0 RD_POLYA_MAD_ZERO; T < win RD_POLYA_SHORT
+ *   windows   nw = T / win; window j covers samples [j win, (j+1) win); the last T mod win samples belong to no window.
+ *             S_j = sum x, Q_j = sum x^2, V_j = win Q_j - S_j^2 (>= 0: win^2 times the variance)
+ *   flat      A = win flat_q d4 (below 2^41), thr = floor(A^2 / 2^20) saturated to 2^64 - 1.  Window j is flat iff V_j <= thr -- that is
+ *             sd <= (flat_q / 256) MAD with no rounding anywhere -- and, with use_level, lo_q d4 win <= 512 (2 S_j - win m2) <= hi_q d4 win
+ *   segments  two flat windows i < j with no flat window between them belong to the same segment iff j - i <= max_gap + 1.  A segment
+ *             [a, b] (its first and last flat window) is a CANDIDATE iff (b - a + 1) win >= min_samples and (search_limit == 0 or
+ *             a win < search_limit)
+ *   choice    the candidate with the largest b - a + 1; on a tie the smallest a.  No candidate: RD_POLYA_NONE
+ *   outputs   status; tail_start = a win, tail_end = (b + 1) win; n_flat = the flat windows inside the chosen segment; sum / sumsq over
+ *             all samples of [tail_start, tail_end) (gap windows included); m2, d4; n_candidates.  For any status other than OK the two
+ *             ends are -1 and everything else is 0, except m2 and d4, which are reported whenever T > 0 (not for RD_POLYA_TOO_LARGE)
+ * A read never affects its neighbours; a result does not depend on what else is in the call, on the order of the reads or on the
+ * launches.  RD_ERR_ARG before anything is launched: a null pointer, read offsets that are not monotone, a parameter outside its range.
+ * n_reads == 0 is RD_OK.
+ *   rd_polya_segment        on the GPU; synchronous, uses the context's stream.  budget_bytes: device workspace one launch may take
+ *                           (rd_polya_workspace_bytes per read); 0 = a quarter of the free device memory.  Reads are packed into
+ *                           launches under it in the caller's order; a read that alone exceeds it is not looked at: status
+ *                           RD_POLYA_TOO_LARGE, and the call returns RD_ERR_NOMEM naming it after doing the others
+ *   rd_polya_segment_host   host, no GPU: the same rules (csrc/polya_rules.h) in a plain loop, counting over the keys for the order statistics
+ *   rd_polya_workspace_bytes   2 n_samples + 14 (n_samples / win) + 2048: the samples, 13 B per window (flag, S, Q) and the descriptors
+ *   rd_polya_diag_windows   the first two stages alone, through their own kernels, for stage tests (it changes no result and has no
+ *                           budget): per read m2, d4 and thr; per window S_j, Q_j and the flag, the reads' windows back to back
+ *                           (read r's window 0 at the sum of T / win over the reads before it).  Computed whatever the read's status */
+#define RD_POLYA_OK 0
+#define RD_POLYA_NONE 1
+#define RD_POLYA_MAD_ZERO 2
+#define RD_POLYA_SHORT 3
+#define RD_POLYA_EMPTY 4
+#define RD_POLYA_TOO_LARGE 5
+int rd_polya_segment(rd_ctx* ctx, const int16_t* raw, const int64_t* read_off, int n_reads, int win, int flat_q, int use_level, int lo_q,
+                     int hi_q, int max_gap, int64_t min_samples, int64_t search_limit, int64_t budget_bytes, int32_t* status,
+                     int64_t* tail_start, int64_t* tail_end, int32_t* n_flat, int64_t* sum, int64_t* sumsq, int32_t* m2, int32_t* d4,
+                     int32_t* n_candidates);
+int rd_polya_segment_host(const int16_t* raw, const int64_t* read_off, int n_reads, int win, int flat_q, int use_level, int lo_q, int hi_q,
+                          int max_gap, int64_t min_samples, int64_t search_limit, int32_t* status, int64_t* tail_start, int64_t* tail_end,
+                          int32_t* n_flat, int64_t* sum, int64_t* sumsq, int32_t* m2, int32_t* d4, int32_t* n_candidates);
+int64_t rd_polya_workspace_bytes(int64_t n_samples, int win);
+int rd_polya_diag_windows(rd_ctx* ctx, const int16_t* raw, const int64_t* read_off, int n_reads, int win, int flat_q, int use_level, int lo_q,
+                          int hi_q, int32_t* m2, int32_t* d4, uint64_t* thr, int32_t* win_sum, int64_t* win_sumsq, uint8_t* win_flat);
+
 /* ---- model evaluation on labelled windows: the reference's val_loss (radian/model.py:77-98, radian/train.py:48-79) ------------
  * Labelled windows as the reference stores them: TFRecord shards of tf.train.Example records (radian/data.py:9-31), read on the
  * HOST without TensorFlow (tfrecord.hip).  Framing: u64 length, u32 masked crc32c of it, the data, u32 masked crc32c of the data;

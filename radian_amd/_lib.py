@@ -92,6 +92,10 @@ SIGNATURES = {
     "rd_event_stats": (c_i, [c_vp, c_vp, c_vp, c_i] + [c_vp] * 11),
     "rd_event_stats_host": (c_i, [c_vp, c_vp, c_i] + [c_vp] * 11),
     "rd_resquiggle_raw": (c_i, [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_i64] + [c_vp] * 12),
+    "rd_polya_segment": (c_i, [c_vp, c_vp, c_vp, c_i] + [c_i] * 6 + [c_i64] * 3 + [c_vp] * 9),
+    "rd_polya_segment_host": (c_i, [c_vp, c_vp, c_i] + [c_i] * 6 + [c_i64] * 2 + [c_vp] * 9),
+    "rd_polya_workspace_bytes": (c_i64, [c_i64, c_i]),
+    "rd_polya_diag_windows": (c_i, [c_vp, c_vp, c_vp, c_i] + [c_i] * 5 + [c_vp] * 6),
     "rd_tfrecord_open": (c_i, [ctypes.c_char_p, ctypes.POINTER(c_vp)]),
     "rd_tfrecord_open_mem": (c_i, [c_vp, c_sz, ctypes.POINTER(c_vp)]),
     "rd_tfrecord_close": (None, [c_vp]),

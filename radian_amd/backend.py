@@ -125,6 +125,62 @@ def event_stats_host(raws, aln):
     return _events_of(bufs, cut)
 
 
+# rd_polya_segment per-read status (include/radian_hip.h RD_POLYA_*)
+POLYA_OK, POLYA_NONE, POLYA_MAD_ZERO, POLYA_SHORT, POLYA_EMPTY, POLYA_TOO_LARGE = 0, 1, 2, 3, 4, 5
+POLYA_STATUS_NAMES = ("ok", "none", "mad-zero", "short", "empty", "too-large")
+POLYA_FIELDS = ("status", "tail_start", "tail_end", "n_flat", "sum", "sumsq", "m2", "d4", "n_candidates")
+
+
+def polya_q(z):
+    """a threshold of z in mad_normalise's units as the integer the C ABI takes (units of MAD / 256)"""
+    return int(round(float(z) * 1.4826 * 256))
+
+
+class PolyaParams:
+    """rd_polya_segment's parameters, all integers (the contract is in include/radian_hip.h)"""
+    __slots__ = ("win", "flat_q", "use_level", "lo_q", "hi_q", "max_gap", "min_samples", "search_limit")
+
+    def __init__(self, win=32, flat_q=polya_q(0.12), use_level=0, lo_q=0, hi_q=0, max_gap=2, min_samples=480, search_limit=0):
+        self.win, self.flat_q, self.use_level, self.lo_q, self.hi_q = int(win), int(flat_q), int(use_level), int(lo_q), int(hi_q)
+        self.max_gap, self.min_samples, self.search_limit = int(max_gap), int(min_samples), int(search_limit)
+
+    def args(self):
+        return (self.win, self.flat_q, self.use_level, self.lo_q, self.hi_q, self.max_gap, self.min_samples, self.search_limit)
+
+
+class PolyaResult:
+    """one entry per read: status (int32, POLYA_*), tail_start / tail_end (int64 samples, -1 unless OK), n_flat (int32), sum / sumsq (int64
+    over the samples of the tail), m2 / d4 (int32: twice the median, four times the MAD), n_candidates (int32)"""
+    __slots__ = POLYA_FIELDS
+
+    def __init__(self, n):
+        for name in POLYA_FIELDS:
+            setattr(self, name, np.zeros(n + 1, dtype=np.int64 if name in ("tail_start", "tail_end", "sum", "sumsq") else np.int32))
+
+    def _bufs(self):
+        return [_p(getattr(self, name)) for name in POLYA_FIELDS]
+
+    def _cut(self, n):
+        for name in POLYA_FIELDS:
+            setattr(self, name, getattr(self, name)[:n])
+        return self
+
+
+def polya_segment_host(raws, params):
+    """Backend.polya_segment on the host (rd_polya_segment_host: the same rules in a plain loop; no GPU, no context)"""
+    L = _lib.load()
+    flat, off = Backend._pack_raw(raws)
+    res = PolyaResult(len(raws))
+    if L.rd_polya_segment_host(_p(flat), _p(off), len(raws), *params.args(), *res._bufs()) != 0:
+        raise RadianHipError(L.rd_last_error().decode())
+    return res._cut(len(raws))
+
+
+def polya_workspace_bytes(n_samples, win):
+    """device workspace Backend.polya_segment needs for one read (rd_polya_workspace_bytes)"""
+    return int(_lib.load().rd_polya_workspace_bytes(int(n_samples), int(win)))
+
+
 # rd_fit_batch per-query status (include/radian_hip.h RD_FIT_*)
 FIT_OK, FIT_EMPTY, FIT_TOO_LARGE = 0, 1, 2
 
@@ -971,6 +1027,35 @@ class Backend:
         cut = [(int(label_off[i]), int(label_off[i] + label_len[i])) for i in range(n)]
         return CtcAlignResult([first[a:b].copy() for a, b in cut], [last[a:b].copy() for a, b in cut], [qual[a:b].copy() for a, b in cut],
                               score, status)
+
+    # ------------------------------------------------------------------ poly(A) tail estimation
+    def polya_segment(self, raws, params, budget_bytes=0, allow_too_large=False):
+        """The longest flat segment of every read's raw samples (rd_polya_segment, on the GPU): raws -- one int16 array per read; params --
+        a PolyaParams.  budget_bytes: device workspace per launch, 0 = a quarter of free memory.  A read that does not fit it raises,
+        unless allow_too_large: status POLYA_TOO_LARGE.  -> PolyaResult."""
+        flat, off = self._pack_raw(raws)
+        res = PolyaResult(len(raws))
+        rc = self._L.rd_polya_segment(self._h, _p(flat), _p(off), len(raws), *params.args(), int(budget_bytes), *res._bufs())
+        if rc != 0 and not (allow_too_large and rc == -4 and (res.status == POLYA_TOO_LARGE).any()):
+            self._check(rc)
+        return res._cut(len(raws))
+
+    polya_segment_host = staticmethod(polya_segment_host)
+
+    def polya_diag_windows(self, raws, params):
+        """rd_polya_diag_windows (tests): the scale and window stages alone.  -> (m2, d4 int32 [reads], thr uint64 [reads], per read the
+        int32 S, int64 Q and uint8 flag of its windows)"""
+        flat, off = self._pack_raw(raws)
+        n = len(raws)
+        nw = [int(off[r + 1] - off[r]) // params.win for r in range(n)]
+        woff = np.concatenate([[0], np.cumsum(nw)]).astype(np.int64)
+        tot = int(woff[-1])
+        m2, d4, thr = np.zeros(n + 1, np.int32), np.zeros(n + 1, np.int32), np.zeros(n + 1, np.uint64)
+        S, Q, F = np.zeros(tot + 1, np.int32), np.zeros(tot + 1, np.int64), np.zeros(tot + 1, np.uint8)
+        self._check(self._L.rd_polya_diag_windows(self._h, _p(flat), _p(off), n, params.win, params.flat_q, params.use_level, params.lo_q,
+                                                  params.hi_q, _p(m2), _p(d4), _p(thr), _p(S), _p(Q), _p(F)))
+        cut = [(int(woff[r]), int(woff[r + 1])) for r in range(n)]
+        return m2[:n], d4[:n], thr[:n], [(S[a:b].copy(), Q[a:b].copy(), F[a:b].copy()) for a, b in cut]
 
     # ------------------------------------------------------------------ signal-to-reference alignment (DESIGN.md section 17)
     def event_stats(self, raws, aln):

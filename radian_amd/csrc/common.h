@@ -6,6 +6,8 @@
 #include <string>
 #include <vector>
 
+#include "polya_rules.h"
+
 #define RD_OK 0
 #define RD_ERR_ARG (-1)
 #define RD_ERR_HIP (-2)
@@ -198,6 +200,7 @@ struct rd_ctx {
     DevBuf ws_ctc;                  // rd_ctc_* (ctc.hip): window descriptors, labels, per-window results, greedy labels
     DevBuf ws_calign;               // rd_ctc_align_* (ctcalign.hip): a launch's descriptors and results (its DP workspace is ws_align, under the budget)
     DevBuf ws_events, ws_events_io; // rd_event_stats* (events.hip): a launch's group descriptors; the step and event arrays of a host-pointer call
+    DevBuf ws_polya, ws_polya_io;   // rd_polya_* (polya.hip): a launch's descriptors, scales and window arrays; the per-read results of a host-pointer call
     int64_t trie_budget = (int64_t)24 << 30;   // bytes of beam-search workspace one launch may ask for (rd_plan_trie_runs; rd_set_trie_budget)
     // pinned host staging
     void* h_stage = nullptr;
@@ -279,6 +282,10 @@ int rd_event_stats_dev(rd_ctx* ctx, hipStream_t st, const int16_t* d_raw, const 
 int rd_event_stats_steps(rd_ctx* ctx, hipStream_t st, const int16_t* d_raw, const int64_t* read_off, int n_reads, const int32_t* first_step,
                          const int32_t* last_step, const int64_t* label_off, const int32_t* label_len, const int32_t* align_status, int64_t n_labels,
                          int32_t* ev_start, int32_t* ev_end, int64_t* ev_sum, int64_t* ev_sumsq, int16_t* ev_min, int16_t* ev_max);
+// polya.hip: the flat-segment search of reads whose raw samples are on the device already: read r is samples
+// d_raw + read_off[r] .. read_off[r+1] (read_off is a host array), its result goes to d_out[r] on the device.  No argument check and no
+// budget: one launch of each kernel, on a workspace sized to the reads (ws_polya).  Launches on st and waits for it.
+int rd_polya_segment_dev(rd_ctx* ctx, hipStream_t st, const int16_t* d_raw, const int64_t* read_off, int n_reads, const PaParams& p, PaOut* d_out);
 // train.hip
 void rd_train_invalidate(rd_ctx* ctx);   // new weights arrived: the next training call re-reads them and zeroes the Adam moments
 void rd_train_destroy(rd_ctx* ctx);

@@ -88,3 +88,22 @@ def write_alignment_inputs(path_fasta, path_tsv, ids, refs, reads, line_width=60
         f.write("read_id\ttranscript\tsequence\n")
         for rid, s in zip(ids, refs):
             f.write(f"{rid}\tsynthetic\t{s}\n")
+
+
+def tail_read(rng, leader=400, adapter=600, tail=1500, body=4000, leader_level=800.0, adapter_level=450.0, tail_level=620.0,
+              body_levels=(300.0, 700.0), noise=45.0, tail_noise=2.0):
+    """One synthetic direct-RNA read with a poly(A) tail, in the order the pore sees it (3' first): a leader and an adapter at their own
+    levels with moderate noise, a TAIL of constant level with small noise, then a body of piecewise-constant levels (uniform over
+    body_levels, dwell 8..60 samples, Gaussian noise: the jumps are large against it, and the noise is large against what counts as flat).
+    rng: a numpy Generator.  -> (int16 samples, (tail_start, tail_end)): the tail is samples [tail_start, tail_end)."""
+    parts = [leader_level + noise * rng.standard_normal(leader), adapter_level + noise * rng.standard_normal(adapter),
+             tail_level + tail_noise * rng.standard_normal(tail)]
+    levels = np.empty(body)
+    i = 0
+    while i < body:
+        d = int(rng.integers(8, 61))
+        levels[i:i + d] = rng.uniform(*body_levels)
+        i += d
+    parts.append(levels + noise * rng.standard_normal(body))
+    x = np.clip(np.round(np.concatenate(parts)), -32768, 32767).astype(np.int16)
+    return x, (leader + adapter, leader + adapter + tail)
