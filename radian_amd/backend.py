@@ -193,13 +193,27 @@ class FitResult:
         self.score, self.ref_start, self.ref_end, self.counts, self.status = score, ref_start, ref_end, counts, status
 
 
+def _pack(arrays, dtype, pad=0):
+    """list of arrays -> (their elements as one flat buffer of dtype, int64 offsets [n + 1]); a buffer without elements has `pad` zeros (1
+    where the library wants a pointer it can check)"""
+    arrs = [np.ascontiguousarray(a, dtype=dtype).reshape(-1) for a in arrays]
+    off = np.zeros(len(arrs) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([a.size for a in arrs])
+    return (np.concatenate(arrs) if off[-1] else np.zeros(pad, dtype=dtype)), off
+
+
 def _concat_codes(seqs):
     """list of code sequences (uint8 arrays / bytes / lists) -> (uint8 buffer, int64 offsets [n + 1])"""
-    arrs = [np.ascontiguousarray(np.frombuffer(s, dtype=np.uint8) if isinstance(s, (bytes, bytearray)) else s, dtype=np.uint8).reshape(-1) for s in seqs]
-    off = np.zeros(len(arrs) + 1, dtype=np.int64)
-    np.cumsum([a.size for a in arrs], out=off[1:])
-    buf = np.concatenate(arrs) if off[-1] else np.zeros(1, dtype=np.uint8)
-    return np.ascontiguousarray(buf), off
+    return _pack([np.frombuffer(s, dtype=np.uint8) if isinstance(s, (bytes, bytearray)) else s for s in seqs], np.uint8, pad=1)
+
+
+def _window_labels(labels, lens, nw):
+    """chunk mode's label matrix [n_windows, chunk_len] and lengths [n_windows] -> per read (nw[r] windows) the list of its windows' label arrays"""
+    out, w = [], 0
+    for n in nw:
+        out.append([labels[w + i, : lens[w + i]].copy() for i in range(n)])
+        w += n
+    return out
 
 
 # rd_map_batch per-read status (include/radian_hip.h RD_MAP_*); MAP_EMPTY_SPAN is given by radian_amd.map, never by the library
@@ -355,11 +369,7 @@ class PipeTicket:
         self.wait()
         if self.decode_type == "global":
             return [_labels_of(self.labels, self.off[r], self.lens[r]) for r in range(self.n)], self.status
-        out, w = [], 0
-        for n in self.nw:
-            out.append([self.labels[w + i, : self.lens[w + i]].copy() for i in range(n)])
-            w += n
-        return out, self.status
+        return _window_labels(self.labels, self.lens, self.nw), self.status
 
 
 class Backend:
@@ -575,15 +585,12 @@ class Backend:
     def forward_reads(self, signals, chunk_len, step):
         """sig_model.predict over the windows of whole normalised reads (radian/basecall.py:83-93) through the streamed
         evaluation (rd_forward_reads): -> per read an array [nW, chunk_len, 5] float32 (rows the pad trim drops are zero)"""
-        sigs = [np.ascontiguousarray(s_, dtype=np.float32) for s_ in signals]
-        off = np.zeros(len(sigs) + 1, dtype=np.int64)
-        off[1:] = np.cumsum([s_.shape[0] for s_ in sigs])
-        nws = [self.count_windows(int(s_.shape[0]), chunk_len, step) for s_ in sigs]
+        flat, off = self._pack_reads(signals)
+        nws = [self.count_windows(off[r + 1] - off[r], chunk_len, step) for r in range(len(signals))]
         tot = int(sum(nws))
-        flat = np.concatenate(sigs) if sigs else np.zeros(0, dtype=np.float32)
         out = np.zeros((tot, chunk_len, 5), dtype=np.float32)
         n = ctypes.c_int64(0)
-        self._check(self._L.rd_forward_reads(self._h, _p(flat), _p(off), len(sigs), int(chunk_len), int(step), _p(out), tot, ctypes.byref(n)))
+        self._check(self._L.rd_forward_reads(self._h, _p(flat), _p(off), len(signals), int(chunk_len), int(step), _p(out), tot, ctypes.byref(n)))
         assert n.value == tot
         res, w = [], 0
         for k in nws:
@@ -655,10 +662,7 @@ class Backend:
 
     @staticmethod
     def _pack_reads(signals):
-        sig = [np.ascontiguousarray(x, dtype=np.float32).ravel() for x in signals]
-        off = np.zeros(len(sig) + 1, dtype=np.int64)
-        off[1:] = np.cumsum([x.shape[0] for x in sig])
-        return (np.concatenate(sig) if sig else np.zeros(0, np.float32)), off
+        return _pack(signals, np.float32)
 
     def basecall_reads_chunk(self, signals, chunk_len, step, beam_width):
         """Chunk mode over whole (normalised) reads: returns, per read, the list of per-window label arrays
@@ -670,11 +674,7 @@ class Backend:
         lens = np.zeros(tot, dtype=np.int32)
         self._check(self._L.rd_basecall_reads_chunk(self._h, _p(flat), _p(off), len(signals), int(chunk_len), int(step),
                                                     int(beam_width), _p(labels), _p(lens)))
-        out, w = [], 0
-        for n in nw:
-            out.append([labels[w + i, : lens[w + i]].copy() for i in range(n)])
-            w += n
-        return out
+        return _window_labels(labels, lens, nw)
 
     def basecall_reads_global(self, signals, chunk_len, step, beam_width, use_lm, s_threshold=0.0, r_threshold=0.0):
         """Global mode over whole (normalised) reads (radian/basecall.py:83-109): one label array per read."""
@@ -693,13 +693,7 @@ class Backend:
 
     @staticmethod
     def _pack_raw(raws):
-        sig = [np.ascontiguousarray(x, dtype=np.int16).ravel() for x in raws]
-        off = np.zeros(len(sig) + 1, dtype=np.int64)
-        off[1:] = np.cumsum([x.shape[0] for x in sig])
-        flat = np.concatenate(sig) if sig else np.zeros(0, np.int16)
-        if flat.size == 0:
-            flat = np.zeros(1, np.int16)
-        return flat, off
+        return _pack(raws, np.int16, pad=1)
 
     def normalise_reads(self, raws, outlier_clip):
         """float32(mad_normalise(raw, clip)) per read (radian/preprocess.py:24-49) + status per read (0 ok, 1 MAD zero, 2 empty)."""
@@ -719,11 +713,7 @@ class Backend:
         status = np.zeros(len(raws), dtype=np.int32)
         self._check(self._L.rd_basecall_raw_chunk(self._h, _p(flat), _p(off), len(raws), int(outlier_clip), int(chunk_len), int(step),
                                                   int(beam_width), _p(labels), _p(lens), _p(status)))
-        out, w = [], 0
-        for n in nw:
-            out.append([labels[w + i, : lens[w + i]].copy() for i in range(n)])
-            w += n
-        return out, status
+        return _window_labels(labels, lens, nw), status
 
     def basecall_raw_global(self, raws, outlier_clip, chunk_len, step, beam_width, use_lm, s_threshold=0.0, r_threshold=0.0):
         flat, off = self._pack_raw(raws)
@@ -1144,7 +1134,7 @@ class Backend:
         """Map reads (code sequences 0..3, anything else a break) against the context's index (rd_map_batch): seeds, anchors, chains, the
         best and second-best transcript of every read.  budget_bytes: the anchor workspace of one launch, 0 = a quarter of free memory.  A
         read that does not fit it raises, unless allow_too_large: it then comes back with MAP_TOO_LARGE."""
-        buf, off = _concat_codes(reads) if len(reads) else (np.zeros(1, dtype=np.uint8), np.zeros(1, dtype=np.int64))
+        buf, off = _concat_codes(reads)
         return self.map_batch_flat(buf, off, min_anchors, min_score, max_gap, bandwidth, budget_bytes, allow_too_large, with_stats)
 
     def map_batch_flat(self, buf, off, min_anchors=3, min_score=40, max_gap=1000, bandwidth=500, budget_bytes=0, allow_too_large=False, with_stats=False):

@@ -27,6 +27,7 @@
 // Traceback (align_tb_kernel): one lane per pair; writes the pair's column ops ('M' match, 'X' mismatch, 'D' deletion,
 // 'I' insertion) to its slot of n + m bytes, then clips and counts them (align_clip_count, below).
 #include "common.h"
+#include "budget.h"
 
 #include <algorithm>
 #include <cstring>
@@ -313,60 +314,30 @@ extern "C" int rd_align_batch(rd_ctx* ctx, const uint8_t* refs, const int64_t* r
     RD_REQUIRE(ref_off[n_pairs] == 0 || refs, "rd_align_batch: null refs");
     RD_REQUIRE(read_off[n_pairs] == 0 || reads, "rd_align_batch: null reads");
     RD_HIP(hipSetDevice(ctx->device));
-    if (budget_bytes == 0) {
-        size_t fr = 0, tot = 0;
-        RD_HIP(hipMemGetInfo(&fr, &tot));
-        budget_bytes = (int64_t)((fr + ctx->ws_align.cap) / 4);   // a quarter of what is free (the workspace this context holds counts as free)
-    }
+    if (int rc = rd_resolve_budget(&budget_bytes, ctx->ws_align.cap)) return rc;
     // largest pairs first (load balance of a launch), packed into batches under the budget; a pair that alone exceeds it is
     // reported, not launched
     std::vector<int> order(n_pairs);
     std::iota(order.begin(), order.end(), 0);
     std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return cells[x] > cells[y]; });
-    int too_large = 0, first_too_large = -1;
-    std::vector<std::pair<int, int>> batches;   // [k0, k1) of the launched order
-    std::vector<int> run;
-    run.reserve(n_pairs);
-    int64_t acc = 0, max_batch = 0;
-    for (int p : order) {
+    const BudgetPlan plan = rd_plan_budget(n_pairs, order.data(), budget_bytes, (int64_t)ALN_BATCH_BYTES, false,
+                                           [&](int p, int) { return bytes[p]; }, rd_budget_never_closes);
+    const std::vector<int32_t>& run = plan.run;
+    const int too_large = (int)plan.too_large, first_too_large = (int)plan.first_too_large;
+    for (int p = 0; p < n_pairs; p++) {   // until its batch has run
         status[p] = ALN_TOO_LARGE;
         score[p] = 0;
         for (int c = 0; c < 4; c++) counts[4 * (int64_t)p + c] = 0;
         if (ops_len) ops_len[p] = 0;
-        if (bytes[p] + (int64_t)ALN_BATCH_BYTES > budget_bytes) {
-            if (too_large++ == 0 || p < first_too_large) first_too_large = p;
-            continue;
-        }
-        const int k = (int)run.size();
-        if (batches.empty() || acc + bytes[p] + (int64_t)ALN_BATCH_BYTES > budget_bytes) {
-            batches.push_back({k, k});
-            acc = 0;
-        }
-        run.push_back(p);
-        batches.back().second = k + 1;
-        acc += bytes[p];
-        max_batch = std::max(max_batch, acc + (int64_t)ALN_BATCH_BYTES);
     }
-    if (!batches.empty() && ctx->ws_align.cap < (size_t)max_batch) {
-        // exactly the largest batch (DevBuf::reserve would add headroom beyond the budget)
-        ctx->ws_align.release();
-        void* p = nullptr;
-        const hipError_t e = hipMalloc(&p, (size_t)max_batch);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            rd_set_error("rd_align_batch: hipMalloc(%lld bytes) of the workspace failed: %s", (long long)max_batch, hipGetErrorString(e));
-            return RD_ERR_NOMEM;
-        }
-        ctx->ws_align.p = p;
-        ctx->ws_align.cap = (size_t)max_batch;
-    }
+    if (ctx->ws_align.reserve_exact((size_t)plan.max_bytes, "rd_align_batch")) return RD_ERR_NOMEM;
     const AlnScores sc{match, mismatch, gap_open, gap_extend};
     std::vector<uint8_t> stage;
     std::vector<AlnPair> desc;
     std::vector<int32_t> res;
     std::vector<uint8_t> ops_h;
-    for (auto [k0, k1] : batches) {
-        const int nb = k1 - k0;
+    for (auto [k0, k1] : plan.launches) {
+        const int nb = (int)(k1 - k0);
         const size_t res_at = align_up((size_t)nb * sizeof(AlnPair), 256);
         size_t at = res_at + align_up((size_t)nb * ALN_RES * 4, 256);
         desc.resize(nb);

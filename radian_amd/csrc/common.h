@@ -39,6 +39,7 @@ struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
     int reserve(size_t bytes);
+    int reserve_exact(size_t bytes, const char* who);   // exactly `bytes` when it has to grow (a budgeted workspace); the error names `who`
     void release();
     template <typename T> T* as() const { return (T*)p; }
 };
@@ -196,7 +197,8 @@ struct rd_ctx {
     DevBuf ws_in, ws_probs, ws_mat, ws_seq, ws_nodes_child, ws_nodes_back, ws_labels, ws_misc;
     DevBuf ws_queue;                // the work-queue counter of beam_search_queue_kernel (decode.hip)
     DevBuf ws_wide, ws_wide_slot;   // beam widths above 51 (decode_wide.hip): per-sequence scratch block, per-trie-node slot map
-    DevBuf ws_align;                // rd_align_batch (align.hip): one batch of pairs, sized exactly to the batch under the caller's budget
+    DevBuf ws_align;                // the budgeted workspace of rd_align_batch, rd_fit_batch, rd_ctc_align_*, rd_map_batch and rd_map_diag_chain: one
+                                    // launch at a time, sized exactly to the largest launch under the caller's budget (budget.h, reserve_exact)
     DevBuf ws_ctc;                  // rd_ctc_* (ctc.hip): window descriptors, labels, per-window results, greedy labels
     DevBuf ws_calign;               // rd_ctc_align_* (ctcalign.hip): a launch's descriptors and results (its DP workspace is ws_align, under the budget)
     DevBuf ws_events, ws_events_io; // rd_event_stats* (events.hip): a launch's group descriptors; the step and event arrays of a host-pointer call
@@ -286,6 +288,8 @@ int rd_event_stats_steps(rd_ctx* ctx, hipStream_t st, const int16_t* d_raw, cons
 // d_raw + read_off[r] .. read_off[r+1] (read_off is a host array), its result goes to d_out[r] on the device.  No argument check and no
 // budget: one launch of each kernel, on a workspace sized to the reads (ws_polya).  Launches on st and waits for it.
 int rd_polya_segment_dev(rd_ctx* ctx, hipStream_t st, const int16_t* d_raw, const int64_t* read_off, int n_reads, const PaParams& p, PaOut* d_out);
+// context.hip: budget_bytes == 0 of a budgeted entry point becomes rd_default_budget (budget.h) of the device's free memory and `held`
+int rd_resolve_budget(int64_t* budget_bytes, size_t held);
 // train.hip
 void rd_train_invalidate(rd_ctx* ctx);   // new weights arrived: the next training call re-reads them and zeroes the Adam moments
 void rd_train_destroy(rd_ctx* ctx);

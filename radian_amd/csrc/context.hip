@@ -1,6 +1,7 @@
 // context.hip -- the context of libradian_hip.so: error string, device workspaces, rd_create / rd_destroy, the rd_set_* switches,
 // device-memory helpers and the kernel timers (declared in include/radian_hip.h and radian_hip_diag.h).
 #include "common.h"
+#include "budget.h"
 #include "../../include/radian_hip.h"
 #include "../../include/radian_hip_diag.h"
 
@@ -55,6 +56,34 @@ int DevBuf::reserve(size_t bytes)
     p = np;
     cap = want;
     return 0;
+}
+
+// A workspace that lives under a caller's budget: DevBuf::reserve would add headroom beyond it, so this one takes exactly what the largest
+// launch needs.  It grows on a context's first budgeted call or for a larger batch only; the device is idle before the old block goes
+// (release() itself does not wait, and the block is shared by entry points that run on different streams).
+int DevBuf::reserve_exact(size_t bytes, const char* who)
+{
+    if (cap >= bytes) return 0;
+    (void)hipDeviceSynchronize();
+    release();
+    const hipError_t e = hipMalloc(&p, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        p = nullptr;
+        rd_set_error("%s: hipMalloc(%zu bytes) of the workspace failed: %s", who, bytes, hipGetErrorString(e));
+        return -1;
+    }
+    cap = bytes;
+    return 0;
+}
+
+int rd_resolve_budget(int64_t* budget_bytes, size_t held)
+{
+    if (*budget_bytes != 0) return RD_OK;
+    size_t fr = 0, tot = 0;
+    RD_HIP(hipMemGetInfo(&fr, &tot));
+    *budget_bytes = rd_default_budget(fr, held);
+    return RD_OK;
 }
 
 void DevBuf::release()

@@ -28,6 +28,7 @@
 //                   the 50 thresholds 10^(-k/10).
 // No atomics; a sequence's result does not depend on what else is in its launch.
 #include "common.h"
+#include "budget.h"
 #include "glibc_math.h"
 #include "glibc_tables.h"
 #include "../../include/radian_hip.h"
@@ -359,57 +360,28 @@ int rd_ctc_align_dev(rd_ctx* ctx, hipStream_t st, const void* d_probs, int ptype
     }
     RD_REQUIRE(labs_end == 0 || (d_labels && first_step && last_step && qual), "ctc_align: null label or per-base buffer");
     RD_REQUIRE(d_probs, "ctc_align: null probs");
-    if (budget_bytes == 0) {
-        size_t fr = 0, tot = 0;
-        RD_HIP(hipMemGetInfo(&fr, &tot));
-        budget_bytes = (int64_t)((fr + ctx->ws_align.cap) / 4);   // a quarter of what is free (the workspace this context holds counts as free)
-    }
+    if (int rc = rd_resolve_budget(&budget_bytes, ctx->ws_align.cap)) return rc;
     // launches: the sequences in the caller's order, as many as fit the budget; one that alone exceeds it is reported, not launched
-    int too_large = 0, first_too_large = -1;
-    std::vector<int> run;
-    std::vector<std::pair<int, int>> launches;   // [k0, k1) of run
-    int64_t acc = 0, max_launch = 0;
-    for (int i = 0; i < n_seq; i++) {
-        const int64_t bytes = (int64_t)ca_seq_bytes(seq_len[i], label_len[i]);
-        if (bytes > budget_bytes) {
-            status[i] = CA_TOO_LARGE;
-            score[i] = -INFINITY;
-            for (int k = 0; k < label_len[i]; k++) {
-                first_step[out_off[i] + k] = last_step[out_off[i] + k] = -1;
-                qual[out_off[i] + k] = 0;
-            }
-            if (too_large++ == 0) first_too_large = i;
-            continue;
+    const BudgetPlan plan = rd_plan_budget(n_seq, nullptr, budget_bytes, 0, false,
+                                           [&](int i, int) { return (int64_t)ca_seq_bytes(seq_len[i], label_len[i]); },
+                                           [](int, int, int64_t count, int64_t) { return count >= CA_MAX_LAUNCH; });
+    const std::vector<int32_t>& run = plan.run;
+    const int too_large = (int)plan.too_large, first_too_large = (int)plan.first_too_large;
+    for (int i = 0; i < n_seq; i++) {   // until its launch has run
+        status[i] = CA_TOO_LARGE;
+        score[i] = -INFINITY;
+        for (int k = 0; k < label_len[i]; k++) {
+            first_step[out_off[i] + k] = last_step[out_off[i] + k] = -1;
+            qual[out_off[i] + k] = 0;
         }
-        const int k = (int)run.size();
-        if (launches.empty() || acc + bytes > budget_bytes || k - launches.back().first >= CA_MAX_LAUNCH) {
-            launches.push_back({k, k});
-            acc = 0;
-        }
-        run.push_back(i);
-        launches.back().second = k + 1;
-        acc += bytes;
-        max_launch = std::max(max_launch, acc);
     }
-    if (!launches.empty() && ctx->ws_align.cap < (size_t)max_launch) {
-        RD_HIP(hipStreamSynchronize(st));
-        ctx->ws_align.release();   // exactly the largest launch (DevBuf::reserve would add headroom beyond the budget)
-        void* p = nullptr;
-        const hipError_t e = hipMalloc(&p, (size_t)max_launch);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            rd_set_error("ctc_align: hipMalloc(%lld bytes) of the workspace failed: %s", (long long)max_launch, hipGetErrorString(e));
-            return RD_ERR_NOMEM;
-        }
-        ctx->ws_align.p = p;
-        ctx->ws_align.cap = (size_t)max_launch;
-    }
+    if (ctx->ws_align.reserve_exact((size_t)plan.max_bytes, "ctc_align")) return RD_ERR_NOMEM;
     std::vector<CaSeq> desc;
     std::vector<double> h_score;
     std::vector<int32_t> h_status, h_first, h_last;
     std::vector<uint8_t> h_qual;
-    for (auto [k0, k1] : launches) {
-        const int nb = k1 - k0;
+    for (auto [k0, k1] : plan.launches) {
+        const int nb = (int)(k1 - k0);
         desc.resize(nb);
         size_t at = 0;
         int64_t lab_lo = INT64_MAX, lab_hi = 0, max_T = 0, max_L = 0;

@@ -26,6 +26,7 @@
 // No LDS, no atomics.  A 30-label query takes 16 lanes of B = 2 (94 % of them useful) where one wave of 64 reference rows per pair would
 // keep under a third of its steps; the sweep's n + G - 1 steps cost G - 1 rows of fill, under 2 % at n = 1.5 kb.
 #include "common.h"
+#include "budget.h"
 #include "../../include/radian_hip.h"
 
 #include <algorithm>
@@ -239,67 +240,35 @@ extern "C" int rd_fit_batch(rd_ctx* ctx, const uint8_t* refs, const int64_t* ref
                    (long long)n_refs);
     }
     RD_HIP(hipSetDevice(ctx->device));
-    if (budget_bytes == 0) {
-        size_t fr = 0, tot = 0;
-        RD_HIP(hipMemGetInfo(&fr, &tot));
-        budget_bytes = (int64_t)((fr + ctx->ws_align.cap) / 4);   // a quarter of what is free (the workspace this context holds counts as free)
-    }
+    if (int rc = rd_resolve_budget(&budget_bytes, ctx->ws_align.cap)) return rc;
     // queries in the order of their references (stable), so that a reference is uploaded once per batch and the groups of a wave sweep
     // references of one length; batches are cut where the references and queries gathered so far would pass the budget
-    std::vector<int32_t> order;
-    order.reserve((size_t)n_queries);
-    int64_t too_large = 0, first_too_large = -1;
+    std::vector<int32_t> sorted((size_t)n_queries);
+    std::iota(sorted.begin(), sorted.end(), 0);
+    std::stable_sort(sorted.begin(), sorted.end(), [&](int32_t x, int32_t y) { return query_ref[x] < query_ref[y]; });
+    // a query pays for its reference at the head of a batch and wherever the query before it names another one; empty queries take no part
+    const BudgetPlan plan = rd_plan_budget(n_queries, sorted.data(), budget_bytes, (int64_t)FIT_BATCH_BYTES, false,
+                                           [&](int32_t p, int32_t prev) -> int64_t {
+                                               const int32_t r = query_ref[p];
+                                               if (query_off[p + 1] == query_off[p]) return -1;
+                                               const size_t rb = prev >= 0 && query_ref[prev] == r ? 0 : fit_ref_bytes(ref_off[r + 1] - ref_off[r]);
+                                               return (int64_t)(fit_query_bytes(query_off[p + 1] - query_off[p]) + rb);
+                                           },
+                                           rd_budget_never_closes);
+    const std::vector<int32_t>& order = plan.run;
+    const int64_t too_large = plan.too_large, first_too_large = plan.first_too_large;
     for (int64_t p = 0; p < n_queries; p++) {
-        const int64_t m = query_off[p + 1] - query_off[p], n = ref_off[query_ref[p] + 1] - ref_off[query_ref[p]];
         score[p] = ref_start[p] = ref_end[p] = 0;
         for (int c = 0; c < 4; c++) counts[4 * p + c] = 0;
-        if (m == 0) {
-            status[p] = RD_FIT_EMPTY;
-        } else if ((int64_t)(fit_ref_bytes(n) + fit_query_bytes(m) + FIT_BATCH_BYTES) > budget_bytes) {
-            status[p] = RD_FIT_TOO_LARGE;
-            if (too_large++ == 0) first_too_large = p;
-        } else {
-            status[p] = RD_FIT_TOO_LARGE;   // until its batch has run
-            order.push_back((int32_t)p);
-        }
+        status[p] = query_off[p + 1] == query_off[p] ? RD_FIT_EMPTY : RD_FIT_TOO_LARGE;   // until its batch has run
     }
-    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return query_ref[x] < query_ref[y]; });
-    std::vector<std::pair<size_t, size_t>> batches;   // [k0, k1) of order
-    int64_t acc = 0, max_batch = 0;
-    int32_t last_ref = -1;
-    for (size_t k = 0; k < order.size(); k++) {
-        const int32_t p = order[k], r = query_ref[p];
-        const int64_t qb = (int64_t)fit_query_bytes(query_off[p + 1] - query_off[p]), rb = (int64_t)fit_ref_bytes(ref_off[r + 1] - ref_off[r]);
-        int64_t add = qb + (r != last_ref ? rb : 0);
-        if (batches.empty() || acc + add + (int64_t)FIT_BATCH_BYTES > budget_bytes) {
-            batches.push_back({k, k});
-            acc = 0;
-            add = qb + rb;
-        }
-        batches.back().second = k + 1;
-        acc += add;
-        last_ref = r;
-        max_batch = std::max(max_batch, acc + (int64_t)FIT_BATCH_BYTES);
-    }
-    if (!batches.empty() && ctx->ws_align.cap < (size_t)max_batch) {
-        // exactly the largest batch (DevBuf::reserve would add headroom beyond the budget)
-        ctx->ws_align.release();
-        void* p = nullptr;
-        const hipError_t e = hipMalloc(&p, (size_t)max_batch);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            rd_set_error("rd_fit_batch: hipMalloc(%lld bytes) of the workspace failed: %s", (long long)max_batch, hipGetErrorString(e));
-            return RD_ERR_NOMEM;
-        }
-        ctx->ws_align.p = p;
-        ctx->ws_align.cap = (size_t)max_batch;
-    }
+    if (ctx->ws_align.reserve_exact((size_t)plan.max_bytes, "rd_fit_batch")) return RD_ERR_NOMEM;
     const FitScores sc{match, mismatch, gap_open, gap_extend};
     std::vector<uint8_t> stage;
     std::vector<FitQuery> desc;
     std::vector<int32_t> res;
-    for (auto [k0, k1] : batches) {
-        const size_t nb = k1 - k0;
+    for (auto [k0, k1] : plan.launches) {
+        const size_t nb = (size_t)(k1 - k0);
         // layout: descriptors (sorted by class) | results | references, 4-aligned each | queries
         const size_t res_at = align_up(nb * sizeof(FitQuery), 256);
         size_t at = res_at + align_up(nb * FIT_RES * 4, 256);

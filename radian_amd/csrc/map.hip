@@ -3,6 +3,7 @@
 // (rd_map_index, rd_map_batch; rd_map_minimizers is the host twin of the seed definition).  The contract is in include/radian_hip.h,
 // the shapes and figures in DESIGN.md section 15.  Everything is integer arithmetic: no output depends on how reads are packed.
 #include "common.h"
+#include "budget.h"
 #include "../../include/radian_hip.h"
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -453,24 +454,6 @@ struct LaunchWs {
     size_t sort_bytes, scan_bytes;
 };
 
-// ctx->ws_align for launches of at most max_anchors anchors: exactly that size (DevBuf::reserve would add headroom beyond the budget)
-int reserve_launch_ws(rd_ctx* ctx, const char* who, int64_t max_anchors)
-{
-    const size_t need = (size_t)(max_anchors * MAP_ANCHOR_BYTES + MAP_LAUNCH_BYTES);
-    if (ctx->ws_align.cap >= need) return RD_OK;
-    ctx->ws_align.release();
-    void* p = nullptr;
-    const hipError_t e = hipMalloc(&p, need);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        rd_set_error("%s: hipMalloc(%zu bytes) of the anchor workspace failed: %s", who, need, hipGetErrorString(e));
-        return RD_ERR_NOMEM;
-    }
-    ctx->ws_align.p = p;
-    ctx->ws_align.cap = need;
-    return RD_OK;
-}
-
 int carve_launch_ws(rd_ctx* ctx, const char* who, int64_t A, int end_bit, LaunchWs& W)
 {
     uint8_t* base = ctx->ws_align.as<uint8_t>();
@@ -665,11 +648,7 @@ extern "C" int rd_map_batch(rd_ctx* ctx, const uint8_t* reads, const int64_t* re
     }
     if (n_reads == 0) return RD_OK;
     RD_HIP(hipSetDevice(ctx->device));
-    if (budget_bytes == 0) {
-        size_t fr = 0, tot = 0;
-        RD_HIP(hipMemGetInfo(&fr, &tot));
-        budget_bytes = (int64_t)((fr + ctx->ws_align.cap) / 4);
-    }
+    if (int rc = rd_resolve_budget(&budget_bytes, ctx->ws_align.cap)) return rc;
     const int k = st->k;
     double t_stage[6] = {0, 0, 0, 0, 0, 0};   // seeds, lookup, fill, sort, chain, best
     double t0 = now_us();
@@ -705,34 +684,26 @@ extern "C" int rd_map_batch(rd_ctx* ctx, const uint8_t* reads, const int64_t* re
     RD_HIP(hipMemcpyAsync(read_a.data(), st->ra.p, read_a.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
     RD_HIP(hipStreamSynchronize(ctx->stream));
     t_stage[1] = now_us() - t0;
-    // launches: consecutive reads whose anchors fit the budget together
+    // launches: consecutive reads whose anchors fit the budget together.  A read over the budget closes the launch before it: a launch's
+    // anchors are one range of the scan.  Reads without anchors take no part (RD_MAP_NO_SEED already) and lie inside the launch around them.
+    const auto anchors = [&](int64_t r) { return read_a[r + 1] - read_a[r]; };
+    const BudgetPlan plan = rd_plan_budget(n_reads, nullptr, budget_bytes, MAP_LAUNCH_BYTES, true,
+                                           [&](int r, int) -> int64_t {
+                                               const int64_t a = anchors(r);
+                                               return a == 0 ? -1 : a >= ((int64_t)1 << 31) ? INT64_MAX : a * MAP_ANCHOR_BYTES;
+                                           },
+                                           [&](int r, int r0, int64_t, int64_t acc) {
+                                               return r + 1 - r0 > MAP_MAX_LAUNCH_READS || acc / MAP_ANCHOR_BYTES + anchors(r) >= ((int64_t)1 << 31);
+                                           });
+    const int64_t too_large = plan.too_large, first_too_large = plan.first_too_large;
+    for (int64_t r = 0; r < n_reads; r++)
+        if (anchors(r)) status[r] = RD_MAP_TOO_LARGE;   // until its launch has run
     struct Launch {
         int64_t r0, r1;
     };
     std::vector<Launch> launches;
-    int64_t too_large = 0, first_too_large = -1, acc = 0, max_anchors = 0;
-    bool open = false;   // a read over the budget closes the launch before it: a launch's anchors are one range of the scan
-    for (int64_t r = 0; r < n_reads; r++) {
-        const int64_t a = read_a[r + 1] - read_a[r];
-        if (a == 0) continue;   // RD_MAP_NO_SEED already
-        if (a * MAP_ANCHOR_BYTES + MAP_LAUNCH_BYTES > budget_bytes || a >= ((int64_t)1 << 31)) {
-            status[r] = RD_MAP_TOO_LARGE;
-            if (too_large++ == 0) first_too_large = r;
-            open = false;
-            continue;
-        }
-        if (!open || (acc + a) * MAP_ANCHOR_BYTES + MAP_LAUNCH_BYTES > budget_bytes || r + 1 - launches.back().r0 > MAP_MAX_LAUNCH_READS ||
-            acc + a >= ((int64_t)1 << 31)) {
-            launches.push_back({r, r});
-            acc = 0;
-            open = true;
-        }
-        launches.back().r1 = r + 1;
-        acc += a;
-        max_anchors = std::max(max_anchors, acc);
-    }
-    if (!launches.empty())
-        if (int rc = reserve_launch_ws(ctx, "rd_map_batch", max_anchors)) return rc;
+    for (auto [k0, k1] : plan.launches) launches.push_back({plan.run[k0], plan.run[k1 - 1] + 1});
+    if (ctx->ws_align.reserve_exact((size_t)plan.max_bytes, "rd_map_batch")) return RD_ERR_NOMEM;
     RD_HIP(hipMemsetAsync(st->out.p, 0, (size_t)n_reads * 9 * 4, ctx->stream));
     int64_t total_anchors = 0, total_segments = 0;
     for (const Launch& L : launches) {
@@ -781,7 +752,6 @@ extern "C" int rd_map_batch(rd_ctx* ctx, const uint8_t* reads, const int64_t* re
     RD_HIP(hipStreamSynchronize(ctx->stream));
     for (const Launch& L : launches)
         for (int64_t r = L.r0; r < L.r1; r++) {
-            if (status[r] == RD_MAP_TOO_LARGE) continue;
             status[r] = out[(size_t)r * 9];
             for (int c = 0; c < 8; c++) hits[8 * r + c] = out[(size_t)r * 9 + 1 + c];
         }
@@ -851,7 +821,7 @@ extern "C" int rd_map_diag_chain(rd_ctx* ctx, const uint32_t* t, const uint32_t*
     *n_seg_out = 0;
     if (n == 0) return RD_OK;
     RD_HIP(hipSetDevice(ctx->device));
-    if (int rc = reserve_launch_ws(ctx, "rd_map_diag_chain", n)) return rc;
+    if (ctx->ws_align.reserve_exact((size_t)(n * MAP_ANCHOR_BYTES + MAP_LAUNCH_BYTES), "rd_map_diag_chain")) return RD_ERR_NOMEM;
     LaunchWs W;
     if (int rc = carve_launch_ws(ctx, "rd_map_diag_chain", n, 48, W)) return rc;   // read 0 of one launch: no bit above 48 in use
     std::vector<uint64_t> keys((size_t)n);

@@ -29,6 +29,7 @@
 //                      descending, start ascending) is a workgroup max-reduction; the chosen segment's sums come from S and Q.
 // No floating point, no atomics but the select's LDS histogram, no inline assembly.  A result does not depend on the launch's other reads.
 #include "common.h"
+#include "budget.h"
 #include "polya_rules.h"
 #include "../../include/radian_hip.h"
 
@@ -444,56 +445,34 @@ extern "C" int rd_polya_segment(rd_ctx* ctx, const int16_t* raw, const int64_t* 
     int rc = pa_check_args("rd_polya_segment", raw, read_off, n_reads, p, outs, 9);
     if (rc || n_reads == 0) return rc;
     RD_HIP(hipSetDevice(ctx->device));
-    if (budget_bytes == 0) {
-        size_t fr = 0, tot = 0;
-        RD_HIP(hipMemGetInfo(&fr, &tot));
-        budget_bytes = (int64_t)((fr + ctx->ws_raw.cap + ctx->ws_polya.cap) / 4);   // a quarter of what is free (this context's blocks count as free)
-    }
+    if ((rc = rd_resolve_budget(&budget_bytes, ctx->ws_raw.cap + ctx->ws_polya.cap))) return rc;   // (this context's blocks count as free)
     // launches: the reads in the caller's order, as many as fit the budget; a read that alone exceeds it is reported, not launched
-    int first_too_large = -1, too_large = 0;
-    std::vector<int> members;
+    const BudgetPlan plan = rd_plan_budget(n_reads, nullptr, budget_bytes, 0, false,
+                                           [&](int r, int) { return rd_polya_workspace_bytes(read_off[r + 1] - read_off[r], win); },
+                                           rd_budget_never_closes);
+    const int too_large = (int)plan.too_large, first_too_large = (int)plan.first_too_large;
+    for (int r = 0; r < n_reads; r++)   // until its launch has run
+        pa_scatter(PaOut{-1, -1, 0, 0, PA_TOO_LARGE, 0, 0, 0, 0, 0}, r, status, tail_start, tail_end, n_flat, sum, sumsq, m2, d4, n_candidates);
     std::vector<int64_t> off;
     std::vector<PaOut> got;
     hipStream_t st = ctx->stream;
-    const auto launch = [&]() -> int {
-        const int n = (int)members.size();
-        if (n == 0) return RD_OK;
+    for (auto [k0, k1] : plan.launches) {
+        const int n = (int)(k1 - k0);
+        const int32_t* members = plan.run.data() + k0;
+        off.assign(1, 0);
+        for (int i = 0; i < n; i++) off.push_back(off.back() + read_off[members[i] + 1] - read_off[members[i]]);
         if (ctx->ws_raw.reserve((size_t)off[n] * 2 + 16) || ctx->ws_polya_io.reserve((size_t)n * sizeof(PaOut))) return RD_ERR_NOMEM;
         for (int i = 0, k; i < n; i = k) {   // one copy per run of consecutive reads (their samples are contiguous on both sides)
             for (k = i + 1; k < n && members[k] == members[k - 1] + 1; k++) {}
             const int64_t T = off[k] - off[i];
             if (T) RD_HIP(hipMemcpyAsync(ctx->ws_raw.as<int16_t>() + off[i], raw + read_off[members[i]], (size_t)T * 2, hipMemcpyHostToDevice, st));
         }
-        const int rc2 = rd_polya_segment_dev(ctx, st, ctx->ws_raw.as<int16_t>(), off.data(), n, p, ctx->ws_polya_io.as<PaOut>());
-        if (rc2) return rc2;
+        if ((rc = rd_polya_segment_dev(ctx, st, ctx->ws_raw.as<int16_t>(), off.data(), n, p, ctx->ws_polya_io.as<PaOut>()))) return rc;
         got.resize(n);
         RD_HIP(hipMemcpyAsync(got.data(), ctx->ws_polya_io.p, (size_t)n * sizeof(PaOut), hipMemcpyDeviceToHost, st));
         RD_HIP(hipStreamSynchronize(st));
         for (int i = 0; i < n; i++) pa_scatter(got[i], members[i], status, tail_start, tail_end, n_flat, sum, sumsq, m2, d4, n_candidates);
-        members.clear();
-        return RD_OK;
-    };
-    int64_t acc = 0;
-    for (int r = 0; r < n_reads; r++) {
-        const int64_t T = read_off[r + 1] - read_off[r], bytes = rd_polya_workspace_bytes(T, win);
-        if (bytes > budget_bytes) {
-            pa_scatter(PaOut{-1, -1, 0, 0, PA_TOO_LARGE, 0, 0, 0, 0, 0}, r, status, tail_start, tail_end, n_flat, sum, sumsq, m2, d4, n_candidates);
-            if (first_too_large < 0) first_too_large = r;
-            too_large++;
-            continue;
-        }
-        if (!members.empty() && acc + bytes > budget_bytes) {
-            if ((rc = launch())) return rc;
-        }
-        if (members.empty()) {
-            acc = 0;
-            off.assign(1, 0);
-        }
-        members.push_back(r);
-        off.push_back(off.back() + T);
-        acc += bytes;
     }
-    if ((rc = launch())) return rc;
     if (too_large) {
         rd_set_error("rd_polya_segment: read %d (%lld samples) needs %lld bytes of workspace, over the budget of %lld; %d read(s) not segmented "
                      "(status RD_POLYA_TOO_LARGE), the others were", first_too_large, (long long)(read_off[first_too_large + 1] - read_off[first_too_large]),

@@ -702,6 +702,27 @@ def test_tile_planner_properties_under_address_sanitizer(tmp_path):
     assert r.returncode == 0 and b"every property holds" in r.stdout, (r.stdout.decode()[-800:], r.stderr.decode()[-3000:])
 
 
+def test_budget_cutter_properties_under_address_sanitizer(tmp_path):
+    """csrc/budget.h -- the one cutter that packs the items of rd_align_batch, rd_fit_batch, rd_ctc_align_*, rd_map_batch and
+    rd_polya_segment into launches under the caller's device-memory budget -- compiled for the CPU with -fsanitize=address,undefined and
+    checked on 4000 seeded random instances of each entry point's configuration (tests/asan_budget.cpp): the launches tile the launched
+    items in order, every launch fits the budget, none ends early, the largest launch is reported exactly, exactly the items over the budget
+    alone are too large and the lowest index among them is reported, no launch spans a too-large item where those close one; and the
+    launches equal, instance by instance, those of the five loops the cutter replaced (kept in the test program as the yardstick)."""
+    import shutil
+    import subprocess
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not available")
+    exe = tmp_path / "asan_budget"
+    r = subprocess.run(["g++", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g", "-O1", "-std=c++17",
+                        os.path.join(ROOT, "tests", "asan_budget.cpp"), "-o", str(exe)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    if r.returncode != 0 and b"sanitize" in r.stderr and b"cannot find" in r.stderr:
+        pytest.skip("the sanitizer runtimes are not installed")
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    r = subprocess.run([str(exe), "4000"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert r.returncode == 0 and b"every property holds" in r.stdout and b"no sanitizer report" in r.stdout, (r.stdout.decode()[-800:], r.stderr.decode()[-3000:])
+
+
 def test_host_budget_placement_rule(tmp_path, monkeypatch):
     """radian_amd/hostbudget.py: every local rank gets a disjoint, contiguous share of the usable cores -- the cores of
     its GPU's NUMA node when the (fake) sysfs tells -- and sizes its threads from the share: eight chunk-mode ranks on 64 cores start 8 x 6
