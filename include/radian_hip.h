@@ -539,6 +539,56 @@ int64_t rd_polya_workspace_bytes(int64_t n_samples, int win);
 int rd_polya_diag_windows(rd_ctx* ctx, const int16_t* raw, const int64_t* read_off, int n_reads, int win, int flat_q, int use_level, int lo_q,
                           int hi_q, int32_t* m2, int32_t* d4, uint64_t* thr, int32_t* win_sum, int64_t* win_sumsq, uint8_t* win_flat);
 
+/* ---- two-sample site comparison of event tables (sitecmp.hip) --------------------------------------------
+ * NO reference behaviour.  The events of two samples (cond 0: e.g. native, cond 1: e.g. in-vitro transcribed) are put side by side
+ * transcript position by transcript position, one channel (level or dwell) per call.  Integer arithmetic only; met exactly.
+ * Event i: site[i] (< n_sites), cond[i] (0 or 1), value[i] (int16).  One output entry per DISTINCT site with at least one event, in
+ * ascending site order (*n_out of them, at most `capacity`: the entries the output arrays hold; n, sum, sumsq, vmin, vmax and med2 hold
+ * two values per entry, [entry][cond]).  With a / b the sorted values of sample 0 / 1 of the site and n0, n1 their counts:
+ *   out_site  the site
+ *   n         n0, n1
+ *   sum, sumsq   over the values of each sample
+ *   vmin, vmax   of each sample
+ *   med2      the sum of the two middle order statistics of each sample (ranks (n-1)/2 and n/2): twice the median
+ *   u2        sum over x in a of ( 2 #{y in b : y < x} + #{y in b : y = x} ): twice the Mann-Whitney U of sample 0
+ *   ks_num    max over the values x present in either sample of | #{a <= x} n1 - #{b <= x} n0 |: n0 n1 times the Kolmogorov-Smirnov D
+ *   ks_x      the SMALLEST x that attains that maximum
+ *   tie       sum over the values x of t^3 - t, t the multiplicity of x in both samples together
+ *   status    RD_SITE_ONE_SIDED  n0 == 0 or n1 == 0; otherwise
+ *             RD_SITE_DEEP       n0 + n1 > 2^20 (moments, vmin, vmax and med2 are still filled); otherwise RD_SITE_OK
+ *             RD_SITE_TOO_LARGE  the site alone exceeds the budget: only out_site and n are filled
+ * Fields of an absent sample are 0; the rank fields u2, ks_num, ks_x and tie are 0 unless the status is RD_SITE_OK.
+ * Bounds: with |value| <= 2^15 and n0 + n1 <= 2^20 (the rank fields), sumsq < 2^61 (for any n below 2^31), tie <= 2^60, u2 <= 2^39,
+ * ks_num <= 2^38; ks_num << 16 | (65535 - (ks_x + 32768)), the word the kernels take the maximum of, is below 2^55.  No field overflows.
+ * A site never affects another; a result does not depend on the order of the events, on what else is in the call or on the launches.
+ * RD_ERR_ARG before anything is launched: a null pointer, n_events > 2^31 - 1, a site >= n_sites, a cond > 1, a capacity below the
+ * number of distinct sites.  n_events == 0 is RD_OK with *n_out = 0.
+ *   rd_site_compare         on the GPU; synchronous, uses the context's stream.  budget_bytes: device workspace one launch may take
+ *                           (rd_site_workspace_bytes of a site's events); 0 = a quarter of the free device memory.  Sites are packed
+ *                           into launches under it in ascending order; a site that alone exceeds it is not looked at: status
+ *                           RD_SITE_TOO_LARGE, and the call returns RD_ERR_NOMEM naming it after doing the others
+ *   rd_site_compare_host    host, no GPU: the same rules (csrc/site_rules.h) over std::sort and plain loops
+ *   rd_site_workspace_bytes   160 n_events: 31 B per event (its three inputs, two key buffers, head flag and scan) and up to 124 B per
+ *                           site (a site has at least one event); the remainder stands for the sort's temporary storage, which is
+ *                           sized by the sort's own query
+ *   rd_site_diag_segments   the pack, sort and segment stages alone, through the same kernels, for stage tests (it changes no result
+ *                           and has no budget): the sorted keys site << 17 | cond << 16 | (value + 32768) [n_events] and per segment
+ *                           (site, start, split, end) as int64 [capacity][4]: the site's keys are [start, end) of the sorted keys,
+ *                           sample 1 begins at split */
+#define RD_SITE_OK 0
+#define RD_SITE_ONE_SIDED 1
+#define RD_SITE_DEEP 2
+#define RD_SITE_TOO_LARGE 3
+int rd_site_compare(rd_ctx* ctx, const uint32_t* site, const uint8_t* cond, const int16_t* value, int64_t n_events, uint32_t n_sites,
+                    int64_t budget_bytes, int64_t capacity, uint32_t* out_site, int32_t* status, int64_t* n, int64_t* sum, int64_t* sumsq,
+                    int32_t* vmin, int32_t* vmax, int32_t* med2, int64_t* u2, int64_t* ks_num, int32_t* ks_x, int64_t* tie, int64_t* n_out);
+int rd_site_compare_host(const uint32_t* site, const uint8_t* cond, const int16_t* value, int64_t n_events, uint32_t n_sites, int64_t capacity,
+                         uint32_t* out_site, int32_t* status, int64_t* n, int64_t* sum, int64_t* sumsq, int32_t* vmin, int32_t* vmax,
+                         int32_t* med2, int64_t* u2, int64_t* ks_num, int32_t* ks_x, int64_t* tie, int64_t* n_out);
+int64_t rd_site_workspace_bytes(int64_t n_events);
+int rd_site_diag_segments(rd_ctx* ctx, const uint32_t* site, const uint8_t* cond, const int16_t* value, int64_t n_events, uint32_t n_sites,
+                          int64_t capacity, uint64_t* sorted_keys, int64_t* segments, int64_t* n_segments);
+
 /* ---- model evaluation on labelled windows: the reference's val_loss (radian/model.py:77-98, radian/train.py:48-79) ------------
  * Labelled windows as the reference stores them: TFRecord shards of tf.train.Example records (radian/data.py:9-31), read on the
  * HOST without TensorFlow (tfrecord.hip).  Framing: u64 length, u32 masked crc32c of it, the data, u32 masked crc32c of the data;

@@ -13,6 +13,7 @@ c_d = ctypes.c_double
 c_dp = ctypes.POINTER(ctypes.c_double)
 c_fp = ctypes.POINTER(ctypes.c_float)
 c_u8p = ctypes.POINTER(ctypes.c_uint8)
+c_u32 = ctypes.c_uint32
 c_vp = ctypes.c_void_p
 c_sz = ctypes.c_size_t
 
@@ -96,6 +97,10 @@ SIGNATURES = {
     "rd_polya_segment_host": (c_i, [c_vp, c_vp, c_i] + [c_i] * 6 + [c_i64] * 2 + [c_vp] * 9),
     "rd_polya_workspace_bytes": (c_i64, [c_i64, c_i]),
     "rd_polya_diag_windows": (c_i, [c_vp, c_vp, c_vp, c_i] + [c_i] * 5 + [c_vp] * 6),
+    "rd_site_compare": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i64, c_u32, c_i64, c_i64] + [c_vp] * 13),
+    "rd_site_compare_host": (c_i, [c_vp, c_vp, c_vp, c_i64, c_u32, c_i64] + [c_vp] * 13),
+    "rd_site_workspace_bytes": (c_i64, [c_i64]),
+    "rd_site_diag_segments": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i64, c_u32, c_i64, c_vp, c_vp, c_vp]),
     "rd_tfrecord_open": (c_i, [ctypes.c_char_p, ctypes.POINTER(c_vp)]),
     "rd_tfrecord_open_mem": (c_i, [c_vp, c_sz, ctypes.POINTER(c_vp)]),
     "rd_tfrecord_close": (None, [c_vp]),

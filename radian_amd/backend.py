@@ -181,6 +181,59 @@ def polya_workspace_bytes(n_samples, win):
     return int(_lib.load().rd_polya_workspace_bytes(int(n_samples), int(win)))
 
 
+# rd_site_compare per-site status (include/radian_hip.h RD_SITE_*)
+SITE_OK, SITE_ONE_SIDED, SITE_DEEP, SITE_TOO_LARGE = 0, 1, 2, 3
+SITE_STATUS_NAMES = ("ok", "one-sided", "deep", "too-large")
+SITE_FIELDS = ("out_site", "status", "n", "sum", "sumsq", "vmin", "vmax", "med2", "u2", "ks_num", "ks_x", "tie")
+_SITE_DTYPES = {"out_site": np.uint32, "status": np.int32, "n": np.int64, "sum": np.int64, "sumsq": np.int64, "vmin": np.int32, "vmax": np.int32,
+                "med2": np.int32, "u2": np.int64, "ks_num": np.int64, "ks_x": np.int32, "tie": np.int64}
+_SITE_PAIRS = ("n", "sum", "sumsq", "vmin", "vmax", "med2")
+
+
+class SiteResult:
+    """one entry per distinct site, ascending: out_site (uint32), status (int32, SITE_*), n / sum / sumsq (int64 [sites, 2]: sample 0 and
+    1), vmin / vmax / med2 (int32 [sites, 2]; med2 is twice the median), u2 / ks_num / tie (int64), ks_x (int32).  include/radian_hip.h"""
+    __slots__ = SITE_FIELDS
+
+    def __init__(self, cap):
+        for name in SITE_FIELDS:
+            setattr(self, name, np.zeros((cap + 1, 2) if name in _SITE_PAIRS else cap + 1, dtype=_SITE_DTYPES[name]))
+
+    def _bufs(self):
+        return [_p(getattr(self, name)) for name in SITE_FIELDS]
+
+    def _cut(self, n):
+        for name in SITE_FIELDS:
+            setattr(self, name, getattr(self, name)[:n])
+        return self
+
+
+def _site_args(site, cond, value, capacity):
+    site = np.ascontiguousarray(site, dtype=np.uint32).ravel()
+    cond = np.ascontiguousarray(cond, dtype=np.uint8).ravel()
+    value = np.ascontiguousarray(value, dtype=np.int16).ravel()
+    if not site.shape == cond.shape == value.shape:
+        raise ValueError("site, cond and value differ in length")
+    if capacity is None:
+        capacity = int(np.unique(site).shape[0])
+    return site, cond, value, int(capacity)
+
+
+def site_compare_host(site, cond, value, n_sites, capacity=None):
+    """Backend.site_compare on the host (rd_site_compare_host: the same rules over std::sort and plain loops; no GPU, no context)"""
+    L = _lib.load()
+    site, cond, value, capacity = _site_args(site, cond, value, capacity)
+    res, n_out = SiteResult(capacity), ctypes.c_int64(0)
+    if L.rd_site_compare_host(_p(site), _p(cond), _p(value), site.shape[0], int(n_sites), capacity, *res._bufs(), ctypes.byref(n_out)) != 0:
+        raise RadianHipError(L.rd_last_error().decode())
+    return res._cut(n_out.value)
+
+
+def site_workspace_bytes(n_events):
+    """device workspace Backend.site_compare needs for a site of n_events events (rd_site_workspace_bytes)"""
+    return int(_lib.load().rd_site_workspace_bytes(int(n_events)))
+
+
 # rd_fit_batch per-query status (include/radian_hip.h RD_FIT_*)
 FIT_OK, FIT_EMPTY, FIT_TOO_LARGE = 0, 1, 2
 
@@ -1046,6 +1099,31 @@ class Backend:
                                                   params.hi_q, _p(m2), _p(d4), _p(thr), _p(S), _p(Q), _p(F)))
         cut = [(int(woff[r]), int(woff[r + 1])) for r in range(n)]
         return m2[:n], d4[:n], thr[:n], [(S[a:b].copy(), Q[a:b].copy(), F[a:b].copy()) for a, b in cut]
+
+    # ------------------------------------------------------------------ two-sample site comparison
+    def site_compare(self, site, cond, value, n_sites, budget_bytes=0, capacity=None, allow_too_large=False):
+        """Both samples' events side by side, site by site (rd_site_compare, on the GPU): site uint32 (< n_sites), cond uint8 (0 / 1), value
+        int16, one entry per event.  capacity: entries the outputs hold (default: the number of distinct sites).  budget_bytes: device
+        workspace per launch, 0 = a quarter of free memory.  A site that does not fit it raises, unless allow_too_large: status
+        SITE_TOO_LARGE.  -> SiteResult."""
+        site, cond, value, capacity = _site_args(site, cond, value, capacity)
+        res, n_out = SiteResult(capacity), ctypes.c_int64(0)
+        rc = self._L.rd_site_compare(self._h, _p(site), _p(cond), _p(value), site.shape[0], int(n_sites), int(budget_bytes), capacity, *res._bufs(),
+                                     ctypes.byref(n_out))
+        if rc != 0 and not (allow_too_large and rc == -4 and (res.status[:n_out.value] == SITE_TOO_LARGE).any()):
+            self._check(rc)
+        return res._cut(n_out.value)
+
+    site_compare_host = staticmethod(site_compare_host)
+
+    def site_diag_segments(self, site, cond, value, n_sites):
+        """rd_site_diag_segments (tests): the pack, sort and segment stages alone.  -> (sorted keys uint64 [events], segments int64 [sites, 4]:
+        site, start, split, end)"""
+        site, cond, value, capacity = _site_args(site, cond, value, None)
+        keys, segs, n_seg = np.zeros(site.shape[0] + 1, np.uint64), np.zeros((capacity + 1, 4), np.int64), ctypes.c_int64(0)
+        self._check(self._L.rd_site_diag_segments(self._h, _p(site), _p(cond), _p(value), site.shape[0], int(n_sites), capacity, _p(keys), _p(segs),
+                                                  ctypes.byref(n_seg)))
+        return keys[:site.shape[0]], segs[:n_seg.value]
 
     # ------------------------------------------------------------------ signal-to-reference alignment (DESIGN.md section 17)
     def event_stats(self, raws, aln):

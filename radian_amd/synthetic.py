@@ -107,3 +107,27 @@ def tail_read(rng, leader=400, adapter=600, tail=1500, body=4000, leader_level=8
     parts.append(levels + noise * rng.standard_normal(body))
     x = np.clip(np.round(np.concatenate(parts)), -32768, 32767).astype(np.int16)
     return x, (leader + adapter, leader + adapter + tail)
+
+
+def site_events(rng, n_sites=300, median_depth=40.0, sigma=0.8, min_depth=1, shifted=(), level_shift=0.5, dwell_stretch=1.6, level_sd=0.3,
+                mean_dwell=12.0):
+    """Two samples' events over n_sites transcript positions, as `resquiggle` would tabulate them.  Every site has a level of its own (uniform
+    over -1.5 .. 1.5 z) and, per sample, a depth drawn from a log-normal (median median_depth, shape sigma, at least min_depth); an
+    event's level is the site's plus Gaussian noise of level_sd, its dwell 1 + a geometric number of samples (mean mean_dwell).  At the
+    sites in `shifted`, sample 1's levels are moved by level_shift and its mean dwell is stretched by dwell_stretch.  rng: a numpy Generator.
+    -> {site int64, cond uint8, level float64 (z units), dwell int64} arrays, one entry per event (sample 0's events first, each sample
+    site by site), and depth int64 [n_sites, 2]."""
+    shifted = set(int(s) for s in shifted)
+    base = rng.uniform(-1.5, 1.5, n_sites)
+    depth = np.maximum(np.rint(median_depth * np.exp(sigma * rng.standard_normal((n_sites, 2)))).astype(np.int64), int(min_depth))
+    site, cond, level, dwell = [], [], [], []
+    for c in (0, 1):
+        for s in range(n_sites):
+            n = int(depth[s, c])
+            moved = c == 1 and s in shifted
+            site.append(np.full(n, s, dtype=np.int64))
+            cond.append(np.full(n, c, dtype=np.uint8))
+            level.append(base[s] + (level_shift if moved else 0.0) + level_sd * rng.standard_normal(n))
+            dwell.append(rng.geometric(1.0 / (mean_dwell * (dwell_stretch if moved else 1.0)), n).astype(np.int64))
+    return {"site": np.concatenate(site), "cond": np.concatenate(cond), "level": np.concatenate(level), "dwell": np.concatenate(dwell),
+            "depth": depth}

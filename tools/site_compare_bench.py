@@ -1,0 +1,132 @@
+#!/usr/bin/env python
+"""Two-sample site comparison cost: whole calls of rd_site_compare at a few (events, sites, skew) shapes, beside rd_site_compare_host
+(std::sort and plain loops on one CPU core), and -- from a profiler run -- the call's radix sort alone, which is the floor of any
+implementation that sorts the events, and the site kernel's share.  DESIGN.md section 20.
+
+    python tools/site_compare_bench.py [--reps 20] [--host-reps 3] [--out results.json]
+    python tools/site_compare_bench.py --stats kernel_trace.csv [--reps 20]      # summarise a rocprofv3 run of this tool
+
+Whole calls are host-clock times around the synchronous entry point (it ends in a stream synchronise): counting pass, upload, pack, sort,
+segmenting, the site kernel and the download of 96 B per site; two untimed calls first.  The input is seeded: events spread over the
+sites by a log-normal weight (`skew` is its shape; 0: every site the same), level-like values (a site's own level plus noise, in 1/1024
+z unit), and -- the skewed shapes -- four sites of 100 000 events each.  With --stats the rows of the kernel_trace.csv of a
+`rocprofv3 --kernel-trace --output-format csv -- python tools/site_compare_bench.py --reps R --only gpu` run are cut into calls at every
+sc_site_kernel launch (one per call under the default budget) and each shape's calls give the median time per call of the sort's
+kernels, the site kernel, the other kernels of sitecmp.hip and the scans."""
+import argparse
+import csv
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+# name, events, sites, skew (shape of the log-normal weight), deep sites of 100 000 events
+SHAPES = (("1M_20k_even", 1_000_000, 20_000, 0.0, 0), ("1M_20k_skewed", 1_000_000, 20_000, 1.5, 4), ("8M_100k_skewed", 8_000_000, 100_000, 1.5, 4))
+CLASSES = ("sort", "site_kernel", "own_other", "scan", "other")
+
+
+def events(n_events, n_sites, skew, n_deep, seed):
+    rng = np.random.default_rng(seed)
+    w = np.exp(skew * rng.standard_normal(n_sites))
+    counts = rng.multinomial(n_events - 100_000 * n_deep, w / w.sum())
+    counts[rng.choice(n_sites, n_deep, replace=False)] += 100_000
+    site = np.repeat(np.arange(n_sites, dtype=np.uint32), counts)
+    cond = rng.integers(0, 2, n_events).astype(np.uint8)
+    level = rng.uniform(-1.5, 1.5, n_sites)[site] + 0.3 * rng.standard_normal(n_events) + 0.1 * cond
+    value = np.clip(np.rint(level * 1024), -32768, 32767).astype(np.int16)
+    p = rng.permutation(n_events)
+    return site[p], cond[p], value[p], counts
+
+
+def timed(fn, reps, warm=2):
+    for _ in range(warm):
+        out = fn()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        out = fn()
+        ts.append(time.perf_counter() - t0)
+    return out, {"median_ms": float(np.median(ts)) * 1e3, "min_ms": min(ts) * 1e3, "max_ms": max(ts) * 1e3}
+
+
+def run(reps, host_reps, seed, only):
+    from radian_amd import Backend
+    from radian_amd.backend import SITE_FIELDS, site_compare_host
+    res = {"reps": reps, "host_reps": host_reps, "shapes": {}}
+    with Backend(0) as be:
+        for name, n_events, n_sites, skew, n_deep in SHAPES:
+            site, cond, value, counts = events(n_events, n_sites, skew, n_deep, seed)
+            b = {"events": n_events, "sites": n_sites, "skew": skew, "deepest_site": int(counts.max()), "median_site": float(np.median(counts))}
+            got, b["site_compare"] = timed(lambda: be.site_compare(site, cond, value, n_sites), reps)
+            b["sites_out"] = int(len(got.status))
+            b["status_ok"] = int((got.status == 0).sum())
+            b["mevents_per_s"] = n_events / b["site_compare"]["median_ms"] / 1e3
+            if only is None:
+                host, b["site_compare_host"] = timed(lambda: site_compare_host(site, cond, value, n_sites), host_reps, warm=1)
+                b["equal_to_host"] = all(np.array_equal(getattr(got, f), getattr(host, f)) for f in SITE_FIELDS)
+                b["host_over_gpu"] = b["site_compare_host"]["median_ms"] / b["site_compare"]["median_ms"]
+            res["shapes"][name] = b
+    return res
+
+
+def classify(kernel):
+    if "sc_site_kernel" in kernel:
+        return "site_kernel"
+    if "sc_" in kernel and "_kernel" in kernel and "rocprim" not in kernel:
+        return "own_other"
+    if "radix" in kernel or "onesweep" in kernel or "sort" in kernel:
+        return "sort"
+    if "scan" in kernel or "lookback" in kernel:
+        return "scan"
+    return "other"
+
+
+def summarise(path, reps):
+    """kernel_trace.csv of a `--only gpu` run: per shape, the median over its reps + 2 calls of each class's kernel time per call"""
+    with open(path) as f:
+        rows = list(csv.DictReader(f))
+    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    calls, cur = [], {c: 0.0 for c in CLASSES}
+    for r in rows:
+        c = classify(r["Kernel_Name"])
+        cur[c] += (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
+        if c == "site_kernel":
+            calls.append(cur)
+            cur = {c: 0.0 for c in CLASSES}
+    per = reps + 2
+    if len(calls) != per * len(SHAPES):
+        raise SystemExit(f"{path}: {len(calls)} launches of sc_site_kernel, expected {per * len(SHAPES)} (--reps must match the profiled run)")
+    out = {"calls_per_shape": per, "kernel_us_per_call_median": {}, "site_kernel_share_of_kernel_time": {}, "site_kernel_over_sort": {}}
+    for i, (name, *_) in enumerate(SHAPES):
+        mine = calls[i * per:(i + 1) * per]
+        med = {c: float(np.median([m[c] for m in mine])) for c in CLASSES}
+        out["kernel_us_per_call_median"][name] = med
+        out["site_kernel_share_of_kernel_time"][name] = med["site_kernel"] / sum(med.values())
+        out["site_kernel_over_sort"][name] = med["site_kernel"] / med["sort"] if med["sort"] else None
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--host-reps", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=2028)
+    ap.add_argument("--only", default=None, choices=["gpu"], help="skip the host twin (a profiler run)")
+    ap.add_argument("--stats", default=None, help="rocprofv3 kernel_trace.csv of a `--only gpu` run of this tool")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    res = summarise(a.stats, a.reps) if a.stats else run(a.reps, a.host_reps, a.seed, a.only)
+    s = json.dumps(res, indent=1)
+    print(s)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(s + "\n")
+
+
+if __name__ == "__main__":
+    main()
