@@ -589,6 +589,65 @@ int64_t rd_site_workspace_bytes(int64_t n_events);
 int rd_site_diag_segments(rd_ctx* ctx, const uint32_t* site, const uint8_t* cond, const int16_t* value, int64_t n_events, uint32_t n_sites,
                           int64_t capacity, uint64_t* sorted_keys, int64_t* segments, int64_t* n_segments);
 
+/* ---- signal simulation: raw samples of reads whose sequence, base boundaries and noise are known (sim.hip) ----
+ * NO reference behaviour.  Sequences plus a pore-model table become raw int16 samples with every base's first sample known.  Integer
+ * arithmetic only; met exactly.
+ *   read      read r has bases codes[seq_off[r] .. seq_off[r+1]), each 0..3, in the order the pore sees them (3'->5': the decode order);
+ *             L = 0 is allowed.  Per read: lead[r] >= 0 samples before the first base, drawn at lead_level_q10[r] (|.| <= 2^15) with
+ *             lead_sd_q10[r] (0..2^15); median[r] in DAQ units (an int16 value); scale_q10[r] = DAQ units per z unit times 1024
+ *             (1..2^26); a 64-bit key, key[2r] and key[2r+1]
+ *   model     k odd, 1 <= k <= 9; level_q10 (int32, |.| <= 2^15), sd_q10 (0..2^15) and dwell_q8 (256..2^23) of 4^k entries each, indexed
+ *             by the k-mer in pore order, first base most significant; dwell_cdf uint32[1024], non-decreasing, each <= 2^20: quantiles
+ *             of the dwell in Q16 multiples of its mean.  Levels and sds are Q10 in mad_normalise's z units, dwells Q8 samples
+ *   k-mer     base b's k-mer is centred on b, h = k / 2 bases to either side; a position outside the read takes the read's nearest end base
+ *   per base  optional, indexed like codes, either may be null: level_shift_q10 (int16), dwell_scale_q8 (uint16, 1..4096; 256 is 1.0)
+ *   random    Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85), counter (i, stream, 0, 0),
+ *             key key[r]; output words w0..w3
+ *   dwell     base b: stream 0, i = b.  m = dwell_q8[kmer] * scale_q8 >> 8; t = dwell_cdf[w0 >> 22];
+ *             d = clamp((m t + 2^23) >> 24, 1, 32767), the product in 64 bits
+ *   positions base_first[b] = lead + the sum of d over the bases before b; n_samples = lead + the sum of every d
+ *   sample    s: stream 1, i = s.  Z = the sum of the twelve 10-bit fields (bits 0-9, 10-19, 20-29 of each word), z = Z - 6138 (mean 0,
+ *             sd sqrt(2^20 - 1): z is in 1/1024 sigma, |z| <= 6138).  The base of s is the b with base_first[b] <= s < base_first[b+1];
+ *             s < lead is the lead.  v = level + shift + floor(sd z / 1024);
+ *             raw = clamp(median + floor((v scale_q10 + 2^19) / 2^20), -32768, 32767)
+ * A read's output depends on its own inputs and key only: not on the batch, the order, the budget or the launches.  RD_ERR_ARG before
+ * anything is launched or written: a null pointer, offsets that are not monotone, a code above 3, a parameter or a table entry outside
+ * its range, a cdf that decreases.  n_reads == 0 is RD_OK.
+ *   rd_sim_lengths          n_samples[r] (int64) on the GPU; synchronous, uses the context's stream.  budget_bytes as below (a read over
+ *                           it: n_samples -1 and RD_ERR_NOMEM)
+ *   rd_sim_signal           the same inputs and the caller's raw_off[n_reads + 1]: read r's samples go to raw[raw_off[r] .. raw_off[r+1]).
+ *                           A difference of raw_off that is not the read's n_samples, or above 2^31 - 1, is RD_ERR_ARG before anything
+ *                           is written.  Outputs: raw; base_first (int32, indexed like codes; may be null); status per read: RD_SIM_OK,
+ *                           RD_SIM_EMPTY (no samples), RD_SIM_TOO_LARGE.  budget_bytes: device workspace one launch may take, DESIGN.md
+ *                           section 19: the sum of rd_sim_workspace_bytes over its reads plus 12 * 4^k + 4096 (rounded up to 256) + 12288
+ *                           for the model and the launch; 0 = a quarter of the free device memory.  Reads are packed into launches under
+ *                           it in the caller's order; a read that alone exceeds it is not looked at (its raw_off neither): status
+ *                           RD_SIM_TOO_LARGE, and the call returns RD_ERR_NOMEM naming it after doing the others
+ *   rd_sim_lengths_host, rd_sim_signal_host   host, no GPU: the same rules (csrc/sim_rules.h) in a plain loop
+ *   rd_sim_workspace_bytes  32 n_bases + 2 n_samples + 128 */
+#define RD_SIM_OK 0
+#define RD_SIM_EMPTY 1
+#define RD_SIM_TOO_LARGE 2
+int rd_sim_lengths(rd_ctx* ctx, const uint8_t* codes, const int64_t* seq_off, int n_reads, const int16_t* level_shift_q10,
+                   const uint16_t* dwell_scale_q8, const int32_t* lead, const int32_t* lead_level_q10, const int32_t* lead_sd_q10,
+                   const int32_t* median, const int32_t* scale_q10, const uint32_t* key, int k, const int32_t* level_q10, const int32_t* sd_q10,
+                   const int32_t* dwell_q8, const uint32_t* dwell_cdf, int64_t budget_bytes, int64_t* n_samples);
+int rd_sim_lengths_host(const uint8_t* codes, const int64_t* seq_off, int n_reads, const int16_t* level_shift_q10, const uint16_t* dwell_scale_q8,
+                        const int32_t* lead, const int32_t* lead_level_q10, const int32_t* lead_sd_q10, const int32_t* median,
+                        const int32_t* scale_q10, const uint32_t* key, int k, const int32_t* level_q10, const int32_t* sd_q10,
+                        const int32_t* dwell_q8, const uint32_t* dwell_cdf, int64_t* n_samples);
+int rd_sim_signal(rd_ctx* ctx, const uint8_t* codes, const int64_t* seq_off, int n_reads, const int16_t* level_shift_q10,
+                  const uint16_t* dwell_scale_q8, const int32_t* lead, const int32_t* lead_level_q10, const int32_t* lead_sd_q10,
+                  const int32_t* median, const int32_t* scale_q10, const uint32_t* key, int k, const int32_t* level_q10, const int32_t* sd_q10,
+                  const int32_t* dwell_q8, const uint32_t* dwell_cdf, const int64_t* raw_off, int64_t budget_bytes, int16_t* raw,
+                  int32_t* base_first, int32_t* status);
+int rd_sim_signal_host(const uint8_t* codes, const int64_t* seq_off, int n_reads, const int16_t* level_shift_q10, const uint16_t* dwell_scale_q8,
+                       const int32_t* lead, const int32_t* lead_level_q10, const int32_t* lead_sd_q10, const int32_t* median,
+                       const int32_t* scale_q10, const uint32_t* key, int k, const int32_t* level_q10, const int32_t* sd_q10,
+                       const int32_t* dwell_q8, const uint32_t* dwell_cdf, const int64_t* raw_off, int16_t* raw, int32_t* base_first,
+                       int32_t* status);
+int64_t rd_sim_workspace_bytes(int64_t n_bases, int64_t n_samples);
+
 /* ---- model evaluation on labelled windows: the reference's val_loss (radian/model.py:77-98, radian/train.py:48-79) ------------
  * Labelled windows as the reference stores them: TFRecord shards of tf.train.Example records (radian/data.py:9-31), read on the
  * HOST without TensorFlow (tfrecord.hip).  Framing: u64 length, u32 masked crc32c of it, the data, u32 masked crc32c of the data;

@@ -101,6 +101,11 @@ SIGNATURES = {
     "rd_site_compare_host": (c_i, [c_vp, c_vp, c_vp, c_i64, c_u32, c_i64] + [c_vp] * 13),
     "rd_site_workspace_bytes": (c_i64, [c_i64]),
     "rd_site_diag_segments": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i64, c_u32, c_i64, c_vp, c_vp, c_vp]),
+    "rd_sim_lengths": (c_i, [c_vp, c_vp, c_vp, c_i] + [c_vp] * 8 + [c_i] + [c_vp] * 4 + [c_i64, c_vp]),
+    "rd_sim_lengths_host": (c_i, [c_vp, c_vp, c_i] + [c_vp] * 8 + [c_i] + [c_vp] * 4 + [c_vp]),
+    "rd_sim_signal": (c_i, [c_vp, c_vp, c_vp, c_i] + [c_vp] * 8 + [c_i] + [c_vp] * 4 + [c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "rd_sim_signal_host": (c_i, [c_vp, c_vp, c_i] + [c_vp] * 8 + [c_i] + [c_vp] * 4 + [c_vp, c_vp, c_vp, c_vp]),
+    "rd_sim_workspace_bytes": (c_i64, [c_i64, c_i64]),
     "rd_tfrecord_open": (c_i, [ctypes.c_char_p, ctypes.POINTER(c_vp)]),
     "rd_tfrecord_open_mem": (c_i, [c_vp, c_sz, ctypes.POINTER(c_vp)]),
     "rd_tfrecord_close": (None, [c_vp]),

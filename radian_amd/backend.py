@@ -246,6 +246,98 @@ class FitResult:
         self.score, self.ref_start, self.ref_end, self.counts, self.status = score, ref_start, ref_end, counts, status
 
 
+# rd_sim_signal per-read status (include/radian_hip.h RD_SIM_*)
+SIM_OK, SIM_EMPTY, SIM_TOO_LARGE = 0, 1, 2
+SIM_STATUS_NAMES = ("ok", "empty", "too-large")
+
+
+class SimModel:
+    """rd_sim_*'s pore model, all integers (the contract is in include/radian_hip.h): k odd 1..9; level_q10, sd_q10, dwell_q8 int32 [4^k],
+    indexed by the k-mer in pore order; dwell_cdf uint32 [1024]"""
+    __slots__ = ("k", "level_q10", "sd_q10", "dwell_q8", "dwell_cdf")
+
+    def __init__(self, k, level_q10, sd_q10, dwell_q8, dwell_cdf):
+        self.k = int(k)
+        self.level_q10 = np.ascontiguousarray(level_q10, dtype=np.int32).ravel()
+        self.sd_q10 = np.ascontiguousarray(sd_q10, dtype=np.int32).ravel()
+        self.dwell_q8 = np.ascontiguousarray(dwell_q8, dtype=np.int32).ravel()
+        self.dwell_cdf = np.ascontiguousarray(dwell_cdf, dtype=np.uint32).ravel()
+        n = 4 ** self.k if 1 <= self.k <= 9 else -1
+        if not (self.level_q10.size == self.sd_q10.size == self.dwell_q8.size == n) or self.dwell_cdf.size != 1024:
+            raise ValueError(f"a SimModel of k = {self.k} takes three tables of 4^k entries and 1024 dwell quantiles")
+
+    def args(self):
+        return (self.k, _p(self.level_q10), _p(self.sd_q10), _p(self.dwell_q8), _p(self.dwell_cdf))
+
+
+class SimResult:
+    """one entry per read: raw (int16 samples), base_first (int32: every base's first sample), status (int32, SIM_*)"""
+    __slots__ = ("raw", "base_first", "status")
+
+    def __init__(self, raw, base_first, status):
+        self.raw, self.base_first, self.status = raw, base_first, status
+
+
+def _sim_args(seqs, model, lead, lead_level_q10, lead_sd_q10, median, scale_q10, keys, level_shift, dwell_scale):
+    """-> (the arrays, kept alive by the caller; the sixteen arguments every rd_sim_* entry point starts with; the base offsets)"""
+    n = len(seqs)
+    codes, off = _concat_codes(seqs)
+    per = [np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.int32), (n,)) if np.ndim(a) == 0 else a, dtype=np.int32).ravel()
+           for a in (lead, lead_level_q10, lead_sd_q10, median, scale_q10)]
+    keys = np.ascontiguousarray(keys, dtype=np.uint32).reshape(-1)
+    if any(a.size != n for a in per) or keys.size != 2 * n:
+        raise ValueError(f"per-read arguments that do not hold one entry for each of {n} reads (keys: two)")
+    shift = dscale = None
+    if level_shift is not None:
+        shift, o = _pack(level_shift, np.int16, pad=1)
+        if not np.array_equal(o, off):
+            raise ValueError("level_shift does not hold one entry per base")
+    if dwell_scale is not None:
+        dscale, o = _pack(dwell_scale, np.uint16, pad=1)
+        if not np.array_equal(o, off):
+            raise ValueError("dwell_scale does not hold one entry per base")
+    keep = (codes, off, per, keys, shift, dscale, model)
+    return keep, (_p(codes), _p(off), n, _p(shift), _p(dscale), *[_p(a) for a in per], _p(keys), *model.args()), off
+
+
+def _sim_result(raw, raw_off, bf, off, status, n):
+    return SimResult([raw[raw_off[r]:raw_off[r + 1]].copy() for r in range(n)], [bf[off[r]:off[r + 1]].copy() for r in range(n)], status)
+
+
+def sim_lengths_host(seqs, model, lead, lead_level_q10, lead_sd_q10, median, scale_q10, keys, level_shift=None, dwell_scale=None):
+    """Backend.sim_lengths on the host (rd_sim_lengths_host: the same rules in a plain loop; no GPU, no context)"""
+    L = _lib.load()
+    keep, args, off = _sim_args(seqs, model, lead, lead_level_q10, lead_sd_q10, median, scale_q10, keys, level_shift, dwell_scale)
+    out = np.zeros(len(seqs) + 1, dtype=np.int64)
+    if L.rd_sim_lengths_host(*args, _p(out)) != 0:
+        raise RadianHipError(L.rd_last_error().decode())
+    return out[:len(seqs)]
+
+
+def sim_signal_host(seqs, model, lead, lead_level_q10, lead_sd_q10, median, scale_q10, keys, level_shift=None, dwell_scale=None):
+    """Backend.sim_signal on the host (rd_sim_signal_host: the same rules in a plain loop; no GPU, no context)"""
+    L = _lib.load()
+    n = len(seqs)
+    ns = sim_lengths_host(seqs, model, lead, lead_level_q10, lead_sd_q10, median, scale_q10, keys, level_shift, dwell_scale)
+    keep, args, off = _sim_args(seqs, model, lead, lead_level_q10, lead_sd_q10, median, scale_q10, keys, level_shift, dwell_scale)
+    raw_off = np.zeros(n + 1, dtype=np.int64)
+    raw_off[1:] = np.cumsum(ns)
+    raw, bf, status = np.zeros(int(raw_off[-1]) + 1, np.int16), np.zeros(int(off[-1]) + 1, np.int32), np.zeros(n + 1, np.int32)
+    if L.rd_sim_signal_host(*args, _p(raw_off), _p(raw), _p(bf), _p(status)) != 0:
+        raise RadianHipError(L.rd_last_error().decode())
+    return _sim_result(raw, raw_off, bf, off, status[:n], n)
+
+
+def sim_workspace_bytes(n_bases, n_samples):
+    """device workspace Backend.sim_signal needs for one read (rd_sim_workspace_bytes); a launch adds sim_launch_bytes(k)"""
+    return int(_lib.load().rd_sim_workspace_bytes(int(n_bases), int(n_samples)))
+
+
+def sim_launch_bytes(k):
+    """what a launch of Backend.sim_signal takes besides its reads: the model tables and the launch's own arrays (include/radian_hip.h)"""
+    return (12 * 4 ** k + 4096 + 255) // 256 * 256 + 12288
+
+
 def _pack(arrays, dtype, pad=0):
     """list of arrays -> (their elements as one flat buffer of dtype, int64 offsets [n + 1]); a buffer without elements has `pad` zeros (1
     where the library wants a pointer it can check)"""
@@ -1124,6 +1216,37 @@ class Backend:
         self._check(self._L.rd_site_diag_segments(self._h, _p(site), _p(cond), _p(value), site.shape[0], int(n_sites), capacity, _p(keys), _p(segs),
                                                   ctypes.byref(n_seg)))
         return keys[:site.shape[0]], segs[:n_seg.value]
+
+    # ------------------------------------------------------------------ signal simulation
+    def sim_lengths(self, seqs, model, lead, lead_level_q10, lead_sd_q10, median, scale_q10, keys, level_shift=None, dwell_scale=None,
+                    budget_bytes=0):
+        """The number of samples every read comes to (rd_sim_lengths, on the GPU): seqs -- one uint8 code array per read, in pore order;
+        model -- a SimModel; the per-read integers as arrays or scalars; keys uint32 [reads, 2]; level_shift / dwell_scale -- None or one
+        array per read with an entry per base.  -> int64 [reads]"""
+        keep, args, off = _sim_args(seqs, model, lead, lead_level_q10, lead_sd_q10, median, scale_q10, keys, level_shift, dwell_scale)
+        out = np.zeros(len(seqs) + 1, dtype=np.int64)
+        self._check(self._L.rd_sim_lengths(self._h, *args, int(budget_bytes), _p(out)))
+        return out[:len(seqs)]
+
+    def sim_signal(self, seqs, model, lead, lead_level_q10, lead_sd_q10, median, scale_q10, keys, level_shift=None, dwell_scale=None,
+                   n_samples=None, budget_bytes=0, allow_too_large=False):
+        """The raw samples of every read and every base's first sample (rd_sim_signal, on the GPU); arguments as sim_lengths.  n_samples:
+        the reads' lengths when the caller has them (sim_lengths otherwise).  budget_bytes: device workspace per launch, 0 = a quarter of
+        free memory.  A read that does not fit it raises, unless allow_too_large: status SIM_TOO_LARGE.  -> SimResult."""
+        n = len(seqs)
+        if n_samples is None:
+            n_samples = self.sim_lengths(seqs, model, lead, lead_level_q10, lead_sd_q10, median, scale_q10, keys, level_shift, dwell_scale)
+        keep, args, off = _sim_args(seqs, model, lead, lead_level_q10, lead_sd_q10, median, scale_q10, keys, level_shift, dwell_scale)
+        raw_off = np.zeros(n + 1, dtype=np.int64)
+        raw_off[1:] = np.cumsum(np.asarray(n_samples, dtype=np.int64))
+        raw, bf, status = np.zeros(int(raw_off[-1]) + 1, np.int16), np.zeros(int(off[-1]) + 1, np.int32), np.zeros(n + 1, np.int32)
+        rc = self._L.rd_sim_signal(self._h, *args, _p(raw_off), int(budget_bytes), _p(raw), _p(bf), _p(status))
+        if rc != 0 and not (allow_too_large and rc == -4 and (status[:n] == SIM_TOO_LARGE).any()):
+            self._check(rc)
+        return _sim_result(raw, raw_off, bf, off, status[:n], n)
+
+    sim_lengths_host = staticmethod(sim_lengths_host)
+    sim_signal_host = staticmethod(sim_signal_host)
 
     # ------------------------------------------------------------------ signal-to-reference alignment (DESIGN.md section 17)
     def event_stats(self, raws, aln):

@@ -235,13 +235,14 @@ class ListSource:
         pass
 
 
-def write_multi_fast5(path, reads, filters=(), chunk=4096):
+def write_multi_fast5(path, reads, filters=(), chunk=4096, track_times=True):
     """Write {read_id: int16 array} as a multi-read fast5 (fixtures / synthetic runs).  filters: h5.File.write's, e.g. (("deflate", 1),)
-    = the gzip level-1 signals of pre-VBZ MinKNOW files."""
+    = the gzip level-1 signals of pre-VBZ MinKNOW files.  track_times=False: no time of writing in the file (the same reads give the
+    same bytes)."""
     with h5.File(path, "w") as f:
         for rid, sig in reads.items():
             sig = np.ascontiguousarray(sig, dtype=np.int16)
             g = f"/read_{rid}"
             f.create_group(g + "/Raw")
-            f.write(g + "/Raw/Signal", sig, chunks=(max(1, min(len(sig), chunk)),), filters=filters)
+            f.write(g + "/Raw/Signal", sig, chunks=(max(1, min(len(sig), chunk)),), filters=filters, track_times=track_times)
             f.set_attr_str(g + "/Raw", "read_id", rid)

@@ -95,6 +95,7 @@ def lib():
         "H5Pset_deflate": (herr_t, [hid_t, ctypes.c_uint]),
         "H5Pset_shuffle": (herr_t, [hid_t]),
         "H5Pset_fletcher32": (herr_t, [hid_t]),
+        "H5Pset_obj_track_times": (herr_t, [hid_t, ctypes.c_uint]),
         "H5Pset_fill_value": (herr_t, [hid_t, hid_t, ctypes.c_void_p]),
         "H5Pclose": (herr_t, [hid_t]),
         "H5Eset_auto2": (herr_t, [hid_t, ctypes.c_void_p, ctypes.c_void_p]),
@@ -307,8 +308,10 @@ class File:
                 raise H5Error(f"cannot create group {cur!r}")
             L.H5Gclose(gid)
 
-    def write(self, path, array, chunks=None, filters=(), fill=None, store=True):
+    def write(self, path, array, chunks=None, filters=(), fill=None, store=True, track_times=True):
         """filters (chunked datasets only), applied in the order given: "shuffle", "fletcher32", ("deflate", level).
+        track_times=False leaves the dataset's header without the time of writing (libhdf5 records it by default), so that the same
+        data give the same bytes.
         fill: the dataset's fill value (H5Pset_fill_value); store=False creates the dataset without writing its elements -- storage
         stays unallocated and reads return the fill value (fixtures for the native fast5 reader's "no verdict" cases)."""
         L = lib()
@@ -319,8 +322,10 @@ class File:
         dims = (hsize_t * max(a.ndim, 1))(*a.shape)
         sid = L.H5Screate_simple(a.ndim, dims, None)
         dcpl = H5P_DEFAULT
-        if fill is not None or (chunks is not None and a.size):
+        if fill is not None or (chunks is not None and a.size) or not track_times:
             dcpl = L.H5Pcreate(_types["dcpl"])
+        if not track_times and L.H5Pset_obj_track_times(dcpl, 0) < 0:
+            raise H5Error("cannot switch the object's times off")
         if fill is not None:
             fv = np.asarray(fill, dtype=a.dtype).reshape(1)
             if L.H5Pset_fill_value(dcpl, _types[a.dtype], fv.ctypes.data_as(ctypes.c_void_p)) < 0:
