@@ -1,7 +1,9 @@
 """HIP TCN forward and assembly (through the C ABI) against the CPU oracle.
 
 Forward tolerance: |softmax difference| <= 1e-4 (north_star); observed ~1e-6 (fp32 MFMA vs fp32 CPU, different
-summation order).  Assembly: bit-exact (float64 gather + one division)."""
+summation order).  Assembly: bit-exact (float64 gather + one division).  The 1e-4 here is the north-star requirement, not the
+sharp check of the forward's arithmetic: on these weights most rows are saturated, and tests/test_gpu_forward_logratio.py holds
+every form to a float64 statement in log-ratio space on unsaturated heads."""
 import json
 import os
 
