@@ -763,6 +763,54 @@ int rd_map_index(rd_ctx* ctx, const uint8_t* codes, const int64_t* offsets, int6
 int rd_map_batch(rd_ctx* ctx, const uint8_t* reads, const int64_t* read_off, int64_t n_reads, int min_anchors, int min_score, int max_gap,
                  int bandwidth, int64_t budget_bytes, int32_t* status, int32_t* hits, int64_t* stats);
 
+/* ---- transcript quantification: the candidate transcripts of every read, then an expectation-maximisation over them in fixed-point
+ * integers (map.hip, quant.hip; radian_amd/quant.py).  No length normalisation: in direct RNA one read is one
+ * molecule.  Everything is integer arithmetic: results are exact against the text below and depend on neither budget, batches nor order.
+ *   rd_map_candidates  the arguments, index, seeds, chains, budget contract and launches of rd_map_batch; per read p the K = max_cand
+ *              (1..RD_MAP_MAX_CAND) best qualifying chains instead of the best one.
+ *              Qualify    a segment (read, t) qualifies as in rd_map_batch: n_anchors >= min_anchors and score >= min_score.
+ *              d3         with transcript length n_t and read length L, d3 = (n_t - r1) - (L - q1): the transcript's bases after the
+ *                         chain's last anchor less the read's bases after it; negative when the read runs past the transcript's end.
+ *                         With max_3p >= 0 (-1: off) a qualifying segment also needs d3 <= max_3p.
+ *              Candidates best = the largest score of the segments that pass; a passing segment is a candidate when
+ *                         score * 1024 >= best * min_frac_q10 (0..1024).  n_qual[p] counts them.
+ *              Order      (score descending, t ascending); the first n_cand[p] = min(n_qual, K) are written, the other rows are 0:
+ *                         cands[(p K + j) 8 ..] = t, score, n_anchors, q0, r0, q1, r1, d3.  With max_3p = -1 row 0 is rd_map_batch's
+ *                         hit of the read (t, score, n_anchors, q0, r0, q1, r1).
+ *              status     RD_MAP_OK; RD_MAP_NO_SEED; RD_MAP_NO_CHAIN (also when the 3' filter leaves nothing); RD_MAP_TOO_LARGE, with
+ *                         RD_ERR_NOMEM naming the read, as rd_map_batch.  stats[16] as rd_map_batch; [13] is 0 and [14] holds the
+ *                         microseconds of the candidate stage.
+ *   rd_quant_em  Read r has the candidates cand_t (int32) / cand_w (uint16) [cand_off[r] .. cand_off[r+1]), cand_off int64 [n_reads + 1]
+ *              from 0; n_reads < 2^31, n_tx < 2^24, max_iter 0..100000.  RD_ERR_ARG before anything is written unless every read has
+ *              0..64 candidates, every t is in 0..n_tx-1, the t of one read are distinct and every w is in 1..4096.  ONE = 2^20:
+ *                step(c)  for every read with candidates: a_j = c[t_j] w_j; S = sum_j a_j; sh = max(0, bitlen(S) - 44); a'_j = a_j >> sh;
+ *                         S' = sum_j a'_j; share_j = floor(a'_j 2^20 / S'); c'[t] = the sum of the shares that name t
+ *                c_0 = step(1, ..., 1); for i = 1 .. max_iter: c_i = step(c_{i-1}), d_i = max_t |c_i[t] - c_{i-1}[t]|; stop after
+ *                iteration i when d_i <= tol_q20
+ *              count_q20 [n_tx] (uint64) = the last c; share_q20 [cand_off[n_reads]] (uint32, nullable) = the shares of the last step
+ *              executed, so count[t] is always the sum of the shares that name t.
+ *              Bounds     c[t] <= n_reads 2^20 < 2^51, so a_j < 2^63; the t of a read are distinct and sum_t c[t] <= n_reads 2^20, so
+ *                         S < 2^63; a'_j < 2^44, so a'_j 2^20 fits 64 bits; S' > 0 always (a read's own shares keep the counts of its
+ *                         transcripts at ONE - 64 together or more; with sh > 0, S' > 2^43 - 64).  A transcript's count can reach 0
+ *                         and then stays 0.  A read loses at most one unit of 2^-20 per candidate to the floors.
+ *              stats[16] (nullable): [0] iterations run, [1] the last d_i, [2] lost units = (reads with candidates) 2^20 - sum count,
+ *                         [3] reads without candidates, [4] single-candidate reads, [5] slots, [8..11] microseconds of upload, first
+ *                         step, iterations, download.
+ *              The candidates stay on the device over the iterations: rd_quant_workspace_bytes(slots, n_reads, n_tx) =
+ *              12 (2 slots + 64) + 24 n_tx + 4096 bounds the workspace (reads are packed into rows of 64 slots that no read
+ *              straddles: at most 2 slots + 64 packed slots of 12 bytes; 24 bytes per transcript).  RD_ERR_NOMEM naming the figure when
+ *              it cannot be reserved: an EM is not cut into launches.  Synchronous; the context's stream.
+ *   rd_quant_em_host  host, no GPU: the same rules (csrc/quant_rules.h) and the same packed form in plain loops */
+#define RD_MAP_MAX_CAND 64
+int rd_map_candidates(rd_ctx* ctx, const uint8_t* reads, const int64_t* read_off, int64_t n_reads, int min_anchors, int min_score, int max_gap,
+                      int bandwidth, int64_t budget_bytes, int max_cand, int min_frac_q10, int max_3p, int32_t* status, int32_t* n_qual,
+                      int32_t* n_cand, int32_t* cands, int64_t* stats);
+int rd_quant_em(rd_ctx* ctx, const int64_t* cand_off, const int32_t* cand_t, const uint16_t* cand_w, int64_t n_reads, int64_t n_tx, int max_iter,
+                uint64_t tol_q20, uint64_t* count_q20, uint32_t* share_q20, int64_t* stats);
+int rd_quant_em_host(const int64_t* cand_off, const int32_t* cand_t, const uint16_t* cand_w, int64_t n_reads, int64_t n_tx, int max_iter,
+                     uint64_t tol_q20, uint64_t* count_q20, uint32_t* share_q20, int64_t* stats);
+int64_t rd_quant_workspace_bytes(int64_t slots, int64_t n_reads, int64_t n_tx);
+
 /* The CTC loss of Keras's ctc_batch_cost and a greedy edit distance, per window, on the GPU (ctc.hip).
  * Window i has RD_CTC_T = 1024 softmax rows y[t][0..4] (A, C, G, T, blank), input_len[i] (1..1024) rows counted, and
  * label_len[i] (0..RD_CTC_MAX_LABEL) labels 0..3 at labels + label_off[i].

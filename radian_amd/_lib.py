@@ -14,6 +14,7 @@ c_dp = ctypes.POINTER(ctypes.c_double)
 c_fp = ctypes.POINTER(ctypes.c_float)
 c_u8p = ctypes.POINTER(ctypes.c_uint8)
 c_u32 = ctypes.c_uint32
+c_u64 = ctypes.c_uint64
 c_vp = ctypes.c_void_p
 c_sz = ctypes.c_size_t
 
@@ -117,6 +118,10 @@ SIGNATURES = {
     "rd_map_minimizers": (c_i, [c_vp, c_i64, c_i, c_i, c_vp, c_vp, c_i64, c_i64p]),
     "rd_map_index": (c_i, [c_vp, c_vp, c_vp, c_i64, c_i, c_i, c_i, c_vp]),
     "rd_map_batch": (c_i, [c_vp, c_vp, c_vp, c_i64, c_i, c_i, c_i, c_i, c_i64, c_vp, c_vp, c_vp]),
+    "rd_map_candidates": (c_i, [c_vp, c_vp, c_vp, c_i64, c_i, c_i, c_i, c_i, c_i64, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rd_quant_em": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i, c_u64, c_vp, c_vp, c_vp]),
+    "rd_quant_em_host": (c_i, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i, c_u64, c_vp, c_vp, c_vp]),
+    "rd_quant_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
     "rd_ctc_eval": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rd_ctc_probs": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rd_ctc_probs_resident": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -377,6 +377,64 @@ class MapResult:
             setattr(self, name, hits[:, c])
 
 
+class CandResult:
+    """Backend.map_candidates' per-read arrays: status (MAP_*), n_qual, n_cand int32 [n]; cands int32 [n, K, 8]: t, score, n_anchors, q0, r0,
+    q1, r1, d3 of the read's candidates in (score descending, t ascending) order, rows past n_cand zero; stats as MapResult's, with the
+    candidate stage under stage_us["candidates"]."""
+
+    FIELDS = ("t", "score", "n_anchors", "q0", "r0", "q1", "r1", "d3")
+
+    def __init__(self, status, n_qual, n_cand, cands, stats=None):
+        self.status, self.n_qual, self.n_cand, self.cands, self.stats = status, n_qual, n_cand, cands, stats
+
+
+QUANT_ONE = 1 << 20          # rd_quant_em's fixed point (csrc/quant_rules.h)
+QUANT_MAX_W = 4096
+QUANT_STATS = ("iterations", "last_delta", "lost", "reads_empty", "reads_single", "slots")
+
+
+class QuantResult:
+    """count uint64 [n_tx] and share uint32 [slots] (None when not asked for) in units of 2^-20 reads; stats: iterations, last_delta,
+    lost, reads_empty, reads_single, slots, stage_us (upload, init, iterations, download; zeros from the host twin)."""
+
+    def __init__(self, count, share, st):
+        self.count, self.share = count, share
+        self.stats = {nm: int(st[i]) for i, nm in enumerate(QUANT_STATS)}
+        self.stats["stage_us"] = {nm: int(st[8 + i]) for i, nm in enumerate(("upload", "init", "iterations", "download"))}
+
+
+def _quant_args(cand_off, cand_t, cand_w, n_tx, with_share):
+    off = np.ascontiguousarray(cand_off, dtype=np.int64).reshape(-1)
+    t = np.ascontiguousarray(cand_t, dtype=np.int32).reshape(-1)
+    w_in = np.asarray(cand_w).reshape(-1)
+    if w_in.size and (int(w_in.min()) < 0 or int(w_in.max()) > 65535):
+        raise ValueError("quant_em: a weight does not fit 16 bits (1 .. 4096)")
+    w = np.ascontiguousarray(w_in, dtype=np.uint16)
+    if off.size < 1:
+        raise ValueError("quant_em: cand_off needs n_reads + 1 entries")
+    if t.size != w.size or (off.size and int(off.max(initial=0)) > t.size):
+        raise ValueError("quant_em: cand_off ends beyond cand_t / cand_w, or the two differ in length")
+    count = np.zeros(max(int(n_tx), 1), dtype=np.uint64)
+    share = np.zeros(max(t.size, 1), dtype=np.uint32) if with_share else None
+    pad = lambda a, dt: a if a.size else np.zeros(1, dtype=dt)
+    return off, pad(t, np.int32), pad(w, np.uint16), t.size, count, share
+
+
+def quant_em_host(cand_off, cand_t, cand_w, n_tx, max_iter=1000, tol_q20=1024, with_share=True):
+    """Backend.quant_em on the host (rd_quant_em_host: the same rules and packed form in plain loops; no GPU, no context)"""
+    L = _lib.load()
+    off, t, w, slots, count, share = _quant_args(cand_off, cand_t, cand_w, n_tx, with_share)
+    st = np.zeros(16, dtype=np.int64)
+    if L.rd_quant_em_host(_p(off), _p(t), _p(w), off.size - 1, int(n_tx), int(max_iter), int(tol_q20), _p(count), _p(share), _p(st)) != 0:
+        raise RadianHipError(L.rd_last_error().decode())
+    return QuantResult(count[:int(n_tx)], None if share is None else share[:slots], st)
+
+
+def quant_workspace_bytes(slots, n_reads, n_tx):
+    """an upper bound of the device workspace Backend.quant_em reserves (rd_quant_workspace_bytes)"""
+    return int(_lib.load().rd_quant_workspace_bytes(int(slots), int(n_reads), int(n_tx)))
+
+
 def map_minimizers(codes, k, w):
     """(positions int32, hashes uint32) of the (w,k)-minimizers of one record of codes (0..3; anything else a break): the library's
     own seed code on the host (rd_map_minimizers; no GPU)."""
@@ -1359,6 +1417,41 @@ class Backend:
             stats = {"launches": int(st[0]), "minimizers": int(st[1]), "anchors": int(st[2]), "segments": int(st[3]),
                      "stage_us": {nm: int(st[8 + i]) for i, nm in enumerate(names)}}
         return MapResult(status[:n], hits[:n], stats)
+
+    def map_candidates(self, reads, max_cand=16, min_frac_q10=922, max_3p=-1, min_anchors=3, min_score=40, max_gap=1000, bandwidth=500, budget_bytes=0,
+                       allow_too_large=False, with_stats=False):
+        """The max_cand best qualifying chains of every read against the context's index (rd_map_candidates): those
+        within min_frac_q10 / 1024 of the read's best score and, with max_3p >= 0, ending at most max_3p bases before the transcript's 3'
+        end.  Budget and allow_too_large as map_batch.  -> CandResult."""
+        buf, off = _concat_codes(reads)
+        n, K = len(off) - 1, int(max_cand)
+        rows = max(K, 1) if 1 <= K <= 64 else 1
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        n_qual, n_cand = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
+        cands = np.zeros((max(n, 1), rows, 8), dtype=np.int32)
+        st = np.zeros(16, dtype=np.int64) if with_stats else None
+        rc = self._L.rd_map_candidates(self._h, _p(buf), _p(off), n, int(min_anchors), int(min_score), int(max_gap), int(bandwidth), int(budget_bytes), K,
+                                       int(min_frac_q10), int(max_3p), _p(status), _p(n_qual), _p(n_cand), _p(cands), _p(st))
+        if rc != 0 and not (allow_too_large and rc == -4 and (status[:n] == MAP_TOO_LARGE).any()):
+            self._check(rc)
+        stats = None
+        if with_stats:
+            names = ("seeds", "lookup", "fill", "sort", "chain", "best", "candidates")
+            stats = {"launches": int(st[0]), "minimizers": int(st[1]), "anchors": int(st[2]), "segments": int(st[3]),
+                     "stage_us": {nm: int(st[8 + i]) for i, nm in enumerate(names)}}
+        return CandResult(status[:n], n_qual[:n], n_cand[:n], cands[:n], stats)
+
+    def quant_em(self, cand_off, cand_t, cand_w, n_tx, max_iter=1000, tol_q20=1024, with_share=True):
+        """The integer EM over every read's candidate transcripts on the GPU (rd_quant_em): cand_off int64
+        [n_reads + 1], cand_t (transcripts, distinct within a read, at most 64 per read) and cand_w (weights 1..4096) per slot.
+        -> QuantResult."""
+        off, t, w, slots, count, share = _quant_args(cand_off, cand_t, cand_w, n_tx, with_share)
+        st = np.zeros(16, dtype=np.int64)
+        self._check(self._L.rd_quant_em(self._h, _p(off), _p(t), _p(w), off.size - 1, int(n_tx), int(max_iter), int(tol_q20), _p(count), _p(share), _p(st)))
+        return QuantResult(count[:int(n_tx)], None if share is None else share[:slots], st)
+
+    quant_em_host = staticmethod(quant_em_host)
+    quant_workspace_bytes = staticmethod(quant_workspace_bytes)
 
     def map_diag_minimizers(self, codes, offsets, k, w):
         """rd_map_diag_minimizers (tests): the device's seed stage alone.  Ascending positions (uint32) of the minimizers in the flat image

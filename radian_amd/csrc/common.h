@@ -205,6 +205,7 @@ struct rd_ctx {
     DevBuf ws_polya, ws_polya_io;   // rd_polya_* (polya.hip): a launch's descriptors, scales and window arrays; the per-read results of a host-pointer call
     DevBuf ws_sim;                  // rd_sim_* (sim.hip): the model tables, then a launch's bases, dwells, positions and samples
     DevBuf ws_site;                 // rd_site_* (sitecmp.hip): a launch's events, keys, segments and per-site results
+    DevBuf ws_quant;                // rd_quant_em (quant.hip): the packed candidates, the counts and the shares of one call, resident over its iterations
     int64_t trie_budget = (int64_t)24 << 30;   // bytes of beam-search workspace one launch may ask for (rd_plan_trie_runs; rd_set_trie_budget)
     // pinned host staging
     void* h_stage = nullptr;

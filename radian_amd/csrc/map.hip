@@ -1,7 +1,8 @@
 // map.hip -- reads onto transcripts: (w,k)-minimizer seeds, a sorted seed index kept in the context, anchors by count / scan / fill,
 // a radix sort by (read, transcript, r, q), one wave per (read, transcript) segment for the chain recurrence and a reduction per read
-// (rd_map_index, rd_map_batch; rd_map_minimizers is the host twin of the seed definition).  The contract is in include/radian_hip.h,
-// the shapes and figures in DESIGN.md section 15.  Everything is integer arithmetic: no output depends on how reads are packed.
+// (rd_map_index, rd_map_batch; rd_map_minimizers is the host twin of the seed definition), or the K best qualifying chains of every read
+// in place of that reduction (rd_map_candidates).  The contract is in include/radian_hip.h, the shapes and figures
+// in DESIGN.md section 15.  Everything is integer arithmetic: no output depends on how reads are packed.
 #include "common.h"
 #include "budget.h"
 #include "../../include/radian_hip.h"
@@ -364,11 +365,127 @@ __global__ void map_best_kernel(const uint64_t* __restrict__ keys, const uint32_
     }
 }
 
+// ---- the K best candidate segments of every read of the launch (rd_map_candidates) ---------------------------------------------------------
+// One wave per read.  The read's segments [lo, hi) by two binary searches, lanes striding over them.  A segment passes with min_anchors
+// anchors, a score of min_score and, when max_3p >= 0, d3 <= max_3p; pass 1 is the wave maximum of the passing scores, a candidate is a
+// passing segment with score * 1024 >= best * min_frac_q10.  Pass 2: a candidate's row is its rank, the number of the read's candidates
+// that come before it in (score descending, t ascending) -- segments are in ascending t, so of equal scores the smaller segment index --
+// counted against 64 segments at a time, one per lane, handed round by readlane.  A candidate of rank < K writes its row: one writer per
+// row, no atomics.  The host has zeroed the rows.  out: MAP_CAND_HEAD + 8 K ints per read: status, n_qual, n_cand, then the rows.
+constexpr int MAP_CAND_HEAD = 3;
+
+struct CandSeg {
+    int score, t, n_anchors, q0, r0, q1, r1, d3;
+    bool pass;
+};
+
+__device__ __forceinline__ CandSeg map_cand_eval(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ qs, const int4* __restrict__ seg_res,
+                                                 int64_t s, int min_anchors, int min_score, int L, const int32_t* __restrict__ tlen, int max_3p)
+{
+    const int4 r = seg_res[s];
+    const uint64_t kf = keys[r.y], kl = keys[r.w];
+    CandSeg c;
+    c.score = r.x;
+    c.t = (int)((kf >> 24) & 0xFFFFFFu);
+    c.n_anchors = r.z;
+    c.q0 = (int)qs[r.y];
+    c.r0 = (int)(kf & 0xFFFFFFu);
+    c.q1 = (int)qs[r.w];
+    c.r1 = (int)(kl & 0xFFFFFFu);
+    c.d3 = (tlen[c.t] - c.r1) - (L - c.q1);
+    c.pass = r.z >= min_anchors && r.x >= min_score && (max_3p < 0 || c.d3 <= max_3p);
+    return c;
+}
+
+__global__ __launch_bounds__(256) void map_cand_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ qs, const uint32_t* __restrict__ seg_start,
+                                                       uint32_t n_seg, const int4* __restrict__ seg_res, int n_local, int min_anchors, int min_score,
+                                                       const int64_t* __restrict__ read_flat_off, const int32_t* __restrict__ tlen, int K, int min_frac_q10,
+                                                       int max_3p, int32_t* __restrict__ out)
+{
+    const int rl = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (rl >= n_local) return;
+    const int lane = threadIdx.x & 63;
+    int64_t lo = 0, hi = n_seg;   // first segment of a read >= rl
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((int)(keys[seg_start[mid]] >> 48) < rl) lo = mid + 1;
+        else hi = mid;
+    }
+    int64_t end = lo;
+    hi = n_seg;                   // first segment of a read > rl
+    while (end < hi) {
+        const int64_t mid = (end + hi) >> 1;
+        if ((int)(keys[seg_start[mid]] >> 48) <= rl) end = mid + 1;
+        else hi = mid;
+    }
+    const int64_t n = end - lo;
+    const int L = (int)(read_flat_off[rl + 1] - read_flat_off[rl] - 1);   // (the flat image has one break after every read)
+    int32_t* o = out + (int64_t)rl * (MAP_CAND_HEAD + 8 * K);
+    // pass 1: the best passing score (scores are >= min_score >= 0)
+    int best = -1;
+    for (int64_t i = lane; i < n; i += 64) {
+        const CandSeg c = map_cand_eval(keys, qs, seg_res, lo + i, min_anchors, min_score, L, tlen, max_3p);
+        if (c.pass) best = max(best, c.score);
+    }
+    best = wave_max(best);
+    if (best < 0) {
+        if (lane == 0) {
+            o[0] = n == 0 ? RD_MAP_NO_SEED : RD_MAP_NO_CHAIN;
+            o[1] = o[2] = 0;
+        }
+        return;
+    }
+    const int64_t need = (int64_t)best * min_frac_q10;
+    // pass 2
+    int n_qual = 0;
+    for (int64_t b = 0; b < n; b += 64) {
+        const int64_t i = b + lane;
+        CandSeg mine;
+        mine.pass = false;
+        mine.score = -1;
+        if (i < n) mine = map_cand_eval(keys, qs, seg_res, lo + i, min_anchors, min_score, L, tlen, max_3p);
+        const bool cand = mine.pass && (int64_t)mine.score * 1024 >= need;
+        n_qual += __popcll(__ballot(cand));
+        int rank = 0;
+        for (int64_t b2 = 0; b2 < n; b2 += 64) {
+            const int64_t j = b2 + lane;
+            int other = -1;   // the score of segment j when it is a candidate
+            if (b2 == b) {
+                other = cand ? mine.score : -1;
+            } else if (j < n) {
+                const CandSeg c = map_cand_eval(keys, qs, seg_res, lo + j, min_anchors, min_score, L, tlen, max_3p);
+                if (c.pass && (int64_t)c.score * 1024 >= need) other = c.score;
+            }
+            for (int l = 0; l < 64; l++) {
+                const int sj = __builtin_amdgcn_readlane(other, l);
+                if (sj > mine.score || (sj == mine.score && b2 + l < i)) rank++;
+            }
+        }
+        if (cand && rank < K) {
+            int32_t* row = o + MAP_CAND_HEAD + 8 * rank;
+            row[0] = mine.t;
+            row[1] = mine.score;
+            row[2] = mine.n_anchors;
+            row[3] = mine.q0;
+            row[4] = mine.r0;
+            row[5] = mine.q1;
+            row[6] = mine.r1;
+            row[7] = mine.d3;
+        }
+    }
+    if (lane == 0) {
+        o[0] = RD_MAP_OK;
+        o[1] = n_qual;
+        o[2] = min(n_qual, K);
+    }
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
 struct MapState {
     int k = 0, w = 0, max_occ = 0;
     int64_t n_idx = 0, n_records = 0;
     DevBuf keys, vals;                                           // the index: uint32 keys ascending, uint64 values in (transcript, position) order
+    DevBuf tlen;                                                 // int32 per transcript: its length in codes (rd_map_candidates' 3' distance)
     DevBuf codes, off, flags, bcnt, boff, pos, tmp, hit, cnt, scan, rm, ra, out;   // per call
 };
 
@@ -511,7 +628,7 @@ void rd_map_destroy(rd_ctx* ctx)
 {
     MapState* st = (MapState*)ctx->map;
     if (!st) return;
-    DevBuf* bufs[] = {&st->keys, &st->vals, &st->codes, &st->off, &st->flags, &st->bcnt, &st->boff, &st->pos, &st->tmp, &st->hit, &st->cnt, &st->scan, &st->rm, &st->ra, &st->out};
+    DevBuf* bufs[] = {&st->keys, &st->vals, &st->tlen, &st->codes, &st->off, &st->flags, &st->bcnt, &st->boff, &st->pos, &st->tmp, &st->hit, &st->cnt, &st->scan, &st->rm, &st->ra, &st->out};
     for (DevBuf* b : bufs) b->release();
     delete st;
     ctx->map = nullptr;
@@ -608,6 +725,13 @@ extern "C" int rd_map_index(rd_ctx* ctx, const uint8_t* codes, const int64_t* of
         v2.release();
         if (rc != RD_OK) return rc;
     }
+    {
+        std::vector<int32_t> tlen((size_t)n_records);
+        for (int64_t r = 0; r < n_records; r++) tlen[(size_t)r] = (int32_t)(offsets[r + 1] - offsets[r]);
+        RD_RESERVE(st->tlen, (size_t)n_records * 4);
+        RD_HIP(hipMemcpyAsync(st->tlen.p, tlen.data(), (size_t)n_records * 4, hipMemcpyHostToDevice, ctx->stream));
+        RD_HIP(hipStreamSynchronize(ctx->stream));
+    }
     const double t2 = now_us();
     st->k = k;
     st->w = w;
@@ -625,32 +749,52 @@ extern "C" int rd_map_index(rd_ctx* ctx, const uint8_t* codes, const int64_t* of
     return RD_OK;
 }
 
-extern "C" int rd_map_batch(rd_ctx* ctx, const uint8_t* reads, const int64_t* read_off, int64_t n_reads, int min_anchors, int min_score, int max_gap,
-                            int bandwidth, int64_t budget_bytes, int32_t* status, int32_t* hits, int64_t* stats)
+// what rd_map_candidates asks of a call in place of rd_map_batch's hits
+struct MapCand {
+    int K, min_frac_q10, max_3p;
+    int32_t *n_qual, *n_cand, *cands;
+};
+
+// rd_map_batch (cd == nullptr: hits) and rd_map_candidates (cd: hits unused): seeds, count + scan, the launches under the budget, fill, sort
+// and chains are one code; the calls differ in the kernel that reduces a read's segments and in what it leaves per read
+static int map_run(rd_ctx* ctx, const char* who, const uint8_t* reads, const int64_t* read_off, int64_t n_reads, int min_anchors, int min_score, int max_gap,
+                   int bandwidth, int64_t budget_bytes, int32_t* status, int32_t* hits, const MapCand* cd, int64_t* stats)
 {
-    RD_REQUIRE(ctx != nullptr && status != nullptr && hits != nullptr, "rd_map_batch: null argument");
+    RD_REQUIRE(ctx != nullptr && status != nullptr && (cd ? cd->n_qual != nullptr && cd->n_cand != nullptr && cd->cands != nullptr : hits != nullptr),
+               "%s: null argument", who);
     MapState* st = (MapState*)ctx->map;
     if (!st || st->k == 0) {
-        rd_set_error("rd_map_batch: no index in this context (rd_map_index first)");
+        rd_set_error("%s: no index in this context (rd_map_index first)", who);
         return RD_ERR_STATE;
     }
-    RD_REQUIRE(min_anchors >= 1, "rd_map_batch: min_anchors = %d (at least 1)", min_anchors);
-    RD_REQUIRE(min_score >= 0, "rd_map_batch: min_score = %d (at least 0)", min_score);
-    RD_REQUIRE(max_gap >= 1 && max_gap < (1 << 24), "rd_map_batch: max_gap = %d (1 .. 2^24 - 1)", max_gap);
-    RD_REQUIRE(bandwidth >= 0 && bandwidth < (1 << 24), "rd_map_batch: bandwidth = %d (0 .. 2^24 - 1)", bandwidth);
-    RD_REQUIRE(budget_bytes >= 0, "rd_map_batch: negative budget");
-    if (int rc = check_records("rd_map_batch", reads, read_off, n_reads)) return rc;
+    RD_REQUIRE(min_anchors >= 1, "%s: min_anchors = %d (at least 1)", who, min_anchors);
+    RD_REQUIRE(min_score >= 0, "%s: min_score = %d (at least 0)", who, min_score);
+    RD_REQUIRE(max_gap >= 1 && max_gap < (1 << 24), "%s: max_gap = %d (1 .. 2^24 - 1)", who, max_gap);
+    RD_REQUIRE(bandwidth >= 0 && bandwidth < (1 << 24), "%s: bandwidth = %d (0 .. 2^24 - 1)", who, bandwidth);
+    RD_REQUIRE(budget_bytes >= 0, "%s: negative budget", who);
+    if (cd) {
+        RD_REQUIRE(cd->K >= 1 && cd->K <= RD_MAP_MAX_CAND, "%s: max_cand = %d (1 .. %d)", who, cd->K, RD_MAP_MAX_CAND);
+        RD_REQUIRE(cd->min_frac_q10 >= 0 && cd->min_frac_q10 <= 1024, "%s: min_frac_q10 = %d (0 .. 1024)", who, cd->min_frac_q10);
+        RD_REQUIRE(cd->max_3p >= -1, "%s: max_3p = %d (-1: off, or at least 0)", who, cd->max_3p);
+    }
+    if (int rc = check_records(who, reads, read_off, n_reads)) return rc;
+    const int per_read = cd ? MAP_CAND_HEAD + 8 * cd->K : 9;   // ints a read has in st->out
     if (stats)
         for (int c = 0; c < 16; c++) stats[c] = 0;
     for (int64_t r = 0; r < n_reads; r++) {
         status[r] = RD_MAP_NO_SEED;
-        for (int c = 0; c < 8; c++) hits[8 * r + c] = 0;
+        if (cd) {
+            cd->n_qual[r] = cd->n_cand[r] = 0;
+            for (int c = 0; c < 8 * cd->K; c++) cd->cands[(int64_t)8 * cd->K * r + c] = 0;
+        } else {
+            for (int c = 0; c < 8; c++) hits[8 * r + c] = 0;
+        }
     }
     if (n_reads == 0) return RD_OK;
     RD_HIP(hipSetDevice(ctx->device));
     if (int rc = rd_resolve_budget(&budget_bytes, ctx->ws_align.cap)) return rc;
     const int k = st->k;
-    double t_stage[6] = {0, 0, 0, 0, 0, 0};   // seeds, lookup, fill, sort, chain, best
+    double t_stage[7] = {0, 0, 0, 0, 0, 0, 0};   // seeds, lookup, fill, sort, chain, best, candidates
     double t0 = now_us();
     std::vector<uint8_t> flat;
     std::vector<int64_t> flat_off;
@@ -666,7 +810,7 @@ extern "C" int rd_map_batch(rd_ctx* ctx, const uint8_t* reads, const int64_t* re
     RD_RESERVE(st->scan, (size_t)(M + 1) * 8);
     RD_RESERVE(st->rm, (size_t)(n_reads + 1) * 8);
     RD_RESERVE(st->ra, (size_t)(n_reads + 1) * 8);
-    RD_RESERVE(st->out, (size_t)n_reads * 9 * 4);
+    RD_RESERVE(st->out, (size_t)n_reads * per_read * 4);
     hipLaunchKernelGGL(lookup_count_kernel, dim3((unsigned)((M + 1 + 255) / 256)), dim3(256), 0, ctx->stream, st->codes.as<uint8_t>(), st->pos.as<uint32_t>(), M,
                        st->off.as<int64_t>(), n_reads, k, st->keys.as<uint32_t>(), st->n_idx, st->max_occ, st->hit.as<MzHit>(), st->cnt.as<uint64_t>());
     RD_HIP(hipGetLastError());
@@ -703,8 +847,8 @@ extern "C" int rd_map_batch(rd_ctx* ctx, const uint8_t* reads, const int64_t* re
     };
     std::vector<Launch> launches;
     for (auto [k0, k1] : plan.launches) launches.push_back({plan.run[k0], plan.run[k1 - 1] + 1});
-    if (ctx->ws_align.reserve_exact((size_t)plan.max_bytes, "rd_map_batch")) return RD_ERR_NOMEM;
-    RD_HIP(hipMemsetAsync(st->out.p, 0, (size_t)n_reads * 9 * 4, ctx->stream));
+    if (ctx->ws_align.reserve_exact((size_t)plan.max_bytes, who)) return RD_ERR_NOMEM;
+    RD_HIP(hipMemsetAsync(st->out.p, 0, (size_t)n_reads * per_read * 4, ctx->stream));
     int64_t total_anchors = 0, total_segments = 0;
     for (const Launch& L : launches) {
         const int64_t m0 = read_m[L.r0], m1 = read_m[L.r1], a0 = read_a[L.r0], A = read_a[L.r1] - a0;
@@ -712,7 +856,7 @@ extern "C" int rd_map_batch(rd_ctx* ctx, const uint8_t* reads, const int64_t* re
         int end_bit = 48;
         while (end_bit < 64 && (n_local - 1) >> (end_bit - 48)) end_bit++;
         LaunchWs W;
-        if (int rc = carve_launch_ws(ctx, "rd_map_batch", A, end_bit, W)) return rc;
+        if (int rc = carve_launch_ws(ctx, who, A, end_bit, W)) return rc;
         rocprim::double_buffer<uint64_t> dk(W.ka, W.kb);
         rocprim::double_buffer<uint32_t> dq(W.qa, W.qb);
         t0 = now_us();
@@ -739,38 +883,64 @@ extern "C" int rd_map_batch(rd_ctx* ctx, const uint8_t* reads, const int64_t* re
             t_stage[4] += now_us() - t0;
             t0 = now_us();
         }
-        hipLaunchKernelGGL(map_best_kernel, dim3((unsigned)((n_local + 255) / 256)), dim3(256), 0, ctx->stream, keys, qs, W.seg_start, n_seg, W.seg_res, n_local,
-                           min_anchors, min_score, st->out.as<int32_t>() + L.r0 * 9);
+        if (cd)
+            hipLaunchKernelGGL(map_cand_kernel, dim3((unsigned)((n_local + 3) / 4)), dim3(256), 0, ctx->stream, keys, qs, W.seg_start, n_seg, W.seg_res, n_local,
+                               min_anchors, min_score, st->off.as<int64_t>() + L.r0, st->tlen.as<int32_t>(), cd->K, cd->min_frac_q10, cd->max_3p,
+                               st->out.as<int32_t>() + L.r0 * per_read);
+        else
+            hipLaunchKernelGGL(map_best_kernel, dim3((unsigned)((n_local + 255) / 256)), dim3(256), 0, ctx->stream, keys, qs, W.seg_start, n_seg, W.seg_res,
+                               n_local, min_anchors, min_score, st->out.as<int32_t>() + L.r0 * 9);
         RD_HIP(hipGetLastError());
         RD_HIP(hipStreamSynchronize(ctx->stream));   // the next launch reuses the workspace
-        if (stats) t_stage[5] += now_us() - t0;
+        if (stats) t_stage[cd ? 6 : 5] += now_us() - t0;
         total_anchors += A;
         total_segments += n_seg;
     }
-    std::vector<int32_t> out((size_t)n_reads * 9);
+    std::vector<int32_t> out((size_t)n_reads * per_read);
     RD_HIP(hipMemcpyAsync(out.data(), st->out.p, out.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
     RD_HIP(hipStreamSynchronize(ctx->stream));
     for (const Launch& L : launches)
         for (int64_t r = L.r0; r < L.r1; r++) {
-            status[r] = out[(size_t)r * 9];
-            for (int c = 0; c < 8; c++) hits[8 * r + c] = out[(size_t)r * 9 + 1 + c];
+            const int32_t* o = out.data() + (size_t)r * per_read;
+            status[r] = o[0];
+            if (cd) {
+                cd->n_qual[r] = o[1];
+                cd->n_cand[r] = o[2];
+                memcpy(cd->cands + (int64_t)8 * cd->K * r, o + MAP_CAND_HEAD, (size_t)8 * cd->K * 4);
+            } else {
+                for (int c = 0; c < 8; c++) hits[8 * r + c] = o[1 + c];
+            }
         }
     if (stats) {
         stats[0] = (int64_t)launches.size();
         stats[1] = M;
         stats[2] = total_anchors;
         stats[3] = total_segments;
-        for (int c = 0; c < 6; c++) stats[8 + c] = (int64_t)t_stage[c];
+        for (int c = 0; c < 7; c++) stats[8 + c] = (int64_t)t_stage[c];
     }
     if (too_large) {
         const int64_t r = first_too_large;
-        rd_set_error("rd_map_batch: read %lld has %lld anchors and needs %lld bytes of workspace, over the budget of %lld; %lld read%s not mapped "
-                     "(status RD_MAP_TOO_LARGE), the others were", (long long)r, (long long)(read_a[r + 1] - read_a[r]),
+        rd_set_error("%s: read %lld has %lld anchors and needs %lld bytes of workspace, over the budget of %lld; %lld read%s not mapped "
+                     "(status RD_MAP_TOO_LARGE), the others were", who, (long long)r, (long long)(read_a[r + 1] - read_a[r]),
                      (long long)((read_a[r + 1] - read_a[r]) * MAP_ANCHOR_BYTES + MAP_LAUNCH_BYTES), (long long)budget_bytes, (long long)too_large,
                      too_large == 1 ? "" : "s");
         return RD_ERR_NOMEM;
     }
     return RD_OK;
+}
+
+extern "C" int rd_map_batch(rd_ctx* ctx, const uint8_t* reads, const int64_t* read_off, int64_t n_reads, int min_anchors, int min_score, int max_gap,
+                            int bandwidth, int64_t budget_bytes, int32_t* status, int32_t* hits, int64_t* stats)
+{
+    return map_run(ctx, "rd_map_batch", reads, read_off, n_reads, min_anchors, min_score, max_gap, bandwidth, budget_bytes, status, hits, nullptr, stats);
+}
+
+extern "C" int rd_map_candidates(rd_ctx* ctx, const uint8_t* reads, const int64_t* read_off, int64_t n_reads, int min_anchors, int min_score, int max_gap,
+                                 int bandwidth, int64_t budget_bytes, int max_cand, int min_frac_q10, int max_3p, int32_t* status, int32_t* n_qual,
+                                 int32_t* n_cand, int32_t* cands, int64_t* stats)
+{
+    const MapCand cd{max_cand, min_frac_q10, max_3p, n_qual, n_cand, cands};
+    return map_run(ctx, "rd_map_candidates", reads, read_off, n_reads, min_anchors, min_score, max_gap, bandwidth, budget_bytes, status, nullptr, &cd, stats);
 }
 
 // ---- diagnostic seams (include/radian_hip_diag.h): the stages above, one at a time, through the same kernels ----------------------------
