@@ -78,6 +78,30 @@ int rd_map_diag_minimizers(rd_ctx* ctx, const uint8_t* codes, const int64_t* off
 int rd_map_diag_chain(rd_ctx* ctx, const uint32_t* t, const uint32_t* r, const uint32_t* q, int64_t n, int k, int min_anchors, int max_gap,
                       int bandwidth, int32_t* seg_out, int64_t cap_seg, int64_t* n_seg_out);
 
+/* ---- score arithmetic, routine by routine (scoremath.hip; for tests) ------------------------ */
+/* The scalar routines every beam-search score goes through, evaluated alone: out[i] = routine(x[i]) or routine(x[i], y[i]), one device
+ * thread per element, through the routines of csrc/decode_common.h and csrc/glibc_math.h themselves (the kernel includes the headers).
+ * The "fast" arithmetic (rd_set_decode_math 0) exists on the device only: */
+#define RD_SM_EXP_NONPOS 0    /* exp_nonpos(x), x <= 0 */
+#define RD_SM_LOG1P_UNIT 1    /* log1p_unit(x), 0 <= x <= 1 */
+#define RD_SM_LAE 2           /* lae(x, y) = log(e^x + e^y) */
+#define RD_SM_SAFE_LOG 3      /* safe_log<false>(x): the device library's log; -inf for anything that is no probability */
+/* the "glibc" arithmetic (rd_set_decode_math 1), also compiled for the host: */
+#define RD_SM_GM_EXP 4        /* gm_exp(x), the table read from LDS as in the search kernels */
+#define RD_SM_GM_LOG 5        /* gm_log(x) */
+#define RD_SM_GM_LOG1P 6      /* gm_log1p(x) */
+#define RD_SM_GM_LOG1P_UNIT 7 /* gm_log1p_unit(x), 0 <= x <= 1 */
+#define RD_SM_LAE_GX 8        /* lae_gx(x, y) */
+#define RD_SM_SAFE_LOG_GX 9   /* safe_log<true>(x) */
+/* the ranking's compare-and-count (device only): x holds 4 n keys, out[i] = count4_gt(0, x[4i], .., x[4i+3], y[i]) as a double */
+#define RD_SM_COUNT4_GT 10
+/* y may be null for the one-argument routines.  RD_ERR_ARG -- before anything is copied or launched, out untouched -- for a null pointer,
+ * n < 0, n > 2^24 or an unknown `which`.  Copies x (and y) in and out back on the context's stream and waits for it. */
+int rd_diag_score_math(rd_ctx* ctx, int which, const double* x, const double* y, int64_t n, double* out);
+/* The glibc selections (RD_SM_GM_EXP .. RD_SM_SAFE_LOG_GX) from the same header compiled for the host: no GPU, no context.  The same
+ * refusals, and RD_ERR_ARG for a device-only routine. */
+int rd_diag_score_math_host(int which, const double* x, const double* y, int64_t n, double* out);
+
 /* ---- kernel timing on the launch stream (HIP events) --------------------------------------- */
 #define RD_TIMER_CONV 0   /* dilated conv 256->256 (MFMA), the dominant kernel */
 #define RD_TIMER_DECODE 1 /* beam search */

@@ -155,6 +155,8 @@ DIAG_SIGNATURES = {
     "rd_set_trie_budget": (c_i, [c_vp, c_i64]),
     "rd_map_diag_minimizers": (c_i, [c_vp, c_vp, c_vp, c_i64, c_i, c_i, c_vp, c_i64, c_i64p]),
     "rd_map_diag_chain": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i, c_i, c_i, c_i, c_vp, c_i64, c_i64p]),
+    "rd_diag_score_math": (c_i, [c_vp, c_i, c_vp, c_vp, c_i64, c_vp]),
+    "rd_diag_score_math_host": (c_i, [c_i, c_vp, c_vp, c_i64, c_vp]),
     "rd_timer_enable": (c_i, [c_vp, c_i, c_i]),
     "rd_timer_read": (c_i, [c_vp, c_i, c_dp, ctypes.POINTER(c_i), c_dp, c_dp]),
     "rd_timer_read_launches": (c_i, [c_vp, c_i, c_i, c_vp, c_vp, c_vp, ctypes.POINTER(c_i)]),

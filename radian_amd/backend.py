@@ -430,6 +430,34 @@ def quant_em_host(cand_off, cand_t, cand_w, n_tx, max_iter=1000, tol_q20=1024, w
     return QuantResult(count[:int(n_tx)], None if share is None else share[:slots], st)
 
 
+# rd_diag_score_math's routines (include/radian_hip_diag.h RD_SM_*): 0..3 and 10 exist on the device only
+(SM_EXP_NONPOS, SM_LOG1P_UNIT, SM_LAE, SM_SAFE_LOG, SM_GM_EXP, SM_GM_LOG, SM_GM_LOG1P, SM_GM_LOG1P_UNIT, SM_LAE_GX, SM_SAFE_LOG_GX,
+ SM_COUNT4_GT) = range(11)
+
+
+def _score_math_args(which, x, y):
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+    n = x.size // 4 if which == SM_COUNT4_GT else x.size
+    if y is not None:
+        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        if y.size != n or (which == SM_COUNT4_GT and x.size != 4 * n):
+            raise ValueError("score_math: x and y differ in length (count4_gt: x holds four keys per entry of y)")
+        if n == 0:
+            y = np.zeros(1, dtype=np.float64)
+    return (x if x.size else np.zeros(4, dtype=np.float64)), y, n
+
+
+def score_math_host(which, x, y=None):
+    """Backend.score_math on the host (rd_diag_score_math_host: the glibc routines, SM_GM_EXP .. SM_SAFE_LOG_GX, from the same header
+    compiled for the host; no GPU, no context)"""
+    L = _lib.load()
+    x, y, n = _score_math_args(which, x, y)
+    out = np.zeros(max(n, 1), dtype=np.float64)
+    if L.rd_diag_score_math_host(int(which), _p(x), _p(y), n, _p(out)) != 0:
+        raise RadianHipError(L.rd_last_error().decode())
+    return out[:n]
+
+
 def quant_workspace_bytes(slots, n_reads, n_tx):
     """an upper bound of the device workspace Backend.quant_em reserves (rd_quant_workspace_bytes)"""
     return int(_lib.load().rd_quant_workspace_bytes(int(slots), int(n_reads), int(n_tx)))
@@ -1475,6 +1503,14 @@ class Backend:
         self._check(self._L.rd_map_diag_chain(self._h, _p(t), _p(r), _p(q), n, int(k), int(min_anchors), int(max_gap), int(bandwidth), _p(seg), seg.shape[0],
                                               ctypes.byref(got)))
         return seg[: got.value].copy()
+
+    def score_math(self, which, x, y=None):
+        """rd_diag_score_math (tests): one routine of the beam search's score arithmetic (SM_*) on the device, element by element.  float64
+        [n]; for SM_COUNT4_GT x holds 4 n keys and y the n keys they are counted against."""
+        x, y, n = _score_math_args(which, x, y)
+        out = np.zeros(max(n, 1), dtype=np.float64)
+        self._check(self._L.rd_diag_score_math(self._h, int(which), _p(x), _p(y), n, _p(out)))
+        return out[:n]
 
     @staticmethod
     def map_minimizers(codes, k, w):

@@ -25,6 +25,11 @@ constexpr double kLogE2 = 0.693147180559945309417232121458176568;
 // for the pair against ~175 (the generic log1p runs a double-double reduction) -- at the same accuracy class: measured
 // against 80-bit references over 2.5e7 arguments, exp_nonpos <= 0.68 ulp, log1p_unit <= 0.63 ulp, their composition
 // <= 1.55 ulp (glibc's: 0.51 / 0.82 / 1.54).  So scores keep agreeing with the reference's to a few ulp.
+// Corrected by tests/test_gpu_score_math.py (the routines alone on reduction boundaries, subnormal results, t next to 1;
+// mpmath as the reference): log1p_unit reaches 0.7103 ulp at t = 0.9945960893620833 -- its figure is <= 0.72 ulp, not 0.63.
+// The quotient's rounding is compensated in the series' first term only: the s^3 / 3 term takes the rounded s, whose
+// error (up to ~1.5 ulp through the reciprocal) costs up to ~0.18 ulp where s is largest, next to t = 1.  Still faithfully
+// rounded.  exp_nonpos there: 0.6441 ulp, and 0.7487 units of 2^-1074 on subnormal results.
 #pragma clang fp contract(off)
 // Horner chains with the coefficients in scalar register pairs.  As plain C++ hipcc keeps all ~30 coefficients in VGPRs
 // across the time loop and spends a v_mov_b64 + v_fmac_f64 per step (the VOP2 form accumulates into the coefficient's

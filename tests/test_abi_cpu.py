@@ -40,17 +40,17 @@ def test_diag_header_holds_the_measurement_entry_points_and_the_product_header_n
     from radian_amd import _lib
     diag = declared_symbols("radian_hip_diag.h")
     prod = declared_symbols()
-    assert sorted(_lib.DIAG_SIGNATURES) == diag and len(diag) == 12
+    assert sorted(_lib.DIAG_SIGNATURES) == diag and len(diag) == 14
     assert not set(diag) & set(prod)
     for n in diag:
         assert hasattr(lib, n), f"libradian_hip.so does not export {n}"
-    for word in ("rd_timer_", "rd_set_conv_shape", "rd_set_conv_fuse", "rd_set_decode_form", "rd_split3", "rd_pipe_stats", "rd_pipe_policy_read", "rd_set_trie_budget", "rd_map_diag_", "RD_TIMER_"):
+    for word in ("rd_timer_", "rd_set_conv_shape", "rd_set_conv_fuse", "rd_set_decode_form", "rd_split3", "rd_pipe_stats", "rd_pipe_policy_read", "rd_set_trie_budget", "rd_map_diag_", "rd_diag_score_math", "RD_SM_", "RD_TIMER_"):
         assert word not in open(os.path.join(ROOT, "include", "radian_hip.h")).read(), word
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
     exported = sorted({ln.split()[-1] for ln in out.splitlines() if re.search(r"\s[TW]\s+rd_[a-z0-9_]+$", ln)})
     assert exported == sorted(prod + diag), sorted(set(exported) ^ set(prod + diag))
     # the command line's modules never reach a diagnostic wrapper of Backend
-    wrappers = ("set_conv_shape", "set_conv_fuse", "split3", "set_decode_form", "pipe_policy_read", "pipe_stats", "timer_enable", "timer_read", "timer_read_launches", "set_trie_budget", "map_diag_minimizers", "map_diag_chain")
+    wrappers = ("set_conv_shape", "set_conv_fuse", "split3", "set_decode_form", "pipe_policy_read", "pipe_stats", "timer_enable", "timer_read", "timer_read_launches", "set_trie_budget", "map_diag_minimizers", "map_diag_chain", "score_math", "score_math_host")
     pkg = os.path.join(ROOT, "radian_amd")
     for f in sorted(os.listdir(pkg)):
         if f.endswith(".py") and f not in ("backend.py", "_lib.py"):
