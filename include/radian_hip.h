@@ -811,6 +811,63 @@ int rd_quant_em_host(const int64_t* cand_off, const int32_t* cand_t, const uint1
                      uint64_t tol_q20, uint64_t* count_q20, uint32_t* share_q20, int64_t* stats);
 int64_t rd_quant_workspace_bytes(int64_t slots, int64_t n_reads, int64_t n_tx);
 
+/* ---- pileup: per-site base counts and an error profile (pileup.hip, csrc/pileup_rules.h) ---------------------
+ * NO reference behaviour.  Pair p is a span refs[ref_off[p] .. ref_off[p+1]) of n characters whose first character is site site0[p] of a
+ * table of n_sites sites, against a read of m characters, and the column ops of their alignment ('M' 'X' 'D' 'I' as rd_align_batch
+ * writes them).  Bytes are taken as they are (no U -> T here); code(byte): A 0, C 1, G 2, T 3, anything else 4.
+ *   The covered interval of a pair runs from its first M / X column to its last; a pair without one has status RD_PILEUP_NO_BASE and
+ *   adds nothing.  Columns outside the interval add nothing: I columns there are soft clip, D columns shorten the covered range.
+ *   Site channels (uint32 [8] per site): A C G T other (the read byte of an M / X column at this site), del (a D column), ins (a maximal
+ *   run of I columns, at the site of the nearest ref-consuming column before it), starts (the interval's first column).  A channel
+ *   grows by at most one per pair and site; at most 2^31 - 1 pairs are accepted between open and close (RD_ERR_ARG beyond).
+ *   Profile (uint64 [RD_PILEUP_PROFILE_LEN], the covered interval only):
+ *     [RD_PILEUP_CONF + 6 a + b]      span code a (0..4) x outcome b (read code 0..4 of an M / X column, 5 = a D column)
+ *     [RD_PILEUP_INS_BASE + c]        inserted read bytes by code
+ *     [RD_PILEUP_KMER + 4 k + e]      k: the 5-mer span[i-2 .. i+2], A = 0 .. T = 3, leftmost base most significant; e: 0 an M column at
+ *                                     i, 1 an X column, 2 a D column, 3 an insertion run attributed to i.  Offsets within 2 of a span end
+ *                                     and 5-mers with a non-ACGT byte count in conf only.
+ *     [RD_PILEUP_INS_LEN + b], [RD_PILEUP_DEL_LEN + b]   maximal run lengths 1..63 in b = 0..62, 64 and longer in b = 63
+ *   The column kind is the caller's (M against X), the channel comes from the read byte: rd_pileup_add_ops does not require them to agree.
+ *   out [n_pairs][RD_PILEUP_RES] int32: status, alignment score (0 from rd_pileup_add_ops and rd_pileup_host), ref_lo, ref_hi (the covered
+ *     span offsets, half-open), clip_head, clip_tail (read characters before / after the interval), n_match, n_sub, n_ins, n_del: the
+ *     M, X, I and D columns INSIDE THE COVERED INTERVAL.  These are not rd_align_batch's counts, which follow analyse_alignment's clip
+ *     (three non-gap ref characters, gap columns against a non-ACGT character dropped).  RD_PILEUP_NO_BASE: clip_head = m, the rest 0.
+ *   rd_pileup_open      allocates and zeroes the tables of n_sites (0 .. 2^30) sites in the context; a second open starts again from zero
+ *   rd_pileup_close     frees them
+ *   rd_pileup_add       aligns exactly as rd_align_batch does (scores, tie-break, optional ops, budget) and accumulates.  Requires
+ *                       site0[p] + n <= n_sites.  A pair that alone exceeds the budget is not aligned and adds nothing: status
+ *                       RD_PILEUP_TOO_LARGE, and the call returns RD_ERR_NOMEM naming it after the others ran.  A pair takes
+ *                       rd_pileup_workspace_bytes(n, m) = rd_align_workspace_bytes(n, m) + 48 + 256.
+ *   rd_pileup_add_ops   the same accumulation from columns the caller has (ops + ops_off[p] .. ops_off[p+1]); no alignment runs.
+ *                       RD_ERR_ARG before anything is added unless every op is M / X / D / I and the ops of a pair consume exactly its n
+ *                       and m characters; n + m < 2^28.
+ *   rd_pileup_read      the sites whose depth (channels A .. del summed) is >= min_depth >= 1, in site order: site [n_out] and counts
+ *                       [8 n_out]; profile (nullable) is always written.  *n_out is the number of such sites; when capacity is smaller
+ *                       the call returns RD_ERR_ARG with *n_out set and no site written.
+ *   rd_pileup_host      host, no GPU, no context: the same rules in plain loops ADDED into the caller's sites [8 n_sites] and profile.
+ * Integer adds only: the tables do not depend on launch order, budget or batching.  Synchronous; the context's stream. */
+#define RD_PILEUP_OK 0
+#define RD_PILEUP_NO_BASE 1
+#define RD_PILEUP_TOO_LARGE 2
+#define RD_PILEUP_RES 10
+#define RD_PILEUP_CONF 0
+#define RD_PILEUP_INS_BASE 30
+#define RD_PILEUP_KMER 35
+#define RD_PILEUP_INS_LEN 4131
+#define RD_PILEUP_DEL_LEN 4195
+#define RD_PILEUP_PROFILE_LEN 4259
+int rd_pileup_open(rd_ctx* ctx, int64_t n_sites);
+int rd_pileup_close(rd_ctx* ctx);
+int rd_pileup_add(rd_ctx* ctx, const uint8_t* refs, const int64_t* ref_off, const uint8_t* reads, const int64_t* read_off, int n_pairs,
+                  const int64_t* site0, int match, int mismatch, int gap_open, int gap_extend, int64_t budget_bytes, int32_t* out,
+                  uint8_t* ops_out, const int64_t* ops_off, int32_t* ops_len);
+int rd_pileup_add_ops(rd_ctx* ctx, const uint8_t* ops, const int64_t* ops_off, const uint8_t* refs, const int64_t* ref_off,
+                      const uint8_t* reads, const int64_t* read_off, int n_pairs, const int64_t* site0, int32_t* out);
+int rd_pileup_read(rd_ctx* ctx, uint32_t min_depth, int64_t capacity, uint32_t* site, uint32_t* counts, uint64_t* profile, int64_t* n_out);
+int64_t rd_pileup_workspace_bytes(int64_t n, int64_t m);
+int rd_pileup_host(const uint8_t* ops, const int64_t* ops_off, const uint8_t* refs, const int64_t* ref_off, const uint8_t* reads,
+                   const int64_t* read_off, int n_pairs, const int64_t* site0, int64_t n_sites, uint32_t* sites, uint64_t* profile, int32_t* out);
+
 /* The CTC loss of Keras's ctc_batch_cost and a greedy edit distance, per window, on the GPU (ctc.hip).
  * Window i has RD_CTC_T = 1024 softmax rows y[t][0..4] (A, C, G, T, blank), input_len[i] (1..1024) rows counted, and
  * label_len[i] (0..RD_CTC_MAX_LABEL) labels 0..3 at labels + label_off[i].

@@ -122,6 +122,13 @@ SIGNATURES = {
     "rd_quant_em": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i, c_u64, c_vp, c_vp, c_vp]),
     "rd_quant_em_host": (c_i, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i, c_u64, c_vp, c_vp, c_vp]),
     "rd_quant_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
+    "rd_pileup_open": (c_i, [c_vp, c_i64]),
+    "rd_pileup_close": (c_i, [c_vp]),
+    "rd_pileup_add": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_vp, c_i, c_i, c_i, c_i, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "rd_pileup_add_ops": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_vp, c_vp]),
+    "rd_pileup_read": (c_i, [c_vp, c_u32, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "rd_pileup_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "rd_pileup_host": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "rd_ctc_eval": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rd_ctc_probs": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rd_ctc_probs_resident": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

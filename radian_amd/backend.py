@@ -536,6 +536,64 @@ class AlignResult:
         self.score, self.counts, self.status, self.ops = score, counts, status, ops
 
 
+# rd_pileup_* (include/radian_hip.h RD_PILEUP_*)
+PILEUP_OK, PILEUP_NO_BASE, PILEUP_TOO_LARGE = 0, 1, 2
+PILEUP_CHANNELS = ("A", "C", "G", "T", "other", "del", "ins", "starts")
+PILEUP_FIELDS = ("status", "score", "ref_lo", "ref_hi", "clip_head", "clip_tail", "n_match", "n_sub", "n_ins", "n_del")
+PILEUP_CONF, PILEUP_INS_BASE, PILEUP_KMER, PILEUP_INS_LEN, PILEUP_DEL_LEN, PILEUP_PROFILE_LEN = 0, 30, 35, 4131, 4195, 4259
+
+
+class PileupPairs:
+    """Per-pair results of Backend.pileup_add / pileup_add_ops / pileup_host: out int32 [n, 10] (PILEUP_FIELDS: the counts are those of
+    the covered interval, not Backend.align's), every field also as an attribute; ops (list of bytes, or None when not asked for)."""
+
+    def __init__(self, out, ops=None):
+        self.out, self.ops = out, ops
+        for i, nm in enumerate(PILEUP_FIELDS):
+            setattr(self, nm, out[:, i])
+
+
+class PileupTable:
+    """Backend.pileup_read: site uint32 [n_out] (ascending), counts uint32 [n_out, 8] (PILEUP_CHANNELS), profile uint64 [PILEUP_PROFILE_LEN]"""
+
+    def __init__(self, site, counts, profile):
+        self.site, self.counts, self.profile = site, counts, profile
+
+
+def _pileup_args(refs, reads, site0, ops=None):
+    n = len(refs)
+    if len(reads) != n or len(site0) != n or (ops is not None and len(ops) != n):
+        raise ValueError(f"{len(refs)} spans, {len(reads)} reads, {len(site0)} sites" + ("" if ops is None else f", {len(ops)} op strings"))
+    rbuf, roff = _concat(refs)
+    qbuf, qoff = _concat(reads)
+    s0 = np.ascontiguousarray(np.asarray(site0, dtype=np.int64).reshape(-1)) if n else np.zeros(1, dtype=np.int64)
+    out = np.zeros((max(n, 1), 10), dtype=np.int32)
+    obuf, ooff = _concat(ops) if ops is not None else (None, None)
+    return n, rbuf, roff, qbuf, qoff, s0, out, obuf, ooff
+
+
+def pileup_host(ops, refs, reads, site0, n_sites, sites=None, profile=None):
+    """The pileup rules on the host (rd_pileup_host: plain loops; no GPU, no context), ADDED into sites uint32 [n_sites, 8] and profile
+    uint64 [PILEUP_PROFILE_LEN] (fresh zeroed tables when None).  Returns (PileupPairs, sites, profile)."""
+    L = _lib.load()
+    n, rbuf, roff, qbuf, qoff, s0, out, obuf, ooff = _pileup_args(refs, reads, site0, ops)
+    if sites is None:
+        sites = np.zeros((max(int(n_sites), 1), 8), dtype=np.uint32)
+    if profile is None:
+        profile = np.zeros(PILEUP_PROFILE_LEN, dtype=np.uint64)
+    if sites.dtype != np.uint32 or profile.dtype != np.uint64 or not sites.flags.c_contiguous or sites.size < 8 * int(n_sites) or profile.size < PILEUP_PROFILE_LEN:
+        raise ValueError("pileup_host: sites is uint32 [n_sites, 8], profile uint64 [PILEUP_PROFILE_LEN]")
+    rc = L.rd_pileup_host(_p(obuf), _p(ooff), _p(rbuf), _p(roff), _p(qbuf), _p(qoff), n, _p(s0), int(n_sites), _p(sites), _p(profile), _p(out))
+    if rc != 0:
+        raise RadianHipError(f"[rd error {rc}] " + L.rd_last_error().decode("utf-8", "replace"))
+    return PileupPairs(out[:n]), sites, profile
+
+
+def pileup_workspace_bytes(n, m):
+    """device workspace (bytes) rd_pileup_add needs for one n x m pair alone (rd_pileup_workspace_bytes; no GPU)"""
+    return int(_lib.load().rd_pileup_workspace_bytes(int(n), int(m)))
+
+
 # rd_ctc_* per-window status (include/radian_hip.h RD_CTC_*)
 CTC_OK, CTC_INFEASIBLE = 0, 1
 CTC_T, CTC_MAX_LABEL = 1024, 255
@@ -1211,6 +1269,54 @@ class Backend:
         if with_ops:
             ops_list = [ops[ops_off[p]: ops_off[p] + ops_len[p]].tobytes() for p in range(n)]
         return AlignResult(score, counts, status, ops_list)
+
+    # ------------------------------------------------------------------ pileup
+    def pileup_open(self, n_sites):
+        """Allocate and zero the context's pileup tables for n_sites sites (rd_pileup_open); a second open starts again from zero."""
+        self._check(self._L.rd_pileup_open(self._h, int(n_sites)))
+
+    def pileup_close(self):
+        self._check(self._L.rd_pileup_close(self._h))
+
+    def pileup_add(self, refs, reads, site0, scores=ALIGN_SCORES, budget_bytes=0, with_ops=False, allow_too_large=False):
+        """Align reads[p] against the span refs[p] exactly as Backend.align does and add the alignment's columns to the open pileup, the
+        span's first base being site site0[p] (rd_pileup_add).  A pair over the budget raises, unless allow_too_large: status
+        PILEUP_TOO_LARGE, nothing added for it."""
+        n, rbuf, roff, qbuf, qoff, s0, out, _, _ = _pileup_args(refs, reads, site0)
+        ops = ops_off = ops_len = None
+        if with_ops:
+            ops_off = np.zeros(n + 1, dtype=np.int64)
+            np.cumsum((roff[1:] - roff[:-1]) + (qoff[1:] - qoff[:-1]), out=ops_off[1:])
+            ops = np.zeros(max(int(ops_off[-1]), 1), dtype=np.uint8)
+            ops_len = np.zeros(max(n, 1), dtype=np.int32)
+        m, x, go, ge = (int(v) for v in scores)
+        rc = self._L.rd_pileup_add(self._h, _p(rbuf), _p(roff), _p(qbuf), _p(qoff), n, _p(s0), m, x, go, ge, int(budget_bytes), _p(out),
+                                   _p(ops), _p(ops_off), _p(ops_len))
+        if rc != 0 and not (allow_too_large and rc == -4 and (out[:n, 0] == PILEUP_TOO_LARGE).any()):
+            self._check(rc)
+        ops_list = [ops[ops_off[p]: ops_off[p] + ops_len[p]].tobytes() for p in range(n)] if with_ops else None
+        return PileupPairs(out[:n], ops_list)
+
+    def pileup_add_ops(self, ops, refs, reads, site0):
+        """Add alignments the caller already has (ops[p]: bytes of M / X / D / I that consume refs[p] and reads[p] exactly) to the open
+        pileup; no alignment runs (rd_pileup_add_ops)."""
+        n, rbuf, roff, qbuf, qoff, s0, out, obuf, ooff = _pileup_args(refs, reads, site0, ops)
+        self._check(self._L.rd_pileup_add_ops(self._h, _p(obuf), _p(ooff), _p(rbuf), _p(roff), _p(qbuf), _p(qoff), n, _p(s0), _p(out)))
+        return PileupPairs(out[:n])
+
+    def pileup_read(self, min_depth=1, capacity=None):
+        """The sites at depth >= min_depth, in site order, and the profile (rd_pileup_read).  capacity None: asked for first."""
+        profile = np.zeros(PILEUP_PROFILE_LEN, dtype=np.uint64)
+        n_out = ctypes.c_int64(0)
+        if capacity is None:
+            rc = self._L.rd_pileup_read(self._h, int(min_depth), 0, None, None, _p(profile), ctypes.byref(n_out))
+            if rc != 0 and n_out.value == 0:
+                self._check(rc)
+            capacity = n_out.value
+        site = np.zeros(max(int(capacity), 1), dtype=np.uint32)
+        counts = np.zeros((max(int(capacity), 1), 8), dtype=np.uint32)
+        self._check(self._L.rd_pileup_read(self._h, int(min_depth), int(capacity), _p(site), _p(counts), _p(profile), ctypes.byref(n_out)))
+        return PileupTable(site[:n_out.value], counts[:n_out.value], profile)
 
     # ------------------------------------------------------------------ forced CTC alignment (DESIGN.md section 16)
     def ctc_align(self, mats, seq_off, seq_len, labels, budget_bytes=0, allow_too_large=False):

@@ -28,6 +28,7 @@
 // 'I' insertion) to its slot of n + m bytes, then clips and counts them (align_clip_count, below).
 #include "common.h"
 #include "budget.h"
+#include "align_batch.h"
 
 #include <algorithm>
 #include <cstring>
@@ -37,18 +38,9 @@ namespace {
 
 constexpr int ALN_NEG = -(1 << 30);
 constexpr int ALN_OK = 0, ALN_CLIP_INDEX_ERROR = 1, ALN_EMPTY_AFTER_CLIP = 2, ALN_TOO_LARGE = 3;   // radian_hip.h RD_ALIGN_*
-constexpr int ALN_RES = 7;   // per-pair result ints: score, n_match, n_sub, n_ins, n_del, status, n_ops
 
 struct AlnScores {
     int match, mismatch, open, extend;
-};
-
-struct AlnPair {
-    int64_t ref, read;   // byte offsets of the sequences in the workspace
-    int64_t ops;         // byte offset of the op slot (n + m bytes)
-    int64_t bnd;         // int32 offset of the boundary rows: H [m + 1], then E [m + 1]
-    int64_t dir;         // uint32 offset of the direction words
-    int32_t n, m;
 };
 
 __host__ __device__ inline int aln_gap(int len, const AlnScores& s) { return len == 0 ? 0 : s.open + (len - 1) * s.extend; }
@@ -288,31 +280,34 @@ extern "C" int rd_align_clip_count(const uint8_t* ops, int64_t n_ops, const uint
     return RD_OK;
 }
 
-extern "C" int rd_align_batch(rd_ctx* ctx, const uint8_t* refs, const int64_t* ref_off, const uint8_t* reads, const int64_t* read_off,
-                              int n_pairs, int match, int mismatch, int gap_open, int gap_extend, int64_t budget_bytes, int32_t* score,
-                              int32_t* counts, int32_t* status, uint8_t* ops_out, const int64_t* ops_off, int32_t* ops_len)
+// The argument checks, the budget plan, the staging and the two kernels of a batch alignment; after align_tb_kernel every launch goes
+// through the hook (align_batch.h).  rd_align_batch is this with an empty hook.
+int rd_align_batch_run(rd_ctx* ctx, const char* who, const char* too_large_name, const uint8_t* refs, const int64_t* ref_off, const uint8_t* reads,
+                       const int64_t* read_off, int n_pairs, int match, int mismatch, int gap_open, int gap_extend, int64_t budget_bytes,
+                       int32_t* score, int32_t* counts, int32_t* status, uint8_t* ops_out, const int64_t* ops_off, int32_t* ops_len, AlnHook& hook)
 {
-    RD_REQUIRE(ctx && ref_off && read_off && score && counts && status, "rd_align_batch: null argument");
-    RD_REQUIRE(n_pairs >= 0, "rd_align_batch: n_pairs %d", n_pairs);
+    RD_REQUIRE(ctx && ref_off && read_off && score && counts && status, "%s: null argument", who);
+    RD_REQUIRE(n_pairs >= 0, "%s: n_pairs %d", who, n_pairs);
     RD_REQUIRE((ops_out == nullptr) == (ops_off == nullptr) && (ops_out == nullptr) == (ops_len == nullptr),
-               "rd_align_batch: ops_out, ops_off and ops_len are given together or not at all");
-    RD_REQUIRE(budget_bytes >= 0, "rd_align_batch: negative budget");
+               "%s: ops_out, ops_off and ops_len are given together or not at all", who);
+    RD_REQUIRE(budget_bytes >= 0, "%s: negative budget", who);
     const int lim = 1 << 16;
-    RD_REQUIRE(abs(match) < lim && abs(mismatch) < lim && abs(gap_open) < lim && abs(gap_extend) < lim, "rd_align_batch: score out of range");
-    RD_REQUIRE(ref_off[0] == 0 && read_off[0] == 0, "rd_align_batch: offsets must start at 0");
+    RD_REQUIRE(abs(match) < lim && abs(mismatch) < lim && abs(gap_open) < lim && abs(gap_extend) < lim, "%s: score out of range", who);
+    RD_REQUIRE(ref_off[0] == 0 && read_off[0] == 0, "%s: offsets must start at 0", who);
     std::vector<int64_t> cells(n_pairs), bytes(n_pairs);
+    const size_t extra = hook.extra_pair_bytes, batch_bytes = ALN_BATCH_BYTES + (extra ? 256 : 0);
     const int64_t smax = std::max(std::max(abs(match), abs(mismatch)), std::max(abs(gap_open), abs(gap_extend)));
     for (int p = 0; p < n_pairs; p++) {
         const int64_t n = ref_off[p + 1] - ref_off[p], m = read_off[p + 1] - read_off[p];
-        RD_REQUIRE(n >= 0 && m >= 0, "rd_align_batch: pair %d has a negative length", p);
+        RD_REQUIRE(n >= 0 && m >= 0, "%s: pair %d has a negative length", who, p);
         // scores stay far from ALN_NEG: |H| <= smax * (n + m + 1)
-        RD_REQUIRE(n < (1 << 30) && m < (1 << 30) && smax * (n + m + 1) < (1 << 28), "rd_align_batch: pair %d (%lld x %lld) is too long for int32 scores",
+        RD_REQUIRE(n < (1 << 30) && m < (1 << 30) && smax * (n + m + 1) < (1 << 28), "%s: pair %d (%lld x %lld) is too long for int32 scores", who,
                    p, (long long)n, (long long)m);
         cells[p] = n * m;
-        bytes[p] = (int64_t)aln_pair_bytes(n, m);
+        bytes[p] = (int64_t)(aln_pair_bytes(n, m) + extra);
     }
-    RD_REQUIRE(ref_off[n_pairs] == 0 || refs, "rd_align_batch: null refs");
-    RD_REQUIRE(read_off[n_pairs] == 0 || reads, "rd_align_batch: null reads");
+    RD_REQUIRE(ref_off[n_pairs] == 0 || refs, "%s: null refs", who);
+    RD_REQUIRE(read_off[n_pairs] == 0 || reads, "%s: null reads", who);
     RD_HIP(hipSetDevice(ctx->device));
     if (int rc = rd_resolve_budget(&budget_bytes, ctx->ws_align.cap)) return rc;
     // largest pairs first (load balance of a launch), packed into batches under the budget; a pair that alone exceeds it is
@@ -320,7 +315,7 @@ extern "C" int rd_align_batch(rd_ctx* ctx, const uint8_t* refs, const int64_t* r
     std::vector<int> order(n_pairs);
     std::iota(order.begin(), order.end(), 0);
     std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return cells[x] > cells[y]; });
-    const BudgetPlan plan = rd_plan_budget(n_pairs, order.data(), budget_bytes, (int64_t)ALN_BATCH_BYTES, false,
+    const BudgetPlan plan = rd_plan_budget(n_pairs, order.data(), budget_bytes, (int64_t)batch_bytes, false,
                                            [&](int p, int) { return bytes[p]; }, rd_budget_never_closes);
     const std::vector<int32_t>& run = plan.run;
     const int too_large = (int)plan.too_large, first_too_large = (int)plan.first_too_large;
@@ -330,7 +325,7 @@ extern "C" int rd_align_batch(rd_ctx* ctx, const uint8_t* refs, const int64_t* r
         for (int c = 0; c < 4; c++) counts[4 * (int64_t)p + c] = 0;
         if (ops_len) ops_len[p] = 0;
     }
-    if (ctx->ws_align.reserve_exact((size_t)plan.max_bytes, "rd_align_batch")) return RD_ERR_NOMEM;
+    if (ctx->ws_align.reserve_exact((size_t)plan.max_bytes, who)) return RD_ERR_NOMEM;
     const AlnScores sc{match, mismatch, gap_open, gap_extend};
     std::vector<uint8_t> stage;
     std::vector<AlnPair> desc;
@@ -368,8 +363,11 @@ extern "C" int rd_align_batch(rd_ctx* ctx, const uint8_t* refs, const int64_t* r
                 d.bnd = d.dir = 0;
             }
         }
+        at = align_up(at, 256);
+        const size_t extra_at = at;
+        at += (size_t)nb * extra;
         if (at > ctx->ws_align.cap) {
-            rd_set_error("rd_align_batch: internal workspace accounting (%zu > %zu)", at, ctx->ws_align.cap);
+            rd_set_error("%s: internal workspace accounting (%zu > %zu)", who, at, ctx->ws_align.cap);
             return RD_ERR_STATE;
         }
         stage.assign(up_bytes, 0);
@@ -393,7 +391,10 @@ extern "C" int rd_align_batch(rd_ctx* ctx, const uint8_t* refs, const int64_t* r
             ops_h.resize(ops_hi - ops_lo);
             RD_HIP(hipMemcpyAsync(ops_h.data(), dws + ops_lo, ops_hi - ops_lo, hipMemcpyDeviceToHost, ctx->stream));
         }
+        const AlnLaunch launch{dpairs, dws, dres, extra ? dws + extra_at : nullptr, nb, &run[k0], desc.data(), ctx->stream};
+        if (int rc = hook.launched(launch)) return rc;
         RD_HIP(hipStreamSynchronize(ctx->stream));
+        if (int rc = hook.finished(launch)) return rc;
         for (int k = 0; k < nb; k++) {
             const int p = run[k0 + k];
             const int32_t* r = &res[(size_t)k * ALN_RES];
@@ -407,11 +408,20 @@ extern "C" int rd_align_batch(rd_ctx* ctx, const uint8_t* refs, const int64_t* r
         }
     }
     if (too_large) {
-        rd_set_error("rd_align_batch: pair %d (%lld x %lld) needs %lld bytes of workspace, over the budget of %lld; %d pair(s) not aligned "
-                     "(status RD_ALIGN_TOO_LARGE), the others were", first_too_large, (long long)(ref_off[first_too_large + 1] - ref_off[first_too_large]),
-                     (long long)(read_off[first_too_large + 1] - read_off[first_too_large]), (long long)(bytes[first_too_large] + ALN_BATCH_BYTES),
-                     (long long)budget_bytes, too_large);
+        rd_set_error("%s: pair %d (%lld x %lld) needs %lld bytes of workspace, over the budget of %lld; %d pair(s) not aligned "
+                     "(status %s), the others were", who, first_too_large, (long long)(ref_off[first_too_large + 1] - ref_off[first_too_large]),
+                     (long long)(read_off[first_too_large + 1] - read_off[first_too_large]), (long long)(bytes[first_too_large] + (int64_t)batch_bytes),
+                     (long long)budget_bytes, too_large, too_large_name);
         return RD_ERR_NOMEM;
     }
     return RD_OK;
+}
+
+extern "C" int rd_align_batch(rd_ctx* ctx, const uint8_t* refs, const int64_t* ref_off, const uint8_t* reads, const int64_t* read_off,
+                              int n_pairs, int match, int mismatch, int gap_open, int gap_extend, int64_t budget_bytes, int32_t* score,
+                              int32_t* counts, int32_t* status, uint8_t* ops_out, const int64_t* ops_off, int32_t* ops_len)
+{
+    AlnHook none;
+    return rd_align_batch_run(ctx, "rd_align_batch", "RD_ALIGN_TOO_LARGE", refs, ref_off, reads, read_off, n_pairs, match, mismatch, gap_open,
+                              gap_extend, budget_bytes, score, counts, status, ops_out, ops_off, ops_len, none);
 }

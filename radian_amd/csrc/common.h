@@ -206,6 +206,12 @@ struct rd_ctx {
     DevBuf ws_sim;                  // rd_sim_* (sim.hip): the model tables, then a launch's bases, dwells, positions and samples
     DevBuf ws_site;                 // rd_site_* (sitecmp.hip): a launch's events, keys, segments and per-site results
     DevBuf ws_quant;                // rd_quant_em (quant.hip): the packed candidates, the counts and the shares of one call, resident over its iterations
+    // rd_pileup_* (pileup.hip): the accumulator lives from rd_pileup_open to rd_pileup_close, across calls (as the seed index of rd_map_index does)
+    DevBuf pileup_sites;            // [pileup_n_sites][8] uint32: A C G T other del ins starts
+    DevBuf pileup_profile;          // [RD_PILEUP_PROFILE_LEN] uint64
+    DevBuf ws_pileup;               // a launch of rd_pileup_add_ops (descriptors, sequences, ops, results); the flags, scan and rows of rd_pileup_read
+    int64_t pileup_n_sites = -1;    // -1: not open
+    int64_t pileup_pairs = 0;       // pairs added since rd_pileup_open (at most 2^31 - 1: no 32-bit site counter can overflow)
     int64_t trie_budget = (int64_t)24 << 30;   // bytes of beam-search workspace one launch may ask for (rd_plan_trie_runs; rd_set_trie_budget)
     // pinned host staging
     void* h_stage = nullptr;
