@@ -648,6 +648,66 @@ int rd_sim_signal_host(const uint8_t* codes, const int64_t* seq_off, int n_reads
                        int32_t* status);
 int64_t rd_sim_workspace_bytes(int64_t n_bases, int64_t n_samples);
 
+/* ---- eventalign: raw samples against a k-mer pore model, Viterbi (eventalign.hip) -------------------------
+ * NO reference behaviour.  The inverse of rd_sim_signal: given samples, a sequence and a pore-model table, which samples belong to which
+ * base.  No neural network takes part.  Integer arithmetic only; met exactly.
+ *   read      read r is samples raw + read_off[r] .. read_off[r+1] (n of them); only the window [t_lo[r], t_hi[r]) takes part,
+ *             0 <= t_lo <= t_hi <= n, T = t_hi - t_lo rows.  L = ref_len[r] bases codes[ref_off[r] ..], each 0..3, in the order the pore
+ *             sees them (3'->5': the decode order); L = 0 is valid.  Per-base outputs are indexed by ref_off[r] + b (ref_off[r+1] >=
+ *             ref_off[r] + ref_len[r])
+ *   scale     d4_in[r] > 0: (m2_in[r], d4_in[r]) as given (|m2_in| <= 2^17, d4_in <= 2^20).  d4_in[r] == 0: the window's own, as
+ *             rd_polya_segment: m2 = the sum of the two middle order statistics of the window's samples, d4 = the sum of the two middle
+ *             order statistics of |2x - m2|
+ *   model     k odd, 1 <= k <= 9; per k-mer (4^k entries, pore order, first base most significant) lvl (int32, |.| < 2^14: the level in
+ *             MAD/256), w (uint32: the inverse variance in Q32) and bias (int32, |.| <= 256: the log-sd term in 1/32 nat); the same three
+ *             numbers for the background, lvl_bg, w_bg, bias_bg.  Base b's k-mer by rd_sim_signal's rule: centred on b, a position outside
+ *             the span takes the nearest end base
+ *   sample    u = 512 (2x - m2); zq = clamp(floor((2u + d4) / (2 d4)), -2^14, 2^14), the division in 64 bits: the sample in MAD/256,
+ *             rounded half up
+ *   states    s = 0 .. L + 1: 0 is the lead and L + 1 the trail (both the background), s in 1 .. L is base s - 1
+ *   cell      d = zq[t] - lvl(s) (d^2 < 2^30); c(t, s) = min(floor(d^2 w(s) / 2^32), 1024) + bias(s)
+ *   path      int32.  V[0][0] = c(0, 0), V[0][1] = c(0, 1); a cell with s > t + 1 is unreachable (2^30);
+ *             V[t][s] = c(t, s) + min(V[t-1][s], V[t-1][s-1]), the advance from s - 1 taken only if STRICTLY smaller.  Every cell with
+ *             s <= t + 1 is reachable, so 2^30 is never added to a result.  With T <= 2^19 every finite value stays below 2^19 * 1280 <
+ *             2^30 and an unreachable cell computed unmasked from 2^30 stays above 2^30 - 2^19 * 256: it never wins.  There are no skips
+ *             and no dwell prior.  The path ends in state L + 1 at row T - 1, or in L if V[T-1][L+1] is not strictly smaller
+ *   status    in this order: T == 0 RD_EVAL_EMPTY; T > 2^19 RD_EVAL_TOO_LONG; a computed d4 == 0 RD_EVAL_MAD_ZERO; T < L
+ *             RD_EVAL_NO_PATH; over the budget alone RD_EVAL_TOO_LARGE; otherwise RD_EVAL_OK
+ *   outputs   status; score (int64: the end value); m2, d4 as used (0, 0 for EMPTY and TOO_LONG; whatever the status otherwise);
+ *             first_step / last_step per base in READ sample coordinates (t_lo added): last_step[b] = first_step[b+1] - 1, last_step[L-1]
+ *             is the last row in state L -- exactly what rd_event_stats accepts; ev_start .. ev_max: rd_event_stats of those steps;
+ *             fit_sums[5 r ..]: N, sum l, sum l^2, sum x, sum x l over the samples that sit in base states, l the base's lvl and x the
+ *             raw sample (all below 2^49): the normal equations of x = alpha + beta l.  A read that is not OK has score 0, zero sums and
+ *             the "no path" outputs of rd_event_stats (-1, -1 and zeros; steps -1); it never affects its neighbours
+ * A result does not depend on the batch, the order, the budget or the launches.  RD_ERR_ARG before anything is launched: a null pointer,
+ * offsets that are not monotone, a code above 3, a window outside its read, a scale or a table entry outside its range.  n_reads == 0 is
+ * RD_OK.
+ *   rd_eventalign        on the GPU; synchronous, uses the context's stream.  budget_bytes and RD_ERR_NOMEM as rd_ctc_align_batch
+ *                        (DESIGN.md section 19): the DP workspace one launch may take, rd_eventalign_workspace_bytes per read, 0 = a
+ *                        quarter of the free device memory; a read that alone exceeds it is not aligned: RD_EVAL_TOO_LARGE, and the
+ *                        call returns RD_ERR_NOMEM naming it after doing the others
+ *   rd_eventalign_host   host, no GPU: the same rules (csrc/eventalign_rules.h) in a plain loop
+ *   rd_eventalign_workspace_bytes   of a window of n_rows rows and n_bases bases, each term rounded up to 256:
+ *                        4 n_rows (quantised samples) + 4 n_rows ceil((n_bases + 2) / 32) (back-pointers, one bit per cell)
+ *                        + 8 n_rows (two band columns) when n_bases + 2 > 4096 */
+#define RD_EVAL_OK 0
+#define RD_EVAL_EMPTY 1
+#define RD_EVAL_TOO_LONG 2
+#define RD_EVAL_MAD_ZERO 3
+#define RD_EVAL_NO_PATH 4
+#define RD_EVAL_TOO_LARGE 5
+int rd_eventalign(rd_ctx* ctx, const int16_t* raw, const int64_t* read_off, int n_reads, const int64_t* t_lo, const int64_t* t_hi,
+                  const uint8_t* codes, const int64_t* ref_off, const int32_t* ref_len, const int32_t* m2_in, const int32_t* d4_in, int k,
+                  const int32_t* lvl, const uint32_t* w, const int32_t* bias, int32_t lvl_bg, uint32_t w_bg, int32_t bias_bg,
+                  int64_t budget_bytes, int32_t* status, int64_t* score, int32_t* m2, int32_t* d4, int32_t* first_step, int32_t* last_step,
+                  int32_t* ev_start, int32_t* ev_end, int64_t* ev_sum, int64_t* ev_sumsq, int16_t* ev_min, int16_t* ev_max, int64_t* fit_sums);
+int rd_eventalign_host(const int16_t* raw, const int64_t* read_off, int n_reads, const int64_t* t_lo, const int64_t* t_hi, const uint8_t* codes,
+                       const int64_t* ref_off, const int32_t* ref_len, const int32_t* m2_in, const int32_t* d4_in, int k, const int32_t* lvl,
+                       const uint32_t* w, const int32_t* bias, int32_t lvl_bg, uint32_t w_bg, int32_t bias_bg, int32_t* status, int64_t* score,
+                       int32_t* m2, int32_t* d4, int32_t* first_step, int32_t* last_step, int32_t* ev_start, int32_t* ev_end, int64_t* ev_sum,
+                       int64_t* ev_sumsq, int16_t* ev_min, int16_t* ev_max, int64_t* fit_sums);
+int64_t rd_eventalign_workspace_bytes(int64_t n_rows, int64_t n_bases);
+
 /* ---- model evaluation on labelled windows: the reference's val_loss (radian/model.py:77-98, radian/train.py:48-79) ------------
  * Labelled windows as the reference stores them: TFRecord shards of tf.train.Example records (radian/data.py:9-31), read on the
  * HOST without TensorFlow (tfrecord.hip).  Framing: u64 length, u32 masked crc32c of it, the data, u32 masked crc32c of the data;

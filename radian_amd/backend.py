@@ -338,6 +338,86 @@ def sim_launch_bytes(k):
     return (12 * 4 ** k + 4096 + 255) // 256 * 256 + 12288
 
 
+# rd_eventalign per-read status (include/radian_hip.h RD_EVAL_*)
+EVAL_OK, EVAL_EMPTY, EVAL_TOO_LONG, EVAL_MAD_ZERO, EVAL_NO_PATH, EVAL_TOO_LARGE = 0, 1, 2, 3, 4, 5
+EVAL_STATUS_NAMES = ("ok", "empty", "too-long", "mad-zero", "no-path", "too-large")
+
+
+class EvalModel:
+    """rd_eventalign's pore model, all integers (the contract is in include/radian_hip.h): k odd 1..9; per k-mer in pore order lvl (int32,
+    MAD/256), w (uint32, Q32 inverse variance), bias (int32, 1/32 nat); bg = (lvl, w, bias) of the background"""
+    __slots__ = ("k", "lvl", "w", "bias", "bg")
+
+    def __init__(self, k, lvl, w, bias, bg):
+        self.k = int(k)
+        self.lvl = np.ascontiguousarray(lvl, dtype=np.int32).ravel()
+        self.w = np.ascontiguousarray(w, dtype=np.uint32).ravel()
+        self.bias = np.ascontiguousarray(bias, dtype=np.int32).ravel()
+        self.bg = (int(bg[0]), int(bg[1]), int(bg[2]))
+        n = 4 ** self.k if 1 <= self.k <= 9 else -1
+        if not (self.lvl.size == self.w.size == self.bias.size == n):
+            raise ValueError(f"an EvalModel of k = {self.k} takes three tables of 4^k entries")
+
+    def args(self):
+        return (self.k, _p(self.lvl), _p(self.w), _p(self.bias), *self.bg)
+
+
+class EvalResult:
+    """per read: status (int32, EVAL_*), score (int64), m2 / d4 (int32: the scale as used), fit_sums (int64 [reads, 5]: N, sum l, sum l^2,
+    sum x, sum x l); per read and base: first_step / last_step (int32 arrays, read sample coordinates) and events (an EventsResult)"""
+    __slots__ = ("status", "score", "m2", "d4", "fit_sums", "first_step", "last_step", "events")
+
+    def __init__(self, status, score, m2, d4, fit_sums, first_step, last_step, events):
+        self.status, self.score, self.m2, self.d4, self.fit_sums = status, score, m2, d4, fit_sums
+        self.first_step, self.last_step, self.events = first_step, last_step, events
+
+
+def _eval_args(raws, seqs, model, t_lo, t_hi, m2, d4):
+    """-> (the arrays, kept alive by the caller; the arguments up to the budget; the output buffers; the per-base cut)"""
+    flat, off = Backend._pack_raw(raws)
+    n = len(raws)
+    if len(seqs) != n:
+        raise ValueError(f"{len(seqs)} sequences for {n} reads")
+    codes, coff = _concat_codes(seqs)
+    ref_len = np.diff(coff).astype(np.int32)
+    ref_off = np.ascontiguousarray(coff[:-1] if n else np.zeros(1), dtype=np.int64)
+    lens = np.diff(off)
+    lo = np.zeros(n, dtype=np.int64) if t_lo is None else np.ascontiguousarray(t_lo, dtype=np.int64).ravel()
+    hi = lens.astype(np.int64) if t_hi is None else np.ascontiguousarray(t_hi, dtype=np.int64).ravel()
+    m2 = np.zeros(n, dtype=np.int32) if m2 is None else np.ascontiguousarray(m2, dtype=np.int32).ravel()
+    d4 = np.zeros(n, dtype=np.int32) if d4 is None else np.ascontiguousarray(d4, dtype=np.int32).ravel()
+    if not (lo.size == hi.size == m2.size == d4.size == n):
+        raise ValueError(f"per-read arguments that do not hold one entry for each of {n} reads")
+    lo, hi, m2, d4 = (np.concatenate([a, np.zeros(1, a.dtype)]) for a in (lo, hi, m2, d4))   # (a pointer the library can check when n = 0)
+    tot = int(coff[-1])
+    outs = [np.zeros(n + 1, np.int32), np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int32), np.zeros(n + 1, np.int32),
+            np.full(tot + 1, -1, np.int32), np.full(tot + 1, -1, np.int32), *_event_buffers(tot), np.zeros((n + 1, 5), np.int64)]
+    keep = (flat, off, codes, ref_off, ref_len, lo, hi, m2, d4, model)
+    head = (_p(flat), _p(off), n, _p(lo), _p(hi), _p(codes), _p(ref_off), _p(ref_len), _p(m2), _p(d4), *model.args())
+    cut = [(int(coff[i]), int(coff[i + 1])) for i in range(n)]
+    return keep, head, outs, cut
+
+
+def _eval_result(outs, cut, n):
+    status, score, m2, d4, first, last = outs[:6]
+    return EvalResult(status[:n], score[:n], m2[:n], d4[:n], outs[12][:n], [first[a:b].copy() for a, b in cut], [last[a:b].copy() for a, b in cut],
+                      _events_of(outs[6:12], cut))
+
+
+def eventalign_host(raws, seqs, model, t_lo=None, t_hi=None, m2=None, d4=None):
+    """Backend.eventalign on the host (rd_eventalign_host: the same rules in a plain loop; no GPU, no context)"""
+    L = _lib.load()
+    keep, head, outs, cut = _eval_args(raws, seqs, model, t_lo, t_hi, m2, d4)
+    if L.rd_eventalign_host(*head, *[_p(b) for b in outs]) != 0:
+        raise RadianHipError(L.rd_last_error().decode())
+    return _eval_result(outs, cut, len(raws))
+
+
+def eventalign_workspace_bytes(n_rows, n_bases):
+    """device workspace Backend.eventalign needs for one window of n_rows samples and n_bases bases (rd_eventalign_workspace_bytes)"""
+    return int(_lib.load().rd_eventalign_workspace_bytes(int(n_rows), int(n_bases)))
+
+
 def _pack(arrays, dtype, pad=0):
     """list of arrays -> (their elements as one flat buffer of dtype, int64 offsets [n + 1]); a buffer without elements has `pad` zeros (1
     where the library wants a pointer it can check)"""
@@ -1439,6 +1519,21 @@ class Backend:
 
     sim_lengths_host = staticmethod(sim_lengths_host)
     sim_signal_host = staticmethod(sim_signal_host)
+
+    # ------------------------------------------------------------------ eventalign against a pore model
+    def eventalign(self, raws, seqs, model, t_lo=None, t_hi=None, m2=None, d4=None, budget_bytes=0, allow_too_large=False):
+        """The Viterbi path of every read's bases through its samples under a k-mer pore model (rd_eventalign, on the GPU): raws -- one
+        int16 array per read; seqs -- one uint8 code array per read, in pore order; model -- an EvalModel; t_lo / t_hi -- the window of
+        every read (default: the whole read); m2 / d4 -- the scale of every read (d4 0, the default: the window's own).  budget_bytes:
+        device workspace per launch, 0 = a quarter of free memory.  A read that does not fit it raises, unless allow_too_large: status
+        EVAL_TOO_LARGE.  -> EvalResult."""
+        keep, head, outs, cut = _eval_args(raws, seqs, model, t_lo, t_hi, m2, d4)
+        rc = self._L.rd_eventalign(self._h, *head, int(budget_bytes), *[_p(b) for b in outs])
+        if rc != 0 and not (allow_too_large and rc == -4 and (outs[0][:len(raws)] == EVAL_TOO_LARGE).any()):
+            self._check(rc)
+        return _eval_result(outs, cut, len(raws))
+
+    eventalign_host = staticmethod(eventalign_host)
 
     # ------------------------------------------------------------------ signal-to-reference alignment (DESIGN.md section 17)
     def event_stats(self, raws, aln):

@@ -1,5 +1,5 @@
 // budget.h -- the device-memory budget contract of rd_align_batch, rd_fit_batch, rd_ctc_align_*, rd_map_batch, rd_polya_segment,
-// rd_site_compare and rd_sim_lengths / rd_sim_signal, once.  Plain host C++ without a HIP type: tests/asan_budget.cpp compiles it with g++ and checks its properties.
+// rd_site_compare, rd_sim_lengths / rd_sim_signal and rd_eventalign, once.  Plain host C++ without a HIP type: tests/asan_budget.cpp compiles it with g++ and checks its properties.
 //
 // An entry point gives its items in its own launch order and gets back the launches that fit the caller's budget.  An item that alone
 // exceeds the budget is counted, not launched; the entry point gives it its *_TOO_LARGE status and returns RD_ERR_NOMEM after the others

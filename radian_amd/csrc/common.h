@@ -204,6 +204,7 @@ struct rd_ctx {
     DevBuf ws_events, ws_events_io; // rd_event_stats* (events.hip): a launch's group descriptors; the step and event arrays of a host-pointer call
     DevBuf ws_polya, ws_polya_io;   // rd_polya_* (polya.hip): a launch's descriptors, scales and window arrays; the per-read results of a host-pointer call
     DevBuf ws_sim;                  // rd_sim_* (sim.hip): the model tables, then a launch's bases, dwells, positions and samples
+    DevBuf ws_eval, ws_eval_model;  // rd_eventalign (eventalign.hip): a launch's descriptors, scales and results (its DP workspace is ws_align, under the budget); the pore-model tables
     DevBuf ws_site;                 // rd_site_* (sitecmp.hip): a launch's events, keys, segments and per-site results
     DevBuf ws_quant;                // rd_quant_em (quant.hip): the packed candidates, the counts and the shares of one call, resident over its iterations
     // rd_pileup_* (pileup.hip): the accumulator lives from rd_pileup_open to rd_pileup_close, across calls (as the seed index of rd_map_index does)

@@ -1,0 +1,674 @@
+// eventalign.hip -- raw samples against a k-mer pore model: the Viterbi path of a reference span through a read's window of samples, the
+// samples every base sits on, their event table and the sums a rescaling needs.  No neural network takes part.  DESIGN.md section 24.
+//
+// Contract (integer arithmetic only, met exactly; include/radian_hip.h, rd_eventalign; the rules themselves are eventalign_rules.h).  A
+// window of T samples x, L bases, a scale (m2, d4), a model (lvl, w, bias per k-mer and for the background):
+//   zq[t]     = clamp(floor((2 u + d4) / (2 d4)), +-2^14), u = 512 (2 x[t] - m2): the sample in MAD/256
+//   states    s = 0 .. L + 1: 0 the lead and L + 1 the trail (background), s in 1 .. L base s - 1 by its k-mer
+//   c(t, s)   = min(floor((zq[t] - lvl(s))^2 w(s) / 2^32), 1024) + bias(s)
+//   V[0][0]   = c(0, 0), V[0][1] = c(0, 1); V[t][s] = c(t, s) + min(V[t-1][s], V[t-1][s-1]), the advance only if STRICTLY smaller (bit 1)
+//   end       = state L + 1, or L if V[T-1][L+1] is not strictly smaller; score = that value
+//
+// Kernels, on one stream:
+//   ea_scale_kernel   once per call, one 256-thread workgroup per read: the scale as given, or the window's own by radix_select2
+//                     (select.h) twice, as pa_scale_kernel
+//   per launch (a set of reads whose workspace fits the budget):
+//   ea_quant_kernel   zq rows, one int32 per sample
+//   ea_dp_kernel      one workgroup of 256 threads per read.  A thread owns 16 consecutive states in registers (value, level, weight
+//                     and bias of each), a workgroup pass a BAND of 4096 states; a read of more states is swept band after band, the last
+//                     state of a band at every row going through a 4-byte-per-row column in global memory (two columns, written and read
+//                     in turn).  Row t of a thread needs its left neighbour's last state of row t-1 only: one DPP wave_shr:1 inside a
+//                     wave, one LDS word and the row's single barrier between waves.  A read of at most 1024 states runs on its first wave
+//                     alone and has no barrier.  The zq rows and the band's incoming column values come through LDS in tiles of 128 rows,
+//                     fetched from global memory a tile ahead and read from LDS a row ahead.  Back-pointers: 1 bit per cell, a thread's 16
+//                     cells = one uint16, a wave's 64 stores = 128 consecutive bytes, a row = 4 ceil((L + 2) / 32) bytes.  Band b > 0
+//                     starts at row 4096 b - 1: the cells above (s > t + 1) are unreachable.  Unreachable cells are computed unmasked from
+//                     2^30: they stay above 2^30 - 2^19 * 256, every finite value stays below 2^19 * 1280, so none ever wins.
+//   ea_tb_kernel      one wave per read: end state, score, then the walk, 64 rows at a time -- lane r holds row t - r's two words (the one
+//                     of the path's state and the one below), a ballot of the state's bit over the rows not yet walked finds the nearest
+//                     row the state was entered at, and the state moves down; the path dwells tens of rows per state, so a step of the
+//                     walk is a transition, not a row.  Steps are stored in read coordinates (t_lo added).
+//   ev_stats_kernel   events.hip's, on the steps while the samples are on the device
+//   ea_sums_kernel    one workgroup per read: N, sum l, sum l^2, sum x, sum x l over its events (int64 adds: any order gives the same)
+// No floating point, no atomics but the select's LDS histogram, no scratch.  A read's result does not depend on its launch's other reads.
+#include "common.h"
+#include "budget.h"
+#include "eventalign_rules.h"
+#include "../../include/radian_hip.h"
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+namespace {
+
+struct EaModel {
+    int k;
+    const int32_t* lvl;
+    const uint32_t* w;
+    const int32_t* bias;
+    EaState bg;
+};
+
+struct EaCall {
+    const int16_t* raw;
+    const int64_t *read_off, *t_lo, *t_hi;
+    int n_reads;
+    const uint8_t* codes;
+    const int64_t* ref_off;
+    const int32_t *ref_len, *m2_in, *d4_in;
+    EaModel m;
+    int32_t* status;
+    int64_t* score;
+    int32_t *m2, *d4, *first_step, *last_step, *ev_start, *ev_end;
+    int64_t *ev_sum, *ev_sumsq;
+    int16_t *ev_min, *ev_max;
+    int64_t* fit_sums;
+};
+
+int ea_check_args(const char* who, const EaCall& c, int64_t* n_bases)
+{
+    *n_bases = 0;
+    RD_REQUIRE(c.n_reads >= 0, "%s: negative n_reads", who);
+    RD_REQUIRE(sim_k_ok(c.m.k), "%s: k = %d, not odd and 1..9", who, c.m.k);
+    RD_REQUIRE(c.m.lvl && c.m.w && c.m.bias, "%s: null model table", who);
+    const int64_t n_kmers = (int64_t)1 << (2 * c.m.k);
+    for (int64_t i = 0; i < n_kmers; i++)
+        RD_REQUIRE(ea_entry_ok(c.m.lvl[i], c.m.bias[i]), "%s: model entry %lld (lvl %d, bias %d) is outside |lvl| < 2^14, |bias| <= 256", who,
+                   (long long)i, c.m.lvl[i], c.m.bias[i]);
+    RD_REQUIRE(ea_entry_ok(c.m.bg.lvl, c.m.bg.bias), "%s: the background (lvl %d, bias %d) is outside |lvl| < 2^14, |bias| <= 256", who, c.m.bg.lvl,
+               c.m.bg.bias);
+    if (c.n_reads == 0) return RD_OK;
+    RD_REQUIRE(c.raw && c.read_off && c.t_lo && c.t_hi && c.ref_off && c.ref_len && c.m2_in && c.d4_in, "%s: null argument", who);
+    RD_REQUIRE(c.status && c.score && c.m2 && c.d4 && c.fit_sums, "%s: null output", who);
+    RD_REQUIRE(c.read_off[0] >= 0, "%s: negative read offset", who);
+    int64_t end = 0;
+    for (int r = 0; r < c.n_reads; r++) {
+        const int64_t n = c.read_off[r + 1] - c.read_off[r];
+        RD_REQUIRE(n >= 0, "%s: read offsets must be non-decreasing (read %d)", who, r);
+        RD_REQUIRE(n <= INT32_MAX, "%s: read %d has more than 2^31 - 1 samples", who, r);
+        RD_REQUIRE(0 <= c.t_lo[r] && c.t_lo[r] <= c.t_hi[r] && c.t_hi[r] <= n, "%s: read %d: the window [%lld, %lld) is outside its %lld samples", who,
+                   r, (long long)c.t_lo[r], (long long)c.t_hi[r], (long long)n);
+        RD_REQUIRE(c.ref_len[r] >= 0 && c.ref_len[r] < (1 << 29), "%s: read %d has %d bases", who, r, c.ref_len[r]);
+        RD_REQUIRE(c.ref_off[r] >= end, "%s: base offsets must be non-decreasing and the reads' bases must not overlap (read %d)", who, r);
+        RD_REQUIRE(ea_scale_ok(c.m2_in[r], c.d4_in[r]), "%s: read %d: the scale (m2 %d, d4 %d) is outside |m2| <= 2^17, 0 <= d4 <= 2^20", who, r,
+                   c.m2_in[r], c.d4_in[r]);
+        end = c.ref_off[r] + c.ref_len[r];
+    }
+    *n_bases = end;
+    if (end) {
+        RD_REQUIRE(c.codes && c.first_step && c.last_step && c.ev_start && c.ev_end && c.ev_sum && c.ev_sumsq && c.ev_min && c.ev_max,
+                   "%s: null code or per-base buffer", who);
+        for (int r = 0; r < c.n_reads; r++)
+            for (int b = 0; b < c.ref_len[r]; b++)
+                RD_REQUIRE(c.codes[c.ref_off[r] + b] < 4, "%s: base %d of read %d is %d, not in 0..3", who, b, r, c.codes[c.ref_off[r] + b]);
+    }
+    return RD_OK;
+}
+
+// the "no path" outputs of read r with this status and scale
+void ea_blank(const EaCall& c, int r, int status, int32_t m2, int32_t d4)
+{
+    c.status[r] = status;
+    c.score[r] = 0;
+    c.m2[r] = m2;
+    c.d4[r] = d4;
+    for (int i = 0; i < 5; i++) c.fit_sums[5 * (int64_t)r + i] = 0;
+    const int64_t o = c.ref_off[r];
+    for (int b = 0; b < c.ref_len[r]; b++) {
+        c.first_step[o + b] = c.last_step[o + b] = c.ev_start[o + b] = c.ev_end[o + b] = -1;
+        c.ev_sum[o + b] = c.ev_sumsq[o + b] = 0;
+        c.ev_min[o + b] = c.ev_max[o + b] = 0;
+    }
+}
+
+// the two middle order statistics of n keys counted in cnt[0 .. n_keys)
+int32_t ea_middle2(const std::vector<int64_t>& cnt, int n_keys, int64_t n)
+{
+    const int64_t k1 = (n - 1) / 2, k2 = n / 2;
+    int64_t c = 0;
+    int v1 = -1, v2 = -1;
+    for (int k = 0; k < n_keys; k++) {
+        c += cnt[k];
+        if (v1 < 0 && k1 < c) v1 = k;
+        if (v2 < 0 && k2 < c) { v2 = k; break; }
+    }
+    return v1 + v2;
+}
+
+// the window's own scale, as rd_polya_segment's
+void ea_host_scale(const int16_t* x, int64_t T, std::vector<int64_t>& cnt, int32_t* m2, int32_t* d4)
+{
+    cnt.assign(65536, 0);
+    for (int64_t i = 0; i < T; i++) cnt[(int)x[i] + 32768]++;
+    *m2 = ea_middle2(cnt, 65536, T) - 65536;
+    cnt.assign(131072, 0);
+    for (int64_t i = 0; i < T; i++) {
+        const int v = 2 * (int)x[i] - *m2;
+        cnt[v < 0 ? -v : v]++;
+    }
+    *d4 = ea_middle2(cnt, 131072, T);
+}
+
+// the five fit sums of an OK read from its events
+void ea_host_sums(const EaCall& c, int r)
+{
+    const int64_t o = c.ref_off[r];
+    const int32_t L = c.ref_len[r];
+    int64_t* s = c.fit_sums + 5 * (int64_t)r;
+    for (int32_t b = 0; b < L; b++) {
+        const int64_t l = c.m.lvl[sim_kmer(c.codes + o, L, b, c.m.k)], n = c.ev_end[o + b] - c.ev_start[o + b], x = c.ev_sum[o + b];
+        s[0] += n;
+        s[1] += n * l;
+        s[2] += n * l * l;
+        s[3] += x;
+        s[4] += x * l;
+    }
+}
+
+size_t ea_zq_bytes(int64_t T) { return align_up((size_t)T * 4, 256); }
+size_t ea_bp_bytes(int64_t T, int64_t L) { return align_up((size_t)T * (size_t)((L + 2 + 31) / 32) * 4, 256); }
+size_t ea_col_bytes(int64_t T, int64_t L) { return L + 2 > 4096 ? align_up((size_t)T * 8, 256) : 0; }
+size_t ea_read_bytes(int64_t T, int64_t L) { return ea_zq_bytes(T) + ea_bp_bytes(T, L) + ea_col_bytes(T, L); }
+
+}  // namespace
+
+extern "C" int64_t rd_eventalign_workspace_bytes(int64_t n_rows, int64_t n_bases)
+{
+    if (n_rows < 0 || n_bases < 0) return -1;
+    return (int64_t)ea_read_bytes(n_rows, n_bases);
+}
+
+extern "C" int rd_eventalign_host(const int16_t* raw, const int64_t* read_off, int n_reads, const int64_t* t_lo, const int64_t* t_hi,
+                                  const uint8_t* codes, const int64_t* ref_off, const int32_t* ref_len, const int32_t* m2_in, const int32_t* d4_in,
+                                  int k, const int32_t* lvl, const uint32_t* w, const int32_t* bias, int32_t lvl_bg, uint32_t w_bg, int32_t bias_bg,
+                                  int32_t* status, int64_t* score, int32_t* m2, int32_t* d4, int32_t* first_step, int32_t* last_step,
+                                  int32_t* ev_start, int32_t* ev_end, int64_t* ev_sum, int64_t* ev_sumsq, int16_t* ev_min, int16_t* ev_max,
+                                  int64_t* fit_sums)
+{
+    const EaCall c{raw, read_off, t_lo, t_hi, n_reads, codes, ref_off, ref_len, m2_in, d4_in, EaModel{k, lvl, w, bias, EaState{lvl_bg, w_bg, bias_bg}},
+                   status, score, m2, d4, first_step, last_step, ev_start, ev_end, ev_sum, ev_sumsq, ev_min, ev_max, fit_sums};
+    int64_t n_bases = 0;
+    int rc = ea_check_args("rd_eventalign_host", c, &n_bases);
+    if (rc || n_reads == 0) return rc;
+    std::vector<int64_t> cnt;
+    std::vector<int32_t> zq, V, ev_status(n_reads);
+    std::vector<EaState> st;
+    std::vector<uint8_t> bp;
+    for (int r = 0; r < n_reads; r++) {
+        const int64_t T = t_hi[r] - t_lo[r], L = ref_len[r], S = L + 2, o = ref_off[r];
+        const int16_t* x = raw + read_off[r] + t_lo[r];
+        int32_t um2 = m2_in[r], ud4 = d4_in[r];
+        ev_status[r] = 1;
+        if (T <= 0 || T > EA_MAX_T) {
+            ea_blank(c, r, ea_status(T, L, 1), 0, 0);
+            continue;
+        }
+        if (ud4 == 0) ea_host_scale(x, T, cnt, &um2, &ud4);
+        const int stat = ea_status(T, L, ud4);
+        ea_blank(c, r, stat, um2, ud4);
+        if (stat != EA_OK) continue;
+        ev_status[r] = 0;
+        zq.resize(T);
+        for (int64_t t = 0; t < T; t++) zq[t] = ea_quant(x[t], um2, ud4);
+        st.resize(S);
+        for (int64_t s = 0; s < S; s++) st[s] = ea_state((int32_t)s, (int32_t)L, codes + o, k, lvl, w, bias, c.m.bg);
+        V.assign(S, EA_INF);
+        bp.assign((size_t)((T * S + 7) / 8), 0);
+        V[0] = ea_cost(zq[0], st[0].lvl, st[0].w, st[0].bias);
+        V[1] = ea_cost(zq[0], st[1].lvl, st[1].w, st[1].bias);
+        for (int64_t t = 1; t < T; t++) {
+            const int64_t top = t + 1 < S - 1 ? t + 1 : S - 1;   // cells with s > t + 1 stay unreachable
+            for (int64_t s = top; s >= 0; s--) {
+                int32_t best = V[s];
+                if (s > 0 && ea_advance(V[s], V[s - 1])) {
+                    best = V[s - 1];
+                    bp[(size_t)((t * S + s) >> 3)] |= (uint8_t)(1u << ((t * S + s) & 7));
+                }
+                V[s] = ea_cost(zq[t], st[s].lvl, st[s].w, st[s].bias) + best;
+            }
+        }
+        int64_t s = ea_ends_in_trail(V[L + 1], V[L]) ? L + 1 : L;
+        score[r] = V[s];
+        const int32_t off = (int32_t)t_lo[r];
+        if (s >= 1 && s <= L) last_step[o + s - 1] = (int32_t)(T - 1) + off;
+        for (int64_t t = T - 1; t > 0; t--) {
+            if (!((bp[(size_t)((t * S + s) >> 3)] >> ((t * S + s) & 7)) & 1)) continue;
+            if (s <= L) first_step[o + s - 1] = (int32_t)t + off;
+            if (s - 1 >= 1) last_step[o + s - 2] = (int32_t)t - 1 + off;
+            s--;
+        }
+        if (s == 1 && L >= 1) first_step[o] = off;
+    }
+    if (n_bases &&
+        (rc = rd_event_stats_host(raw, read_off, n_reads, first_step, last_step, ref_off, ref_len, ev_status.data(), ev_start, ev_end, ev_sum, ev_sumsq,
+                                  ev_min, ev_max)))
+        return rc;
+    for (int r = 0; r < n_reads; r++)
+        if (status[r] == EA_OK) ea_host_sums(c, r);
+    return RD_OK;
+}
+
+#if defined(__HIPCC__)
+// ------------------------------------------------------------------------------------------------------------------ device half
+#include "select.h"
+
+namespace {
+
+constexpr int EA_NT = 256;                 // threads of a DP workgroup
+constexpr int EA_K = 16;                   // states a thread owns
+constexpr int EA_BAND = EA_NT * EA_K;      // states of one workgroup pass
+constexpr int EA_TR = 128;                 // rows of a tile in LDS (2 EA_TR elements -- zq and the incoming column: one per thread, four per lane of a lone wave)
+constexpr int EA_WAVE_STATES = 64 * EA_K;  // at most this many states: the first wave alone, no barrier
+constexpr int EA_MAX_LAUNCH = 32768;       // reads of one launch (grid.y of the row kernel)
+
+struct EaScaleIn {
+    int64_t raw0;   // the window's sample 0 in the raw buffer
+    int32_t T, m2, d4, pad_;
+};
+struct EaSeq {
+    int64_t raw0;    // the window's sample 0 in the raw buffer
+    int64_t codes;   // the read's base 0 in the code buffer
+    int64_t lab;     // its base 0 in the launch's per-base arrays
+    int64_t zq, bp, col;   // byte offsets into the workspace
+    int32_t T, L, m2, d4, t_lo, pad_;
+};
+struct EaOut {
+    int64_t score, sums[5];
+};
+
+__global__ __launch_bounds__(256) void ea_scale_kernel(const EaScaleIn* __restrict__ in, const int16_t* __restrict__ raw, int32_t* __restrict__ out)
+{
+    __shared__ unsigned hist[512];
+    __shared__ int sh[8];
+    const EaScaleIn q = in[blockIdx.x];
+    int m2 = q.m2, d4 = q.d4;
+    if (q.T <= 0 || q.T > EA_MAX_T) m2 = d4 = 0;   // (the same in every thread)
+    else if (q.d4 == 0) {
+        const int16_t* x = raw + q.raw0;
+        const int64_t n = q.T, k1 = (n - 1) / 2, k2 = n / 2;
+        const SelectResult m = radix_select2<8>(n, k1, k2, [&](int64_t i) { return (int)x[i] + 32768; }, hist, sh);
+        m2 = (m.v1 - 32768) + (m.v2 - 32768);
+        const SelectResult d = radix_select2<9>(n, k1, k2, [&](int64_t i) { const int v = 2 * (int)x[i] - m2; return v < 0 ? -v : v; }, hist, sh);
+        d4 = d.v1 + d.v2;
+    }
+    if (threadIdx.x == 0) {
+        out[2 * (int64_t)blockIdx.x] = m2;
+        out[2 * (int64_t)blockIdx.x + 1] = d4;
+    }
+}
+
+// grid (ceil(max T / 256), reads)
+__global__ __launch_bounds__(256) void ea_quant_kernel(const EaSeq* __restrict__ seqs, const int16_t* __restrict__ raw, uint8_t* __restrict__ ws,
+                                                       int32_t* __restrict__ fin)
+{
+    const EaSeq q = seqs[blockIdx.y];
+    if (blockIdx.x == 0 && threadIdx.x < 2) fin[2 * (int64_t)blockIdx.y + threadIdx.x] = EA_INF;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= q.T) return;
+    ((int32_t*)(ws + q.zq))[t] = ea_quant(raw[q.raw0 + t], q.m2, q.d4);
+}
+
+// lane l receives v of lane l - 1; lane 0 keeps its own (DPP wave_shr:1, bound_ctrl off)
+__device__ __forceinline__ int32_t ea_shr1(int32_t v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false); }
+
+__global__ __launch_bounds__(EA_NT) void ea_dp_kernel(const EaSeq* __restrict__ seqs, const uint8_t* __restrict__ codes, const int32_t* __restrict__ lvl_t,
+                                                      const uint32_t* __restrict__ w_t, const int32_t* __restrict__ bias_t, EaState bg, int k,
+                                                      uint8_t* __restrict__ ws, int32_t* __restrict__ fin)
+{
+    const EaSeq q = seqs[blockIdx.x];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int T = q.T, L = q.L, S = L + 2;
+    const bool single = S <= EA_WAVE_STATES;
+    if (single && wave) return;   // (the first wave never waits at a barrier then)
+    const int32_t* __restrict__ zq = (const int32_t*)(ws + q.zq);
+    uint16_t* __restrict__ bp = (uint16_t*)(ws + q.bp);
+    int32_t* col = (int32_t*)(ws + q.col);
+    const uint8_t* cod = codes + q.codes;
+    const int hpr = 2 * ((S + 31) / 32);   // 16-bit words of a back-pointer row
+    const int bands = (S + EA_BAND - 1) / EA_BAND;
+    __shared__ int32_t xch[2][EA_NT / 64];
+    __shared__ int32_t tile[2][2][EA_TR];   // [buffer][0: zq, 1: the band's incoming column value V[t-1][s_lo-1]][row]
+    const int nact = single ? 64 : EA_NT, per = 2 * EA_TR / nact;   // threads at work, tile elements each
+
+    for (int b = 0; b < bands; b++) {
+        const int s0 = b * EA_BAND + tid * EA_K;
+        const int t_lo = b ? b * EA_BAND - 1 : 0;   // rows above have s > t + 1 in the whole band
+        if (t_lo >= T) break;                       // (then the states of this band and the later ones are unreachable in the last row too)
+        int32_t lv[EA_K], bi[EA_K], v[EA_K];
+        uint32_t wt[EA_K];
+#pragma unroll
+        for (int j = 0; j < EA_K; j++) {
+            EaState st{0, 0, 0};   // a state past the read: its value stays where it starts
+            if (s0 + j < S) st = ea_state(s0 + j, L, cod, k, lvl_t, w_t, bias_t, bg);
+            lv[j] = st.lvl;
+            wt[j] = st.w;
+            bi[j] = st.bias;
+            v[j] = EA_INF;
+        }
+        // row -1 of band 0: V = 0 in state 0 and unreachable elsewhere makes row 0 the contract's start
+        if (b == 0 && tid == 0) v[0] = 0;
+        const int32_t* cin = col + (size_t)((b + 1) & 1) * T;   // written by band b - 1
+        int32_t* cout = col + (size_t)(b & 1) * T;
+        const bool write_col = tid == EA_NT - 1 && b + 1 < bands;
+        const bool store = s0 < S;
+        if (!single) {
+            __syncthreads();   // the previous band's last exchange reads and column writes
+            if (lane == 63) xch[(t_lo + 1) & 1][wave] = EA_INF;
+            __syncthreads();
+        }
+        auto tile_load = [&](int tbase, int32_t* pre) {
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                if (i < per) {
+                    const int e = tid + i * nact, which = e / EA_TR, t = tbase + (e % EA_TR);
+                    int32_t x = EA_INF;
+                    if (t < T) {
+                        if (which == 0) x = zq[t];
+                        else if (b > 0) x = cin[t - 1];   // t >= t_lo >= 1
+                    }
+                    pre[i] = x;
+                }
+        };
+        auto tile_store = [&](int buf, const int32_t* pre) {
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                if (i < per) {
+                    const int e = tid + i * nact;
+                    tile[buf][e / EA_TR][e % EA_TR] = pre[i];
+                }
+        };
+        int32_t pre[4];
+        tile_load(t_lo, pre);
+        tile_store(0, pre);
+        if (single) __builtin_amdgcn_wave_barrier();
+        else __syncthreads();
+        int buf = 0;
+        for (int tb = t_lo; tb < T; tb += EA_TR, buf ^= 1) {
+            const bool more = tb + EA_TR < T;
+            if (more) tile_load(tb + EA_TR, pre);
+            const int nr = T - tb < EA_TR ? T - tb : EA_TR;
+            int32_t nz = tile[buf][0][0], nc = tile[buf][1][0];
+            for (int r = 0; r < nr; r++) {
+                const int t = tb + r;
+                const int32_t z = nz, cc = nc;
+                if (r + 1 < nr) {
+                    nz = tile[buf][0][r + 1];
+                    nc = tile[buf][1][r + 1];
+                }
+                int32_t left = ea_shr1(v[EA_K - 1]);
+                if (lane == 0) left = wave > 0 ? xch[(t + 1) & 1][wave - 1] : cc;
+                uint32_t bits = 0;
+#pragma unroll
+                for (int j = EA_K - 1; j >= 0; j--) {
+                    const int32_t adv = j >= 1 ? v[j - 1] : left;
+                    const bool take = ea_advance(v[j], adv);
+                    v[j] = ea_cost(z, lv[j], wt[j], bi[j]) + (take ? adv : v[j]);
+                    bits |= (take ? 1u : 0u) << j;
+                }
+                if (store) bp[(size_t)t * hpr + (s0 >> 4)] = (uint16_t)bits;
+                if (write_col) cout[t] = v[EA_K - 1];
+                if (!single) {
+                    if (lane == 63) xch[t & 1][wave] = v[EA_K - 1];
+                    __syncthreads();
+                }
+            }
+            if (more) {
+                tile_store(buf ^ 1, pre);
+                if (single) __builtin_amdgcn_wave_barrier();
+                else __syncthreads();
+            }
+        }
+        // the two states the path may end in
+#pragma unroll
+        for (int j = 0; j < EA_K; j++) {
+            if (s0 + j == L + 1) fin[2 * (int64_t)blockIdx.x] = v[j];
+            if (s0 + j == L) fin[2 * (int64_t)blockIdx.x + 1] = v[j];
+        }
+        if (!single) __threadfence_block();
+    }
+}
+
+// one wave per read
+__global__ __launch_bounds__(64) void ea_tb_kernel(const EaSeq* __restrict__ seqs, const uint8_t* __restrict__ ws, const int32_t* __restrict__ fin,
+                                                   EaOut* __restrict__ out, int32_t* __restrict__ first, int32_t* __restrict__ last)
+{
+    const int p = blockIdx.x, lane = threadIdx.x;
+    const EaSeq q = seqs[p];
+    const int L = q.L, off = q.t_lo;
+    const int32_t v_trail = fin[2 * (int64_t)p], v_last = fin[2 * (int64_t)p + 1];
+    int s = ea_ends_in_trail(v_trail, v_last) ? L + 1 : L;   // (s, t and r0 below are the same in every lane)
+    const uint32_t* __restrict__ bp = (const uint32_t*)(ws + q.bp);
+    const int64_t wpr = (L + 2 + 31) / 32;
+    int32_t* fs = first + q.lab;
+    int32_t* ls = last + q.lab;
+    int t = q.T - 1;
+    if (lane == 0) {
+        out[p].score = s == L + 1 ? v_trail : v_last;
+        if (s >= 1 && s <= L) ls[s - 1] = t + off;
+    }
+    while (t > 0) {
+        // lane r holds the two words of row t - r that the path can be in while it stays within 32 states below s's word
+        const int n = t < 64 ? t : 64, w0 = s >> 5;
+        uint32_t a = 0, b = 0;
+        if (lane < n) {
+            a = bp[(int64_t)(t - lane) * wpr + w0];
+            if (w0 > 0) b = bp[(int64_t)(t - lane) * wpr + w0 - 1];
+        }
+        int r0 = 0;   // rows t .. t - r0 + 1 are walked
+        while (r0 < n && s > 0 && (s >> 5) >= w0 - 1) {
+            const uint32_t word = (s >> 5) == w0 ? a : b;
+            const unsigned long long m = __ballot(lane >= r0 && lane < n && ((word >> (s & 31)) & 1u));
+            if (m == 0) {   // the path stays in s for the rest of these rows
+                r0 = n;
+                break;
+            }
+            const int r1 = __ffsll((long long)m) - 1, tt = t - r1;   // the nearest row that was entered from s - 1
+            if (lane == 0) {
+                if (s <= L) fs[s - 1] = tt + off;
+                if (s - 1 >= 1) ls[s - 2] = tt - 1 + off;
+            }
+            s--;
+            r0 = r1 + 1;
+        }
+        if (s == 0) break;   // the lead: nothing is left to record
+        t -= r0;
+    }
+    if (lane == 0 && s == 1 && L >= 1) fs[0] = off;
+}
+
+__global__ __launch_bounds__(256) void ea_sums_kernel(const EaSeq* __restrict__ seqs, const uint8_t* __restrict__ codes, const int32_t* __restrict__ lvl_t,
+                                                      int k, const int32_t* __restrict__ ev_start, const int32_t* __restrict__ ev_end,
+                                                      const int64_t* __restrict__ ev_sum, EaOut* __restrict__ out)
+{
+    __shared__ int64_t sh[4][5];
+    const EaSeq q = seqs[blockIdx.x];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int64_t a[5] = {0, 0, 0, 0, 0};
+    for (int b = tid; b < q.L; b += 256) {
+        const int64_t l = lvl_t[sim_kmer(codes + q.codes, q.L, b, k)], n = ev_end[q.lab + b] - ev_start[q.lab + b], x = ev_sum[q.lab + b];
+        a[0] += n;
+        a[1] += n * l;
+        a[2] += n * l * l;
+        a[3] += x;
+        a[4] += x * l;
+    }
+#pragma unroll
+    for (int i = 0; i < 5; i++) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) a[i] += __shfl_xor(a[i], d);
+        if (lane == 0) sh[wave][i] = a[i];
+    }
+    __syncthreads();
+    if (tid < 5) out[blockIdx.x].sums[tid] = sh[0][tid] + sh[1][tid] + sh[2][tid] + sh[3][tid];
+}
+
+}  // namespace
+
+extern "C" int rd_eventalign(rd_ctx* ctx, const int16_t* raw, const int64_t* read_off, int n_reads, const int64_t* t_lo, const int64_t* t_hi,
+                             const uint8_t* codes, const int64_t* ref_off, const int32_t* ref_len, const int32_t* m2_in, const int32_t* d4_in, int k,
+                             const int32_t* lvl, const uint32_t* w, const int32_t* bias, int32_t lvl_bg, uint32_t w_bg, int32_t bias_bg,
+                             int64_t budget_bytes, int32_t* status, int64_t* score, int32_t* m2, int32_t* d4, int32_t* first_step,
+                             int32_t* last_step, int32_t* ev_start, int32_t* ev_end, int64_t* ev_sum, int64_t* ev_sumsq, int16_t* ev_min,
+                             int16_t* ev_max, int64_t* fit_sums)
+{
+    RD_REQUIRE(ctx, "rd_eventalign: null context");
+    RD_REQUIRE(budget_bytes >= 0, "rd_eventalign: negative budget");
+    const EaCall c{raw, read_off, t_lo, t_hi, n_reads, codes, ref_off, ref_len, m2_in, d4_in, EaModel{k, lvl, w, bias, EaState{lvl_bg, w_bg, bias_bg}},
+                   status, score, m2, d4, first_step, last_step, ev_start, ev_end, ev_sum, ev_sumsq, ev_min, ev_max, fit_sums};
+    int64_t n_bases = 0;
+    int rc = ea_check_args("rd_eventalign", c, &n_bases);
+    if (rc || n_reads == 0) return rc;
+    RD_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    // the samples the reads span, rebased to the first read's; the bases; the model
+    const int64_t lo = read_off[0], n_samples = read_off[n_reads] - lo, n_kmers = (int64_t)1 << (2 * k);
+    const size_t b_tab = align_up((size_t)n_kmers * 4, 256);
+    if (ctx->ws_raw.reserve((size_t)n_samples * 2 + 16) || ctx->ws_labels.reserve((size_t)n_bases + 16) || ctx->ws_eval_model.reserve(3 * b_tab))
+        return RD_ERR_NOMEM;
+    const int16_t* d_raw = ctx->ws_raw.as<int16_t>();
+    const uint8_t* d_codes = ctx->ws_labels.as<uint8_t>();
+    const int32_t* d_lvl = (const int32_t*)ctx->ws_eval_model.as<uint8_t>();
+    const uint32_t* d_w = (const uint32_t*)(ctx->ws_eval_model.as<uint8_t>() + b_tab);
+    const int32_t* d_bias = (const int32_t*)(ctx->ws_eval_model.as<uint8_t>() + 2 * b_tab);
+    if (n_samples) RD_HIP(hipMemcpyAsync(ctx->ws_raw.p, raw + lo, (size_t)n_samples * 2, hipMemcpyHostToDevice, st));
+    if (n_bases) RD_HIP(hipMemcpyAsync(ctx->ws_labels.p, codes, (size_t)n_bases, hipMemcpyHostToDevice, st));
+    RD_HIP(hipMemcpyAsync((void*)d_lvl, lvl, (size_t)n_kmers * 4, hipMemcpyHostToDevice, st));
+    RD_HIP(hipMemcpyAsync((void*)d_w, w, (size_t)n_kmers * 4, hipMemcpyHostToDevice, st));
+    RD_HIP(hipMemcpyAsync((void*)d_bias, bias, (size_t)n_kmers * 4, hipMemcpyHostToDevice, st));
+    std::vector<int64_t> off(n_reads + 1);
+    for (int r = 0; r <= n_reads; r++) off[r] = read_off[r] - lo;
+    // every read's scale: a property of the read alone, whatever the budget does with it afterwards
+    std::vector<EaScaleIn> scin(n_reads);
+    std::vector<int32_t> scale(2 * (size_t)n_reads);
+    for (int r = 0; r < n_reads; r++) {
+        const int64_t T = t_hi[r] - t_lo[r];
+        scin[r] = EaScaleIn{off[r] + t_lo[r], (int32_t)(T > EA_MAX_T ? EA_MAX_T + 1 : T), m2_in[r], d4_in[r], 0};
+    }
+    const size_t b_sin = align_up((size_t)n_reads * sizeof(EaScaleIn), 256);
+    if (ctx->ws_eval.reserve(b_sin + (size_t)n_reads * 8 + 256)) return RD_ERR_NOMEM;
+    int32_t* d_scale = (int32_t*)(ctx->ws_eval.as<uint8_t>() + b_sin);
+    RD_HIP(hipMemcpyAsync(ctx->ws_eval.p, scin.data(), (size_t)n_reads * sizeof(EaScaleIn), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(ea_scale_kernel, dim3(n_reads), dim3(256), 0, st, (const EaScaleIn*)ctx->ws_eval.p, d_raw, d_scale);
+    RD_HIP(hipGetLastError());
+    RD_HIP(hipMemcpyAsync(scale.data(), d_scale, (size_t)n_reads * 8, hipMemcpyDeviceToHost, st));
+    RD_HIP(hipStreamSynchronize(st));
+    // statuses that need no alignment, then the launches: the other reads in the caller's order, as many as fit the budget; a read that
+    // alone exceeds it is reported, not launched
+    for (int r = 0; r < n_reads; r++) {
+        const int stat = ea_status(t_hi[r] - t_lo[r], ref_len[r], scale[2 * (size_t)r + 1]);   // (EMPTY and TOO_LONG come before the scale is looked at)
+        ea_blank(c, r, stat == EA_OK ? EA_TOO_LARGE : stat, scale[2 * (size_t)r], scale[2 * (size_t)r + 1]);   // OK: until its launch has run
+    }
+    if ((rc = rd_resolve_budget(&budget_bytes, ctx->ws_align.cap))) return rc;
+    const BudgetPlan plan = rd_plan_budget(n_reads, nullptr, budget_bytes, 0, false,
+                                           [&](int r, int) { return status[r] == EA_TOO_LARGE ? (int64_t)ea_read_bytes(t_hi[r] - t_lo[r], ref_len[r]) : (int64_t)-1; },
+                                           [](int, int, int64_t count, int64_t) { return count >= EA_MAX_LAUNCH; });
+    const int too_large = (int)plan.too_large, first_too_large = (int)plan.first_too_large;
+    if (plan.max_bytes && ctx->ws_align.reserve_exact((size_t)plan.max_bytes, "rd_eventalign")) return RD_ERR_NOMEM;
+    std::vector<EaSeq> desc;
+    std::vector<EaOut> h_out;
+    std::vector<int32_t> h_i32, ev_len, ev_status;
+    std::vector<int64_t> h_i64, ev_lab;
+    std::vector<int16_t> h_i16;
+    for (auto [k0, k1] : plan.launches) {
+        const int nb = (int)(k1 - k0);
+        const int32_t* members = plan.run.data() + k0;
+        const int r_lo = members[0], r_hi = members[nb - 1] + 1;   // the launch's reads lie in [r_lo, r_hi) of the call's
+        desc.resize(nb);
+        ev_len.assign(r_hi - r_lo, 0);
+        ev_lab.assign(r_hi - r_lo, 0);
+        ev_status.assign(r_hi - r_lo, 0);
+        size_t at = 0;
+        int64_t nlab = 0, max_T = 0;
+        for (int i = 0; i < nb; i++) {
+            const int r = members[i];
+            EaSeq& d = desc[i];
+            d.raw0 = off[r] + t_lo[r];
+            d.codes = ref_off[r];
+            d.lab = nlab;
+            d.T = (int32_t)(t_hi[r] - t_lo[r]);
+            d.L = ref_len[r];
+            d.m2 = m2[r];
+            d.d4 = d4[r];
+            d.t_lo = (int32_t)t_lo[r];
+            d.pad_ = 0;
+            d.zq = (int64_t)at;
+            at += ea_zq_bytes(d.T);
+            d.bp = (int64_t)at;
+            at += ea_bp_bytes(d.T, d.L);
+            d.col = (int64_t)at;
+            at += ea_col_bytes(d.T, d.L);
+            ev_len[r - r_lo] = d.L;   // (a read between two members that is not one has no labels in this launch)
+            ev_lab[r - r_lo] = d.lab;
+            nlab += d.L;
+            max_T = std::max<int64_t>(max_T, d.T);
+        }
+        if (at > ctx->ws_align.cap) {
+            rd_set_error("rd_eventalign: internal workspace accounting (%zu > %zu)", at, ctx->ws_align.cap);
+            return RD_ERR_STATE;
+        }
+        // descriptors | end values [2] | score and sums | first, last, start, end | sum, sumsq | min, max
+        const size_t n = (size_t)nlab, a4 = align_up(n * 4 + 16, 256), a8 = align_up(n * 8 + 16, 256), a2 = align_up(n * 2 + 16, 256);
+        const size_t o_fin = align_up((size_t)nb * sizeof(EaSeq), 256), o_out = o_fin + align_up((size_t)nb * 8, 256);
+        const size_t o_i32 = o_out + align_up((size_t)nb * sizeof(EaOut), 256), o_i64 = o_i32 + 4 * a4, o_i16 = o_i64 + 2 * a8;
+        if (ctx->ws_eval.reserve(o_i16 + 2 * a2)) return RD_ERR_NOMEM;
+        uint8_t* io = ctx->ws_eval.as<uint8_t>();
+        uint8_t* dws = ctx->ws_align.as<uint8_t>();
+        const EaSeq* d_seqs = (const EaSeq*)io;
+        int32_t* d_fin = (int32_t*)(io + o_fin);
+        EaOut* d_out = (EaOut*)(io + o_out);
+        int32_t *d_first = (int32_t*)(io + o_i32), *d_last = (int32_t*)(io + o_i32 + a4), *d_start = (int32_t*)(io + o_i32 + 2 * a4),
+                *d_end = (int32_t*)(io + o_i32 + 3 * a4);
+        int64_t *d_sum = (int64_t*)(io + o_i64), *d_sumsq = (int64_t*)(io + o_i64 + a8);
+        int16_t *d_min = (int16_t*)(io + o_i16), *d_max = (int16_t*)(io + o_i16 + a2);
+        RD_HIP(hipMemcpyAsync(io, desc.data(), (size_t)nb * sizeof(EaSeq), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(ea_quant_kernel, dim3((unsigned)((max_T + 255) / 256), nb), dim3(256), 0, st, d_seqs, d_raw, dws, d_fin);
+        RD_HIP(hipGetLastError());
+        hipLaunchKernelGGL(ea_dp_kernel, dim3(nb), dim3(EA_NT), 0, st, d_seqs, d_codes, d_lvl, d_w, d_bias, c.m.bg, k, dws, d_fin);
+        RD_HIP(hipGetLastError());
+        hipLaunchKernelGGL(ea_tb_kernel, dim3(nb), dim3(64), 0, st, d_seqs, dws, d_fin, d_out, d_first, d_last);
+        RD_HIP(hipGetLastError());
+        if ((rc = rd_event_stats_dev(ctx, st, d_raw, off.data() + r_lo, r_hi - r_lo, d_first, d_last, ev_lab.data(), ev_len.data(), ev_status.data(),
+                                     d_start, d_end, d_sum, d_sumsq, d_min, d_max)))
+            return rc;
+        hipLaunchKernelGGL(ea_sums_kernel, dim3(nb), dim3(256), 0, st, d_seqs, d_codes, d_lvl, k, d_start, d_end, d_sum, d_out);
+        RD_HIP(hipGetLastError());
+        h_out.resize(nb);
+        h_i32.resize(4 * a4 / 4);
+        h_i64.resize(2 * a8 / 8);
+        h_i16.resize(2 * a2 / 2);
+        RD_HIP(hipMemcpyAsync(h_out.data(), d_out, (size_t)nb * sizeof(EaOut), hipMemcpyDeviceToHost, st));
+        if (n) {
+            RD_HIP(hipMemcpyAsync(h_i32.data(), io + o_i32, 4 * a4, hipMemcpyDeviceToHost, st));
+            RD_HIP(hipMemcpyAsync(h_i64.data(), io + o_i64, 2 * a8, hipMemcpyDeviceToHost, st));
+            RD_HIP(hipMemcpyAsync(h_i16.data(), io + o_i16, 2 * a2, hipMemcpyDeviceToHost, st));
+        }
+        RD_HIP(hipStreamSynchronize(st));
+        for (int i = 0; i < nb; i++) {
+            const int r = members[i];
+            const EaSeq& d = desc[i];
+            const size_t L = (size_t)d.L, o = (size_t)ref_off[r], s = (size_t)d.lab;
+            status[r] = EA_OK;
+            score[r] = h_out[i].score;
+            memcpy(fit_sums + 5 * (int64_t)r, h_out[i].sums, 40);
+            if (!L) continue;
+            memcpy(first_step + o, h_i32.data() + s, L * 4);
+            memcpy(last_step + o, h_i32.data() + a4 / 4 + s, L * 4);
+            memcpy(ev_start + o, h_i32.data() + 2 * (a4 / 4) + s, L * 4);
+            memcpy(ev_end + o, h_i32.data() + 3 * (a4 / 4) + s, L * 4);
+            memcpy(ev_sum + o, h_i64.data() + s, L * 8);
+            memcpy(ev_sumsq + o, h_i64.data() + a8 / 8 + s, L * 8);
+            memcpy(ev_min + o, h_i16.data() + s, L * 2);
+            memcpy(ev_max + o, h_i16.data() + a2 / 2 + s, L * 2);
+        }
+    }
+    if (too_large) {
+        const int r = first_too_large;
+        rd_set_error("rd_eventalign: read %d (%lld samples x %d bases) needs %lld bytes of workspace, over the budget of %lld; %d read(s) not "
+                     "aligned (status RD_EVAL_TOO_LARGE), the others were", r, (long long)(t_hi[r] - t_lo[r]), ref_len[r],
+                     (long long)ea_read_bytes(t_hi[r] - t_lo[r], ref_len[r]), (long long)budget_bytes, too_large);
+        return RD_ERR_NOMEM;
+    }
+    return RD_OK;
+}
+#endif  // __HIPCC__

@@ -1,0 +1,75 @@
+// eventalign_rules.h -- the rules of the eventalign contract (include/radian_hip.h, rd_eventalign), once: the host
+// loop (rd_eventalign_host), the argument check and the kernels of eventalign.hip all call these.  Integer arithmetic only.
+#pragma once
+#include <stdint.h>
+
+#include "sim_rules.h"   // sim_kmer, sim_mulhi, sim_k_ok: the k-mer rule is the simulator's
+
+#if defined(__HIPCC__)
+#define EA_HD __host__ __device__
+#else
+#define EA_HD
+#endif
+
+// per-read status (radian_hip.h RD_EVAL_*)
+constexpr int EA_OK = 0, EA_EMPTY = 1, EA_TOO_LONG = 2, EA_MAD_ZERO = 3, EA_NO_PATH = 4, EA_TOO_LARGE = 5;
+
+constexpr int32_t EA_INF = 1 << 30;       // an unreachable cell
+constexpr int64_t EA_MAX_T = 1 << 19;     // rows of one alignment: finite values stay below 2^19 * 1280 < 2^30
+constexpr int32_t EA_ZMAX = 1 << 14;      // |zq| <= 2^14 and |lvl| < 2^14: |d| < 2^15, d^2 < 2^30
+constexpr int32_t EA_COST_CAP = 1024;     // the squared-distance term of a cell, in 1/32 nat
+constexpr int32_t EA_BIAS_MAX = 256;
+constexpr int32_t EA_M2_MAX = 1 << 17, EA_D4_MAX = 1 << 20;   // ranges of a given scale
+
+// one state's model: the level in MAD/256, the Q32 inverse variance, the log-sd term in 1/32 nat
+struct EaState {
+    int32_t lvl;
+    uint32_t w;
+    int32_t bias;
+};
+
+EA_HD inline bool ea_entry_ok(int32_t lvl, int32_t bias) { return lvl > -EA_ZMAX && lvl < EA_ZMAX && bias >= -EA_BIAS_MAX && bias <= EA_BIAS_MAX; }
+EA_HD inline bool ea_scale_ok(int32_t m2, int32_t d4) { return m2 >= -EA_M2_MAX && m2 <= EA_M2_MAX && d4 >= 0 && d4 <= EA_D4_MAX; }
+
+// the status a read has before anything is aligned (EA_OK: go on); T rows, L bases, d4 as used
+EA_HD inline int ea_status(int64_t T, int64_t L, int32_t d4)
+{
+    return T <= 0 ? EA_EMPTY : T > EA_MAX_T ? EA_TOO_LONG : d4 == 0 ? EA_MAD_ZERO : T < L ? EA_NO_PATH : EA_OK;
+}
+
+// the sample in MAD/256, rounded half up: u = 512 (2x - m2), zq = clamp(floor((2u + d4) / (2 d4)), +-2^14); d4 >= 1
+EA_HD inline int32_t ea_quant(int32_t x, int32_t m2, int32_t d4)
+{
+    const int64_t u = 512 * (2 * (int64_t)x - m2), num = 2 * u + d4, den = 2 * (int64_t)d4;
+    int64_t q = num / den;
+    if (num % den < 0) q--;   // floor: den > 0
+    return (int32_t)(q < -EA_ZMAX ? -EA_ZMAX : q > EA_ZMAX ? EA_ZMAX : q);
+}
+
+// c(t, s) = min(floor(d^2 w / 2^32), 1024) + bias, d = zq - lvl
+EA_HD inline int32_t ea_cost(int32_t zq, int32_t lvl, uint32_t w, int32_t bias)
+{
+    const int32_t d = zq - lvl;
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t d2 = (uint32_t)__mul24(d, d);   // |d| < 2^15: the 24-bit multiply is exact
+#else
+    const uint32_t d2 = (uint32_t)(d * d);
+#endif
+    const uint32_t q = sim_mulhi(d2, w);
+    return (int32_t)(q < (uint32_t)EA_COST_CAP ? q : (uint32_t)EA_COST_CAP) + bias;
+}
+
+// the model of state s of 0 .. L + 1: 0 and L + 1 are the background, s in 1 .. L is base s - 1 by its k-mer (sim_rules.h)
+EA_HD inline EaState ea_state(int32_t s, int32_t L, const uint8_t* codes, int k, const int32_t* lvl, const uint32_t* w, const int32_t* bias,
+                              const EaState& bg)
+{
+    if (s <= 0 || s > L) return bg;
+    const int32_t i = sim_kmer(codes, L, s - 1, k);
+    return EaState{lvl[i], w[i], bias[i]};
+}
+
+// the advance from s - 1 is taken only if strictly smaller
+EA_HD inline bool ea_advance(int32_t stay, int32_t adv) { return adv < stay; }
+
+// the path ends in L + 1, or in L if V[T-1][L+1] is not strictly smaller
+EA_HD inline bool ea_ends_in_trail(int32_t v_trail, int32_t v_last) { return v_trail < v_last; }

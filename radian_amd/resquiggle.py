@@ -83,11 +83,12 @@ def event_level(mean, median, mad):
     return (mean - median) / (1.4826 * mad)
 
 
-def event_rows(read_id, ref_name, span, raw, ev, qual):
+def event_rows(read_id, ref_name, span, raw, ev, qual, scale=None):
     """the rows of one `ok` read: span as written (5'->3'); ev = (start, end, sum, sumsq, min, max) and qual in decode order (label k is
-    span position L - 1 - k).  -> [(columns as strings)], levels, dwells in span order"""
+    span position L - 1 - k); scale: the (median, MAD) the levels are taken on (default: the read's own).  -> [(columns as strings)], levels,
+    dwells in span order"""
     L = len(span)
-    median, mad = read_scale(raw)
+    median, mad = scale if scale is not None else read_scale(raw)
     start, end, s, sq, mn, mx = ev
     rows, levels, dwells = [], [], []
     for p in range(L):
