@@ -708,6 +708,57 @@ int rd_eventalign_host(const int16_t* raw, const int64_t* read_off, int n_reads,
                        int64_t* ev_sumsq, int16_t* ev_min, int16_t* ev_max, int64_t* fit_sums);
 int64_t rd_eventalign_workspace_bytes(int64_t n_rows, int64_t n_bases);
 
+/* ---- sigmap: raw samples against a panel of targets, subsequence Viterbi with a free start and end (sigmap.hip)
+ * NO reference behaviour.  Which targets of a panel a window of samples fits best, where the fit ends in each and where it began.  No
+ * basecall and no neural network take part.  Integer arithmetic only; met exactly.  Sample, cell and the three model tables are
+ * rd_eventalign's (no background).
+ *   panel     n_tgt targets, base codes 0..3 in pore order: codes[tgt_off[j] .. tgt_off[j+1]); tgt_off[0] = 0, non-decreasing; an empty
+ *             target holds no state.  State s is a global index 0 .. R - 1, R = tgt_off[n_tgt] <= 2^31 - 1; its model is the k-mer centred
+ *             on it WITHIN ITS OWN TARGET (rd_sim_signal's rule: a position outside the target takes the nearest end base)
+ *   query     q of n_q: rows are the samples raw[q_lo[q] .. q_hi[q]), T = q_hi - q_lo <= 2^14; all indices are absolute into raw
+ *             (n_raw samples), and several queries may name the same samples.  Scale: d4_in[q] > 0: (m2_in[q], d4_in[q]) as given;
+ *             d4_in[q] == 0: that of the scale window raw[sc_lo[q] .. sc_hi[q]) (at most 2^31 - 1 samples) by rd_eventalign's rule, an
+ *             empty scale window giving (0, 0).  States: the range [s_lo[q], s_hi[q])
+ *   path      int32.  head(s): s is the first state of its target, or s == s_lo.  V[0][s] = c(0, s), O[0][s] = s;
+ *             V[t][s] = c(t, s) + (adv ? V[t-1][s-1] : V[t-1][s]), adv = !head(s) and V[t-1][s-1] STRICTLY smaller than V[t-1][s];
+ *             O[t][s] is the O of the predecessor taken.  No cell is unreachable, no path crosses from a target into the next, every
+ *             value stays inside +-2^14 * 1280 < 2^25
+ *   result    per target with a state in range: the smallest V[T-1][s] over them, the smallest s on ties.  Per query the n_best (1..8)
+ *             such targets ordered by (score, j): best_tgt / best_score / best_end / best_org, int32 [n_q][n_best], end and origin state
+ *             local to the target (tgt_off[j] subtracted); slots past the number of targets hold -1 in all four
+ *   status    in this order: T == 0 RD_SIGMAP_EMPTY; T > 2^14 RD_SIGMAP_TOO_LONG; a computed d4 == 0 RD_SIGMAP_MAD_ZERO; s_lo == s_hi
+ *             RD_SIGMAP_NO_TARGET; over the budget alone RD_SIGMAP_TOO_LARGE; otherwise RD_SIGMAP_OK.  m2, d4 as used (0, 0 for EMPTY
+ *             and TOO_LONG; whatever the status otherwise).  A query that is not OK has -1 in every slot
+ * A result does not depend on the batch, the order, the budget or the launches.  RD_ERR_ARG before anything is launched: a null pointer,
+ * offsets that are not monotone, a code above 3, a window or a range out of order or outside its array, a scale or a table entry outside
+ * rd_eventalign's ranges, n_best outside 1..8.  n_q == 0 is RD_OK.
+ *   rd_sigmap        on the GPU; synchronous, uses the context's stream.  Every query's scale is settled first.  budget_bytes and
+ *                    RD_ERR_NOMEM as rd_eventalign: the DP workspace one launch may take, rd_sigmap_workspace_bytes per query, 0 = a
+ *                    quarter of the free device memory; a query that alone exceeds it is not mapped: RD_SIGMAP_TOO_LARGE, and the call
+ *                    returns RD_ERR_NOMEM naming the first such query after doing the others
+ *   rd_sigmap_host   host, no GPU: the same rules (csrc/sigmap_rules.h) in a plain loop
+ *   rd_sigmap_workspace_bytes   of a query of n_rows rows over n_states states whose first and last state lie in targets j_lo and j_hi,
+ *                    n_tgt_in_range = j_hi - j_lo + 1; each term rounded up to 256; P = 6145, the end states one stripe reports:
+ *                    4 n_rows (quantised samples) + 4 n_states (the origin of every end state) + 8 n_tgt_in_range (one key per target)
+ *                    + ceil(n_states / P) * round256(16 n_rows) (two band columns per stripe) when min(n_states, P + n_rows - 1) > 4096 */
+#define RD_SIGMAP_OK 0
+#define RD_SIGMAP_EMPTY 1
+#define RD_SIGMAP_TOO_LONG 2
+#define RD_SIGMAP_MAD_ZERO 3
+#define RD_SIGMAP_NO_TARGET 4
+#define RD_SIGMAP_TOO_LARGE 5
+int rd_sigmap(rd_ctx* ctx, const int16_t* raw, int64_t n_raw, int n_q, const int64_t* q_lo, const int64_t* q_hi, const int64_t* sc_lo,
+              const int64_t* sc_hi, const int32_t* m2_in, const int32_t* d4_in, const int64_t* s_lo, const int64_t* s_hi, const uint8_t* codes,
+              const int64_t* tgt_off, int n_tgt, int k, const int32_t* lvl, const uint32_t* w, const int32_t* bias, int n_best,
+              int64_t budget_bytes, int32_t* status, int32_t* m2, int32_t* d4, int32_t* best_tgt, int32_t* best_score, int32_t* best_end,
+              int32_t* best_org);
+int rd_sigmap_host(const int16_t* raw, int64_t n_raw, int n_q, const int64_t* q_lo, const int64_t* q_hi, const int64_t* sc_lo,
+                   const int64_t* sc_hi, const int32_t* m2_in, const int32_t* d4_in, const int64_t* s_lo, const int64_t* s_hi,
+                   const uint8_t* codes, const int64_t* tgt_off, int n_tgt, int k, const int32_t* lvl, const uint32_t* w, const int32_t* bias,
+                   int n_best, int32_t* status, int32_t* m2, int32_t* d4, int32_t* best_tgt, int32_t* best_score, int32_t* best_end,
+                   int32_t* best_org);
+int64_t rd_sigmap_workspace_bytes(int64_t n_rows, int64_t n_states, int64_t n_tgt_in_range);
+
 /* ---- model evaluation on labelled windows: the reference's val_loss (radian/model.py:77-98, radian/train.py:48-79) ------------
  * Labelled windows as the reference stores them: TFRecord shards of tf.train.Example records (radian/data.py:9-31), read on the
  * HOST without TensorFlow (tfrecord.hip).  Framing: u64 length, u32 masked crc32c of it, the data, u32 masked crc32c of the data;

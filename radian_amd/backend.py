@@ -418,6 +418,93 @@ def eventalign_workspace_bytes(n_rows, n_bases):
     return int(_lib.load().rd_eventalign_workspace_bytes(int(n_rows), int(n_bases)))
 
 
+# rd_sigmap per-query status (include/radian_hip.h RD_SIGMAP_*)
+SIGMAP_OK, SIGMAP_EMPTY, SIGMAP_TOO_LONG, SIGMAP_MAD_ZERO, SIGMAP_NO_TARGET, SIGMAP_TOO_LARGE = 0, 1, 2, 3, 4, 5
+SIGMAP_STATUS_NAMES = ("ok", "empty", "too-long", "mad-zero", "no-target", "too-large")
+SIGMAP_MAX_T = 1 << 14     # rows of one query
+SIGMAP_PAYLOAD = 6145      # end states one stripe of the DP kernel reports (csrc/sigmap_rules.h SM_PAYLOAD)
+SIGMAP_BAND = 4096         # states of one workgroup pass (SM_BAND)
+
+
+class SigmapResult:
+    """per query: status (int32, SIGMAP_*), m2 / d4 (int32: the scale as used); per query and rank, int32 [queries, n_best], -1 past the
+    number of targets: tgt (target index), score, end and org (the end and the origin state, local to the target)"""
+    __slots__ = ("status", "m2", "d4", "tgt", "score", "end", "org")
+
+    def __init__(self, status, m2, d4, tgt, score, end, org):
+        self.status, self.m2, self.d4, self.tgt, self.score, self.end, self.org = status, m2, d4, tgt, score, end, org
+
+
+class SigmapPanel:
+    """a panel as rd_sigmap takes it: codes (uint8, 0..3, the targets end to end in pore order) and off (int64 [targets + 1], from 0)"""
+    __slots__ = ("codes", "off")
+
+    def __init__(self, codes, off):
+        self.codes = np.ascontiguousarray(codes, dtype=np.uint8).ravel()
+        self.off = np.ascontiguousarray(off, dtype=np.int64).ravel()
+        if self.off.size == 0:
+            raise ValueError("a SigmapPanel's offsets hold at least the 0 they start from")
+        if self.codes.size == 0:
+            self.codes = np.zeros(1, np.uint8)      # (a pointer the library can check)
+
+
+def sigmap_panel(targets):
+    """a sequence of uint8 code arrays, one per target (0..3, pore order) -> the SigmapPanel; a SigmapPanel is passed through.  (A pair of
+    packed arrays is never guessed from a 2-tuple: two targets are two targets.)"""
+    if isinstance(targets, SigmapPanel):
+        return targets
+    return SigmapPanel(*_pack(targets, np.uint8, pad=1))
+
+
+def _sigmap_args(raw, targets, model, q_lo, q_hi, sc_lo, sc_hi, m2, d4, s_lo, s_hi, n_best):
+    """-> (the arrays, kept alive by the caller; the arguments up to n_best; the output buffers)"""
+    raw = np.ascontiguousarray(raw, dtype=np.int16).ravel()
+    n_raw = raw.size
+    if n_raw == 0:
+        raw = np.zeros(1, np.int16)
+    pnl = sigmap_panel(targets)
+    codes, off = pnl.codes, pnl.off
+    q_lo = np.ascontiguousarray(q_lo, dtype=np.int64).ravel()
+    n = q_lo.size
+    R = int(off[-1])
+
+    def per_query(a, default, dtype=np.int64):
+        a = np.full(n, default, dtype=dtype) if a is None else np.ascontiguousarray(a, dtype=dtype).ravel()
+        if a.size != n:
+            raise ValueError(f"per-query arguments that do not hold one entry for each of {n} queries")
+        return np.concatenate([a, np.zeros(1, dtype)])   # (a pointer the library can check when n = 0)
+
+    q_hi = per_query(q_hi, 0)
+    sc_lo = q_lo.copy() if sc_lo is None else sc_lo
+    sc_hi = q_hi[:n].copy() if sc_hi is None else sc_hi
+    arrs = [per_query(q_lo, 0), q_hi, per_query(sc_lo, 0), per_query(sc_hi, 0), per_query(m2, 0, np.int32), per_query(d4, 0, np.int32),
+            per_query(s_lo, 0), per_query(s_hi, R)]
+    nb = max(int(n_best), 1)
+    outs = [np.zeros(n + 1, np.int32) for _ in range(3)] + [np.full((n + 1) * nb, -1, np.int32) for _ in range(4)]
+    keep = (raw, codes, off, arrs, model)
+    head = (_p(raw), n_raw, n, *[_p(a) for a in arrs], _p(codes), _p(off), off.size - 1, model.k, _p(model.lvl), _p(model.w), _p(model.bias), int(n_best))
+    return keep, head, outs
+
+
+def _sigmap_result(outs, n, n_best):
+    return SigmapResult(outs[0][:n], outs[1][:n], outs[2][:n], *[o[:n * n_best].reshape(n, n_best) for o in outs[3:]])
+
+
+def sigmap_host(raw, targets, model, q_lo, q_hi, sc_lo=None, sc_hi=None, m2=None, d4=None, s_lo=None, s_hi=None, n_best=1):
+    """Backend.sigmap on the host (rd_sigmap_host: the same rules in a plain loop; no GPU, no context)"""
+    L = _lib.load()
+    keep, head, outs = _sigmap_args(raw, targets, model, q_lo, q_hi, sc_lo, sc_hi, m2, d4, s_lo, s_hi, n_best)
+    if L.rd_sigmap_host(*head, *[_p(b) for b in outs]) != 0:
+        raise RadianHipError(L.rd_last_error().decode())
+    return _sigmap_result(outs, head[2], int(n_best))
+
+
+def sigmap_workspace_bytes(n_rows, n_states, n_tgt_in_range):
+    """device workspace Backend.sigmap needs for one query of n_rows samples over n_states states that lie in n_tgt_in_range consecutive
+    targets (rd_sigmap_workspace_bytes)"""
+    return int(_lib.load().rd_sigmap_workspace_bytes(int(n_rows), int(n_states), int(n_tgt_in_range)))
+
+
 def _pack(arrays, dtype, pad=0):
     """list of arrays -> (their elements as one flat buffer of dtype, int64 offsets [n + 1]); a buffer without elements has `pad` zeros (1
     where the library wants a pointer it can check)"""
@@ -1534,6 +1621,24 @@ class Backend:
         return _eval_result(outs, cut, len(raws))
 
     eventalign_host = staticmethod(eventalign_host)
+
+    # ------------------------------------------------------------------ signal against a panel of targets
+    def sigmap(self, raw, targets, model, q_lo, q_hi, sc_lo=None, sc_hi=None, m2=None, d4=None, s_lo=None, s_hi=None, n_best=1,
+               budget_bytes=0, allow_too_large=False):
+        """The targets of a panel that every query's samples fit best under a k-mer pore model, with a free start and end in the target
+        (rd_sigmap, on the GPU): raw -- one int16 array, every index below is absolute into it; targets -- one uint8 code array per target
+        in pore order, or a SigmapPanel (sigmap_panel packs one once); model -- an EvalModel (its background is not used); q_lo / q_hi -- the rows of every query;
+        sc_lo / sc_hi -- its scale window (default: the query's); m2 / d4 -- its scale (d4 0, the default: the scale window's own);
+        s_lo / s_hi -- its range of global states (default: the whole panel); n_best 1..8.  budget_bytes: device workspace per launch,
+        0 = a quarter of free memory.  A query that does not fit it raises, unless allow_too_large: status SIGMAP_TOO_LARGE.
+        -> SigmapResult."""
+        keep, head, outs = _sigmap_args(raw, targets, model, q_lo, q_hi, sc_lo, sc_hi, m2, d4, s_lo, s_hi, n_best)
+        rc = self._L.rd_sigmap(self._h, *head, int(budget_bytes), *[_p(b) for b in outs])
+        if rc != 0 and not (allow_too_large and rc == -4 and (outs[0][:head[2]] == SIGMAP_TOO_LARGE).any()):
+            self._check(rc)
+        return _sigmap_result(outs, head[2], int(n_best))
+
+    sigmap_host = staticmethod(sigmap_host)
 
     # ------------------------------------------------------------------ signal-to-reference alignment (DESIGN.md section 17)
     def event_stats(self, raws, aln):

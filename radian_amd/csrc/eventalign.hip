@@ -34,6 +34,7 @@
 #include "common.h"
 #include "budget.h"
 #include "eventalign_rules.h"
+#include "eventalign_host.h"
 #include "../../include/radian_hip.h"
 
 #include <algorithm>
@@ -120,34 +121,6 @@ void ea_blank(const EaCall& c, int r, int status, int32_t m2, int32_t d4)
         c.ev_sum[o + b] = c.ev_sumsq[o + b] = 0;
         c.ev_min[o + b] = c.ev_max[o + b] = 0;
     }
-}
-
-// the two middle order statistics of n keys counted in cnt[0 .. n_keys)
-int32_t ea_middle2(const std::vector<int64_t>& cnt, int n_keys, int64_t n)
-{
-    const int64_t k1 = (n - 1) / 2, k2 = n / 2;
-    int64_t c = 0;
-    int v1 = -1, v2 = -1;
-    for (int k = 0; k < n_keys; k++) {
-        c += cnt[k];
-        if (v1 < 0 && k1 < c) v1 = k;
-        if (v2 < 0 && k2 < c) { v2 = k; break; }
-    }
-    return v1 + v2;
-}
-
-// the window's own scale, as rd_polya_segment's
-void ea_host_scale(const int16_t* x, int64_t T, std::vector<int64_t>& cnt, int32_t* m2, int32_t* d4)
-{
-    cnt.assign(65536, 0);
-    for (int64_t i = 0; i < T; i++) cnt[(int)x[i] + 32768]++;
-    *m2 = ea_middle2(cnt, 65536, T) - 65536;
-    cnt.assign(131072, 0);
-    for (int64_t i = 0; i < T; i++) {
-        const int v = 2 * (int)x[i] - *m2;
-        cnt[v < 0 ? -v : v]++;
-    }
-    *d4 = ea_middle2(cnt, 131072, T);
 }
 
 // the five fit sums of an OK read from its events
@@ -284,14 +257,7 @@ __global__ __launch_bounds__(256) void ea_scale_kernel(const EaScaleIn* __restri
     const EaScaleIn q = in[blockIdx.x];
     int m2 = q.m2, d4 = q.d4;
     if (q.T <= 0 || q.T > EA_MAX_T) m2 = d4 = 0;   // (the same in every thread)
-    else if (q.d4 == 0) {
-        const int16_t* x = raw + q.raw0;
-        const int64_t n = q.T, k1 = (n - 1) / 2, k2 = n / 2;
-        const SelectResult m = radix_select2<8>(n, k1, k2, [&](int64_t i) { return (int)x[i] + 32768; }, hist, sh);
-        m2 = (m.v1 - 32768) + (m.v2 - 32768);
-        const SelectResult d = radix_select2<9>(n, k1, k2, [&](int64_t i) { const int v = 2 * (int)x[i] - m2; return v < 0 ? -v : v; }, hist, sh);
-        d4 = d.v1 + d.v2;
-    }
+    else if (q.d4 == 0) window_scale2(raw + q.raw0, q.T, hist, sh, &m2, &d4);
     if (threadIdx.x == 0) {
         out[2 * (int64_t)blockIdx.x] = m2;
         out[2 * (int64_t)blockIdx.x + 1] = d4;

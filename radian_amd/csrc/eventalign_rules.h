@@ -3,7 +3,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "sim_rules.h"   // sim_kmer, sim_mulhi, sim_k_ok: the k-mer rule is the simulator's
+#include "sim_rules.h"  // sim_kmer, sim_mulhi, sim_k_ok: the k-mer rule is the simulator's
 
 #if defined(__HIPCC__)
 #define EA_HD __host__ __device__

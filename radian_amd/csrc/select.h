@@ -71,4 +71,16 @@ __device__ SelectResult radix_select2(int64_t n, int64_t k1, int64_t k2, KeyFn k
     return r;
 }
 
+// the scale of a window of n >= 1 int16 samples (rd_eventalign's rule, shared by ea_scale_kernel and sm_scale_kernel): m2 = the sum of the
+// two middle order statistics, d4 = the same of |2x - m2|.  One workgroup; hist[512], sh[8]; the result is the same in every thread
+__device__ inline void window_scale2(const int16_t* __restrict__ x, int64_t n, unsigned* hist, int* sh, int* m2_out, int* d4_out)
+{
+    const int64_t k1 = (n - 1) / 2, k2 = n / 2;
+    const SelectResult m = radix_select2<8>(n, k1, k2, [&](int64_t i) { return (int)x[i] + 32768; }, hist, sh);
+    const int m2 = (m.v1 - 32768) + (m.v2 - 32768);
+    const SelectResult d = radix_select2<9>(n, k1, k2, [&](int64_t i) { const int v = 2 * (int)x[i] - m2; return v < 0 ? -v : v; }, hist, sh);
+    *m2_out = m2;
+    *d4_out = d.v1 + d.v2;
+}
+
 }  // namespace
