@@ -12,16 +12,12 @@
 //
 // Kernels, per launch (a set of sequences whose workspace fits the budget):
 //   ca_log_kernel   lp rows, 8 doubles each (A C G T blank, then -inf three times: the class of a label past L), once per row
-//   ca_dp_kernel    one workgroup of 256 threads per sequence.  A thread owns 16 consecutive states in registers, a workgroup
-//                   pass a BAND of 4096 states; a sequence of more states is swept band after band, the last state of a band
-//                   at every row going through an 8-byte-per-row column in global memory (two columns, written and read in turn).
-//                   Row t of a thread needs its left neighbour's last state of row t-1 only (the thread's first state is even,
-//                   a blank: it has no s-2 predecessor): one DPP wave_shr:1 inside a wave, one LDS word and the row's single
-//                   barrier between waves.  A sequence of at most 1024 states runs on its first wave alone and has no barrier.
-//                   The lp rows and the band's incoming column values come through LDS in tiles of 32 rows, fetched from global
-//                   memory a tile ahead and read from LDS a row ahead.  Back-pointers: 2 bits
-//                   per cell, a thread's 16 cells = one uint32, a row = ceil((2L+1)/16) consecutive words.  A band starts at row
-//                   s_lo / 2: the cells above (s > 2t + 1) are -inf and never on a path.
+//   ca_dp_kernel    one workgroup per sequence: band_sweep.h's sweep.  A thread's registers: the fp64 values of its 16 states, the
+//                   classes of its 8 labels and their skip mask; a double crosses a thread boundary (the thread's first state is
+//                   even, a blank: it has no s-2 predecessor, so the left neighbour's last state is all a row needs).  A tile is 32
+//                   lp rows, the incoming column in slot 7.  Back-pointers: 2 bits per cell, a thread's 16 cells = one uint32, a row
+//                   = ceil((2L+1)/16) consecutive words.  A band starts at row s_lo / 2: the cells above (s > 2t + 1) are -inf and
+//                   never on a path.
 //   ca_tb_kernel    one lane per sequence: end state, score, status, then the walk -- 8 rows' words (two per row: the path
 //                   moves down by at most 2 states per row) fetched at once, walked from registers.
 //   ca_qual_kernel  one lane per base: the maximum of P[t][c_i] over its rows, e = 1 - p, and the quality by comparison with
@@ -31,6 +27,7 @@
 #include "budget.h"
 #include "glibc_math.h"
 #include "glibc_tables.h"
+#include "band_sweep.h"
 #include "../../include/radian_hip.h"
 
 #include <algorithm>
@@ -54,11 +51,6 @@ __device__ const double g_ca_thr[50] = {
     0x1.4d2a58423da81p-14, 0x1.08a4876c1311ep-14, 0x1.a46d238da54ebp-15, 0x1.4df4dd27fe99ep-15, 0x1.09456549be1bdp-15,
     0x1.a56cb36416f83p-16, 0x1.4ebfdd286009ap-16, 0x1.09e6a4f05e62bp-16, 0x1.a66cde934de7dp-17, 0x1.4f8b588e368f1p-17};
 
-constexpr int CA_NT = 256;                 // threads of a DP workgroup
-constexpr int CA_K = 16;                   // states a thread owns
-constexpr int CA_BAND = CA_NT * CA_K;      // states of one workgroup pass
-constexpr int CA_TR = 32;                  // rows of an lp tile in LDS (CA_TR * 8 elements: one per thread, four per lane of a lone wave)
-constexpr int CA_WAVE_STATES = 64 * CA_K;  // at most this many states: the first wave alone, no barrier
 constexpr int CA_OK = 0, CA_NO_PATH = 1, CA_TOO_LARGE = 2;   // radian_hip.h RD_CTCALIGN_*
 constexpr int CA_MAX_LAUNCH = 32768;       // sequences of one launch (grid.y of the row and base kernels)
 
@@ -92,43 +84,35 @@ __global__ __launch_bounds__(256) void ca_log_kernel(const CaSeq* __restrict__ s
     ((double*)(ws + q.lp))[t * 8 + c] = v;
 }
 
-// lane l receives v of lane l - 1; lane 0 keeps its own (DPP wave_shr:1, bound_ctrl off)
-__device__ __forceinline__ double ca_shr1(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(lo, lo, 0x138, 0xf, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(hi, hi, 0x138, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
+// band_sweep.h's policy of the CTC alignment
+struct CaSweep {
+    using Cell = double;
+    using Elem = double;
+    static constexpr bool AHEAD_CLAMPED = false;
+    static constexpr int TR = 32, SLOTS = 8;   // a tile: [row][lp of A C G T blank, -inf twice, the band's incoming column value V[t-1][s_lo-1] (band 0: -inf)]
+    struct Row {
+        double b, c, l[8];   // lp of the blank, the incoming column, lp of the thread's 8 labels
+    };
+    // the sequence
+    const double* __restrict__ lp;
+    uint32_t* __restrict__ bp;
+    const uint8_t* lab;
+    double* fin;   // the sequence's two end values
+    int L, wpr;    // wpr: back-pointer words of a row
+    // the thread's states of the band
+    int s0, cl[8];   // its 8 labels: class (5 = past the sequence: lp -inf)
+    uint32_t skip;   //   and whether s-2 is allowed
+    double v[BS_K];
 
-__global__ __launch_bounds__(CA_NT) void ca_dp_kernel(const CaSeq* __restrict__ seqs, const uint8_t* __restrict__ labels, uint8_t* __restrict__ ws,
-                                                      double* __restrict__ fin)
-{
-    const CaSeq q = seqs[blockIdx.x];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int T = q.T, L = q.L, S = 2 * L + 1;
-    if (L > T) return;   // no path: the end values stay -inf
-    const bool single = S <= CA_WAVE_STATES;
-    if (single && wave) return;   // (the first wave never waits at a barrier then)
-    const double* __restrict__ lp = (const double*)(ws + q.lp);
-    uint32_t* __restrict__ bp = (uint32_t*)(ws + q.bp);
-    double* col = (double*)(ws + q.col);
-    const uint8_t* lab = labels + q.lab;
-    const int wpr = (S + 15) / 16;
-    const int bands = (S + CA_BAND - 1) / CA_BAND;
-    const double NINF = -INFINITY;
-    __shared__ double xch[2][CA_NT / 64];
-    __shared__ double tile[2][CA_TR][8];
-    const int nact = single ? 64 : CA_NT, per = CA_TR * 8 / nact;   // threads at work, tile elements each
+    static __device__ __forceinline__ int first_row(int b) { return b * (BS_BAND / 2); }   // rows above have s > 2t + 1 in the whole band
+    static __device__ __forceinline__ Cell none() { return -INFINITY; }
+    static __device__ __forceinline__ Cell incoming(const Row& in) { return in.c; }
+    __device__ __forceinline__ Cell last() const { return v[BS_K - 1]; }
 
-    for (int b = 0; b < bands; b++) {
-        const int s0 = b * CA_BAND + tid * CA_K;
-        const int w = s0 >> 4;
-        const int t_lo = b * (CA_BAND / 2);   // rows above have s > 2t + 1 in the whole band
-        if (t_lo >= T) break;                 // (then the states of this band and the later ones are -inf in the last row too)
-        // the thread's 8 labels: class (5 = past the sequence: lp -inf) and whether s-2 is allowed
-        int cl[8];
-        uint32_t skip = 0;
+    __device__ __forceinline__ void begin_band(int b)
+    {
+        s0 = b * BS_BAND + (int)threadIdx.x * BS_K;
+        skip = 0;
 #pragma unroll
         for (int j = 0; j < 8; j++) {
             const int i = (s0 >> 1) + j;
@@ -138,110 +122,70 @@ __global__ __launch_bounds__(CA_NT) void ca_dp_kernel(const CaSeq* __restrict__ 
                 if (i >= 1 && lab[i] != lab[i - 1]) skip |= 1u << j;
             }
         }
-        const double* cin = col + (size_t)((b + 1) & 1) * T;   // written by band b - 1
-        double* cout = col + (size_t)(b & 1) * T;
-        const bool write_col = tid == CA_NT - 1 && b + 1 < bands;
-        double v[CA_K];
 #pragma unroll
-        for (int k = 0; k < CA_K; k++) v[k] = NINF;
+        for (int k = 0; k < BS_K; k++) v[k] = -INFINITY;
         // row -1 of band 0: V = 0 in state 0 and -inf elsewhere makes row 0 the contract's start
-        if (b == 0 && tid == 0) v[0] = 0.0;
-        if (!single) {
-            __syncthreads();   // the previous band's last exchange reads and column writes
-            if (lane == 63) xch[(t_lo + 1) & 1][wave] = NINF;
-            __syncthreads();
-        }
-        // The lp rows come through LDS in tiles of CA_TR rows, fetched a whole tile ahead (loaded from global memory one row ahead,
-        // every row waited for part of a load: DESIGN.md section 16); slot 7 of a tile row holds the band's incoming column value
-        // V[t-1][s_lo-1] (band 0: -inf).
-        auto tile_load = [&](int tbase, double* pre) {
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-                if (i < per) {
-                    const int e = tid + i * nact, c = e & 7, t = tbase + (e >> 3);
-                    double x = NINF;
-                    if (t < T) x = c == 7 && b > 0 ? cin[t - 1] : lp[(size_t)t * 8 + c];
-                    pre[i] = x;
-                }
-        };
-        auto tile_store = [&](int buf, const double* pre) {
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-                if (i < per) {
-                    const int e = tid + i * nact;
-                    tile[buf][e >> 3][e & 7] = pre[i];
-                }
-        };
-        double pre[4];
-        tile_load(t_lo, pre);
-        tile_store(0, pre);
-        if (single) __builtin_amdgcn_wave_barrier();
-        else __syncthreads();
-        int buf = 0;
-        for (int tb = t_lo; tb < T; tb += CA_TR, buf ^= 1) {
-            const bool more = tb + CA_TR < T;
-            if (more) tile_load(tb + CA_TR, pre);
-            const int nr = T - tb < CA_TR ? T - tb : CA_TR;
-            double nb = tile[buf][0][4], nc = tile[buf][0][7], nl[8];
-#pragma unroll
-            for (int j = 0; j < 8; j++) nl[j] = tile[buf][0][cl[j]];
-            for (int r = 0; r < nr; r++) {
-                const int t = tb + r;
-                const double cb = nb, cc = nc;
-                double cur[8];
-#pragma unroll
-                for (int j = 0; j < 8; j++) cur[j] = nl[j];
-                if (r + 1 < nr) {
-                    nb = tile[buf][r + 1][4];
-                    nc = tile[buf][r + 1][7];
-#pragma unroll
-                    for (int j = 0; j < 8; j++) nl[j] = tile[buf][r + 1][cl[j]];
-                }
-                double left = ca_shr1(v[CA_K - 1]);
-                if (lane == 0) left = wave > 0 ? xch[(t + 1) & 1][wave - 1] : cc;
-                uint32_t bits = 0;
-#pragma unroll
-                for (int k = CA_K - 1; k >= 0; k--) {
-                    double best = v[k];
-                    uint32_t d = 0;
-                    const double a1 = k >= 1 ? v[k - 1] : left;
-                    if (a1 > best) {
-                        best = a1;
-                        d = 1;
-                    }
-                    if (k & 1) {
-                        const double a2 = k >= 2 ? v[k - 2] : left;
-                        if (((skip >> (k >> 1)) & 1) && a2 > best) {
-                            best = a2;
-                            d = 2;
-                        }
-                        v[k] = cur[k >> 1] + best;
-                    } else {
-                        v[k] = cb + best;
-                    }
-                    bits |= d << (2 * k);
-                }
-                if (w < wpr) bp[(size_t)t * wpr + w] = bits;
-                if (write_col) cout[t] = v[CA_K - 1];
-                if (!single) {
-                    if (lane == 63) xch[t & 1][wave] = v[CA_K - 1];
-                    __syncthreads();
-                }
-            }
-            if (more) {
-                tile_store(buf ^ 1, pre);
-                if (single) __builtin_amdgcn_wave_barrier();
-                else __syncthreads();
-            }
-        }
-        // the two states the path may end in
-#pragma unroll
-        for (int k = 0; k < CA_K; k++) {
-            if (s0 + k == 2 * L) fin[2 * (int64_t)blockIdx.x] = v[k];
-            if (s0 + k == 2 * L - 1) fin[2 * (int64_t)blockIdx.x + 1] = v[k];
-        }
-        if (!single) __threadfence_block();
+        if (s0 == 0) v[0] = 0.0;
     }
+    __device__ __forceinline__ Elem tile_elem(int e, int tbase, int T, int b, const Cell* cin) const
+    {
+        const int c = e & 7, t = tbase + (e >> 3);
+        Elem x = -INFINITY;
+        if (t < T) x = c == 7 && b > 0 ? cin[t - 1] : lp[(size_t)t * 8 + c];
+        return x;
+    }
+    __device__ __forceinline__ Row read_row(const Elem* tile, int r) const
+    {
+        Row in{tile[r * 8 + 4], tile[r * 8 + 7], {}};
+#pragma unroll
+        for (int j = 0; j < 8; j++) in.l[j] = tile[r * 8 + cl[j]];
+        return in;
+    }
+    __device__ __forceinline__ void row(int t, const Row& in, Cell left)
+    {
+        uint32_t bits = 0;
+#pragma unroll
+        for (int k = BS_K - 1; k >= 0; k--) {
+            double best = v[k];
+            uint32_t d = 0;
+            const double a1 = k >= 1 ? v[k - 1] : left;
+            if (a1 > best) {
+                best = a1;
+                d = 1;
+            }
+            if (k & 1) {
+                const double a2 = k >= 2 ? v[k - 2] : left;
+                if (((skip >> (k >> 1)) & 1) && a2 > best) {
+                    best = a2;
+                    d = 2;
+                }
+                v[k] = in.l[k >> 1] + best;
+            } else {
+                v[k] = in.b + best;
+            }
+            bits |= d << (2 * k);
+        }
+        if ((s0 >> 4) < wpr) bp[(size_t)t * wpr + (s0 >> 4)] = bits;
+    }
+    // the two states the path may end in
+    __device__ __forceinline__ void end_band() const
+    {
+#pragma unroll
+        for (int k = 0; k < BS_K; k++) {
+            if (s0 + k == 2 * L) fin[0] = v[k];
+            if (s0 + k == 2 * L - 1) fin[1] = v[k];
+        }
+    }
+};
+
+__global__ __launch_bounds__(BS_NT) void ca_dp_kernel(const CaSeq* __restrict__ seqs, const uint8_t* __restrict__ labels, uint8_t* __restrict__ ws,
+                                                      double* __restrict__ fin)
+{
+    const CaSeq q = seqs[blockIdx.x];
+    const int S = 2 * q.L + 1;
+    if (q.L > q.T) return;   // no path: the end values stay -inf
+    CaSweep p{(const double*)(ws + q.lp), (uint32_t*)(ws + q.bp), labels + q.lab, fin + 2 * (int64_t)blockIdx.x, q.L, (S + 15) / 16};
+    band_sweep(p, S, q.T, (double*)(ws + q.col));
 }
 
 __global__ __launch_bounds__(64) void ca_tb_kernel(const CaSeq* __restrict__ seqs, int n_seq, const uint8_t* __restrict__ ws,
@@ -429,7 +373,7 @@ int rd_ctc_align_dev(rd_ctx* ctx, hipStream_t st, const void* d_probs, int ptype
         RD_HIP(hipMemcpyAsync(io, desc.data(), (size_t)nb * sizeof(CaSeq), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(ca_log_kernel, dim3((unsigned)((max_T + 31) / 32), nb), dim3(256), 0, st, d_seqs, d_probs, ptype, dws, d_fin);
         RD_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ca_dp_kernel, dim3(nb), dim3(CA_NT), 0, st, d_seqs, d_labels, dws, d_fin);
+        hipLaunchKernelGGL(ca_dp_kernel, dim3(nb), dim3(BS_NT), 0, st, d_seqs, d_labels, dws, d_fin);
         RD_HIP(hipGetLastError());
         hipLaunchKernelGGL(ca_tb_kernel, dim3((nb + 63) / 64), dim3(64), 0, st, d_seqs, nb, dws, d_fin, d_score, d_status, d_first, d_last);
         RD_HIP(hipGetLastError());

@@ -10,20 +10,16 @@
 //   end       = state L + 1, or L if V[T-1][L+1] is not strictly smaller; score = that value
 //
 // Kernels, on one stream:
-//   ea_scale_kernel   once per call, one 256-thread workgroup per read: the scale as given, or the window's own by radix_select2
-//                     (select.h) twice, as pa_scale_kernel
+//   signal_scale_kernel   (signal_dev.h) once per call, one 256-thread workgroup per read: the scale as given, or the window's own by
+//                     radix_select2 (select.h) twice, as pa_scale_kernel
 //   per launch (a set of reads whose workspace fits the budget):
 //   ea_quant_kernel   zq rows, one int32 per sample
-//   ea_dp_kernel      one workgroup of 256 threads per read.  A thread owns 16 consecutive states in registers (value, level, weight
-//                     and bias of each), a workgroup pass a BAND of 4096 states; a read of more states is swept band after band, the last
-//                     state of a band at every row going through a 4-byte-per-row column in global memory (two columns, written and read
-//                     in turn).  Row t of a thread needs its left neighbour's last state of row t-1 only: one DPP wave_shr:1 inside a
-//                     wave, one LDS word and the row's single barrier between waves.  A read of at most 1024 states runs on its first wave
-//                     alone and has no barrier.  The zq rows and the band's incoming column values come through LDS in tiles of 128 rows,
-//                     fetched from global memory a tile ahead and read from LDS a row ahead.  Back-pointers: 1 bit per cell, a thread's 16
-//                     cells = one uint16, a wave's 64 stores = 128 consecutive bytes, a row = 4 ceil((L + 2) / 32) bytes.  Band b > 0
-//                     starts at row 4096 b - 1: the cells above (s > t + 1) are unreachable.  Unreachable cells are computed unmasked from
-//                     2^30: they stay above 2^30 - 2^19 * 256, every finite value stays below 2^19 * 1280, so none ever wins.
+//   ea_dp_kernel      one workgroup per read: band_sweep.h's sweep.  A thread's registers: value, level, weight and bias of its 16
+//                     states; a 4-byte cell crosses a thread boundary; a tile is 128 rows of zq and of the incoming column.
+//                     Back-pointers: 1 bit per cell, a thread's 16 cells = one uint16, a wave's 64 stores = 128 consecutive bytes, a
+//                     row = 4 ceil((L + 2) / 32) bytes.  Band b > 0 starts at row 4096 b - 1: the cells above (s > t + 1) are
+//                     unreachable.  Unreachable cells are computed unmasked from 2^30: they stay above 2^30 - 2^19 * 256, every finite
+//                     value stays below 2^19 * 1280, so none ever wins.
 //   ea_tb_kernel      one wave per read: end state, score, then the walk, 64 rows at a time -- lane r holds row t - r's two words (the one
 //                     of the path's state and the one below), a ballot of the state's bit over the rows not yet walked finds the nearest
 //                     row the state was entered at, and the state moves down; the path dwells tens of rows per state, so a step of the
@@ -224,21 +220,13 @@ extern "C" int rd_eventalign_host(const int16_t* raw, const int64_t* read_off, i
 
 #if defined(__HIPCC__)
 // ------------------------------------------------------------------------------------------------------------------ device half
-#include "select.h"
+#include "band_sweep.h"
+#include "signal_dev.h"
 
 namespace {
 
-constexpr int EA_NT = 256;                 // threads of a DP workgroup
-constexpr int EA_K = 16;                   // states a thread owns
-constexpr int EA_BAND = EA_NT * EA_K;      // states of one workgroup pass
-constexpr int EA_TR = 128;                 // rows of a tile in LDS (2 EA_TR elements -- zq and the incoming column: one per thread, four per lane of a lone wave)
-constexpr int EA_WAVE_STATES = 64 * EA_K;  // at most this many states: the first wave alone, no barrier
 constexpr int EA_MAX_LAUNCH = 32768;       // reads of one launch (grid.y of the row kernel)
 
-struct EaScaleIn {
-    int64_t raw0;   // the window's sample 0 in the raw buffer
-    int32_t T, m2, d4, pad_;
-};
 struct EaSeq {
     int64_t raw0;    // the window's sample 0 in the raw buffer
     int64_t codes;   // the read's base 0 in the code buffer
@@ -249,20 +237,6 @@ struct EaSeq {
 struct EaOut {
     int64_t score, sums[5];
 };
-
-__global__ __launch_bounds__(256) void ea_scale_kernel(const EaScaleIn* __restrict__ in, const int16_t* __restrict__ raw, int32_t* __restrict__ out)
-{
-    __shared__ unsigned hist[512];
-    __shared__ int sh[8];
-    const EaScaleIn q = in[blockIdx.x];
-    int m2 = q.m2, d4 = q.d4;
-    if (q.T <= 0 || q.T > EA_MAX_T) m2 = d4 = 0;   // (the same in every thread)
-    else if (q.d4 == 0) window_scale2(raw + q.raw0, q.T, hist, sh, &m2, &d4);
-    if (threadIdx.x == 0) {
-        out[2 * (int64_t)blockIdx.x] = m2;
-        out[2 * (int64_t)blockIdx.x + 1] = d4;
-    }
-}
 
 // grid (ceil(max T / 256), reads)
 __global__ __launch_bounds__(256) void ea_quant_kernel(const EaSeq* __restrict__ seqs, const int16_t* __restrict__ raw, uint8_t* __restrict__ ws,
@@ -275,36 +249,40 @@ __global__ __launch_bounds__(256) void ea_quant_kernel(const EaSeq* __restrict__
     ((int32_t*)(ws + q.zq))[t] = ea_quant(raw[q.raw0 + t], q.m2, q.d4);
 }
 
-// lane l receives v of lane l - 1; lane 0 keeps its own (DPP wave_shr:1, bound_ctrl off)
-__device__ __forceinline__ int32_t ea_shr1(int32_t v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false); }
+// band_sweep.h's policy of eventalign
+struct EaSweep {
+    using Cell = int32_t;
+    using Elem = int32_t;
+    static constexpr bool AHEAD_CLAMPED = true;
+    static constexpr int TR = 128, SLOTS = 2;   // a tile: [0: zq, 1: the band's incoming column value V[t-1][s_lo-1]][row]
+    struct Row {
+        int32_t z, c;
+    };
+    // the read
+    const int32_t* __restrict__ zq;
+    uint16_t* __restrict__ bp;
+    const uint8_t* cod;
+    const int32_t* __restrict__ lvl_t;
+    const uint32_t* __restrict__ w_t;
+    const int32_t* __restrict__ bias_t;
+    EaState bg;
+    int32_t* fin;   // the read's two end values
+    int k, L, S, hpr;   // hpr: 16-bit words of a back-pointer row
+    // the thread's states of the band
+    int s0;
+    int32_t lv[BS_K], bi[BS_K], v[BS_K];
+    uint32_t wt[BS_K];
 
-__global__ __launch_bounds__(EA_NT) void ea_dp_kernel(const EaSeq* __restrict__ seqs, const uint8_t* __restrict__ codes, const int32_t* __restrict__ lvl_t,
-                                                      const uint32_t* __restrict__ w_t, const int32_t* __restrict__ bias_t, EaState bg, int k,
-                                                      uint8_t* __restrict__ ws, int32_t* __restrict__ fin)
-{
-    const EaSeq q = seqs[blockIdx.x];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int T = q.T, L = q.L, S = L + 2;
-    const bool single = S <= EA_WAVE_STATES;
-    if (single && wave) return;   // (the first wave never waits at a barrier then)
-    const int32_t* __restrict__ zq = (const int32_t*)(ws + q.zq);
-    uint16_t* __restrict__ bp = (uint16_t*)(ws + q.bp);
-    int32_t* col = (int32_t*)(ws + q.col);
-    const uint8_t* cod = codes + q.codes;
-    const int hpr = 2 * ((S + 31) / 32);   // 16-bit words of a back-pointer row
-    const int bands = (S + EA_BAND - 1) / EA_BAND;
-    __shared__ int32_t xch[2][EA_NT / 64];
-    __shared__ int32_t tile[2][2][EA_TR];   // [buffer][0: zq, 1: the band's incoming column value V[t-1][s_lo-1]][row]
-    const int nact = single ? 64 : EA_NT, per = 2 * EA_TR / nact;   // threads at work, tile elements each
+    static __device__ __forceinline__ int first_row(int b) { return b ? b * BS_BAND - 1 : 0; }   // rows above have s > t + 1 in the whole band
+    static __device__ __forceinline__ Cell none() { return EA_INF; }
+    static __device__ __forceinline__ Cell incoming(const Row& in) { return in.c; }
+    __device__ __forceinline__ Cell last() const { return v[BS_K - 1]; }
 
-    for (int b = 0; b < bands; b++) {
-        const int s0 = b * EA_BAND + tid * EA_K;
-        const int t_lo = b ? b * EA_BAND - 1 : 0;   // rows above have s > t + 1 in the whole band
-        if (t_lo >= T) break;                       // (then the states of this band and the later ones are unreachable in the last row too)
-        int32_t lv[EA_K], bi[EA_K], v[EA_K];
-        uint32_t wt[EA_K];
+    __device__ __forceinline__ void begin_band(int b)
+    {
+        s0 = b * BS_BAND + (int)threadIdx.x * BS_K;
 #pragma unroll
-        for (int j = 0; j < EA_K; j++) {
+        for (int j = 0; j < BS_K; j++) {
             EaState st{0, 0, 0};   // a state past the read: its value stays where it starts
             if (s0 + j < S) st = ea_state(s0 + j, L, cod, k, lvl_t, w_t, bias_t, bg);
             lv[j] = st.lvl;
@@ -313,86 +291,51 @@ __global__ __launch_bounds__(EA_NT) void ea_dp_kernel(const EaSeq* __restrict__ 
             v[j] = EA_INF;
         }
         // row -1 of band 0: V = 0 in state 0 and unreachable elsewhere makes row 0 the contract's start
-        if (b == 0 && tid == 0) v[0] = 0;
-        const int32_t* cin = col + (size_t)((b + 1) & 1) * T;   // written by band b - 1
-        int32_t* cout = col + (size_t)(b & 1) * T;
-        const bool write_col = tid == EA_NT - 1 && b + 1 < bands;
-        const bool store = s0 < S;
-        if (!single) {
-            __syncthreads();   // the previous band's last exchange reads and column writes
-            if (lane == 63) xch[(t_lo + 1) & 1][wave] = EA_INF;
-            __syncthreads();
-        }
-        auto tile_load = [&](int tbase, int32_t* pre) {
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-                if (i < per) {
-                    const int e = tid + i * nact, which = e / EA_TR, t = tbase + (e % EA_TR);
-                    int32_t x = EA_INF;
-                    if (t < T) {
-                        if (which == 0) x = zq[t];
-                        else if (b > 0) x = cin[t - 1];   // t >= t_lo >= 1
-                    }
-                    pre[i] = x;
-                }
-        };
-        auto tile_store = [&](int buf, const int32_t* pre) {
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-                if (i < per) {
-                    const int e = tid + i * nact;
-                    tile[buf][e / EA_TR][e % EA_TR] = pre[i];
-                }
-        };
-        int32_t pre[4];
-        tile_load(t_lo, pre);
-        tile_store(0, pre);
-        if (single) __builtin_amdgcn_wave_barrier();
-        else __syncthreads();
-        int buf = 0;
-        for (int tb = t_lo; tb < T; tb += EA_TR, buf ^= 1) {
-            const bool more = tb + EA_TR < T;
-            if (more) tile_load(tb + EA_TR, pre);
-            const int nr = T - tb < EA_TR ? T - tb : EA_TR;
-            int32_t nz = tile[buf][0][0], nc = tile[buf][1][0];
-            for (int r = 0; r < nr; r++) {
-                const int t = tb + r;
-                const int32_t z = nz, cc = nc;
-                if (r + 1 < nr) {
-                    nz = tile[buf][0][r + 1];
-                    nc = tile[buf][1][r + 1];
-                }
-                int32_t left = ea_shr1(v[EA_K - 1]);
-                if (lane == 0) left = wave > 0 ? xch[(t + 1) & 1][wave - 1] : cc;
-                uint32_t bits = 0;
-#pragma unroll
-                for (int j = EA_K - 1; j >= 0; j--) {
-                    const int32_t adv = j >= 1 ? v[j - 1] : left;
-                    const bool take = ea_advance(v[j], adv);
-                    v[j] = ea_cost(z, lv[j], wt[j], bi[j]) + (take ? adv : v[j]);
-                    bits |= (take ? 1u : 0u) << j;
-                }
-                if (store) bp[(size_t)t * hpr + (s0 >> 4)] = (uint16_t)bits;
-                if (write_col) cout[t] = v[EA_K - 1];
-                if (!single) {
-                    if (lane == 63) xch[t & 1][wave] = v[EA_K - 1];
-                    __syncthreads();
-                }
-            }
-            if (more) {
-                tile_store(buf ^ 1, pre);
-                if (single) __builtin_amdgcn_wave_barrier();
-                else __syncthreads();
-            }
-        }
-        // the two states the path may end in
-#pragma unroll
-        for (int j = 0; j < EA_K; j++) {
-            if (s0 + j == L + 1) fin[2 * (int64_t)blockIdx.x] = v[j];
-            if (s0 + j == L) fin[2 * (int64_t)blockIdx.x + 1] = v[j];
-        }
-        if (!single) __threadfence_block();
+        if (s0 == 0) v[0] = 0;
     }
+    __device__ __forceinline__ Elem tile_elem(int e, int tbase, int T, int b, const Cell* cin) const
+    {
+        const int which = e / TR, t = tbase + (e % TR);
+        Elem x = EA_INF;
+        if (t < T) {
+            if (which == 0) x = zq[t];
+            else if (b > 0) x = cin[t - 1];   // t >= first_row(b) >= 1
+        }
+        return x;
+    }
+    __device__ __forceinline__ Row read_row(const Elem* tile, int r) const { return Row{tile[r], tile[TR + r]}; }
+    __device__ __forceinline__ void row(int t, const Row& in, Cell left)
+    {
+        uint32_t bits = 0;
+#pragma unroll
+        for (int j = BS_K - 1; j >= 0; j--) {
+            const int32_t adv = j >= 1 ? v[j - 1] : left;
+            const bool take = ea_advance(v[j], adv);
+            v[j] = ea_cost(in.z, lv[j], wt[j], bi[j]) + (take ? adv : v[j]);
+            bits |= (take ? 1u : 0u) << j;
+        }
+        if (s0 < S) bp[(size_t)t * hpr + (s0 >> 4)] = (uint16_t)bits;
+    }
+    // the two states the path may end in
+    __device__ __forceinline__ void end_band() const
+    {
+#pragma unroll
+        for (int j = 0; j < BS_K; j++) {
+            if (s0 + j == L + 1) fin[0] = v[j];
+            if (s0 + j == L) fin[1] = v[j];
+        }
+    }
+};
+
+__global__ __launch_bounds__(BS_NT) void ea_dp_kernel(const EaSeq* __restrict__ seqs, const uint8_t* __restrict__ codes, const int32_t* __restrict__ lvl_t,
+                                                      const uint32_t* __restrict__ w_t, const int32_t* __restrict__ bias_t, EaState bg, int k,
+                                                      uint8_t* __restrict__ ws, int32_t* __restrict__ fin)
+{
+    const EaSeq q = seqs[blockIdx.x];
+    const int S = q.L + 2;
+    EaSweep p{(const int32_t*)(ws + q.zq), (uint16_t*)(ws + q.bp), codes + q.codes, lvl_t, w_t, bias_t, bg, fin + 2 * (int64_t)blockIdx.x,
+              k, q.L, S, 2 * ((S + 31) / 32)};
+    band_sweep(p, S, q.T, (int32_t*)(ws + q.col));
 }
 
 // one wave per read
@@ -488,37 +431,23 @@ extern "C" int rd_eventalign(rd_ctx* ctx, const int16_t* raw, const int64_t* rea
     RD_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     // the samples the reads span, rebased to the first read's; the bases; the model
-    const int64_t lo = read_off[0], n_samples = read_off[n_reads] - lo, n_kmers = (int64_t)1 << (2 * k);
-    const size_t b_tab = align_up((size_t)n_kmers * 4, 256);
-    if (ctx->ws_raw.reserve((size_t)n_samples * 2 + 16) || ctx->ws_labels.reserve((size_t)n_bases + 16) || ctx->ws_eval_model.reserve(3 * b_tab))
-        return RD_ERR_NOMEM;
+    const int64_t lo = read_off[0], n_samples = read_off[n_reads] - lo;
+    if (ctx->ws_raw.reserve((size_t)n_samples * 2 + 16) || ctx->ws_labels.reserve((size_t)n_bases + 16)) return RD_ERR_NOMEM;
     const int16_t* d_raw = ctx->ws_raw.as<int16_t>();
     const uint8_t* d_codes = ctx->ws_labels.as<uint8_t>();
-    const int32_t* d_lvl = (const int32_t*)ctx->ws_eval_model.as<uint8_t>();
-    const uint32_t* d_w = (const uint32_t*)(ctx->ws_eval_model.as<uint8_t>() + b_tab);
-    const int32_t* d_bias = (const int32_t*)(ctx->ws_eval_model.as<uint8_t>() + 2 * b_tab);
     if (n_samples) RD_HIP(hipMemcpyAsync(ctx->ws_raw.p, raw + lo, (size_t)n_samples * 2, hipMemcpyHostToDevice, st));
     if (n_bases) RD_HIP(hipMemcpyAsync(ctx->ws_labels.p, codes, (size_t)n_bases, hipMemcpyHostToDevice, st));
-    RD_HIP(hipMemcpyAsync((void*)d_lvl, lvl, (size_t)n_kmers * 4, hipMemcpyHostToDevice, st));
-    RD_HIP(hipMemcpyAsync((void*)d_w, w, (size_t)n_kmers * 4, hipMemcpyHostToDevice, st));
-    RD_HIP(hipMemcpyAsync((void*)d_bias, bias, (size_t)n_kmers * 4, hipMemcpyHostToDevice, st));
+    KmerTables tab;
+    if ((rc = signal_upload_tables(ctx, st, k, lvl, w, bias, 0, &tab))) return rc;
+    const int32_t *d_lvl = tab.lvl, *d_bias = tab.bias;
+    const uint32_t* d_w = tab.w;
     std::vector<int64_t> off(n_reads + 1);
     for (int r = 0; r <= n_reads; r++) off[r] = read_off[r] - lo;
     // every read's scale: a property of the read alone, whatever the budget does with it afterwards
-    std::vector<EaScaleIn> scin(n_reads);
-    std::vector<int32_t> scale(2 * (size_t)n_reads);
-    for (int r = 0; r < n_reads; r++) {
-        const int64_t T = t_hi[r] - t_lo[r];
-        scin[r] = EaScaleIn{off[r] + t_lo[r], (int32_t)(T > EA_MAX_T ? EA_MAX_T + 1 : T), m2_in[r], d4_in[r], 0};
-    }
-    const size_t b_sin = align_up((size_t)n_reads * sizeof(EaScaleIn), 256);
-    if (ctx->ws_eval.reserve(b_sin + (size_t)n_reads * 8 + 256)) return RD_ERR_NOMEM;
-    int32_t* d_scale = (int32_t*)(ctx->ws_eval.as<uint8_t>() + b_sin);
-    RD_HIP(hipMemcpyAsync(ctx->ws_eval.p, scin.data(), (size_t)n_reads * sizeof(EaScaleIn), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(ea_scale_kernel, dim3(n_reads), dim3(256), 0, st, (const EaScaleIn*)ctx->ws_eval.p, d_raw, d_scale);
-    RD_HIP(hipGetLastError());
-    RD_HIP(hipMemcpyAsync(scale.data(), d_scale, (size_t)n_reads * 8, hipMemcpyDeviceToHost, st));
-    RD_HIP(hipStreamSynchronize(st));
+    std::vector<SignalScaleIn> scin(n_reads);
+    std::vector<int32_t> scale;
+    for (int r = 0; r < n_reads; r++) scin[r] = signal_scale_in(off[r] + t_lo[r], t_hi[r] - t_lo[r], t_hi[r] - t_lo[r], EA_MAX_T, m2_in[r], d4_in[r]);
+    if ((rc = signal_scales(ctx, st, d_raw, scin, EA_MAX_T, scale))) return rc;
     // statuses that need no alignment, then the launches: the other reads in the caller's order, as many as fit the budget; a read that
     // alone exceeds it is reported, not launched
     for (int r = 0; r < n_reads; r++) {
@@ -590,7 +519,7 @@ extern "C" int rd_eventalign(rd_ctx* ctx, const int16_t* raw, const int64_t* rea
         RD_HIP(hipMemcpyAsync(io, desc.data(), (size_t)nb * sizeof(EaSeq), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(ea_quant_kernel, dim3((unsigned)((max_T + 255) / 256), nb), dim3(256), 0, st, d_seqs, d_raw, dws, d_fin);
         RD_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ea_dp_kernel, dim3(nb), dim3(EA_NT), 0, st, d_seqs, d_codes, d_lvl, d_w, d_bias, c.m.bg, k, dws, d_fin);
+        hipLaunchKernelGGL(ea_dp_kernel, dim3(nb), dim3(BS_NT), 0, st, d_seqs, d_codes, d_lvl, d_w, d_bias, c.m.bg, k, dws, d_fin);
         RD_HIP(hipGetLastError());
         hipLaunchKernelGGL(ea_tb_kernel, dim3(nb), dim3(64), 0, st, d_seqs, dws, d_fin, d_out, d_first, d_last);
         RD_HIP(hipGetLastError());

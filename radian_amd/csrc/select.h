@@ -71,7 +71,7 @@ __device__ SelectResult radix_select2(int64_t n, int64_t k1, int64_t k2, KeyFn k
     return r;
 }
 
-// the scale of a window of n >= 1 int16 samples (rd_eventalign's rule, shared by ea_scale_kernel and sm_scale_kernel): m2 = the sum of the
+// the scale of a window of n >= 1 int16 samples (rd_eventalign's rule; signal_dev.h's signal_scale_kernel): m2 = the sum of the
 // two middle order statistics, d4 = the same of |2x - m2|.  One workgroup; hist[512], sh[8]; the result is the same in every thread
 __device__ inline void window_scale2(const int16_t* __restrict__ x, int64_t n, unsigned* hist, int* sh, int* m2_out, int* d4_out)
 {

@@ -12,22 +12,17 @@
 // Kernels, on one stream:
 //   sm_state_kernel   once per call, one thread per state of the panel: its k-mer within its own target (bit 31: first state of the
 //                     target) and its target
-//   sm_scale_kernel   once per call, one 256-thread workgroup per query: the scale as given, or the scale window's own by select.h's
-//                     window_scale2, which ea_scale_kernel calls too
+//   signal_scale_kernel   (signal_dev.h) once per call, one 256-thread workgroup per query: the scale as given, or the scale window's own
 //   per launch (a set of queries whose workspace fits the budget):
 //   sm_quant_kernel   zq rows, one int32 per sample; the (query, target) keys to "none"
-//   sm_dp_kernel      one workgroup of 256 threads per STRIPE.  A stripe reports the ends [a, b) (SM_PAYLOAD of them) and computes the
-//                     states [left, b), left = max(s_lo, a - (T - 1)), with a free start: cell (t, s) is exact for s >= left + t, so row
-//                     T - 1 is exact on [a, b).  A thread owns 16 consecutive states in registers (value, origin, level, weight, bias and a
-//                     16-bit head mask), a workgroup pass a BAND of 4096 states; a stripe of more states is swept band after band, the last
-//                     state of a band at every row (value and origin) going through an 8-byte-per-row column in global memory (two
-//                     columns, written and read in turn).  The left neighbour: one DPP wave_shr:1 inside a wave, one LDS word pair and
-//                     the row's single barrier between waves.  A stripe of at most 1024 states runs on its first wave alone and has no
-//                     barrier.  zq and the band's incoming column come through LDS in tiles of 128 rows, fetched a tile ahead.  A wave
-//                     that holds no head runs the row without the mask.  Nothing is stored per row but that column.  At the end a
-//                     thread stores the origins of its end states (4 bytes per state of the range) and merges its end values into the
-//                     (query, target) keys, (score + 2^25) << 32 | state, with a 64-bit atomicMin per run of states of one target:
-//                     the minimum does not depend on the order.
+//   sm_dp_kernel      one workgroup per STRIPE: band_sweep.h's sweep.  A stripe reports the ends [a, b) (SM_PAYLOAD of them) and computes
+//                     the states [left, b), left = max(s_lo, a - (T - 1)), with a free start: cell (t, s) is exact for s >= left + t, so
+//                     row T - 1 is exact on [a, b).  A thread's registers: value, origin, level, weight and bias of its 16 states and a
+//                     16-bit head mask; value and origin (8 bytes) cross a thread boundary; a tile is 128 rows of zq and of the incoming
+//                     column's value and origin.  A wave that holds no head runs the row without the mask.  Nothing is stored per row
+//                     but the column.  At the end a thread stores the origins of its end states (4 bytes per state of the range) and
+//                     merges its end values into the (query, target) keys, (score + 2^25) << 32 | state, with a 64-bit atomicMin per
+//                     run of states of one target: the minimum does not depend on the order.
 //   sm_select_kernel  one wave per query: n_best times the smallest (score, j) above the previous one
 // No floating point, no scratch.  A query's result does not depend on its launch's other queries.
 #include "common.h"
@@ -211,21 +206,14 @@ extern "C" int rd_sigmap_host(const int16_t* raw, int64_t n_raw, int n_q, const 
 
 #if defined(__HIPCC__)
 // ------------------------------------------------------------------------------------------------------------------ device half
-#include "select.h"
+#include "band_sweep.h"
+#include "signal_dev.h"
 
 namespace {
 
-constexpr int SM_NT = 256;                 // threads of a DP workgroup
-constexpr int SM_K = 16;                   // states a thread owns
-constexpr int SM_TR = 128;                 // rows of a tile in LDS (3 SM_TR elements: zq and the incoming column's value and origin)
-constexpr int SM_WAVE_STATES = 64 * SM_K;  // at most this many states: the first wave alone, no barrier
 constexpr int SM_MAX_LAUNCH = 4096;        // queries of one launch
-static_assert(SM_BAND == SM_NT * SM_K, "a band is a workgroup pass");
+static_assert(SM_BAND == BS_BAND, "a band is a workgroup pass");
 
-struct SmScaleIn {
-    int64_t raw0, n;   // the scale window's sample 0 in the raw buffer, its samples
-    int32_t T, m2, d4, pad_;
-};
 struct SmQuery {
     int64_t raw0;            // the query window's sample 0 in the raw buffer
     int64_t zq, org, key;    // byte offsets into the workspace
@@ -250,23 +238,6 @@ __global__ __launch_bounds__(256) void sm_state_kernel(const int64_t* __restrict
     tg[s] = j;
 }
 
-__global__ __launch_bounds__(256) void sm_scale_kernel(const SmScaleIn* __restrict__ in, const int16_t* __restrict__ raw, int32_t* __restrict__ out)
-{
-    __shared__ unsigned hist[512];
-    __shared__ int sh[8];
-    const SmScaleIn q = in[blockIdx.x];
-    int m2 = q.m2, d4 = q.d4;
-    if (q.T <= 0 || q.T > SM_MAX_T) m2 = d4 = 0;   // (the same in every thread)
-    else if (q.d4 == 0) {
-        m2 = 0;
-        if (q.n > 0) window_scale2(raw + q.raw0, q.n, hist, sh, &m2, &d4);
-    }
-    if (threadIdx.x == 0) {
-        out[2 * (int64_t)blockIdx.x] = m2;
-        out[2 * (int64_t)blockIdx.x + 1] = d4;
-    }
-}
-
 // grid (ceil(max T / 256), queries)
 __global__ __launch_bounds__(256) void sm_quant_kernel(const SmQuery* __restrict__ qs, const int16_t* __restrict__ raw, uint8_t* __restrict__ ws)
 {
@@ -280,23 +251,19 @@ __global__ __launch_bounds__(256) void sm_quant_kernel(const SmQuery* __restrict
     ((int32_t*)(ws + q.zq))[t] = ea_quant(raw[q.raw0 + t], q.m2, q.d4);
 }
 
-// lane l receives v of lane l - 1; lane 0 keeps its own (DPP wave_shr:1, bound_ctrl off)
-__device__ __forceinline__ int32_t sm_shr1(int32_t v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false); }
-
-// the single-wave path's ordering of LDS writes before other lanes' reads: a wavefront-scope fence, then the scheduling barrier
-__device__ __forceinline__ void sm_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
+// what crosses a thread boundary: a state's value and origin
+struct alignas(8) SmCell {
+    int32_t v, o;
+};
+__device__ __forceinline__ SmCell lane_shr1(SmCell c) { return SmCell{lane_shr1(c.v), lane_shr1(c.o)}; }
 
 // one row of a thread's 16 states, from the last down: every cell still reads the row before
 template <bool HEADS>
-__device__ __forceinline__ void sm_row(int32_t z, int32_t left_v, int32_t left_o, uint32_t hm, const int32_t (&lv)[SM_K], const uint32_t (&wt)[SM_K],
-                                       const int32_t (&bi)[SM_K], int32_t (&v)[SM_K], int32_t (&o)[SM_K])
+__device__ __forceinline__ void sm_row(int32_t z, int32_t left_v, int32_t left_o, uint32_t hm, const int32_t (&lv)[BS_K], const uint32_t (&wt)[BS_K],
+                                       const int32_t (&bi)[BS_K], int32_t (&v)[BS_K], int32_t (&o)[BS_K])
 {
 #pragma unroll
-    for (int j = SM_K - 1; j >= 0; j--) {
+    for (int j = BS_K - 1; j >= 0; j--) {
         const int32_t av = j >= 1 ? v[j - 1] : left_v, ao = j >= 1 ? o[j - 1] : left_o;
         bool take = ea_advance(v[j], av);
         if (HEADS) take = take && !((hm >> j) & 1u);
@@ -305,31 +272,44 @@ __device__ __forceinline__ void sm_row(int32_t z, int32_t left_v, int32_t left_o
     }
 }
 
-__global__ __launch_bounds__(SM_NT) void sm_dp_kernel(const SmQuery* __restrict__ qs, const SmStripe* __restrict__ stripes,
-                                                      const uint32_t* __restrict__ kid, const int32_t* __restrict__ tg,
-                                                      const int32_t* __restrict__ lvl_t, const uint32_t* __restrict__ w_t,
-                                                      const int32_t* __restrict__ bias_t, uint8_t* __restrict__ ws)
-{
-    const SmStripe sp = stripes[blockIdx.x];
-    const SmQuery q = qs[sp.q];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int T = q.T;
-    const int64_t n = (int64_t)sp.b - sp.left;   // at most SM_PAYLOAD + T - 1
-    const bool single = n <= SM_WAVE_STATES;
-    if (single && wave) return;   // (the first wave never waits at a barrier then)
-    const int32_t* __restrict__ zq = (const int32_t*)(ws + q.zq);
-    int2* col = (int2*)(ws + sp.col);
-    const int bands = (int)((n + SM_BAND - 1) / SM_BAND);
-    __shared__ int32_t xch[2][2][SM_NT / 64];   // [row parity][value, origin][wave]
-    __shared__ int32_t tile[2][3][SM_TR];       // [buffer][0: zq, 1 and 2: the band's incoming column, V and O of [t-1][first state - 1]][row]
-    const int nact = single ? 64 : SM_NT;       // threads at work
+// band_sweep.h's policy of sigmap
+struct SmSweep {
+    using Cell = SmCell;
+    using Elem = int32_t;
+    static constexpr bool AHEAD_CLAMPED = true;
+    static constexpr int TR = 128, SLOTS = 3;   // a tile: [0: zq, 1 and 2: the band's incoming column, V and O of [t-1][first state - 1]][row]
+    struct Row {
+        int32_t z;
+        SmCell c;
+    };
+    // the stripe and its query
+    SmStripe sp;
+    const int32_t* __restrict__ zq;
+    const uint32_t* __restrict__ kid;
+    const int32_t* __restrict__ tg;
+    const int32_t* __restrict__ lvl_t;
+    const uint32_t* __restrict__ w_t;
+    const int32_t* __restrict__ bias_t;
+    int32_t* __restrict__ org;
+    unsigned long long* key;
+    int32_t s_lo, j_lo;
+    // the thread's states of the band
+    int64_t s0;
+    int32_t lv[BS_K], bi[BS_K], v[BS_K], o[BS_K];
+    uint32_t wt[BS_K], hm;
+    bool heads;   // (the same in every lane of a wave)
 
-    for (int b = 0; b < bands; b++) {
-        const int64_t s0 = (int64_t)sp.left + (int64_t)b * SM_BAND + tid * SM_K;
-        int32_t lv[SM_K], bi[SM_K], v[SM_K], o[SM_K];
-        uint32_t wt[SM_K], hm = 0;
+    static __device__ __forceinline__ int first_row(int) { return 0; }
+    static __device__ __forceinline__ Cell none() { return SmCell{EA_INF, 0}; }
+    static __device__ __forceinline__ Cell incoming(const Row& in) { return in.c; }
+    __device__ __forceinline__ Cell last() const { return SmCell{v[BS_K - 1], o[BS_K - 1]}; }
+
+    __device__ __forceinline__ void begin_band(int b)
+    {
+        s0 = (int64_t)sp.left + (int64_t)b * SM_BAND + (int)threadIdx.x * BS_K;
+        hm = 0;
 #pragma unroll
-        for (int j = 0; j < SM_K; j++) {
+        for (int j = 0; j < BS_K; j++) {
             lv[j] = bi[j] = 0;   // a state past the stripe: cost 0, reported nowhere
             wt[j] = 0;
             v[j] = 0;            // row -1: all equal, so no advance is taken in row 0 and V[0][s] = c(0, s)
@@ -342,94 +322,37 @@ __global__ __launch_bounds__(SM_NT) void sm_dp_kernel(const SmQuery* __restrict_
                 if ((kd >> 31) || s0 + j == sp.left) hm |= 1u << j;
             }
         }
-        const bool heads = __ballot(hm != 0) != 0;   // (the same in every lane of a wave)
-        const int2* cin = col + (size_t)((b + 1) & 1) * T;   // written by band b - 1
-        int2* cout = col + (size_t)(b & 1) * T;
-        const bool write_col = tid == SM_NT - 1 && b + 1 < bands;
-        if (!single) {
-            __syncthreads();   // the previous band's last exchange reads and column writes
-            if (lane == 63) {
-                xch[1][0][wave] = EA_INF;   // row 0 reads parity 1: nothing comes from the left
-                xch[1][1][wave] = 0;
-            }
-            __syncthreads();
+        heads = __ballot(hm != 0) != 0;
+    }
+    __device__ __forceinline__ Elem tile_elem(int e, int tbase, int T, int b, const Cell* cin) const
+    {
+        const int which = e / TR, t = tbase + (e % TR);
+        Elem x = which == 1 ? EA_INF : 0;   // row 0, band 0: nothing comes from the left
+        if (t < T) {
+            if (which == 0) x = zq[t];
+            else if (b > 0 && t >= 1) x = which == 1 ? cin[t - 1].v : cin[t - 1].o;
         }
-        auto tile_load = [&](int tbase, int32_t* pre) {
-#pragma unroll
-            for (int i = 0; i < 6; i++) {
-                const int e = tid + i * nact;
-                if (e < 3 * SM_TR) {
-                    const int which = e / SM_TR, t = tbase + (e % SM_TR);
-                    int32_t x = which == 1 ? EA_INF : 0;
-                    if (t < T) {
-                        if (which == 0) x = zq[t];
-                        else if (b > 0 && t >= 1) x = which == 1 ? cin[t - 1].x : cin[t - 1].y;
-                    }
-                    pre[i] = x;
-                }
-            }
-        };
-        auto tile_store = [&](int buf, const int32_t* pre) {
-#pragma unroll
-            for (int i = 0; i < 6; i++) {
-                const int e = tid + i * nact;
-                if (e < 3 * SM_TR) tile[buf][e / SM_TR][e % SM_TR] = pre[i];
-            }
-        };
-        int32_t pre[6];
-        tile_load(0, pre);
-        tile_store(0, pre);
-        if (single) sm_wave_sync();
-        else __syncthreads();
-        int buf = 0;
-        for (int tb = 0; tb < T; tb += SM_TR, buf ^= 1) {
-            const bool more = tb + SM_TR < T;
-            if (more) tile_load(tb + SM_TR, pre);
-            const int nr = T - tb < SM_TR ? T - tb : SM_TR;
-            int32_t nz = tile[buf][0][0], ncv = tile[buf][1][0], nco = tile[buf][2][0];
-            for (int r = 0; r < nr; r++) {
-                const int t = tb + r;
-                const int32_t z = nz, cv = ncv, co = nco;
-                if (r + 1 < nr) {
-                    nz = tile[buf][0][r + 1];
-                    ncv = tile[buf][1][r + 1];
-                    nco = tile[buf][2][r + 1];
-                }
-                int32_t left_v = sm_shr1(v[SM_K - 1]), left_o = sm_shr1(o[SM_K - 1]);
-                if (lane == 0) {
-                    left_v = wave > 0 ? xch[(t + 1) & 1][0][wave - 1] : cv;
-                    left_o = wave > 0 ? xch[(t + 1) & 1][1][wave - 1] : co;
-                }
-                if (heads) sm_row<true>(z, left_v, left_o, hm, lv, wt, bi, v, o);
-                else sm_row<false>(z, left_v, left_o, hm, lv, wt, bi, v, o);
-                if (write_col) cout[t] = make_int2(v[SM_K - 1], o[SM_K - 1]);
-                if (!single) {
-                    if (lane == 63) {
-                        xch[t & 1][0][wave] = v[SM_K - 1];
-                        xch[t & 1][1][wave] = o[SM_K - 1];
-                    }
-                    __syncthreads();
-                }
-            }
-            if (more) {
-                tile_store(buf ^ 1, pre);
-                if (single) sm_wave_sync();
-                else __syncthreads();
-            }
-        }
-        // the ends this stripe reports: the origin of every one, the best of every run of one target
-        int32_t* __restrict__ org = (int32_t*)(ws + q.org);
-        unsigned long long* key = (unsigned long long*)(ws + q.key);
+        return x;
+    }
+    __device__ __forceinline__ Row read_row(const Elem* tile, int r) const { return Row{tile[r], SmCell{tile[TR + r], tile[2 * TR + r]}}; }
+    __device__ __forceinline__ void row(int, const Row& in, Cell left)
+    {
+        if (heads) sm_row<true>(in.z, left.v, left.o, hm, lv, wt, bi, v, o);
+        else sm_row<false>(in.z, left.v, left.o, hm, lv, wt, bi, v, o);
+    }
+    // the ends this stripe reports: the origin of every one, the best of every run of one target
+    __device__ __forceinline__ void end_band() const
+    {
         uint64_t best = SM_NO_KEY;
         int32_t cur = -1;
 #pragma unroll
-        for (int j = 0; j < SM_K; j++) {
+        for (int j = 0; j < BS_K; j++) {
             const int64_t s = s0 + j;
             if (s >= sp.a && s < sp.b) {
-                org[s - q.s_lo] = o[j];
+                org[s - s_lo] = o[j];
                 const int32_t jt = tg[s];
                 if (jt != cur) {
-                    if (cur >= 0) atomicMin(key + (cur - q.j_lo), (unsigned long long)best);
+                    if (cur >= 0) atomicMin(key + (cur - j_lo), (unsigned long long)best);
                     cur = jt;
                     best = SM_NO_KEY;
                 }
@@ -437,9 +360,19 @@ __global__ __launch_bounds__(SM_NT) void sm_dp_kernel(const SmQuery* __restrict_
                 best = ky < best ? ky : best;
             }
         }
-        if (cur >= 0) atomicMin(key + (cur - q.j_lo), (unsigned long long)best);
-        if (!single) __threadfence_block();
+        if (cur >= 0) atomicMin(key + (cur - j_lo), (unsigned long long)best);
     }
+};
+
+__global__ __launch_bounds__(BS_NT) void sm_dp_kernel(const SmQuery* __restrict__ qs, const SmStripe* __restrict__ stripes,
+                                                      const uint32_t* __restrict__ kid, const int32_t* __restrict__ tg,
+                                                      const int32_t* __restrict__ lvl_t, const uint32_t* __restrict__ w_t,
+                                                      const int32_t* __restrict__ bias_t, uint8_t* __restrict__ ws)
+{
+    const SmStripe sp = stripes[blockIdx.x];
+    const SmQuery q = qs[sp.q];
+    SmSweep p{sp, (const int32_t*)(ws + q.zq), kid, tg, lvl_t, w_t, bias_t, (int32_t*)(ws + q.org), (unsigned long long*)(ws + q.key), q.s_lo, q.j_lo};
+    band_sweep(p, (int64_t)sp.b - sp.left, q.T, (SmCell*)(ws + sp.col));   // at most SM_PAYLOAD + T - 1 states
 }
 
 // one wave per query
@@ -508,45 +441,30 @@ extern "C" int rd_sigmap(rd_ctx* ctx, const int16_t* raw, int64_t n_raw, int n_q
         lo = std::min(lo, std::min(q_lo[q], sc_lo[q]));
         hi = std::max(hi, std::max(q_hi[q], sc_hi[q]));
     }
-    const int64_t n_samples = hi > lo ? hi - lo : 0, R = tgt_off[n_tgt], n_kmers = (int64_t)1 << (2 * k);
-    const size_t b_tab = align_up((size_t)n_kmers * 4, 256), b_off = align_up((size_t)(n_tgt + 1) * 8, 256), b_st = align_up((size_t)R * 4 + 16, 256);
-    if (ctx->ws_raw.reserve((size_t)n_samples * 2 + 16) || ctx->ws_labels.reserve((size_t)R + 16) ||
-        ctx->ws_eval_model.reserve(3 * b_tab + b_off + 2 * b_st))
-        return RD_ERR_NOMEM;
+    const int64_t n_samples = hi > lo ? hi - lo : 0, R = tgt_off[n_tgt];
+    const size_t b_off = align_up((size_t)(n_tgt + 1) * 8, 256), b_st = align_up((size_t)R * 4 + 16, 256);
+    if (ctx->ws_raw.reserve((size_t)n_samples * 2 + 16) || ctx->ws_labels.reserve((size_t)R + 16)) return RD_ERR_NOMEM;
     const int16_t* d_raw = ctx->ws_raw.as<int16_t>();
     const uint8_t* d_codes = ctx->ws_labels.as<uint8_t>();
-    uint8_t* mb = ctx->ws_eval_model.as<uint8_t>();
-    const int32_t* d_lvl = (const int32_t*)mb;
-    const uint32_t* d_w = (const uint32_t*)(mb + b_tab);
-    const int32_t* d_bias = (const int32_t*)(mb + 2 * b_tab);
-    const int64_t* d_off = (const int64_t*)(mb + 3 * b_tab);
-    uint32_t* d_kid = (uint32_t*)(mb + 3 * b_tab + b_off);
-    int32_t* d_tg = (int32_t*)(mb + 3 * b_tab + b_off + b_st);
     if (n_samples) RD_HIP(hipMemcpyAsync(ctx->ws_raw.p, raw + lo, (size_t)n_samples * 2, hipMemcpyHostToDevice, st));
     if (R) RD_HIP(hipMemcpyAsync(ctx->ws_labels.p, codes, (size_t)R, hipMemcpyHostToDevice, st));
-    RD_HIP(hipMemcpyAsync((void*)d_lvl, lvl, (size_t)n_kmers * 4, hipMemcpyHostToDevice, st));
-    RD_HIP(hipMemcpyAsync((void*)d_w, w, (size_t)n_kmers * 4, hipMemcpyHostToDevice, st));
-    RD_HIP(hipMemcpyAsync((void*)d_bias, bias, (size_t)n_kmers * 4, hipMemcpyHostToDevice, st));
+    KmerTables tab;
+    if ((rc = signal_upload_tables(ctx, st, k, lvl, w, bias, b_off + 2 * b_st, &tab))) return rc;
+    const int32_t *d_lvl = tab.lvl, *d_bias = tab.bias;
+    const uint32_t* d_w = tab.w;
+    const int64_t* d_off = (const int64_t*)tab.extra;
+    uint32_t* d_kid = (uint32_t*)(tab.extra + b_off);
+    int32_t* d_tg = (int32_t*)(tab.extra + b_off + b_st);
     RD_HIP(hipMemcpyAsync((void*)d_off, tgt_off, (size_t)(n_tgt + 1) * 8, hipMemcpyHostToDevice, st));
     if (R) {
         hipLaunchKernelGGL(sm_state_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, d_off, n_tgt, d_codes, k, R, d_kid, d_tg);
         RD_HIP(hipGetLastError());
     }
     // every query's scale: a property of the query alone, whatever the budget does with it afterwards
-    std::vector<SmScaleIn> scin(n_q);
-    std::vector<int32_t> scale(2 * (size_t)n_q);
-    for (int q = 0; q < n_q; q++) {
-        const int64_t T = q_hi[q] - q_lo[q];
-        scin[q] = SmScaleIn{sc_lo[q] - lo, sc_hi[q] - sc_lo[q], (int32_t)(T > SM_MAX_T ? SM_MAX_T + 1 : T), m2_in[q], d4_in[q], 0};
-    }
-    const size_t b_sin = align_up((size_t)n_q * sizeof(SmScaleIn), 256);
-    if (ctx->ws_eval.reserve(b_sin + (size_t)n_q * 8 + 256)) return RD_ERR_NOMEM;
-    int32_t* d_scale = (int32_t*)(ctx->ws_eval.as<uint8_t>() + b_sin);
-    RD_HIP(hipMemcpyAsync(ctx->ws_eval.p, scin.data(), (size_t)n_q * sizeof(SmScaleIn), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(sm_scale_kernel, dim3(n_q), dim3(256), 0, st, (const SmScaleIn*)ctx->ws_eval.p, d_raw, d_scale);
-    RD_HIP(hipGetLastError());
-    RD_HIP(hipMemcpyAsync(scale.data(), d_scale, (size_t)n_q * 8, hipMemcpyDeviceToHost, st));
-    RD_HIP(hipStreamSynchronize(st));
+    std::vector<SignalScaleIn> scin(n_q);
+    std::vector<int32_t> scale;
+    for (int q = 0; q < n_q; q++) scin[q] = signal_scale_in(sc_lo[q] - lo, sc_hi[q] - sc_lo[q], q_hi[q] - q_lo[q], SM_MAX_T, m2_in[q], d4_in[q]);
+    if ((rc = signal_scales(ctx, st, d_raw, scin, SM_MAX_T, scale))) return rc;
     // statuses that need no alignment, then the launches: the other queries in the caller's order, as many as fit the budget; a query that
     // alone exceeds it is reported, not launched
     for (int q = 0; q < n_q; q++) {
@@ -604,7 +522,7 @@ extern "C" int rd_sigmap(rd_ctx* ctx, const int16_t* raw, int64_t n_raw, int n_q
         RD_HIP(hipMemcpyAsync(io + o_str, stripes.data(), stripes.size() * sizeof(SmStripe), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(sm_quant_kernel, dim3((unsigned)((max_T + 255) / 256), nb), dim3(256), 0, st, d_qs, d_raw, dws);
         RD_HIP(hipGetLastError());
-        hipLaunchKernelGGL(sm_dp_kernel, dim3((unsigned)stripes.size()), dim3(SM_NT), 0, st, d_qs, d_str, d_kid, d_tg, d_lvl, d_w, d_bias, dws);
+        hipLaunchKernelGGL(sm_dp_kernel, dim3((unsigned)stripes.size()), dim3(BS_NT), 0, st, d_qs, d_str, d_kid, d_tg, d_lvl, d_w, d_bias, dws);
         RD_HIP(hipGetLastError());
         hipLaunchKernelGGL(sm_select_kernel, dim3(nb), dim3(64), 0, st, d_qs, d_off, dws, n_best, d_out);
         RD_HIP(hipGetLastError());

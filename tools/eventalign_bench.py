@@ -94,7 +94,7 @@ def summarise(path, calls):
         for r in csv.DictReader(f):
             name = r.get("Name") or r.get("KernelName")
             total_ns = float(r.get("TotalDurationNs") or r.get("TotalDuration") or 0)
-            key = next((k for k in ("ea_scale_kernel", "ea_quant_kernel", "ea_dp_kernel", "ea_tb_kernel", "ea_sums_kernel", "ev_stats_kernel") if k in name), "other")
+            key = next((k for k in ("signal_scale_kernel", "ea_quant_kernel", "ea_dp_kernel", "ea_tb_kernel", "ea_sums_kernel", "ev_stats_kernel") if k in name), "other")
             g = groups.setdefault(key, [0.0, 0])
             g[0] += total_ns / calls / 1e6
             g[1] += int(r.get("Calls", 0))

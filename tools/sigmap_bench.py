@@ -24,7 +24,7 @@ from ctcalign_bench import timed   # noqa: E402  (also puts the package on the p
 
 TRANSCRIPTS, PAD, FRAGMENT, QUERY = 1000, 8, 1000, 2048
 ADAPTER, TAIL, SLACK = 30, 60, 32
-KERNELS = ("sm_state_kernel", "sm_scale_kernel", "sm_quant_kernel", "sm_dp_kernel", "sm_select_kernel")
+KERNELS = ("sm_state_kernel", "signal_scale_kernel", "sm_quant_kernel", "sm_dp_kernel", "sm_select_kernel")
 
 
 def workload(be, n_reads, seed):
