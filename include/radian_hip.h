@@ -137,6 +137,15 @@ int rd_set_decode_math(rd_ctx* ctx, int mode);
 int rd_set_head_pack(rd_ctx* ctx, int on);
 int rd_head_pack_active(rd_ctx* ctx);
 int64_t rd_head_pack_tiles(rd_ctx* ctx);
+/* Input staging of the exact-fp32 conv launches behind block 0 (128-row workgroup shape, dilation <= 32): 1 = a workgroup tile that
+ * lies wholly inside one segment (a "slab tile": 128 consecutive interior rows of a window or read, nothing redirected to the read's
+ * stream) copies the 128 + 2 dilation input rows its three taps share into LDS once per 16-channel slice (default), 0 = every tap
+ * copies its own 128 shifted rows.  Same bits: the products and their order are unchanged.  Every other tile runs the per-tap staging
+ * under either setting.  rd_conv_slab_active says whether the context's next forward will take the slab path (1 / 0: the setting, exact
+ * fp32, 128-row shape); rd_conv_slab_tiles how many slab tiles the context's latest forward launched, over all its conv launches. */
+int rd_set_conv_slab(rd_ctx* ctx, int on);
+int rd_conv_slab_active(rd_ctx* ctx);
+int64_t rd_conv_slab_tiles(rd_ctx* ctx);
 
 /* ---- the five seams, host-pointer form ----------------------------------------------------- */
 /* sig_model.predict(windows) -- radian/basecall.py:91,93.

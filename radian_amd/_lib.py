@@ -38,6 +38,9 @@ SIGNATURES = {
     "rd_set_head_pack": (c_i, [c_vp, c_i]),
     "rd_head_pack_active": (c_i, [c_vp]),
     "rd_head_pack_tiles": (c_i64, [c_vp]),
+    "rd_set_conv_slab": (c_i, [c_vp, c_i]),
+    "rd_conv_slab_active": (c_i, [c_vp]),
+    "rd_conv_slab_tiles": (c_i64, [c_vp]),
     "rd_set_decode_partition": (c_i, [c_vp, c_i]),
     "rd_forward": (c_i, [c_vp, c_vp, c_i, c_i, c_vp]),
     "rd_assemble": (c_i, [c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp, c_i64, c_i64p, ctypes.POINTER(c_i)]),

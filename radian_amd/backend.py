@@ -999,6 +999,19 @@ class Backend:
         """packed window-head workgroup tiles the context's latest forward launched (rd_head_pack_tiles)"""
         return int(self._L.rd_head_pack_tiles(self._h))
 
+    def set_conv_slab(self, on):
+        """slab tiles of the exact-fp32 conv launches behind block 0 stage their input rows once per channel slice, or every tile once per
+        tap (rd_set_conv_slab); same bits"""
+        self._check(self._L.rd_set_conv_slab(self._h, 1 if on else 0))
+
+    def conv_slab_active(self):
+        """whether the next forward takes the slab path for its slab tiles (rd_conv_slab_active): the setting, exact fp32, 128-row tiles"""
+        return bool(self._L.rd_conv_slab_active(self._h))
+
+    def conv_slab_tiles(self):
+        """slab workgroup tiles the context's latest forward launched, over all its conv launches (rd_conv_slab_tiles)"""
+        return int(self._L.rd_conv_slab_tiles(self._h))
+
     def set_decode_form(self, form):
         """'auto' (default); 'waves' / 'lanes': launch shape for widths above 12; 'two' / 'one': widths up to 12 always / never as
         two sequences per wave; 'queue': every launch through the work-queue kernel with few resident workgroups (rd_set_decode_form)."""

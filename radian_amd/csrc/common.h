@@ -115,6 +115,32 @@ struct TileDesc {
     int32_t pad_;
 };
 
+// Slab tiles (the exact-fp32 conv kernel of the product shape, layers behind block 0 of dilation <= RD_SLAB_DMAX): a
+// workgroup tile d[0..3] whose four sub-tiles are consecutive interior pieces of ONE segment and whose every conv-input and residual row
+// is the segment's own (nothing redirected to alt_row).  The three taps of such a tile read one run of 128 + 2 dil rows of the segment (or
+// the zero padding in front of it), which the kernel stages once per input-channel slice.  Everything else -- a segment's last partial
+// tile, head tiles, the mixed tile, padding -- runs the per-tap staging.  The kernel decides per tile with this test; the planner counts
+// with it (TileLists::slab).
+constexpr int RD_SLAB_DMAX = 32;
+// (sub-tile j, descriptor dj, of a tile whose sub-tile 0 is d0; without branches: the kernel evaluates it once per lane)
+__host__ __device__ inline bool rd_slab_sub(const TileDesc& d0, const TileDesc& dj, int j)
+{
+    const int64_t end = (int64_t)d0.t0 + 128;
+    return (d0.t0 >= 0) & (end <= d0.seg_len) & (end <= d0.in_len) & (dj.seg_row == d0.seg_row) & (dj.t0 == d0.t0 + 32 * j) &
+           (dj.seg_len == d0.seg_len) & (dj.in_len == d0.in_len) & (dj.alt_in >= end) & (dj.alt_res >= end);
+}
+inline bool rd_slab_tile(const TileDesc* d)
+{
+    return rd_slab_sub(d[0], d[0], 0) && rd_slab_sub(d[0], d[1], 1) && rd_slab_sub(d[0], d[2], 2) && rd_slab_sub(d[0], d[3], 3);
+}
+// workgroup tiles [0, n_tiles) of a host copy of a tile list that are slab tiles
+inline int rd_count_slab_tiles(const TileDesc* list, size_t n_tiles)
+{
+    int n = 0;
+    for (size_t i = 0; i < n_tiles; i++) n += rd_slab_tile(list + 4 * i) ? 1 : 0;
+    return n;
+}
+
 // per-layer tile lists: index 0 = block-0 first conv (C_in = 1); 2b = first conv of block b >= 1; 2b+1 = second conv of
 // block b; 2*nblocks = dense head.  Uniform windows and streams use one list for every layer.
 constexpr int RD_MAX_LAYERS = 2 * 16 + 1;
@@ -143,6 +169,9 @@ struct TileLists {
     // packed heads (plan_fill_packed; plan_fill_lists leaves them off)
     const TileDesc* head_segs[RD_MAX_LAYERS];
     PackLayer pack[RD_MAX_LAYERS];
+    // slab tiles (rd_slab_tile) of the whole list, and of the stream prefix a packed launch runs (without its mixed tile)
+    int slab[RD_MAX_LAYERS];
+    int slab_stream[RD_MAX_LAYERS];
 };
 
 struct KernelTimer {
@@ -175,6 +204,8 @@ struct rd_ctx {
     int conv_fuse = 1;   // rd_set_conv_fuse: 1 = block 0's first conv is computed inside its second (forward.hip, FIN), 0 = its own kernel
     int64_t packed_tiles = 0;   // packed window-head workgroup tiles the latest forward launched (rd_head_pack_tiles)
     int head_pack = 1;   // rd_set_head_pack: 1 = chunk-mode window heads run as packed classes that skip the zero-padding taps (exact fp32 only), 0 = as head tiles
+    int conv_slab = 1;   // rd_set_conv_slab: 1 = slab tiles (rd_slab_tile) stage their input rows once per channel slice (exact fp32, product shape), 0 = per tap
+    int64_t slab_tiles = 0;     // slab workgroup tiles the latest forward launched (rd_conv_slab_tiles)
     int conv_shape = 0;  // rd_set_conv_shape: 0 = 128-row tiles, two 256-thread workgroups per CU; 1 = 256-row tiles, one 512-thread workgroup
     int logits_f16 = 0;  // 1: the reads-level paths keep the softmax rows as f16 in HBM (10 B per time step), the decoder widens them
     hipStream_t stream = nullptr;
@@ -186,6 +217,7 @@ struct rd_ctx {
     // workspaces
     DevBuf ws_tiles, ws_raw;
     int tiles_nW = -1, tiles_T = -1;   // shape the cached uniform tile descriptors were built for
+    int tiles_slab = 0;                // slab tiles among them
     // lanes[0].st == stream; lanes >= 1 are created on first use.  Lanes [RD_MAX_LANES, 2 RD_MAX_LANES) are the PARTITIONED
     // twins of lanes [0, RD_MAX_LANES): their streams are CU-masked to everything but the decode partition (below)
     FwdLane lanes[2 * RD_MAX_LANES];
@@ -240,6 +272,7 @@ void rd_lm_bind(LM& lm);   // the pointers of lm into lm.storage, by lm.table_or
 int rd_lm_finish_device(rd_ctx* ctx, int table_order, int context_len, int hashed);
 // forward.hip
 bool rd_pack_heads(const rd_ctx* ctx);   // the context runs chunk-mode window heads as packed classes (rd_set_head_pack, exact fp32, product shape, Model::pack_ok)
+bool rd_conv_slab(const rd_ctx* ctx);    // the context's exact-fp32 conv launches behind block 0 take the slab path for their slab tiles (rd_set_conv_slab, exact fp32, product shape)
 int rd_forward_dev(rd_ctx* ctx, const float* d_windows, int nW, int T, float* d_probs, int lane = 0);
 int rd_forward_tiles_dev(rd_ctx* ctx, const float* d_signal, const TileLists& tiles, int64_t total_rows, void* d_probs, int lane = 0,
                          int probs_f16 = 0 /* 1: d_probs is _Float16 [rows][5] */);

@@ -271,6 +271,22 @@ extern "C" int rd_head_pack_active(rd_ctx* ctx)
 
 extern "C" int64_t rd_head_pack_tiles(rd_ctx* ctx) { return ctx ? ctx->packed_tiles : 0; }
 
+extern "C" int rd_set_conv_slab(rd_ctx* ctx, int on)
+{
+    RD_REQUIRE(ctx, "rd_set_conv_slab: null context");
+    RD_REQUIRE(on == 0 || on == 1, "rd_set_conv_slab: %d (1 = slab tiles stage their input rows once per channel slice, 0 = once per tap)", on);
+    ctx->conv_slab = on;
+    return RD_OK;
+}
+
+extern "C" int rd_conv_slab_active(rd_ctx* ctx)
+{
+    if (!ctx) return 0;
+    return rd_conv_slab(ctx) ? 1 : 0;
+}
+
+extern "C" int64_t rd_conv_slab_tiles(rd_ctx* ctx) { return ctx ? ctx->slab_tiles : 0; }
+
 extern "C" int rd_set_decode_partition(rd_ctx* ctx, int cus_per_xcd)
 {
     RD_REQUIRE(ctx, "rd_set_decode_partition: null context");

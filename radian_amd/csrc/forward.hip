@@ -22,6 +22,8 @@
 // with XOR-swizzled 16-B slots (conflict-free ds_read_b128).  Three 24-KiB stages, one barrier per chunk, the DMA of
 // chunk c+2 issued piecewise between the MFMAs of chunk c and counted by hand (uncounted inline-asm loads + an explicit
 // s_waitcnt vmcnt(N): with the builtin hipcc drains vmcnt(0) before the next ds_read).  Two workgroups per CU.
+// A tile that lies wholly inside one segment (a slab tile) stages the 128 + 2 dil rows its three taps share once per 16-channel slice
+// instead (tcn_gemm_tile, SLAB): two 12-KiB row regions behind three 16-KiB weight stages.
 // Each wave holds a 64 x 128 accumulator (8 MFMA tiles = 128 VGPRs).  One ds_read_b128 feeds four MFMAs: lane (r, h)
 // reads k = 8g+4h .. 8g+4h+3 of its row, and MFMA number kr of the group consumes element kr of both operands, i.e.
 // k-pair (8g+kr, 8g+4+kr).  Bias, ReLU, the residual add (identity or block-0 1x1 match) and the second ReLU are fused
@@ -89,6 +91,7 @@ struct ConvArgs {
     PackClass cls[3];
     int n_heads;
     int n_stream;
+    int slab;                // 1: the tiles that rd_slab_tile (common.h) accepts stage their A rows once per slice (tcn_gemm_tile, SLAB)
 };
 
 // block 0, first conv, one output: relu(b + w0 x[t - 2d] + w1 x[t - d] + w2 x[t]) as ONE fma chain in this order -- written out so that
@@ -254,22 +257,32 @@ template <int NT, int TAPS, int EPI, int WM, bool FIN> constexpr int conv_smem_f
 // One workgroup tile of tcn_gemm_kernel.  PACKED: a tile of packed window-head rows of class TAP_LO (ConvArgs; PackLayer, common.h) --
 // the A rows and the epilogue's rows come from (class header, head_segs) per row instead of four sub-tile descriptors, and the K loop
 // runs the taps from TAP_LO on.  The class is a template parameter so that the tap of every chunk stays a literal, as on the stream path.
-template <int NT, int TAPS, int EPI, int WM, bool FIN, bool PACKED, int TAP_LO = 0>
+//
+// SLAB: a slab tile (rd_slab_tile, common.h: four consecutive interior sub-tiles of one segment, every A row the segment's own, dil <=
+// RD_SLAB_DMAX).  The three taps of a 16-channel slice read the same 128 + 2 dil input rows, shifted by one dilation: instead of three
+// 128-row A tiles per slice the tile stages ONE region of those rows per slice -- region row r = time step t0 - 2 dil + r, two regions of
+// SLAB_ROWS rows in ping-pong behind three weight-only stages (3 x 16 KiB + 2 x 12 KiB: the same 72 KiB) -- and tap k's fragment is the
+// stream path's ds_read at region row r + k dil, with the 16-B slot key of the row actually read (as FIN reads its regions).  Chunk order,
+// and so every accumulator's sequence of products, is the stream path's: same bits.
+template <int NT, int TAPS, int EPI, int WM, bool FIN, bool PACKED, int TAP_LO = 0, bool SLAB = false>
 __device__ __forceinline__ void tcn_gemm_tile(const ConvArgs& a, float* const smem)
 {
+    static_assert(!SLAB || (NT == 4 && TAPS == 3 && (EPI == EPI_RELU || EPI == EPI_RES_IDENT) && WM == 2 && !FIN && !PACKED), "SLAB: the product shape's conv launches behind block 0");
     static_assert(!FIN || (EPI == EPI_RES_MATCH && WM == 2 && TAPS == 3 && NT == 4), "FIN: block 0's second conv, product shape");
     static_assert(!PACKED || (NT == 4 && TAPS == 3 && (EPI == EPI_RELU || EPI == EPI_RES_IDENT) && WM == 2 && !FIN), "PACKED: the product shape's conv launches behind block 0");
     constexpr int BM = 64 * WM;           // time steps per workgroup tile (shadows the file-scope 128)
     constexpr int NWAVE = 2 * WM;
     constexpr int BN = 2 * NT * 32;       // output channels per workgroup (2 waves along N)
     constexpr int NCHUNK = TAPS * (RD_C / BK);
-    constexpr int A_FLOATS = FIN ? 0 : BM * BK;    // FIN: no A part in the DMA stages
+    constexpr int A_FLOATS = (FIN || SLAB) ? 0 : BM * BK;    // FIN, SLAB: no A part in the DMA stages
     constexpr int STAGE_FLOATS = A_FLOATS + BN * BK;   // one K-chunk of A and B
+    constexpr int SLAB_ROWS = BM + 2 * RD_SLAB_DMAX;   // rows of a slab region: twelve 16-row DMA pieces
+    static_assert(!SLAB || 3 * STAGE_FLOATS + 2 * SLAB_ROWS * BK <= conv_smem_floats<NT, TAPS, EPI, WM, FIN>(), "SLAB: three weight stages and two regions fit the kernel's LDS block");
     constexpr int HEAD_FLOATS = BM * (RD_H + 1) + RD_H * 5 + 8 + BM * 5;
     constexpr int NSTAGE = 3;
     constexpr int MIDROWS = 4 * (32 + 2 * FIN_DMAX);                      // rows of a slice's A region
     constexpr int FIN_FLOATS = FIN ? 2 * MIDROWS * BK + 4 * RD_C : 0;     // two regions + the first conv's [w0 | w1 | w2 | b] x 256
-    static_assert(conv_smem_floats<NT, TAPS, EPI, WM, FIN>() == ((EPI == EPI_HEAD && HEAD_FLOATS > NSTAGE * STAGE_FLOATS) ? HEAD_FLOATS : NSTAGE * STAGE_FLOATS + FIN_FLOATS),
+    static_assert(SLAB || conv_smem_floats<NT, TAPS, EPI, WM, FIN>() == ((EPI == EPI_HEAD && HEAD_FLOATS > NSTAGE * STAGE_FLOATS) ? HEAD_FLOATS : NSTAGE * STAGE_FLOATS + FIN_FLOATS),
                   "the kernel's LDS block");
 
     if constexpr (FIN) clear_zero_rows(a.zr);   // (this kernel is then the forward's first)
@@ -296,8 +309,15 @@ __device__ __forceinline__ void tcn_gemm_tile(const ConvArgs& a, float* const sm
         pk_p0 = (unsigned)((int)blockIdx.x - pkc.first_tile) * BM;
         pk_rows = (unsigned)a.n_heads * (unsigned)pkc.L;
     }
-    const bool mval[2] = {PACKED ? pk_p0 + wm * 64 < pk_rows : sdm[0].seg_len > sdm[0].t0,
-                          PACKED ? pk_p0 + wm * 64 + 32 < pk_rows : sdm[1].seg_len > sdm[1].t0};
+    const bool mval[2] = {SLAB || (PACKED ? pk_p0 + wm * 64 < pk_rows : sdm[0].seg_len > sdm[0].t0),
+                          SLAB || (PACKED ? pk_p0 + wm * 64 + 32 < pk_rows : sdm[1].seg_len > sdm[1].t0)};
+    // SLAB: one segment, 128 interior rows from s_t0 on -- all the path needs of the descriptors (rows are indexed with 32 bits), kept in
+    // scalar registers over the K loop
+    int s_seg = 0, s_t0 = 0;
+    if constexpr (SLAB) {
+        s_seg = __builtin_amdgcn_readfirstlane((int)tds[0].seg_row);
+        s_t0 = __builtin_amdgcn_readfirstlane(tds[0].t0);
+    }
 
     // DMA roles, fixed for the whole tile: a wave-instruction moves 16 rows x 64 B; lane -> (row-in-piece, physical
     // 16-B slot).  Wave w stages sub-tile w (two pieces), so the descriptor fields it needs are wave-uniform scalars.
@@ -312,7 +332,19 @@ __device__ __forceinline__ void tcn_gemm_tile(const ConvArgs& a, float* const sm
     // zero row where the time step lies before the segment (causal padding) or in an empty sub-tile.  Per chunk the
     // address is then one multiply-add on a per-chunk base.
     int arow[TAPS][2];
-    if constexpr (!PACKED) {
+    // SLAB: this lane's source row of the wave's region pieces wave, 4 + wave, 8 + wave (16 region rows each; the same for every slice).
+    // Rows before the segment are causal padding, rows from region row BM + 2 dil on round the region up to whole pieces: the zero row.
+    // slab_p2: the wave has a third piece, i.e. the region's 128 + 2 dil rows reach into piece 8 + wave.
+    int srow[3] = {0, 0, 0};
+    const bool slab_p2 = SLAB && (8 + wave) * 16 < BM + 2 * a.dil;
+    if constexpr (SLAB) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            const int r = (4 * j + wave) * 16 + dma_r;
+            const int t = s_t0 - 2 * a.dil + r;
+            srow[j] = (t >= 0 && r < BM + 2 * a.dil) ? s_seg + t : a.zero_row;
+        }
+    } else if constexpr (!PACKED) {
 #pragma unroll
         for (int tap = 0; tap < TAPS; tap++)
 #pragma unroll
@@ -346,7 +378,7 @@ __device__ __forceinline__ void tcn_gemm_tile(const ConvArgs& a, float* const sm
     // one piece (wave-instruction) of a chunk's staging: pieces 0,1 = this wave's two 16-row pieces of A, 2.. = its
     // BN/64 consecutive 1-KiB pieces of B.  `tap` is the chunk's tap (a literal at every call site).
     constexpr int PB = BN / (16 * NWAVE);   // 1-KiB pieces (16 rows) of B per wave
-    constexpr int NA = FIN ? 0 : 2;         // A pieces per wave (FIN: the A tiles are computed, not loaded)
+    constexpr int NA = (FIN || SLAB) ? 0 : 2;   // A pieces per wave and chunk (FIN: the A tiles are computed, not loaded; SLAB: slab_piece)
     constexpr int NPIECE = NA + PB;
     // (chunk = the weight chunk, cc = its input-channel slice, ar = this lane's A row of piece pc)
     auto stage_piece_at = [&](int chunk, int cc, int ar, float* st, int pc) {
@@ -372,6 +404,13 @@ __device__ __forceinline__ void tcn_gemm_tile(const ConvArgs& a, float* const sm
     auto stage_piece_all = [&](int chunk, int cc, int tap, float* st) {   // (PACKED: weight chunk `chunk` of slice cc, tap `tap`)
 #pragma unroll
         for (int pc = 0; pc < NPIECE; pc++) stage_piece_at(chunk, cc, arow[tap][pc & 1], st, pc);
+    };
+    // SLAB: piece 4 j + wave of slice cc's region (region reg = cc & 1, a literal at every call site), one 16-row wave-instruction like
+    // the A pieces of a chunk
+    float* const slabb = smem + NSTAGE * STAGE_FLOATS;         // [2][SLAB_ROWS][16]
+    auto slab_piece = [&](int cc, int reg, int j) {
+        const char* src = lanebase + (size_t)cc * (BK * 4) + (uint64_t)(unsigned)srow[j] * (RD_C * 4);
+        glds16_uncounted((const float*)src, slabb + reg * (SLAB_ROWS * BK) + (4 * j + wave) * 256);
     };
 
     // ---- FIN: the A tiles computed from the raw samples.  Wave w computes sub-tile w's region rows i = 0 .. 31 + 2 dil (time step
@@ -446,7 +485,18 @@ __device__ __forceinline__ void tcn_gemm_tile(const ConvArgs& a, float* const sm
     // DMA pieces go out one by one between groups of 2 x NT MFMAs, so their address arithmetic issues in the shadow of
     // the matrix pipe instead of in front of it; the second k-group's fragments are requested after the first group of
     // MFMAs (their LDS latency sits under the other 3 groups).  sched_barrier pins that order.
-    const bool work = mval[0] || mval[1];   // (tiles are packed, so a wave with work almost always has both sub-tiles)
+    const bool work = SLAB || mval[0] || mval[1];   // (tiles are packed, so a wave with work almost always has both sub-tiles)
+    // SLAB: this lane's fragment offsets in a slice region, per tap and k-group: region row rr = wm 64 + fr + tap dil for sub-tile 0 (sub-tile
+    // 1 is 32 rows on: the same slot key), 16-B slot (2 g + fh) ^ key(rr).  A dilation that is no multiple of 16 gives every tap its own key.
+    int soff[3][BK / 8] = {{0, 0}, {0, 0}, {0, 0}};
+    if constexpr (SLAB) {
+#pragma unroll
+        for (int tap = 0; tap < 3; tap++) {
+            const int rr = wm * 64 + fr + tap * a.dil;
+#pragma unroll
+            for (int g = 0; g < BK / 8; g++) soff[tap][g] = rr * BK + (((2 * g + fh) ^ ((rr >> 2) & 3)) * 4);
+        }
+    }
     // FIN: this lane's fragment rows in a slice region, per tap and sub-tile: region row = (sub-tile) * RS + fr + tap * dil
     int frow[3][2] = {{0, 0}, {0, 0}, {0, 0}}, fswz[3][2] = {{0, 0}, {0, 0}, {0, 0}};
     if constexpr (FIN) {
@@ -461,7 +511,10 @@ __device__ __forceinline__ void tcn_gemm_tile(const ConvArgs& a, float* const sm
     }
     // (cur = this chunk's index, cur_tap = its tap: literals at every call site)
     // (st_ok: a chunk follows two chunks on -- weight chunk next of slice next_cc, this lane's A rows next_ar0 / next_ar1 -- and is staged into nst)
-    auto chunk_step = [&](const float* st, int cur, int cur_tap, const bool st_ok, int next, int next_cc, int next_ar0, int next_ar1, float* nst) {
+    // (SLAB: st / nst are weight-only stages; Rb = the region of this chunk's slice; a_ok: this wave stages piece next_ar0 of slice next_cc's
+    //  region, region next_ar1, during this chunk, in front of the weight pieces of chunk `next`)
+    auto chunk_step = [&](const float* st, int cur, int cur_tap, const bool st_ok, int next, int next_cc, int next_ar0, int next_ar1, float* nst,
+                          const float* Rb = nullptr, const bool a_ok = false) {
         // MFMA order: k-group g, then N tile n, then (kr, m): 8 MFMAs per (g, n) step on two accumulators.  A step needs
         // the A fragments of its k-group (8 registers) and ONE B fragment (4): the next step's B fragment and, during the
         // last step of a group, the next group's A fragments are requested before the step's MFMAs, so 24 fragment
@@ -476,6 +529,7 @@ __device__ __forceinline__ void tcn_gemm_tile(const ConvArgs& a, float* const sm
 #pragma unroll
             for (int m = 0; m < 2; m++) {
                 if constexpr (FIN) af[g & 1][m] = *(const float4*)(Mb + frow[cur_tap][m] + (((2 * g + fh) ^ fswz[cur_tap][m]) * 4));
+                else if constexpr (SLAB) af[g & 1][m] = *(const float4*)(Rb + m * 32 * BK + soff[cur_tap][g]);
                 else af[g & 1][m] = *(const float4*)(Ab + m * 32 * BK + koff[g]);
             }
         };
@@ -505,7 +559,12 @@ __device__ __forceinline__ void tcn_gemm_tile(const ConvArgs& a, float* const sm
                 __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (st_ok && sidx < NPIECE) stage_piece_at(next, next_cc, sidx == 0 ? next_ar0 : next_ar1, nst, sidx);
+            if constexpr (SLAB) {
+                // the region piece first: it is then older than the chunk's weight pieces, which is what the wait table counts on
+                if (sidx == 0) {
+                    if (a_ok) slab_piece(next_cc, next_ar1, next_ar0);
+                } else if (st_ok && sidx <= NPIECE) stage_piece_at(next, 0, 0, nst, sidx - 1);
+            } else if (st_ok && sidx < NPIECE) stage_piece_at(next, next_cc, sidx == 0 ? next_ar0 : next_ar1, nst, sidx);
             if constexpr (FIN) {
                 // pass cur_tap of the NEXT slice's region, behind the weight pieces: its ~20 vector instructions issue in the shadow
                 // of the matrix pipe like the DMA's address arithmetic (the region it writes was last read two slices ago)
@@ -518,7 +577,20 @@ __device__ __forceinline__ void tcn_gemm_tile(const ConvArgs& a, float* const sm
     // Three stages of one K-chunk each, one barrier per chunk: while chunk c is multiplied, chunk c+1 is landing and chunk
     // c+2 is issued, so a row that comes from HBM has two chunk times; the wait at the top of a chunk leaves the newest
     // chunk's NPIECE instructions in flight.  (Two workgroups per CU: 2 x 72 KiB of LDS, 2 waves per SIMD.)
-    static_assert(NPIECE <= (BK / 8) * NT, "one DMA piece per MFMA step");
+    //
+    // SLAB: the same three stages hold weights only, and a wave's DMA instructions of the three chunks of slice s are
+    //     chunk 3s   (tap 0):  A piece wave     of slice s+1,  then the 4 weight pieces of chunk 3s+2        = 5
+    //     chunk 3s+1 (tap 1):  A piece 4 + wave of slice s+1,  then the 4 weight pieces of chunk 3s+3        = 5
+    //     chunk 3s+2 (tap 2): [A piece 8 + wave of slice s+1], then the 4 weight pieces of chunk 3s+4        = 4 or 5
+    // (the prologue: slice 0's two or three A pieces, then the weights of chunks 0 and 1).  The bracketed piece exists only for the waves
+    // whose third piece holds region rows (slab_p2).  A chunk needs its weights, issued two chunks earlier, and tap 0 also its slice's
+    // region, whose last piece went out in front of the weights issued one chunk earlier.  So the wait at the top of a chunk leaves
+    //     tap 0: 4   (the weights behind the optional piece: the same count with or without it)
+    //     tap 1: 5   (the last slice: 4 -- there is no slice 16 to stage)
+    //     tap 2: 5   (the last slice: 0 -- nothing was issued during chunk 46)
+    // instructions in flight.  The optional piece is counted by no wait: every wait that follows it leaves only weight pieces.
+    // The region written during slice s was last read in slice s-1, which every wave has left at the barrier of chunk 3s.
+    static_assert(NPIECE + (SLAB ? 1 : 0) <= (BK / 8) * NT, "one DMA piece per MFMA step");
     float* st0 = smem;
     float* st1 = smem + STAGE_FLOATS;
     float* st2 = smem + 2 * STAGE_FLOATS;
@@ -537,7 +609,31 @@ __device__ __forceinline__ void tcn_gemm_tile(const ConvArgs& a, float* const sm
             if (chunk + 2 < NCHUNK) step(chunk + 2, T3 ? 2 : 0, st2, T3 ? 1 : 0, st1);
         }
     };
-    if constexpr (PACKED) {
+    if constexpr (SLAB) {
+        constexpr int NSL = RD_C / BK;
+        static_assert(NSL % 2 == 0, "the slab loop advances by the two regions");
+        slab_piece(0, 0, 0);
+        slab_piece(0, 0, 1);
+        if (slab_p2) slab_piece(0, 0, 2);
+#pragma unroll
+        for (int pc = 0; pc < NPIECE; pc++) stage_piece_at(0, 0, 0, st0, pc);
+#pragma unroll
+        for (int pc = 0; pc < NPIECE; pc++) stage_piece_at(1, 0, 0, st1, pc);
+        for (int s2 = 0; s2 < NSL; s2 += 2) {
+#pragma unroll
+            for (int h = 0; h < 2; h++) {   // (region s & 1 = h: a literal)
+                const int s = s2 + h;
+                const bool more = s + 1 < NSL;
+                const float* Rb = slabb + h * (SLAB_ROWS * BK);
+                wait_dma_and_barrier<NPIECE>();
+                chunk_step(st0, 0, 0, true, 3 * s + 2, s + 1, 0, 1 - h, st2, Rb, more);
+                if (more) wait_dma_and_barrier<NPIECE + 1>(); else wait_dma_and_barrier<NPIECE>();
+                chunk_step(st1, 0, 1, more, 3 * s + 3, s + 1, 1, 1 - h, st0, Rb, more);
+                if (more) wait_dma_and_barrier<NPIECE + 1>(); else wait_dma_and_barrier<0>();
+                chunk_step(st2, 0, 2, more, 3 * s + 4, s + 1, 2, 1 - h, st1, Rb, more && slab_p2);
+            }
+        }
+    } else if constexpr (PACKED) {
         // A packed tile's K loop runs the class's live taps only: NCH = 16 (3 - TAP_LO) chunks, chunk i = slice i / NTP, tap TAP_LO + i % NTP,
         // i.e. the surviving chunks of the full loop in its order (weight chunk slice * 3 + tap).  Staging, counting and the stage rotation
         // are the full loop's; the loop advances by a common period of the three stages and the class's taps, so tap and stage are literals.
@@ -643,23 +739,27 @@ __device__ __forceinline__ void tcn_gemm_tile(const ConvArgs& a, float* const sm
 #pragma unroll
         for (int m = 0; m < 2; m++) {
             if (!mval[m]) continue;
-            const TileDesc sd = sdm[m];
+            TileDesc sd = sdm[m];
+            if constexpr (SLAB) {   // (the fast path below uses no other field)
+                sd.seg_row = s_seg;
+                sd.t0 = s_t0 + (wm * 2 + m) * 32;
+            }
             const int T = sd.seg_len;
             float* __restrict__ outw = a.out + (size_t)sd.seg_row * RD_C;
             const float* __restrict__ resw = a.resid + (size_t)sd.seg_row * RD_C;      // block input (separate tensor)
             const float* __restrict__ resalt = a.resid + (size_t)sd.alt_row * RD_C;
-            const bool interior = sd.t0 + 32 <= T;
+            const bool interior = SLAB || sd.t0 + 32 <= T;   // (SLAB: every sub-tile of a slab tile is a fast-path sub-tile, rd_slab_tile)
             // Fast path (every stream tile but a segment's last): the 32 rows are all inside the segment and on one side of the
             // residual switch, so every address is a wave-uniform base + one per-lane offset -- no per-row selects or 64-bit
             // vector adds.  That matters more than it looks: beside the CU partner's MFMA stream a vector instruction of this
             // wave issues about once per MFMA (tools/probe/mfma_valu_probe.hip), so the epilogue's length IS its vector
             // instruction count.  The block input added here is a previous block's output, i.e. already ReLU'd (>= +0): the sum
             // with ReLU(acc) cannot be negative and the second ReLU of keras-tcn's block is the identity on it -- dropped.
-            const bool res_one = EPI != EPI_RES_IDENT || sd.t0 + 32 <= sd.alt_res || sd.t0 >= sd.alt_res;
+            const bool res_one = SLAB || EPI != EPI_RES_IDENT || sd.t0 + 32 <= sd.alt_res || sd.t0 >= sd.alt_res;
             if (EPI != EPI_RES_MATCH && interior && res_one) {
                 const unsigned lbyte = (rrow * RD_C + c4) * 4;
                 float* __restrict__ ob = outw + (size_t)sd.t0 * RD_C + wn * (NT * 32);
-                const float* __restrict__ rb = (sd.t0 < sd.alt_res ? resw : resalt) + (size_t)sd.t0 * RD_C + wn * (NT * 32);
+                const float* __restrict__ rb = ((SLAB || sd.t0 < sd.alt_res) ? resw : resalt) + (size_t)sd.t0 * RD_C + wn * (NT * 32);
 #pragma unroll
                 for (int np = 0; np < NT / 2; np++) {
                     to_patch(m, np);
@@ -771,6 +871,16 @@ __device__ __forceinline__ void tcn_gemm_workgroup(const ConvArgs& a, float* con
             else tcn_gemm_tile<NT, TAPS, EPI, WM, FIN, true, 0>(a, smem);
             return;
         }
+        // a slab tile stages its input rows once per slice (the mixed tile's descriptors never qualify: its head sub-tiles are empty).
+        // Lane l tests sub-tile l & 3 against sub-tile 0, so the wave's test is one round of loads and a vote.
+        if (a.slab) {
+            const TileDesc* __restrict__ tds = (a.mixed && bx == a.n_stream - 1) ? a.mixed : a.tiles + (size_t)bx * 4;
+            const int j = (int)threadIdx.x & 3;
+            if (__all(rd_slab_sub(tds[0], tds[j], j))) {
+                tcn_gemm_tile<NT, TAPS, EPI, WM, FIN, false, 0, true>(a, smem);
+                return;
+            }
+        }
     }
     tcn_gemm_tile<NT, TAPS, EPI, WM, FIN, false>(a, smem);
 }
@@ -780,7 +890,7 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void tcn_gemm_kernel(Con
     __shared__ __attribute__((aligned(1024))) float smem[conv_smem_floats<NT, TAPS, EPI, WM, FIN>()];
     tcn_gemm_workgroup<NT, TAPS, EPI, WM, FIN>(a, smem);
 }
-// The two launches with packed tiles hold four tile paths (stream + three classes).  Each path alone stays within the stream path's
+// The two launches with packed tiles hold five tile paths (stream, slab + three classes).  Each path alone stays within the stream path's
 // register count, but allocated together they came out at 183 / 220 vector registers: bound to the stream path's allocation (176 /
 // 208), which is what leaves room for a beam-search wave beside two of these waves on a SIMD (chunk_step).  (The attribute takes a
 // literal only, hence the two specialisations.)
@@ -1576,10 +1686,11 @@ bool fuse_first_conv(const rd_ctx* ctx)
            ctx->model.dil[0] <= FIN_DMAX;
 }
 
-// (pk / head_segs: the layer's packed heads, null where the plan has none for it)
+// (pk / head_segs: the layer's packed heads, null where the plan has none for it; slab_list / slab_stream: slab tiles of the whole list / of
+// the stream prefix a packed launch runs, TileLists)
 int launch_layer(rd_ctx* ctx, hipStream_t st, int b, int kind /*0 in, 1 conv0, 2 conv1, 3 head*/, const TileDesc* tiles, int n,
                 double rows, int zero_row, const float* d_signal, float* Xin, float* Xout, float* MID, float* d_probs, int probs_f16,
-                const PackLayer* pk, const TileDesc* head_segs)
+                const PackLayer* pk, const TileDesc* head_segs, int slab_list, int slab_stream)
 {
     if (n <= 0) return RD_OK;
     Model& m = ctx->model;
@@ -1707,6 +1818,11 @@ int launch_layer(rd_ctx* ctx, hipStream_t st, int b, int kind /*0 in, 1 conv0, 2
         a.n_stream = pk->n_stream_tiles;
         n = pk->n_tiles;
         ctx->packed_tiles += pk->n_tiles - pk->n_stream_tiles;
+        slab_list = slab_stream;
+    }
+    if (b > 0 && a.dil <= RD_SLAB_DMAX && rd_conv_slab(ctx)) {   // (the two launches whose kernel has the slab path; it finds its slab tiles itself)
+        a.slab = 1;
+        ctx->slab_tiles += slab_list;
     }
     SplitArgs sa = {};
     sa.zero_row = zero_row;
@@ -1761,6 +1877,8 @@ int launch_layer(rd_ctx* ctx, hipStream_t st, int b, int kind /*0 in, 1 conv0, 2
 }
 
 }  // namespace
+
+bool rd_conv_slab(const rd_ctx* ctx) { return ctx->conv_slab && ctx->precision == 0 && ctx->conv_shape == 0; }
 
 bool rd_pack_heads(const rd_ctx* ctx)
 {
@@ -1895,11 +2013,12 @@ int rd_forward_tiles_dev(rd_ctx* ctx, const float* d_signal, const TileLists& tl
     // (the three tensors' zero rows are cleared by the forward's first kernel: clear_zero_rows)
     const int nl = 2 * m.nblocks + 1;
     ctx->packed_tiles = 0;
+    ctx->slab_tiles = 0;
     for (int li = 0; li < nl; li++) {
         const int b = li == nl - 1 ? m.nblocks : li / 2;
         const int kind = li == nl - 1 ? 3 : (li == 0 ? 0 : (li & 1 ? 2 : 1));
         if ((rc = launch_layer(ctx, L->st, b, kind, tl.d[li], tl.n[li], (double)tl.rows[li], zero_row, d_signal, Xin, Xout, MID, (float*)d_probs, probs_f16,
-                               &tl.pack[li], tl.head_segs[li])))
+                               &tl.pack[li], tl.head_segs[li], tl.slab[li], tl.slab_stream[li])))
             return rc;
         if (kind == 2) {   // block finished: its output becomes the next block's input
             float* t = Xin;
@@ -1939,6 +2058,7 @@ int rd_uniform_tiles(rd_ctx* ctx, int nW, int T, TileLists* out)
         RD_HIP(hipMemcpy(ctx->ws_tiles.p, h.data(), h.size() * sizeof(TileDesc), hipMemcpyHostToDevice));
         ctx->tiles_nW = nW;
         ctx->tiles_T = T;
+        ctx->tiles_slab = rd_count_slab_tiles(h.data(), n);
     }
     const int nl = 2 * ctx->model.nblocks + 1;
     for (int li = 0; li < RD_MAX_LAYERS; li++) {
@@ -1947,6 +2067,8 @@ int rd_uniform_tiles(rd_ctx* ctx, int nW, int T, TileLists* out)
         out->rows[li] = li < nl ? (int64_t)nW * T : 0;
         out->head_segs[li] = nullptr;
         out->pack[li] = PackLayer();
+        out->slab[li] = li < nl ? ctx->tiles_slab : 0;
+        out->slab_stream[li] = 0;
     }
     return RD_OK;
 }

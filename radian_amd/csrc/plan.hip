@@ -253,6 +253,7 @@ size_t plan_fill_lists(const ReadsPlan& P, const TileDesc* d_base, TileDesc* h_d
         lists.rows[li] = 0;
         lists.head_segs[li] = nullptr;
         lists.pack[li] = PackLayer();
+        lists.slab[li] = lists.slab_stream[li] = 0;
     }
     for (int li = 0; li < P.n_layers; li++) {
         if (P.per_layer || li == 0) {
@@ -261,11 +262,13 @@ size_t plan_fill_lists(const ReadsPlan& P, const TileDesc* d_base, TileDesc* h_d
             lists.d[li] = d_base + off;
             lists.n[li] = (int)(v.size() / 4);
             lists.rows[li] = P.rows[li];
+            lists.slab[li] = rd_count_slab_tiles(v.data(), v.size() / 4);
             off += v.size();
         } else {
             lists.d[li] = lists.d[0];
             lists.n[li] = lists.n[0];
             lists.rows[li] = lists.rows[0];
+            lists.slab[li] = lists.slab[0];
         }
     }
     return off;
@@ -285,10 +288,12 @@ size_t plan_fill_packed(const ReadsPlan& P, const TileDesc* d_base, TileDesc* h_
         const std::vector<TileDesc>& v = P.head_segs[li];
         lists.head_segs[li] = nullptr;
         lists.pack[li] = PackLayer();
+        lists.slab_stream[li] = 0;
         if (v.empty() || P.pack[li].n_tiles == 0) continue;
         memcpy(h_dst + off, v.data(), v.size() * sizeof(TileDesc));
         lists.head_segs[li] = d_base + off;
         lists.pack[li] = P.pack[li];
+        lists.slab_stream[li] = rd_count_slab_tiles(P.tiles[li].data(), (size_t)(P.pack[li].n_stream_tiles - P.pack[li].mixed));
         off += v.size();
     }
     return off;
