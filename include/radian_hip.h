@@ -598,6 +598,45 @@ int64_t rd_site_workspace_bytes(int64_t n_events);
 int rd_site_diag_segments(rd_ctx* ctx, const uint32_t* site, const uint8_t* cond, const int16_t* value, int64_t n_events, uint32_t n_sites,
                           int64_t capacity, uint64_t* sorted_keys, int64_t* segments, int64_t* n_segments);
 
+/* ---- exact two-cluster split of a site's pooled values (sitecmp.hip, csrc/site_rules.h) ----------------------
+ * NO reference behaviour.  The hard-assignment limit of a two-component mixture in one dimension: the threshold on the pooled values of a
+ * site that splits them into the two clusters of least within-cluster variance.  Integer arithmetic only; met exactly.  Inputs, output
+ * order and capacity as rd_site_compare; one channel per call; n, sum, sumsq, n_lo, sum_lo and sumsq_lo hold two values per entry,
+ * [entry][cond].  With a / b the values of sample 0 / 1 of the site, n0, n1 their counts and N = n0 + n1:
+ *   a CUT c is a value present in either sample other than the pooled maximum; its low cluster is the events with value <= c (pooled
+ *   count n_lo, sum S_lo), its high cluster the rest (n_hi, S_hi).  It is ADMISSIBLE iff n_lo >= 1, n_hi >= 1, 65536 n_lo >= min_frac_q16 N
+ *   and 65536 n_hi >= min_frac_q16 N (min_frac_q16 in 0 .. 32768: the least share of either cluster, in 1/65536).
+ *   D(c) = S_lo n_hi - S_hi n_lo;  J(c) = D^2 / (n_lo n_hi).  The cut chosen is the admissible cut of the largest J, the SMALLEST c among
+ *   equals; J1 against J2 is D1^2 (n_lo2 n_hi2) against D2^2 (n_lo1 n_hi1), compared exactly.
+ *   out_site, n, sum, sumsq   as rd_site_compare's
+ *   cut       the cut chosen (int32);  n_cuts  the number of admissible cuts (int32)
+ *   n_lo, sum_lo, sumsq_lo    per sample, over its values <= cut (the high cluster follows by subtraction)
+ *   status    RD_SITE_ONE_SIDED  n0 == 0 or n1 == 0; otherwise
+ *             RD_SITE_DEEP       N > 2^16 (totals only); otherwise
+ *             RD_SITE_NONE       no admissible cut: every value equal, or min_frac_q16 cannot be met; otherwise RD_SITE_OK
+ *             RD_SITE_TOO_LARGE  the site alone exceeds the budget: only out_site and n are filled
+ * cut, n_cuts, n_lo, sum_lo and sumsq_lo are 0 unless the status is RD_SITE_OK.
+ * Bounds: with |value| <= 2^15 and N <= 2^16, |D| <= 2^16 n_lo n_hi <= 2^46, D^2 <= 2^92 and n_lo n_hi <= 2^30: a cross product is
+ * below 2^122, one unsigned 128-bit product.  No field overflows.
+ * A site never affects another; a result does not depend on the order of the events, on what else is in the call, on the budget or on
+ * the launches.  RD_ERR_ARG before anything is launched: the cases of rd_site_compare, and min_frac_q16 outside 0 .. 32768.
+ * n_events == 0 is RD_OK with *n_out = 0.
+ *   rd_site_split           on the GPU; synchronous, uses the context's stream.  budget_bytes as rd_site_compare's, in units of
+ *                           rd_site_split_workspace_bytes; a site that alone exceeds it: RD_SITE_TOO_LARGE, RD_ERR_NOMEM naming it
+ *                           after doing the others
+ *   rd_site_split_host      host, no GPU: the same rules over std::sort and plain loops
+ *   rd_site_split_workspace_bytes   rd_site_workspace_bytes(n_events) + 16 n_events + 112 ceil(n_events / 256): the two int64 prefix
+ *                           arrays (values and squares) per event; per work item (a chunk of 256 sorted elements of a site) its
+ *                           16 B slot and 96 B that stand for the site's entry (a site has at least one work item) */
+#define RD_SITE_NONE 4
+int rd_site_split(rd_ctx* ctx, const uint32_t* site, const uint8_t* cond, const int16_t* value, int64_t n_events, uint32_t n_sites,
+                  int64_t budget_bytes, int64_t capacity, int min_frac_q16, uint32_t* out_site, int32_t* status, int64_t* n, int64_t* sum,
+                  int64_t* sumsq, int32_t* cut, int32_t* n_cuts, int64_t* n_lo, int64_t* sum_lo, int64_t* sumsq_lo, int64_t* n_out);
+int rd_site_split_host(const uint32_t* site, const uint8_t* cond, const int16_t* value, int64_t n_events, uint32_t n_sites, int64_t capacity,
+                       int min_frac_q16, uint32_t* out_site, int32_t* status, int64_t* n, int64_t* sum, int64_t* sumsq, int32_t* cut,
+                       int32_t* n_cuts, int64_t* n_lo, int64_t* sum_lo, int64_t* sumsq_lo, int64_t* n_out);
+int64_t rd_site_split_workspace_bytes(int64_t n_events);
+
 /* ---- signal simulation: raw samples of reads whose sequence, base boundaries and noise are known (sim.hip) ----
  * NO reference behaviour.  Sequences plus a pore-model table become raw int16 samples with every base's first sample known.  Integer
  * arithmetic only; met exactly.

@@ -105,6 +105,9 @@ SIGNATURES = {
     "rd_site_compare_host": (c_i, [c_vp, c_vp, c_vp, c_i64, c_u32, c_i64] + [c_vp] * 13),
     "rd_site_workspace_bytes": (c_i64, [c_i64]),
     "rd_site_diag_segments": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i64, c_u32, c_i64, c_vp, c_vp, c_vp]),
+    "rd_site_split": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i64, c_u32, c_i64, c_i64, c_i] + [c_vp] * 11),
+    "rd_site_split_host": (c_i, [c_vp, c_vp, c_vp, c_i64, c_u32, c_i64, c_i] + [c_vp] * 11),
+    "rd_site_split_workspace_bytes": (c_i64, [c_i64]),
     "rd_sim_lengths": (c_i, [c_vp, c_vp, c_vp, c_i] + [c_vp] * 8 + [c_i] + [c_vp] * 4 + [c_i64, c_vp]),
     "rd_sim_lengths_host": (c_i, [c_vp, c_vp, c_i] + [c_vp] * 8 + [c_i] + [c_vp] * 4 + [c_vp]),
     "rd_sim_signal": (c_i, [c_vp, c_vp, c_vp, c_i] + [c_vp] * 8 + [c_i] + [c_vp] * 4 + [c_vp, c_i64, c_vp, c_vp, c_vp]),

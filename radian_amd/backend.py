@@ -234,6 +234,49 @@ def site_workspace_bytes(n_events):
     return int(_lib.load().rd_site_workspace_bytes(int(n_events)))
 
 
+# rd_site_split (include/radian_hip.h): the statuses are SITE_* and SITE_NONE
+SITE_NONE = 4
+SPLIT_STATUS_NAMES = SITE_STATUS_NAMES + ("none",)
+SPLIT_FIELDS = ("out_site", "status", "n", "sum", "sumsq", "cut", "n_cuts", "n_lo", "sum_lo", "sumsq_lo")
+_SPLIT_DTYPES = {"out_site": np.uint32, "status": np.int32, "n": np.int64, "sum": np.int64, "sumsq": np.int64, "cut": np.int32, "n_cuts": np.int32,
+                 "n_lo": np.int64, "sum_lo": np.int64, "sumsq_lo": np.int64}
+_SPLIT_PAIRS = ("n", "sum", "sumsq", "n_lo", "sum_lo", "sumsq_lo")
+
+
+class SplitResult:
+    """one entry per distinct site, ascending: out_site (uint32), status (int32: SITE_* or SITE_NONE), n / sum / sumsq (int64 [sites, 2]:
+    sample 0 and 1), cut / n_cuts (int32), n_lo / sum_lo / sumsq_lo (int64 [sites, 2]: each sample's values <= cut).  include/radian_hip.h"""
+    __slots__ = SPLIT_FIELDS
+
+    def __init__(self, cap):
+        for name in SPLIT_FIELDS:
+            setattr(self, name, np.zeros((cap + 1, 2) if name in _SPLIT_PAIRS else cap + 1, dtype=_SPLIT_DTYPES[name]))
+
+    def _bufs(self):
+        return [_p(getattr(self, name)) for name in SPLIT_FIELDS]
+
+    def _cut(self, n):
+        for name in SPLIT_FIELDS:
+            setattr(self, name, getattr(self, name)[:n])
+        return self
+
+
+def site_split_host(site, cond, value, n_sites, min_frac_q16=0, capacity=None):
+    """Backend.site_split on the host (rd_site_split_host: the same rules over std::sort and plain loops; no GPU, no context)"""
+    L = _lib.load()
+    site, cond, value, capacity = _site_args(site, cond, value, capacity)
+    res, n_out = SplitResult(capacity), ctypes.c_int64(0)
+    if L.rd_site_split_host(_p(site), _p(cond), _p(value), site.shape[0], int(n_sites), capacity, int(min_frac_q16), *res._bufs(),
+                            ctypes.byref(n_out)) != 0:
+        raise RadianHipError(L.rd_last_error().decode())
+    return res._cut(n_out.value)
+
+
+def site_split_workspace_bytes(n_events):
+    """device workspace Backend.site_split needs for a site of n_events events (rd_site_split_workspace_bytes)"""
+    return int(_lib.load().rd_site_split_workspace_bytes(int(n_events)))
+
+
 # rd_fit_batch per-query status (include/radian_hip.h RD_FIT_*)
 FIT_OK, FIT_EMPTY, FIT_TOO_LARGE = 0, 1, 2
 
@@ -1579,6 +1622,21 @@ class Backend:
         return res._cut(n_out.value)
 
     site_compare_host = staticmethod(site_compare_host)
+
+    # ------------------------------------------------------------------ exact two-cluster split per site
+    def site_split(self, site, cond, value, n_sites, min_frac_q16=0, budget_bytes=0, capacity=None, allow_too_large=False):
+        """The threshold on every site's pooled values that maximises the between-cluster score, among cuts that leave both clusters at
+        least min_frac_q16 / 65536 of the events (rd_site_split, on the GPU).  Arguments as site_compare.  -> SplitResult."""
+        site, cond, value, capacity = _site_args(site, cond, value, capacity)
+        res, n_out = SplitResult(capacity), ctypes.c_int64(0)
+        rc = self._L.rd_site_split(self._h, _p(site), _p(cond), _p(value), site.shape[0], int(n_sites), int(budget_bytes), capacity,
+                                   int(min_frac_q16), *res._bufs(), ctypes.byref(n_out))
+        if rc != 0 and not (allow_too_large and rc == -4 and (res.status[:n_out.value] == SITE_TOO_LARGE).any()):
+            self._check(rc)
+        return res._cut(n_out.value)
+
+    site_split_host = staticmethod(site_split_host)
+    site_split_workspace_bytes = staticmethod(site_split_workspace_bytes)
 
     def site_diag_segments(self, site, cond, value, n_sites):
         """rd_site_diag_segments (tests): the pack, sort and segment stages alone.  -> (sorted keys uint64 [events], segments int64 [sites, 4]:

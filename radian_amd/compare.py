@@ -4,6 +4,7 @@ the PAFs of `map --paf` in, one TSV out, on one GPU.
 
     python -m radian_amd.compare --a events_dir_A --a-paf A.paf --b events_dir_B --b-paf B.paf -o sites.tsv
            [--min-depth 10] [--min-q 0] [--channel level|dwell|both] [--alpha 0.05] [--device N] [--budget-bytes B]
+           [--split [--split-min-frac 0.1] [--reads-out reads.tsv]]
 
 NO reference behaviour.  Every `*.events.tsv` of the two directories is read in sorted file order (columns read_id, ref_name, ref_pos,
 base, n, level, q); the PAFs give every read's transcript, its length and the start of the read's span (columns 1, 6, 7, 8): an event's
@@ -25,8 +26,21 @@ ks_d ks_p mwu_z mwu_p q (prefixed level_ / dwell_; level columns in z units).  s
 one-sided (one sample has no event), deep (more than 2^20 events: no rank statistics), too-large (does not fit --budget-bytes).  Only
 `ok` rows carry test columns; the rest carry nan.  The file is bit-identical across --budget-bytes and runs.
 
-Out of scope: events held anywhere but host memory (about 7 B per event and channel); a binary event format; mixture models; k-mer
-context and motif calls; more than two samples, or replicates; pooling neighbouring positions; calibrating any threshold.
+--split adds, per channel, one call of rd_site_split: the threshold on the site's pooled values that splits them
+into the two clusters of least within-cluster variance, among cuts that leave each cluster at least --split-min-frac of the events
+(min_frac_q16 = rint(frac * 65536)), met exactly in integers.  Each channel's columns gain, fp64 on the host from those integers only:
+  cut;  frac_hi_a, frac_hi_b: the share of each sample above the cut (the stoichiometry when the high cluster is the modified one);
+  mean_lo, mean_hi of the pooled clusters;  sep = (mean_hi - mean_lo) / the pooled within-cluster sd (N - 2 form; n sumsq - sum^2 in
+  Python integers first);  lor: the log odds ratio of the cluster x sample table with 0.5 added to every cell (positive: sample A is
+  enriched above the cut);  split_p: the G-test of that table, 1 degree of freedom, erfc(sqrt(G / 2));  split_q: Benjamini-Hochberg
+  over split_p of the channel's split sites, ties ordered by site.
+Only `ok` rows whose split status is OK carry them (not: every value equal, no cut that meets --split-min-frac, more than 2^16 events).
+--reads-out writes rows read_id sample ref_name pos channel value cluster in input order, for every event of a site with split_q <=
+--alpha: cluster is value > cut on the quantised value (1: above).  Without --split every byte written and printed is unchanged.
+
+Out of scope: events held anywhere but host memory (about 7 B per event and channel, 4 more with --reads-out); a binary event format;
+a soft EM, two-dimensional level x dwell clusters, more than two components; k-mer context and motif calls; more than two samples, or
+replicates; pooling neighbouring positions; calibrating any threshold.
 THRESHOLDS ARE NOT CALIBRATED: no reads with known modifications were available."""
 import argparse
 import math
@@ -39,6 +53,7 @@ from .backend import SITE_DEEP, SITE_OK, SITE_ONE_SIDED, SITE_TOO_LARGE, Backend
 
 CHANNELS = ("level", "dwell")
 STAT_COLUMNS = ("mean_a", "mean_b", "sd_a", "sd_b", "median_a", "median_b", "ks_d", "ks_p", "mwu_z", "mwu_p", "q")
+SPLIT_COLUMNS = ("cut", "frac_hi_a", "frac_hi_b", "mean_lo", "mean_hi", "sep", "lor", "split_p", "split_q")
 ROW_STATUS = ("ok", "low-depth", "one-sided", "deep", "too-large")
 DROP_REASONS = ("no-mapping", "low-q", "bad-level")
 LEVEL_UNIT = 1024
@@ -97,9 +112,10 @@ def list_event_files(directory):
     return sorted(os.path.join(directory, f) for f in os.listdir(directory) if f.endswith(".events.tsv"))
 
 
-def load_events(paths, paf, offsets, min_q, bases, st):
+def load_events(paths, paf, offsets, min_q, bases, st, reads=None):
     """the events of one sample: (site uint32, level int16, dwell int16) arrays.  bases: {site: base}, shared by both samples; st: the
-    sample's counters"""
+    sample's counters.  reads (--reads-out): {"ids": [read ids], "index": [per kept event, its read's place in ids]}, appended to"""
+    read_at = {}
     site, level, dwell = [], [], []
     skipped = set()
     for path in paths:
@@ -140,6 +156,11 @@ def load_events(paths, paf, offsets, min_q, bases, st):
                 if not math.isfinite(lv):
                     st["bad-level"] += 1
                     continue
+                if reads is not None:
+                    if rid not in read_at:
+                        read_at[rid] = len(reads["ids"])
+                        reads["ids"].append(rid)
+                    reads["index"].append(read_at[rid])
                 site.append(s)
                 level.append(lv)
                 dwell.append(int(n))
@@ -207,6 +228,30 @@ def benjamini_hochberg(ps):
     return q
 
 
+def split_stats(n, n_lo, sum_, sum_lo, sumsq, sumsq_lo, cut, unit):
+    """[cut, frac_hi_a, frac_hi_b, mean_lo, mean_hi, sep, lor, split_p] of one split site from its integers (pairs: sample 0, 1), in units
+    of `unit`.  sep is inf when both clusters have no spread, nan at N = 2"""
+    n, n_lo, sum_, sum_lo, sumsq, sumsq_lo = ([int(v[0]), int(v[1])] for v in (n, n_lo, sum_, sum_lo, sumsq, sumsq_lo))
+    n_hi = [n[c] - n_lo[c] for c in (0, 1)]
+    L, H, N = n_lo[0] + n_lo[1], n_hi[0] + n_hi[1], n[0] + n[1]
+    s_lo, q_lo = sum_lo[0] + sum_lo[1], sumsq_lo[0] + sumsq_lo[1]
+    s_hi, q_hi = sum_[0] + sum_[1] - s_lo, sumsq[0] + sumsq[1] - q_lo
+    mean_lo, mean_hi = s_lo / L / unit, s_hi / H / unit
+    w_lo, w_hi = L * q_lo - s_lo * s_lo, H * q_hi - s_hi * s_hi          # n sumsq - sum^2 >= 0, exact in Python ints
+    if N <= 2:
+        sep = float("nan")
+    elif w_lo == 0 and w_hi == 0:
+        sep = float("inf")
+    else:
+        sep = (mean_hi - mean_lo) / (math.sqrt((w_lo / L + w_hi / H) / (N - 2)) / unit)
+    lor = math.log((n_hi[0] + 0.5) * (n_lo[1] + 0.5) / ((n_lo[0] + 0.5) * (n_hi[1] + 0.5)))
+    g = 0.0
+    for obs, row, col in ((n_lo[0], L, n[0]), (n_lo[1], L, n[1]), (n_hi[0], H, n[0]), (n_hi[1], H, n[1])):
+        if obs:
+            g += 2.0 * obs * math.log(obs * N / (row * col))
+    return [int(cut) / unit, n_hi[0] / n[0], n_hi[1] / n[1], mean_lo, mean_hi, sep, lor, min(1.0, math.erfc(math.sqrt(max(g, 0.0) / 2.0)))]
+
+
 def row_status(status, n0, n1, min_depth):
     if status == SITE_TOO_LARGE:
         return "too-large"
@@ -221,9 +266,11 @@ def _fmt(v, spec):
     return "nan" if math.isnan(v) else format(v, spec)
 
 
-def write_table(out, names, offsets, bases, results, min_depth, alpha):
+def write_table(out, names, offsets, bases, results, min_depth, alpha, splits=None):
     """results: {channel: SiteResult (or anything with its arrays)}, every channel over the same events' sites.  Writes the header and one
-    row per site; returns {row status: sites, "significant": {channel: sites with q <= alpha}}."""
+    row per site; returns {row status: sites, "significant": {channel: sites with q <= alpha}}.  splits (--split): {channel: SplitResult}
+    over the same sites: the SPLIT_COLUMNS follow each channel's, and the return gains "split": {channel: {site: cut of every site with
+    split_q <= alpha}}."""
     channels = [c for c in CHANNELS if c in results]
     first = results[channels[0]]
     n_out = len(first.out_site)
@@ -251,9 +298,26 @@ def write_table(out, names, offsets, bases, results, min_depth, alpha):
         for j, q in zip(tested, benjamini_hochberg(ps)):
             rows[j][10] = q
         cols[ch] = rows
-    out.write("\t".join(["ref_name", "pos", "base", "status", "n_a", "n_b"] + [f"{ch}_{c}" for ch in channels for c in STAT_COLUMNS]) + "\n")
+        if splits is not None:
+            sp = splits[ch]
+            if not np.array_equal(sp.out_site, r.out_site) or not np.array_equal(sp.n, r.n):
+                raise SystemExit(f"compare: internal: the split's sites of channel {ch} are not the comparison's")
+            tested, ps = [], []
+            for j in range(n_out):
+                row = [float("nan")] * 9
+                if status[j] == "ok" and int(sp.status[j]) == SITE_OK:
+                    row[:8] = split_stats(sp.n[j], sp.n_lo[j], sp.sum[j], sp.sum_lo[j], sp.sumsq[j], sp.sumsq_lo[j], sp.cut[j], unit)
+                    tested.append(j)
+                    ps.append(row[7])
+                rows[j] += row
+            for j, q in zip(tested, benjamini_hochberg(ps)):
+                rows[j][19] = q
+    columns = STAT_COLUMNS + (SPLIT_COLUMNS if splits is not None else ())
+    out.write("\t".join(["ref_name", "pos", "base", "status", "n_a", "n_b"] + [f"{ch}_{c}" for ch in channels for c in columns]) + "\n")
     st = {s: 0 for s in ROW_STATUS}
     st["significant"] = {ch: 0 for ch in channels}
+    if splits is not None:
+        st["split"] = {ch: {} for ch in channels}
     t = 0
     for j in range(n_out):
         s = int(first.out_site[j])
@@ -266,6 +330,10 @@ def write_table(out, names, offsets, bases, results, min_depth, alpha):
             row += [_fmt(x, ".6f") for x in v[:7]] + [_fmt(v[7], ".6e"), _fmt(v[8], ".4f"), _fmt(v[9], ".6e"), _fmt(v[10], ".6e")]
             if not math.isnan(v[10]) and v[10] <= alpha:
                 st["significant"][ch] += 1
+            if splits is not None:
+                row += [_fmt(x, ".6f") for x in v[11:18]] + [_fmt(v[18], ".6e"), _fmt(v[19], ".6e")]
+                if not math.isnan(v[19]) and v[19] <= alpha:
+                    st["split"][ch][s] = int(splits[ch].cut[j])
         out.write("\t".join(row) + "\n")
     return st
 
@@ -279,7 +347,29 @@ def summary(sample_st, st, channels, alpha):
     text += "sites: " + "; ".join(f"{s}: {st[s]}" for s in ROW_STATUS) + "\n"
     for ch in channels:
         text += f"{ch}: {st['significant'][ch]} sites with q <= {alpha:g}\n"
+    if "split" in st:
+        for ch in channels:
+            text += f"{ch} split: {len(st['split'][ch])} sites with split_q <= {alpha:g} (thresholds not calibrated)\n"
     return text
+
+
+def write_reads(out, names, offsets, reads, site, cond, values, channels, called):
+    """--reads-out: one row per event, in input order, and channel whose site is in called[channel] ({site: cut}); cluster 1: value > cut"""
+    out.write("read_id\tsample\tref_name\tpos\tchannel\tvalue\tcluster\n")
+    starts = [offsets[name][0] for name in names]
+    n_rows = 0
+    for i in range(len(site)):
+        s = int(site[i])
+        for ch in channels:
+            cut = called[ch].get(s)
+            if cut is None:
+                continue
+            t = int(np.searchsorted(starts, s, side="right")) - 1
+            v = int(values[ch][i])
+            shown = format(v / LEVEL_UNIT, ".6f") if ch == "level" else str(v)
+            out.write(f"{reads['ids'][reads['index'][i]]}\t{'ab'[int(cond[i])]}\t{names[t]}\t{s - starts[t]}\t{ch}\t{shown}\t{int(v > cut)}\n")
+            n_rows += 1
+    return n_rows
 
 
 # ------------------------------------------------------------------------------------------------ the command
@@ -297,6 +387,9 @@ def build_parser():
     ap.add_argument("--alpha", default=0.05, type=float, help="the summary counts sites with q at most this")
     ap.add_argument("--device", default=0, type=int, help="GPU index")
     ap.add_argument("--budget-bytes", default=0, type=int, help="device workspace per launch (0: a quarter of free memory)")
+    ap.add_argument("--split", action="store_true", help="also split every site's pooled values into two clusters, exactly: stoichiometry columns")
+    ap.add_argument("--split-min-frac", default=0.1, type=float, help="the least share of a site's events either cluster may hold (0 .. 0.5)")
+    ap.add_argument("--reads-out", default=None, help="with --split: per-read cluster calls at the sites with split_q at most --alpha")
     return ap
 
 
@@ -309,6 +402,10 @@ def check_args(args):
         raise SystemExit("compare: --alpha must be in (0, 1]")
     if args.budget_bytes < 0:
         raise SystemExit("compare: --budget-bytes must be at least 0")
+    if not 0.0 <= args.split_min_frac <= 0.5:
+        raise SystemExit("compare: --split-min-frac must be in 0 .. 0.5")
+    if args.reads_out is not None and not args.split:
+        raise SystemExit("compare: --reads-out goes with --split")
     for d in (args.a, args.b):
         if not os.path.isdir(d):
             raise SystemExit(f"compare: {d}: no such directory")
@@ -318,26 +415,39 @@ def check_args(args):
 
 
 def load(args):
-    """-> (names, offsets, n_sites, bases, site, cond, {channel: values}, per-sample counters)"""
+    """-> (names, offsets, n_sites, bases, site, cond, {channel: values}, per-sample counters); with --reads-out the counters hold "reads":
+    the read ids and every kept event's index into them (uint32)"""
     pafs = {"a": read_paf(args.a_paf), "b": read_paf(args.b_paf)}
     names, offsets, n_sites = transcript_offsets([pafs["a"], pafs["b"]])
     bases, parts, sample_st = {}, [], {}
+    reads = {"ids": [], "index": []} if getattr(args, "reads_out", None) else None
     for name, directory in (("a", args.a), ("b", args.b)):
         st = sample_st[name] = {"files": 0, "events": 0, "kept": 0, "reads-no-mapping": 0, **{r: 0 for r in DROP_REASONS}}
-        parts.append(load_events(list_event_files(directory), pafs[name], offsets, args.min_q, bases, st))
+        parts.append(load_events(list_event_files(directory), pafs[name], offsets, args.min_q, bases, st, reads))
     if len(parts[0][0]) + len(parts[1][0]) > MAX_EVENTS:
         raise SystemExit(f"compare: {len(parts[0][0]) + len(parts[1][0])} events in all, more than 2^31 - 1")
     site = np.concatenate([parts[0][0], parts[1][0]])
     cond = np.concatenate([np.zeros(len(parts[0][0]), np.uint8), np.ones(len(parts[1][0]), np.uint8)])
     values = {"level": np.concatenate([parts[0][1], parts[1][1]]), "dwell": np.concatenate([parts[0][2], parts[1][2]])}
+    if reads is not None:
+        sample_st["reads"] = {"ids": reads["ids"], "index": np.array(reads["index"], dtype=np.uint32)}
     return names, offsets, n_sites, bases, site, cond, values, sample_st
 
 
 def run(args, be, out):
     names, offsets, n_sites, bases, site, cond, values, sample_st = load(args)
+    reads = sample_st.pop("reads", None)
     channels = [c for c in CHANNELS if args.channel in (c, "both")]
     results = {ch: be.site_compare(site, cond, values[ch], n_sites, budget_bytes=args.budget_bytes, allow_too_large=True) for ch in channels}
-    st = write_table(out, names, offsets, bases, results, args.min_depth, args.alpha)
+    splits = None
+    if args.split:
+        q16 = int(np.rint(args.split_min_frac * 65536))
+        splits = {ch: be.site_split(site, cond, values[ch], n_sites, min_frac_q16=q16, budget_bytes=args.budget_bytes, allow_too_large=True)
+                  for ch in channels}
+    st = write_table(out, names, offsets, bases, results, args.min_depth, args.alpha, splits)
+    if reads is not None:
+        with open(args.reads_out, "w") as f:
+            st["read-rows"] = write_reads(f, names, offsets, reads, site, cond, values, channels, st["split"])
     return sample_st, st, channels
 
 

@@ -1,6 +1,7 @@
 // site_rules.h -- the rules of the two-sample site comparison (include/radian_hip.h, rd_site_compare), once: the
 // argument check, the host twin (rd_site_compare_host), the host's counting pass and launch plan, and the kernels of sitecmp.hip all call
-// these.  Integer arithmetic only; plain C++ without a HIP type (tests/asan_sitecmp.cpp compiles it with g++).
+// these.  So do the rules of the exact two-cluster split (rd_site_split): its host twin, plan and kernels.
+// Integer arithmetic only; plain C++ without a HIP type (tests/asan_sitecmp.cpp and tests/asan_sitesplit.cpp compile it with g++).
 #pragma once
 #include <stdint.h>
 #include <algorithm>
@@ -135,6 +136,105 @@ SC_HD inline void sc_element(const uint64_t* k, int64_t start, int64_t split, in
     if (w > t.ks) t.ks = w;
 }
 
+// ------------------------------------------------------------------------------------------------ the two-cluster split (section 26)
+// rd_site_split: the threshold on a site's pooled values that maximises J(c) = D^2 / (n_lo n_hi), D = S_lo n_hi - S_hi n_lo, among the
+// admissible cuts; ties to the smaller cut.  Everything is an integer; J is compared by cross-multiplication in 128 bits.
+constexpr int SS_NONE = 4;                            // RD_SITE_NONE: no admissible cut (the other statuses are SC_*)
+constexpr int64_t SS_DEEP_LIMIT = (int64_t)1 << 16;   // n0 + n1 above this: totals only (D^2 n_lo n_hi would pass 128 bits)
+constexpr int SS_MIN_FRAC_MAX = 32768;                // min_frac_q16: 0 .. a half
+constexpr int64_t SS_EVENT_BYTES = 16;                // what a split adds per event: the two prefix arrays
+constexpr int64_t SS_ITEM_BYTES = 112;                // and per work item (chunk of SC_CHUNK): its slot, and 96 B that stand for the site's entry
+
+SC_HD inline int ss_status(int64_t n0, int64_t n1) { return n0 == 0 || n1 == 0 ? SC_ONE_SIDED : n0 + n1 > SS_DEEP_LIMIT ? SC_DEEP : SC_OK; }
+
+// a candidate cut: |D|, the pooled counts on both sides, the cut.  n_lo == 0: no candidate (an admissible cut has n_lo >= 1)
+struct SsCand {
+    uint64_t d;
+    uint32_t n_lo, n_hi;
+    int32_t cut;
+};
+
+// a beats b: the larger J = d^2 / (n_lo n_hi), then the smaller cut.  d <= 2^46 and n_lo n_hi <= 2^30: both products are below 2^122
+SC_HD inline bool ss_better(const SsCand& a, const SsCand& b)
+{
+    if (!a.n_lo) return false;
+    if (!b.n_lo) return true;
+    const unsigned __int128 l = (unsigned __int128)a.d * a.d * ((uint64_t)b.n_lo * b.n_hi), r = (unsigned __int128)b.d * b.d * ((uint64_t)a.n_lo * a.n_hi);
+    return l != r ? l > r : a.cut < b.cut;
+}
+
+// the sum of x[a, b), p the inclusive prefix sums of x
+SC_HD inline int64_t ss_range(const int64_t* p, int64_t a, int64_t b) { return (b > 0 ? p[b - 1] : 0) - (a > 0 ? p[a - 1] : 0); }
+
+// Element i of a site whose split status is OK, psum the inclusive prefix sums of the sorted values: true and the candidate when i is the
+// LAST element of a run of equal values of its sample, the value is not the pooled maximum and the cut is admissible.  A value present in
+// both samples is weighed from sample 0's side (the sc_element pattern)
+SC_HD inline bool ss_candidate(const uint64_t* k, const int64_t* psum, int64_t start, int64_t split, int64_t end, int64_t i, int64_t min_frac_q16,
+                               SsCand& out)
+{
+    const uint64_t key = k[i];
+    const int c = i >= split;
+    if (i + 1 < (c ? end : split) && k[i + 1] == key) return false;
+    int64_t cnt_a, cnt_b;
+    if (c == 0) {
+        cnt_a = i + 1 - start;
+        cnt_b = sc_lower(k, split, end, (key | 0x10000) + 1) - split;
+    } else {
+        const uint64_t other = key & ~(uint64_t)0x10000;
+        const int64_t la = sc_lower(k, start, split, other), ua = sc_lower(k, start, split, other + 1);
+        if (ua != la) return false;
+        cnt_a = ua - start;
+        cnt_b = i + 1 - split;
+    }
+    const int64_t N = end - start, n_lo = cnt_a + cnt_b, n_hi = N - n_lo;
+    if (n_hi < 1 || 65536 * n_lo < min_frac_q16 * N || 65536 * n_hi < min_frac_q16 * N) return false;
+    const int64_t s_lo = ss_range(psum, start, start + cnt_a) + ss_range(psum, split, split + cnt_b), s_all = ss_range(psum, start, end);
+    const int64_t d = s_lo * n_hi - (s_all - s_lo) * n_lo;
+    out.d = (uint64_t)(d < 0 ? -d : d);
+    out.n_lo = (uint32_t)n_lo;
+    out.n_hi = (uint32_t)n_hi;
+    out.cut = sc_key_value(key);
+    return true;
+}
+
+// what a site's split comes to, as the kernels store it (96 bytes)
+struct SsOut {
+    int64_t sum[2], sumsq[2], sum_lo[2], sumsq_lo[2];
+    uint32_t site;
+    int32_t status;
+    uint32_t n[2];
+    int32_t cut, n_cuts;
+    uint32_t n_lo[2];
+};
+
+// The entry of the site k[start, end) from the best of its candidates (best.n_lo == 0: none) and their number: totals from the prefix
+// arrays (psum of the values, psq of their squares), the low cluster per sample at the upper bounds of the cut in the two runs
+SC_HD inline SsOut ss_entry(const uint64_t* k, const int64_t* psum, const int64_t* psq, int64_t start, int64_t split, int64_t end, const SsCand& best,
+                            int32_t n_cuts)
+{
+    SsOut o;
+    o.site = sc_key_site(k[start]);
+    o.n[0] = (uint32_t)(split - start);
+    o.n[1] = (uint32_t)(end - split);
+    o.sum[0] = ss_range(psum, start, split), o.sum[1] = ss_range(psum, split, end);
+    o.sumsq[0] = ss_range(psq, start, split), o.sumsq[1] = ss_range(psq, split, end);
+    o.status = ss_status(split - start, end - split);
+    if (o.status == SC_OK && !best.n_lo) o.status = SS_NONE;
+    o.cut = o.n_cuts = 0;
+    for (int c = 0; c < 2; c++) o.n_lo[c] = 0, o.sum_lo[c] = o.sumsq_lo[c] = 0;
+    if (o.status != SC_OK) return o;
+    o.cut = best.cut;
+    o.n_cuts = n_cuts;
+    const int64_t a[2] = {start, split}, b[2] = {split, end};
+    for (int c = 0; c < 2; c++) {
+        const int64_t u = sc_lower(k, a[c], b[c], sc_key(o.site, (uint32_t)c, best.cut) + 1);
+        o.n_lo[c] = (uint32_t)(u - a[c]);
+        o.sum_lo[c] = ss_range(psum, a[c], u);
+        o.sumsq_lo[c] = ss_range(psq, a[c], u);
+    }
+    return o;
+}
+
 // ------------------------------------------------------------------------------------------------ the host's counting pass and plan
 struct ScSite {
     uint32_t site;
@@ -170,6 +270,15 @@ inline int64_t sc_site_chunks(const ScSite& s) { return (s.n[0] + s.n[1] + SC_CH
 inline BudgetPlan sc_plan(const std::vector<ScSite>& sites, int64_t budget)
 {
     return rd_plan_budget((int64_t)sites.size(), nullptr, budget, 0, true, [&](int s, int) { return sc_site_bytes(sites[s]); },
+                          rd_budget_never_closes);
+}
+
+// the same for rd_site_split: a site's need is rd_site_split_workspace_bytes of its events
+inline int64_t ss_bytes(int64_t n_events) { return (SC_EVENT_BYTES + SS_EVENT_BYTES) * n_events + SS_ITEM_BYTES * ((n_events + SC_CHUNK - 1) / SC_CHUNK); }
+inline int64_t ss_site_bytes(const ScSite& s) { return ss_bytes(s.n[0] + s.n[1]); }
+inline BudgetPlan ss_plan(const std::vector<ScSite>& sites, int64_t budget)
+{
+    return rd_plan_budget((int64_t)sites.size(), nullptr, budget, 0, true, [&](int s, int) { return ss_site_bytes(sites[s]); },
                           rd_budget_never_closes);
 }
 

@@ -21,6 +21,14 @@
 //                      ks_num and ks_x are one atomicMax on sc_ks_pack.  Every combination is an integer add or max: the result does not
 //                      depend on how the elements are spread over lanes, waves and launches.
 // No floating point, no LDS, no inline assembly.
+//
+// rd_site_split runs the same pack / sort / flag / scan / compact / head stages (sc_run) and then, per launch:
+//   rocprim::inclusive_scan twice over the sorted keys' values and their squares (int64, read through a transform iterator)
+//   ss_item_kernel     one wave per (site, chunk): a lane takes every 64th element and calls ss_candidate; the lane's best under ss_better,
+//                      the wave's best by xor-shuffles under the same total order into the item's slot; the count of admissible cuts by
+//                      one 32-bit atomic add per wave
+//   ss_pick_kernel     one wave per site: the best over the site's slots under the same order, then lane 0 writes the entry (ss_entry:
+//                      totals and the low cluster's n, sum and sumsq as differences of the two prefix arrays)
 #include "common.h"
 #include "site_rules.h"
 #include "../../include/radian_hip.h"
@@ -123,10 +131,97 @@ extern "C" int rd_site_compare_host(const uint32_t* site, const uint8_t* cond, c
     return RD_OK;
 }
 
+// ------------------------------------------------------------------------------------------------------------------ the split, host half
+namespace {
+
+struct SsArrays {
+    uint32_t* out_site;
+    int32_t* status;
+    int64_t *n, *sum, *sumsq;
+    int32_t *cut, *n_cuts;
+    int64_t *n_lo, *sum_lo, *sumsq_lo;
+};
+
+// entry j of the caller's arrays by the field rules of its status: TOO_LARGE only the site and n, cut fields only for OK (ss_entry zeroes them)
+void ss_scatter(const SsOut& o, int64_t j, const SsArrays& A)
+{
+    const bool rest = o.status != SC_TOO_LARGE;
+    A.out_site[j] = o.site;
+    A.status[j] = o.status;
+    A.cut[j] = rest ? o.cut : 0;
+    A.n_cuts[j] = rest ? o.n_cuts : 0;
+    for (int c = 0; c < 2; c++) {
+        A.n[2 * j + c] = o.n[c];
+        A.sum[2 * j + c] = rest ? o.sum[c] : 0;
+        A.sumsq[2 * j + c] = rest ? o.sumsq[c] : 0;
+        A.n_lo[2 * j + c] = rest ? o.n_lo[c] : 0;
+        A.sum_lo[2 * j + c] = rest ? o.sum_lo[c] : 0;
+        A.sumsq_lo[2 * j + c] = rest ? o.sumsq_lo[c] : 0;
+    }
+}
+
+int ss_check_args(const char* who, const uint32_t* site, const uint8_t* cond, const int16_t* value, int64_t n_events, int min_frac_q16,
+                  const SsArrays& A, const int64_t* n_out)
+{
+    const void* const outs[11] = {A.out_site, A.status, A.n, A.sum, A.sumsq, A.cut, A.n_cuts, A.n_lo, A.sum_lo, A.sumsq_lo, n_out};
+    const int rc = sc_check_args(who, site, cond, value, n_events, outs, 11);
+    if (rc) return rc;
+    RD_REQUIRE(min_frac_q16 >= 0 && min_frac_q16 <= SS_MIN_FRAC_MAX, "%s: min_frac_q16 must be 0 .. 32768", who);
+    return RD_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t rd_site_split_workspace_bytes(int64_t n_events)
+{
+    if (n_events < 0 || n_events > INT32_MAX) return -1;
+    return ss_bytes(n_events);
+}
+
+extern "C" int rd_site_split_host(const uint32_t* site, const uint8_t* cond, const int16_t* value, int64_t n_events, uint32_t n_sites,
+                                  int64_t capacity, int min_frac_q16, uint32_t* out_site, int32_t* status, int64_t* n, int64_t* sum, int64_t* sumsq,
+                                  int32_t* cut, int32_t* n_cuts, int64_t* n_lo, int64_t* sum_lo, int64_t* sumsq_lo, int64_t* n_out)
+{
+    const SsArrays A{out_site, status, n, sum, sumsq, cut, n_cuts, n_lo, sum_lo, sumsq_lo};
+    int rc = ss_check_args("rd_site_split_host", site, cond, value, n_events, min_frac_q16, A, n_out);
+    if (rc) return rc;
+    RD_REQUIRE(capacity >= 0, "rd_site_split_host: negative capacity");
+    std::vector<ScSite> sites;
+    if ((rc = sc_count_checked("rd_site_split_host", site, cond, n_events, n_sites, capacity, sites))) return rc;
+    *n_out = (int64_t)sites.size();
+    if (n_events == 0) return RD_OK;
+    std::vector<uint64_t> k((size_t)n_events);
+    for (int64_t i = 0; i < n_events; i++) k[i] = sc_key(site[i], cond[i], value[i]);
+    std::sort(k.begin(), k.end());
+    std::vector<int64_t> psum((size_t)n_events), psq((size_t)n_events);
+    int64_t s = 0, q = 0;
+    for (int64_t i = 0; i < n_events; i++) {
+        const int64_t v = sc_key_value(k[i]);
+        psum[i] = s += v;
+        psq[i] = q += v * v;
+    }
+    int64_t start = 0;
+    for (size_t j = 0; j < sites.size(); j++) {
+        const int64_t end = start + sites[j].n[0] + sites[j].n[1], split = sc_split(k.data(), start, end);
+        SsCand best{0, 0, 0, 0}, cand;
+        int32_t n_cuts_j = 0;
+        if (ss_status(split - start, end - split) == SC_OK)
+            for (int64_t i = start; i < end; i++)
+                if (ss_candidate(k.data(), psum.data(), start, split, end, i, min_frac_q16, cand)) {
+                    n_cuts_j++;
+                    if (ss_better(cand, best)) best = cand;
+                }
+        ss_scatter(ss_entry(k.data(), psum.data(), psq.data(), start, split, end, best, n_cuts_j), (int64_t)j, A);
+        start = end;
+    }
+    return RD_OK;
+}
+
 #if defined(__HIPCC__)
 // ------------------------------------------------------------------------------------------------------------------ device half
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
 
 namespace {
 
@@ -241,6 +336,8 @@ struct ScWs {
     void* tmp;
     size_t tmp_bytes;
     const uint64_t* sorted;
+    size_t extra_bytes = 0, min_tmp = 0;   // set by the caller before sc_run: bytes of its own after the block's arrays, the least tmp_bytes
+    char* extra = nullptr;
 };
 
 // pack, sort and segment n events expected to fall into S sites; with n_items > 0 the head and site kernels too.  Leaves the stream running
@@ -252,7 +349,7 @@ int sc_run(rd_ctx* ctx, hipStream_t st, const uint32_t* site, const uint8_t* con
     RD_HIP(rocprim::radix_sort_keys(nullptr, sort_bytes, probe, (size_t)n, 0u, (unsigned)end_bit, st));
     RD_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
     RD_HIP(rocprim::exclusive_scan(nullptr, scan2_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)S + 1, rocprim::plus<uint32_t>(), st));
-    W.tmp_bytes = std::max(sort_bytes, std::max(scan_bytes, scan2_bytes));
+    W.tmp_bytes = std::max(std::max(sort_bytes, W.min_tmp), std::max(scan_bytes, scan2_bytes));
     size_t at = 0;
     const auto take = [&](size_t bytes) {
         const size_t o = at;
@@ -262,7 +359,7 @@ int sc_run(rd_ctx* ctx, hipStream_t st, const uint32_t* site, const uint8_t* con
     const size_t o_site = take((size_t)n * 4), o_cond = take((size_t)n), o_value = take((size_t)n * 2), o_ka = take((size_t)n * 8),
                  o_kb = take((size_t)n * 8), o_flag = take((size_t)n * 4), o_pos = take((size_t)n * 4), o_start = take((size_t)(S + 1) * 4),
                  o_chunk = take((size_t)(S + 1) * 4), o_item = take((size_t)(S + 1) * 4), o_nseg = take(4), o_seg = take((size_t)S * sizeof(ScSeg)),
-                 o_out = take((size_t)S * sizeof(ScOut)), o_tmp = take(W.tmp_bytes);
+                 o_out = take((size_t)S * sizeof(ScOut)), o_tmp = take(W.tmp_bytes), o_extra = take(W.extra_bytes);
     if (ctx->ws_site.reserve(at)) return RD_ERR_NOMEM;
     char* base = (char*)ctx->ws_site.p;
     W.in_site = (uint32_t*)(base + o_site);
@@ -279,6 +376,7 @@ int sc_run(rd_ctx* ctx, hipStream_t st, const uint32_t* site, const uint8_t* con
     W.seg = (ScSeg*)(base + o_seg);
     W.out = (ScOut*)(base + o_out);
     W.tmp = base + o_tmp;
+    W.extra = base + o_extra;
     RD_HIP(hipMemcpyAsync(W.in_site, site, (size_t)n * 4, hipMemcpyHostToDevice, st));
     RD_HIP(hipMemcpyAsync(W.in_cond, cond, (size_t)n, hipMemcpyHostToDevice, st));
     RD_HIP(hipMemcpyAsync(W.in_value, value, (size_t)n * 2, hipMemcpyHostToDevice, st));
@@ -416,6 +514,189 @@ extern "C" int rd_site_diag_segments(rd_ctx* ctx, const uint32_t* site, const ui
         segments[4 * s + 3] = seg[(size_t)s].end;
     }
     *n_segments = S;
+    return RD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ the split, device half
+namespace {
+
+struct SsValue {
+    __host__ __device__ int64_t operator()(uint64_t key) const { return sc_key_value(key); }
+};
+struct SsSquare {
+    __host__ __device__ int64_t operator()(uint64_t key) const { return (int64_t)sc_key_value(key) * sc_key_value(key); }
+};
+
+// a work item's best candidate (n_lo == 0: none); n_hi is the site's count less n_lo
+struct SsSlot {
+    uint64_t d;
+    uint32_t n_lo;
+    int32_t cut;
+};
+
+// the wave's best under ss_better (a total order over the candidates of a site: their cuts differ), in every lane
+__device__ inline SsCand ss_wave_best(SsCand b)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        SsCand o;
+        o.d = (uint64_t)__shfl_xor((long long)b.d, d);
+        o.n_lo = (uint32_t)__shfl_xor((int)b.n_lo, d);
+        o.n_hi = (uint32_t)__shfl_xor((int)b.n_hi, d);
+        o.cut = __shfl_xor(b.cut, d);
+        if (ss_better(o, b)) b = o;
+    }
+    return b;
+}
+
+__global__ __launch_bounds__(64 * SC_WAVES) void ss_item_kernel(const uint64_t* __restrict__ keys, const int64_t* __restrict__ psum,
+                                                                const ScSeg* __restrict__ seg, const uint32_t* __restrict__ item_off, uint32_t n_seg,
+                                                                uint32_t n_items, const uint32_t* __restrict__ found, int min_frac_q16,
+                                                                SsSlot* __restrict__ slot, int32_t* __restrict__ n_cuts)
+{
+    const int lane = threadIdx.x & 63;
+    const uint32_t item = blockIdx.x * (uint32_t)SC_WAVES + (threadIdx.x >> 6);   // (the same in every lane of the wave)
+    if (item >= n_items || *found != n_seg || item_off[n_seg] != n_items) return;
+    uint32_t lo = 0, hi = n_seg;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (item_off[mid] <= item) lo = mid;
+        else hi = mid;
+    }
+    const ScSeg sg = seg[lo];
+    SsCand best{0, 0, 0, 0};
+    int count = 0;
+    if (ss_status((int64_t)sg.split - sg.start, (int64_t)sg.end - sg.split) == SC_OK) {
+        const int64_t i0 = (int64_t)sg.start + (int64_t)(item - item_off[lo]) * SC_CHUNK, i1 = i0 + SC_CHUNK < (int64_t)sg.end ? i0 + SC_CHUNK : (int64_t)sg.end;
+        for (int64_t i = i0 + lane; i < i1; i += 64) {
+            SsCand cand;
+            if (ss_candidate(keys, psum, sg.start, sg.split, sg.end, i, min_frac_q16, cand)) {
+                count++;
+                if (ss_better(cand, best)) best = cand;
+            }
+        }
+        best = ss_wave_best(best);
+        count = (int)sc_wave_add(count);
+    }
+    if (lane != 0) return;
+    slot[item] = SsSlot{best.d, best.n_lo, best.cut};
+    if (count) atomicAdd(n_cuts + lo, count);
+}
+
+__global__ __launch_bounds__(64 * SC_WAVES) void ss_pick_kernel(const uint64_t* __restrict__ keys, const int64_t* __restrict__ psum,
+                                                                const int64_t* __restrict__ psq, const ScSeg* __restrict__ seg,
+                                                                const uint32_t* __restrict__ item_off, uint32_t n_seg, uint32_t n_items,
+                                                                const uint32_t* __restrict__ found, const SsSlot* __restrict__ slot,
+                                                                const int32_t* __restrict__ n_cuts, SsOut* __restrict__ out)
+{
+    const int lane = threadIdx.x & 63;
+    const uint32_t s = blockIdx.x * (uint32_t)SC_WAVES + (threadIdx.x >> 6);
+    if (s >= n_seg || *found != n_seg || item_off[n_seg] != n_items) return;
+    const ScSeg sg = seg[s];
+    const uint32_t N = sg.end - sg.start;
+    SsCand best{0, 0, 0, 0};
+    for (uint32_t it = item_off[s] + (uint32_t)lane; it < item_off[s + 1]; it += 64) {
+        const SsSlot t = slot[it];
+        const SsCand cand{t.d, t.n_lo, N - t.n_lo, t.cut};
+        if (ss_better(cand, best)) best = cand;
+    }
+    best = ss_wave_best(best);
+    if (lane == 0) out[s] = ss_entry(keys, psum, psq, sg.start, sg.split, sg.end, best, n_cuts[s]);
+}
+
+}  // namespace
+
+extern "C" int rd_site_split(rd_ctx* ctx, const uint32_t* site, const uint8_t* cond, const int16_t* value, int64_t n_events, uint32_t n_sites,
+                             int64_t budget_bytes, int64_t capacity, int min_frac_q16, uint32_t* out_site, int32_t* status, int64_t* n, int64_t* sum,
+                             int64_t* sumsq, int32_t* cut, int32_t* n_cuts, int64_t* n_lo, int64_t* sum_lo, int64_t* sumsq_lo, int64_t* n_out)
+{
+    RD_REQUIRE(ctx, "rd_site_split: null context");
+    RD_REQUIRE(budget_bytes >= 0 && capacity >= 0, "rd_site_split: negative budget or capacity");
+    const SsArrays A{out_site, status, n, sum, sumsq, cut, n_cuts, n_lo, sum_lo, sumsq_lo};
+    int rc = ss_check_args("rd_site_split", site, cond, value, n_events, min_frac_q16, A, n_out);
+    if (rc) return rc;
+    std::vector<ScSite> sites;
+    if ((rc = sc_count_checked("rd_site_split", site, cond, n_events, n_sites, capacity, sites))) return rc;
+    *n_out = (int64_t)sites.size();
+    if (n_events == 0) return RD_OK;
+    RD_HIP(hipSetDevice(ctx->device));
+    if ((rc = rd_resolve_budget(&budget_bytes, ctx->ws_site.cap))) return rc;   // (this context's block counts as free)
+    const BudgetPlan plan = ss_plan(sites, budget_bytes);
+    for (size_t j = 0; j < sites.size(); j++) {   // until its launch has run
+        SsOut o;
+        memset(&o, 0, sizeof o);
+        o.site = sites[j].site;
+        o.status = SC_TOO_LARGE;
+        o.n[0] = (uint32_t)sites[j].n[0];
+        o.n[1] = (uint32_t)sites[j].n[1];
+        ss_scatter(o, (int64_t)j, A);
+    }
+    std::vector<int64_t> off;
+    std::vector<uint32_t> g_site;
+    std::vector<uint8_t> g_cond;
+    std::vector<int16_t> g_value;
+    const bool whole = plan.launches.size() == 1 && plan.too_large == 0;
+    if (!whole) sc_bucket(site, cond, value, n_events, sites, plan, off, g_site, g_cond, g_value);
+    std::vector<SsOut> got;
+    hipStream_t st = ctx->stream;
+    const int end_bit = sc_sort_bits(n_sites);
+    for (size_t l = 0; l < plan.launches.size(); l++) {
+        const int64_t k0 = plan.launches[l].first, k1 = plan.launches[l].second, S = k1 - k0, j0 = plan.run[k0];
+        int64_t nl = 0, items = 0;
+        for (int64_t k = k0; k < k1; k++) {
+            nl += sites[plan.run[k]].n[0] + sites[plan.run[k]].n[1];
+            items += sc_site_chunks(sites[plan.run[k]]);
+        }
+        const int64_t e0 = whole ? 0 : off[l];
+        // after the block's arrays: the two prefix arrays, the slots, the admissible-cut counts and the entries
+        const size_t b_pre = align_up((size_t)nl * 8, 256), b_slot = align_up((size_t)items * sizeof(SsSlot), 256), b_cnt = align_up((size_t)S * 4, 256);
+        size_t scan_bytes = 0;
+        RD_HIP(rocprim::inclusive_scan(nullptr, scan_bytes, rocprim::make_transform_iterator((const uint64_t*)nullptr, SsValue()), (int64_t*)nullptr,
+                                       (size_t)nl, rocprim::plus<int64_t>(), st));
+        ScWs W;
+        W.extra_bytes = 2 * b_pre + b_slot + b_cnt + (size_t)S * sizeof(SsOut);
+        W.min_tmp = scan_bytes;
+        if ((rc = sc_run(ctx, st, (whole ? site : g_site.data()) + e0, (whole ? cond : g_cond.data()) + e0, (whole ? value : g_value.data()) + e0, nl, S,
+                         0, end_bit, W)))
+            return rc;
+        int64_t *psum = (int64_t*)W.extra, *psq = (int64_t*)(W.extra + b_pre);
+        SsSlot* slot = (SsSlot*)(W.extra + 2 * b_pre);
+        int32_t* cnt = (int32_t*)(W.extra + 2 * b_pre + b_slot);
+        SsOut* out = (SsOut*)(W.extra + 2 * b_pre + b_slot + b_cnt);
+        size_t tb = W.tmp_bytes;
+        RD_HIP(rocprim::exclusive_scan(W.tmp, tb, W.n_chunk, W.item_off, 0u, (size_t)S + 1, rocprim::plus<uint32_t>(), st));
+        tb = W.tmp_bytes;
+        RD_HIP(rocprim::inclusive_scan(W.tmp, tb, rocprim::make_transform_iterator(W.sorted, SsValue()), psum, (size_t)nl, rocprim::plus<int64_t>(), st));
+        tb = W.tmp_bytes;
+        RD_HIP(rocprim::inclusive_scan(W.tmp, tb, rocprim::make_transform_iterator(W.sorted, SsSquare()), psq, (size_t)nl, rocprim::plus<int64_t>(), st));
+        RD_HIP(hipMemsetAsync(cnt, 0, (size_t)S * 4, st));
+        RD_HIP(hipMemsetAsync(out, 0, (size_t)S * sizeof(SsOut), st));
+        hipLaunchKernelGGL(ss_item_kernel, dim3((unsigned)((items + SC_WAVES - 1) / SC_WAVES)), dim3(64 * SC_WAVES), 0, st, W.sorted, psum, W.seg, W.item_off,
+                           (uint32_t)S, (uint32_t)items, W.n_seg, min_frac_q16, slot, cnt);
+        RD_HIP(hipGetLastError());
+        hipLaunchKernelGGL(ss_pick_kernel, dim3((unsigned)((S + SC_WAVES - 1) / SC_WAVES)), dim3(64 * SC_WAVES), 0, st, W.sorted, psum, psq, W.seg, W.item_off,
+                           (uint32_t)S, (uint32_t)items, W.n_seg, slot, cnt, out);
+        RD_HIP(hipGetLastError());
+        got.resize((size_t)S);
+        uint32_t n_seg = 0, n_it = 0;
+        RD_HIP(hipMemcpyAsync(&n_seg, W.n_seg, 4, hipMemcpyDeviceToHost, st));
+        RD_HIP(hipMemcpyAsync(&n_it, W.item_off + S, 4, hipMemcpyDeviceToHost, st));
+        RD_HIP(hipMemcpyAsync(got.data(), out, (size_t)S * sizeof(SsOut), hipMemcpyDeviceToHost, st));
+        RD_HIP(hipStreamSynchronize(st));
+        if ((int64_t)n_seg != S || (int64_t)n_it != items) {
+            rd_set_error("rd_site_split: internal: the device found %u sites and %u chunks in a launch of %lld and %lld", n_seg, n_it, (long long)S,
+                         (long long)items);
+            return RD_ERR_STATE;
+        }
+        for (int64_t j = 0; j < S; j++) ss_scatter(got[(size_t)j], j0 + j, A);
+    }
+    if (plan.too_large) {
+        const ScSite& s = sites[(size_t)plan.first_too_large];
+        rd_set_error("rd_site_split: site %u (%lld events) needs %lld bytes of workspace, over the budget of %lld; %lld site(s) not split "
+                     "(status RD_SITE_TOO_LARGE), the others were", s.site, (long long)(s.n[0] + s.n[1]), (long long)ss_site_bytes(s),
+                     (long long)budget_bytes, (long long)plan.too_large);
+        return RD_ERR_NOMEM;
+    }
     return RD_OK;
 }
 #endif  // __HIPCC__

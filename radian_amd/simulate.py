@@ -4,7 +4,7 @@
            [--kmer-table T.tsv [--fill-missing] | --model-seed S --kmer 5] [--protein-coding | --field N --value S]
            [--length-median 1200 --length-sigma 0.5 --min-length 200] [--tail-median 80 --tail-sigma 0.5 | --tail N] [--adapter SEQ]
            [--lead-samples 400 --lead-level 2.0 --lead-sd 0.3] [--dwell-min-frac 0.2] [--median 600 --mad 60] [--noise-scale 1.0]
-           [--modify sites.tsv] [--reads-per-file 4000]
+           [--modify sites.tsv [--mods-out mods.tsv]] [--reads-per-file 4000]
            [--shards DIR --chunk-len 1024 --step-size 128 --outlier-clip 4 --val-fraction 0.05 --windows-per-shard 50000 --max-label-len 255]
            [--device N] [--batch-reads R] [--budget-bytes B]
 
@@ -22,6 +22,8 @@ the k-mer, sd 0.3 z, mean dwell 30 samples, the all-A k-mer at sd 0.04 z.  The s
 
 --modify takes rows `ref_name pos level_shift dwell_scale fraction` (pos 0-based on the transcript, level_shift in z, no header): a read
 that covers the site is modified there with probability `fraction` (drawn on the host): that base's level moves and its dwell stretches.
+--mods-out writes that draw: rows `read_id ref_name pos modified` (0 / 1, with a header), one for every read and --modify site the read
+covers, in read order; no other output changes with it.
 
 Outputs under out_dir: sim_{k:04d}.fast5 (--reads-per-file each); truth.tsv (read_id ref_name ref_start ref_end n_samples lead tail_nt
 tail_start tail_end -- the tail is the samples of the bases whose whole k-mer is A, -1 -1 without one); read_ref.tsv (what `align`,
@@ -143,11 +145,13 @@ def build_model(args):
 # ------------------------------------------------------------------------------------------------ the reads
 class ReadPlan:
     """what the host decides about one read: transcript t, the fragment [ref_start, ref_end) of it, the tail's length, the key and the
-    modified sites [(transcript position, level_shift_q10, dwell_scale_q8)]"""
-    __slots__ = ("read_id", "t", "ref_start", "ref_end", "tail", "key", "mods")
+    modified sites [(transcript position, level_shift_q10, dwell_scale_q8)]; covered: [(transcript position, 0 / 1)] of every --modify
+    site the fragment covers, in the file's order (--mods-out)"""
+    __slots__ = ("read_id", "t", "ref_start", "ref_end", "tail", "key", "mods", "covered")
 
-    def __init__(self, read_id, t, ref_start, ref_end, tail, key, mods=()):
+    def __init__(self, read_id, t, ref_start, ref_end, tail, key, mods=(), covered=()):
         self.read_id, self.t, self.ref_start, self.ref_end, self.tail, self.key, self.mods = read_id, t, ref_start, ref_end, tail, key, list(mods)
+        self.covered = list(covered)
 
 
 def read_sites(path, tr):
@@ -187,12 +191,24 @@ def draw_reads(args, tr, rng, sites=None):
             raise SystemExit("simulate: a thousand draws in a row gave no fragment of ACGTU alone")
         tail = args.tail if args.tail is not None else int(round(args.tail_median * math.exp(args.tail_sigma * rng.standard_normal())))
         key = rng.integers(0, 1 << 32, 2, dtype=np.uint64).astype(np.uint32)
-        mods = []
+        mods, covered = [], []
         for pos, shift, scale, frac in (sites or {}).get(t, ()):
-            if n - F <= pos < n and rng.random() < frac:
-                mods.append((pos, shift, scale))
-        plans.append(ReadPlan(f"sim{args.seed}_{i:08d}", t, n - F, n, max(tail, 0), key, mods))
+            if n - F <= pos < n:
+                hit = rng.random() < frac
+                covered.append((pos, int(hit)))
+                if hit:
+                    mods.append((pos, shift, scale))
+        plans.append(ReadPlan(f"sim{args.seed}_{i:08d}", t, n - F, n, max(tail, 0), key, mods, covered))
     return plans
+
+
+def write_mods(path, plans, tr):
+    """--mods-out: read_id ref_name pos modified for every (read, --modify site it covers), from the draw of draw_reads"""
+    with open(path, "w") as f:
+        f.write("read_id\tref_name\tpos\tmodified\n")
+        for p in plans:
+            for pos, hit in p.covered:
+                f.write(f"{p.read_id}\t{tr.names[p.t]}\t{pos}\t{hit}\n")
 
 
 def compose(plan, tr, adapter):
@@ -382,6 +398,7 @@ def build_parser():
     ap.add_argument("--mad", default=60.0, type=float, help="DAQ units of one MAD: z = (x - median) / (1.4826 mad)")
     ap.add_argument("--noise-scale", default=1.0, type=float, help="multiplies every sd")
     ap.add_argument("--modify", default=None, help="sites to modify: ref_name pos level_shift dwell_scale fraction")
+    ap.add_argument("--mods-out", default=None, help="with --modify: write which reads were modified at which site (read_id ref_name pos modified)")
     ap.add_argument("--reads-per-file", default=4000, type=int)
     ap.add_argument("--shards", default=None, help="also write truth-labelled training shards under this directory")
     ap.add_argument("--chunk-len", default=WINDOW, type=int)
@@ -419,6 +436,8 @@ def check_args(args):
         raise SystemExit("simulate: --dwell-min-frac must be 0..1")
     if not -32768 <= args.median <= 32767 or not 1 <= round(args.mad * 1.4826 * 1024) <= 1 << 26:
         raise SystemExit("simulate: --median must be an int16 value and --mad positive, at most 44000")
+    if args.mods_out is not None and not args.modify:
+        raise SystemExit("simulate: --mods-out goes with --modify")
     if args.shards:
         if args.chunk_len != WINDOW:
             raise SystemExit(f"simulate: --chunk-len must be {WINDOW}: a shard's `signal` feature holds {WINDOW} samples")
@@ -438,6 +457,8 @@ def main(argv=None):
     model = build_model(args)
     sites = read_sites(args.modify, tr) if args.modify else None
     plans = draw_reads(args, tr, np.random.Generator(np.random.PCG64(args.seed)), sites)
+    if args.mods_out is not None:
+        write_mods(args.mods_out, plans, tr)
     os.makedirs(args.output, exist_ok=True)
     for f in os.listdir(args.output):   # a rerun into the same directory leaves no file of the run before
         if f.startswith("sim_") and f.endswith(".fast5"):
