@@ -807,6 +807,59 @@ int rd_sigmap_host(const int16_t* raw, int64_t n_raw, int n_q, const int64_t* q_
                    int32_t* best_org);
 int64_t rd_sigmap_workspace_bytes(int64_t n_rows, int64_t n_states, int64_t n_tgt_in_range);
 
+/* ---- event detection: a read's raw samples cut into stretches of roughly constant level (segment.hip) -------
+ * NO reference behaviour.  Two sliding Welch t-tests, a short and a long window, and non-maximum suppression of their t^2; no sequential
+ * peak state as in scrappie's detector.  Integer arithmetic only; met exactly.  Read r is samples raw + read_off[r] .. read_off[r+1]
+ * (T of them).  Parameters (anything outside its range is RD_ERR_ARG): w1 2..32 (short window); w2 0 (detector 2 off) or
+ * w1 < w2 <= 64 (long window); th1, th2 (uint32: the t^2 thresholds in sixteenths); v0 1..65536 (variance floor in DAQ^2).
+ * For a detector with window w and a sample i in [w, T - w]:
+ *   S1, Q1 = the sum and the sum of squares of x[i - w .. i), S2, Q2 of x[i .. i + w)
+ *   N(i) = w (S1 - S2)^2; D(i) = w Q1 - S1^2 + w Q2 - S2^2 + 2 w^2 v0; t^2(i) = N / D.  Outside that range N = 0, D = 1.
+ *   N < 2^50 and 2 w^2 <= D < 2^44; t(j) < t(i) means N(j) D(i) < N(i) D(j), the products in 128 bits
+ *   candidate  N(i) > 0 and 16 N(i) >= th D(i)
+ *   peak       a candidate with t(j) < t(i) for every j in [i - w, i) and t(j) <= t(i) for every j in (i, i + w], j inside the read:
+ *              non-maximum suppression of radius w, ties to the smaller index
+ *   boundary   a peak of detector 1, or a peak of detector 2 with no peak of detector 1 at |j - i| < w2
+ *   events     event 0 starts at sample 0, every boundary starts the next event; an event ends where the next starts, or at T.
+ *              Boundaries lie more than w1 apart: every event is non-empty and n_events <= T / (w1 + 1) + 1 = rd_segment_max_events
+ *   status     in this order: T == 0 RD_SEGMENT_EMPTY; T > 2^30 RD_SEGMENT_TOO_LONG (its samples are never read); over the budget alone
+ *              RD_SEGMENT_TOO_LARGE; otherwise RD_SEGMENT_OK
+ *   outputs    per read status and n_events (0 unless OK).  Per event, at ev_off[r] + e (ev_off [n_reads + 1], non-decreasing; an OK
+ *              read's room ev_off[r+1] - ev_off[r] is at least rd_segment_max_events(T, w1)): ev_start (sample of the read), ev_sum,
+ *              ev_sumsq, ev_min, ev_max over its samples, ev_src (0 for event 0, otherwise 1 or 2: the detector that cut it).  With
+ *              sc_lo / sc_hi (both or neither; absolute indices into raw, read_off[r] <= sc_lo[r] <= sc_hi[r] <= read_off[r+1]) m2 and
+ *              d4 of an OK read are the scale of raw[sc_lo[r] .. sc_hi[r]) by rd_eventalign's rule, (0, 0) for an empty window and for
+ *              every other status; without them m2 and d4 may be null
+ * A read never affects its neighbours; a result does not depend on the batch, the order, the budget or the launches.  RD_ERR_ARG before
+ * anything is launched: a null pointer, offsets that are not monotone, too little room for a read's events, a scale window outside its
+ * read, a parameter outside its range.  n_reads == 0 is RD_OK.
+ *   rd_segment        on the GPU; synchronous, uses the context's stream.  budget_bytes and RD_ERR_NOMEM as rd_polya_segment:
+ *                     rd_segment_workspace_bytes per read, 0 = a quarter of the free device memory; a read that alone exceeds it is not
+ *                     looked at: RD_SEGMENT_TOO_LARGE, and the call returns RD_ERR_NOMEM naming it after doing the others
+ *   rd_segment_host   host, no GPU: the same rules (csrc/segment_rules.h) in plain loops
+ *   rd_segment_workspace_bytes   8 T + T / 32 + 32 (T / (w1 + 1) + 1) + 8 (T / 2048 + 1) + 8192: the samples, two flag bytes and a scan
+ *                     entry per sample, the scan's own block, 29 B per possible event, the tile descriptors
+ *   rd_segment_max_events        T / (w1 + 1) + 1 (-1 for a negative T or a w1 outside its range, as rd_segment_workspace_bytes)
+ *   rd_segment_diag_tstat  the first stage alone, through the same kernel, for stage tests (it changes no result and has no budget; at
+ *                     most 2^31 - 1 samples, no read above 2^30): with n = read_off[n_reads] - read_off[0] and g = the sample's index
+ *                     minus read_off[0], t_num / t_den [2][n] hold N and D of detector d at [d n + g] (N = 0, D = 1 throughout for
+ *                     w2 == 0) and peak [n] bit 0 for a peak of detector 1, bit 1 of detector 2 */
+#define RD_SEGMENT_OK 0
+#define RD_SEGMENT_EMPTY 1
+#define RD_SEGMENT_TOO_LONG 2
+#define RD_SEGMENT_TOO_LARGE 3
+int rd_segment(rd_ctx* ctx, const int16_t* raw, const int64_t* read_off, int n_reads, int w1, int w2, uint32_t th1, uint32_t th2, int v0,
+               const int64_t* sc_lo, const int64_t* sc_hi, const int64_t* ev_off, int64_t budget_bytes, int32_t* status, int32_t* n_events,
+               int32_t* m2, int32_t* d4, int32_t* ev_start, int64_t* ev_sum, int64_t* ev_sumsq, int16_t* ev_min, int16_t* ev_max,
+               uint8_t* ev_src);
+int rd_segment_host(const int16_t* raw, const int64_t* read_off, int n_reads, int w1, int w2, uint32_t th1, uint32_t th2, int v0,
+                    const int64_t* sc_lo, const int64_t* sc_hi, const int64_t* ev_off, int32_t* status, int32_t* n_events, int32_t* m2,
+                    int32_t* d4, int32_t* ev_start, int64_t* ev_sum, int64_t* ev_sumsq, int16_t* ev_min, int16_t* ev_max, uint8_t* ev_src);
+int64_t rd_segment_workspace_bytes(int64_t n_samples, int w1);
+int64_t rd_segment_max_events(int64_t n_samples, int w1);
+int rd_segment_diag_tstat(rd_ctx* ctx, const int16_t* raw, const int64_t* read_off, int n_reads, int w1, int w2, uint32_t th1, uint32_t th2,
+                          int v0, uint64_t* t_num, uint64_t* t_den, uint8_t* peak);
+
 /* ---- model evaluation on labelled windows: the reference's val_loss (radian/model.py:77-98, radian/train.py:48-79) ------------
  * Labelled windows as the reference stores them: TFRecord shards of tf.train.Example records (radian/data.py:9-31), read on the
  * HOST without TensorFlow (tfrecord.hip).  Framing: u64 length, u32 masked crc32c of it, the data, u32 masked crc32c of the data;

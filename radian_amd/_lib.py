@@ -119,6 +119,11 @@ SIGNATURES = {
     "rd_sigmap": (c_i, [c_vp, c_vp, c_i64, c_i] + [c_vp] * 10 + [c_i, c_i] + [c_vp] * 3 + [c_i, c_i64] + [c_vp] * 7),
     "rd_sigmap_host": (c_i, [c_vp, c_i64, c_i] + [c_vp] * 10 + [c_i, c_i] + [c_vp] * 3 + [c_i] + [c_vp] * 7),
     "rd_sigmap_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
+    "rd_segment": (c_i, [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_u32, c_u32, c_i, c_vp, c_vp, c_vp, c_i64] + [c_vp] * 10),
+    "rd_segment_host": (c_i, [c_vp, c_vp, c_i, c_i, c_i, c_u32, c_u32, c_i, c_vp, c_vp, c_vp] + [c_vp] * 10),
+    "rd_segment_workspace_bytes": (c_i64, [c_i64, c_i]),
+    "rd_segment_max_events": (c_i64, [c_i64, c_i]),
+    "rd_segment_diag_tstat": (c_i, [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_u32, c_u32, c_i, c_vp, c_vp, c_vp]),
     "rd_tfrecord_open": (c_i, [ctypes.c_char_p, ctypes.POINTER(c_vp)]),
     "rd_tfrecord_open_mem": (c_i, [c_vp, c_sz, ctypes.POINTER(c_vp)]),
     "rd_tfrecord_close": (None, [c_vp]),

@@ -181,6 +181,73 @@ def polya_workspace_bytes(n_samples, win):
     return int(_lib.load().rd_polya_workspace_bytes(int(n_samples), int(win)))
 
 
+# rd_segment per-read status (include/radian_hip.h RD_SEGMENT_*)
+SEGMENT_OK, SEGMENT_EMPTY, SEGMENT_TOO_LONG, SEGMENT_TOO_LARGE = 0, 1, 2, 3
+SEGMENT_STATUS_NAMES = ("ok", "empty", "too-long", "too-large")
+SEGMENT_EVENT_FIELDS = (("start", np.int32), ("sum", np.int64), ("sumsq", np.int64), ("min", np.int16), ("max", np.int16), ("src", np.uint8))
+
+
+def segment_th(t):
+    """a threshold on t as the integer the C ABI takes: t^2 in sixteenths"""
+    return int(np.rint(16.0 * float(t) * float(t)))
+
+
+class SegmentParams:
+    """rd_segment's parameters, all integers (the contract is in include/radian_hip.h).  The defaults are `segment`'s."""
+    __slots__ = ("w1", "w2", "th1", "th2", "v0")
+
+    def __init__(self, w1=4, w2=12, th1=segment_th(2.5), th2=segment_th(5.0), v0=1):
+        self.w1, self.w2, self.th1, self.th2, self.v0 = int(w1), int(w2), int(th1), int(th2), int(v0)
+
+    def args(self):
+        return (self.w1, self.w2, self.th1, self.th2, self.v0)
+
+
+class SegmentResult:
+    """status, n_events (int32 per read), m2 / d4 (int32 per read: the scale of the read's scale window, zeros without one) and per read a
+    dict of its events' arrays: start (int32), sum / sumsq (int64), min / max (int16), src (uint8)"""
+    __slots__ = ("status", "n_events", "m2", "d4", "events")
+
+
+def _segment_call(fn, raws, params, scale_windows, extra):
+    flat, off = Backend._pack_raw(raws)
+    n = len(raws)
+    room = [max(int(_lib.load().rd_segment_max_events(int(off[r + 1] - off[r]), params.w1)), 0) for r in range(n)]
+    ev_off = np.concatenate([[0], np.cumsum(room)]).astype(np.int64)
+    res = SegmentResult()
+    res.status, res.n_events, res.m2, res.d4 = (np.zeros(n + 1, np.int32) for _ in range(4))
+    ev = [np.zeros(int(ev_off[-1]) + 1, dt) for _, dt in SEGMENT_EVENT_FIELDS]
+    sc_lo = sc_hi = None
+    if scale_windows is not None:
+        sc_lo = np.array([off[r] + scale_windows[r][0] for r in range(n)] + [0], np.int64)
+        sc_hi = np.array([off[r] + scale_windows[r][1] for r in range(n)] + [0], np.int64)
+    rc = fn(_p(flat), _p(off), n, *params.args(), None if sc_lo is None else _p(sc_lo), None if sc_hi is None else _p(sc_hi), _p(ev_off), *extra,
+            _p(res.status), _p(res.n_events), _p(res.m2), _p(res.d4), *[_p(a) for a in ev])
+    res.status, res.n_events, res.m2, res.d4 = res.status[:n], res.n_events[:n], res.m2[:n], res.d4[:n]
+    res.events = [{name: a[int(ev_off[r]):int(ev_off[r]) + int(res.n_events[r])].copy() for (name, _), a in zip(SEGMENT_EVENT_FIELDS, ev)}
+                  for r in range(n)]
+    return rc, res
+
+
+def segment_host(raws, params, scale_windows=None):
+    """Backend.segment on the host (rd_segment_host: the same rules in plain loops; no GPU, no context)"""
+    L = _lib.load()
+    rc, res = _segment_call(L.rd_segment_host, raws, params, scale_windows, ())
+    if rc != 0:
+        raise RadianHipError(L.rd_last_error().decode())
+    return res
+
+
+def segment_workspace_bytes(n_samples, w1):
+    """device workspace Backend.segment needs for one read (rd_segment_workspace_bytes)"""
+    return int(_lib.load().rd_segment_workspace_bytes(int(n_samples), int(w1)))
+
+
+def segment_max_events(n_samples, w1):
+    """the event slots a read of n_samples needs (rd_segment_max_events)"""
+    return int(_lib.load().rd_segment_max_events(int(n_samples), int(w1)))
+
+
 # rd_site_compare per-site status (include/radian_hip.h RD_SITE_*)
 SITE_OK, SITE_ONE_SIDED, SITE_DEEP, SITE_TOO_LARGE = 0, 1, 2, 3
 SITE_STATUS_NAMES = ("ok", "one-sided", "deep", "too-large")
@@ -1606,6 +1673,29 @@ class Backend:
                                                   params.hi_q, _p(m2), _p(d4), _p(thr), _p(S), _p(Q), _p(F)))
         cut = [(int(woff[r]), int(woff[r + 1])) for r in range(n)]
         return m2[:n], d4[:n], thr[:n], [(S[a:b].copy(), Q[a:b].copy(), F[a:b].copy()) for a, b in cut]
+
+    # ------------------------------------------------------------------ event detection
+    def segment(self, raws, params, scale_windows=None, budget_bytes=0, allow_too_large=False):
+        """Every read's raw samples cut into events (rd_segment, on the GPU): raws -- one int16 array per read; params -- a SegmentParams;
+        scale_windows -- per read (lo, hi) in the read's samples, whose scale comes back as m2 / d4.  budget_bytes: device workspace per
+        launch, 0 = a quarter of free memory.  A read that does not fit it raises, unless allow_too_large: status SEGMENT_TOO_LARGE.
+        -> SegmentResult."""
+        rc, res = _segment_call(lambda *a: self._L.rd_segment(self._h, *a), raws, params, scale_windows, (int(budget_bytes),))
+        if rc != 0 and not (allow_too_large and rc == -4 and (res.status == SEGMENT_TOO_LARGE).any()):
+            self._check(rc)
+        return res
+
+    segment_host = staticmethod(segment_host)
+
+    def segment_diag_tstat(self, raws, params):
+        """rd_segment_diag_tstat (tests): the first stage alone.  -> per read (N uint64 [2][T], D uint64 [2][T], peak bits uint8 [T])"""
+        flat, off = self._pack_raw(raws)
+        n, tot = len(raws), int(off[-1])
+        F = np.zeros(tot + 1, np.uint8)
+        Nc, Dc =np.zeros(2 * tot + 1, np.uint64), np.zeros(2 * tot + 1, np.uint64)
+        self._check(self._L.rd_segment_diag_tstat(self._h, _p(flat), _p(off), n, *params.args(), _p(Nc), _p(Dc), _p(F)))
+        N, D = Nc[:2 * tot].reshape(2, tot), Dc[:2 * tot].reshape(2, tot)
+        return [(N[:, int(off[r]):int(off[r + 1])].copy(), D[:, int(off[r]):int(off[r + 1])].copy(), F[int(off[r]):int(off[r + 1])].copy()) for r in range(n)]
 
     # ------------------------------------------------------------------ two-sample site comparison (DESIGN.md section 20)
     def site_compare(self, site, cond, value, n_sites, budget_bytes=0, capacity=None, allow_too_large=False):

@@ -235,6 +235,7 @@ struct rd_ctx {
     DevBuf ws_calign;               // rd_ctc_align_* (ctcalign.hip): a launch's descriptors and results (its DP workspace is ws_align, under the budget)
     DevBuf ws_events, ws_events_io; // rd_event_stats* (events.hip): a launch's group descriptors; the step and event arrays of a host-pointer call
     DevBuf ws_polya, ws_polya_io;   // rd_polya_* (polya.hip): a launch's descriptors, scales and window arrays; the per-read results of a host-pointer call
+    DevBuf ws_segment;              // rd_segment* (segment.hip): a launch's descriptors, flags, scan and dense event arrays
     DevBuf ws_sim;                  // rd_sim_* (sim.hip): the model tables, then a launch's bases, dwells, positions and samples
     DevBuf ws_eval, ws_eval_model;  // rd_eventalign (eventalign.hip): a launch's descriptors, scales and results (its DP workspace is ws_align, under the budget); the pore-model tables
     DevBuf ws_site;                 // rd_site_* (sitecmp.hip): a launch's events, keys, segments and per-site results

@@ -3,6 +3,7 @@ that `eventalign`, `align`, `label_build` and `pileup` take.  No basecall, no si
 
     python -m radian_amd.sigmap fast5_dir transcripts.fa[.gz] -o read_ref.tsv (--kmer-table T.tsv [--fill-missing] | --model-seed S --kmer 5)
            --bounds PATH [--start-slack 32] [--query-samples 2048] [--tail-pad 8] [--max-cand 8] [--cand-slack 2] [--max-cost 0]
+           [--events [--w1 4 --t1 2.5 --w2 12 --t2 5.0 --var-floor 1] [--query-events 256]]
            [--paf PATH] [--summary PATH] [--protein-coding | --field N --value S] [--bg-sd 1.0]
            [--device N] [--batch-reads R] [--budget-bytes B]
 
@@ -21,6 +22,10 @@ pass 2       the read's last --query-samples samples (never before t_lo), on pas
              state to its target's end.  Transcripts that share their 3' end tie exactly in pass 1; the 5' end of the read tells them apart.
              The read goes to the candidate with the smallest sum of both scores, the smaller transcript index on ties; the candidates
              that tie with it are counted (n_tied).  A read that ends inside what its candidates share stays tied.
+--events     the rows of both passes are EVENTS, not samples: rd_segment (`segment`'s options) cuts the samples from
+             t_lo on, and a row is an event's mean, floor((2 sum + n) / (2 n)), on the scale of the samples from t_lo on.  Pass 1 takes the
+             first --query-events events, pass 2 the last.  One event is one row whatever its length; there are still no skips, so an event
+             that merges two bases costs a mismatch.  --cand-slack and --max-cost are per row.  --summary gains the column n_events.
 --max-cost   c > 0: a read whose sum exceeds c x the rows of both passes is `unmapped` (1/32 nat per sample; UNCALIBRATED; 0 = off).
 
 read_ref.tsv `map`'s format: one header line, then `read_id <tab> transcript name <tab> span` per mapped read, in input order.  The span runs,
@@ -42,10 +47,11 @@ import sys
 import numpy as np
 
 from . import fast5
-from .backend import (Backend, SigmapPanel, SIGMAP_EMPTY, SIGMAP_MAD_ZERO, SIGMAP_MAX_T, SIGMAP_OK, SIGMAP_TOO_LARGE)
+from .backend import (Backend, SigmapPanel, SEGMENT_OK, SEGMENT_TOO_LARGE, SIGMAP_EMPTY, SIGMAP_MAD_ZERO, SIGMAP_MAX_T, SIGMAP_OK, SIGMAP_TOO_LARGE)
 from .eventalign import model_tables, read_bounds, window_start
 from .fastq import _batches
 from .map import TSV_HEADER, Transcripts
+from .segment import add_detector_arguments, check_detector_arguments, event_ends, event_rows, params_of
 from .simulate import read_kmer_table, standin_tables
 
 STATUSES = ("ok", "no-bound", "signal", "too-large", "unmapped")
@@ -82,11 +88,27 @@ class Panel:
         return L - 1 - (max(end, self.pad) - self.pad), L - (max(org, self.pad) - self.pad)
 
 
-def map_batch(sig, batch, panel, bounds, args):
+def event_arrays(seg, windows):
+    """seg(raws) -> SegmentResult is Backend.segment or segment_host bound to the detector's parameters, with every window as its own scale
+    window.  -> (the windows' event rows back to back, the first row of every window, its rows (0: no scale or no events), the result)"""
+    ev = seg(windows)
+    parts, cnt = [], np.zeros(len(windows), dtype=np.int64)
+    for k, x in enumerate(windows):
+        if int(ev.status[k]) != SEGMENT_OK or int(ev.d4[k]) == 0:
+            continue
+        e = ev.events[k]
+        parts.append(event_rows(e["sum"], event_ends(e["start"].astype(np.int64), len(x)) - e["start"]))
+        cnt[k] = len(parts[-1])
+    first = np.zeros(len(windows), dtype=np.int64)
+    first[1:] = np.cumsum(cnt)[:-1]
+    return (np.concatenate(parts) if parts else np.zeros(1, np.int16)), first, cnt, ev
+
+
+def map_batch(sig, batch, panel, bounds, args, seg=None):
     """batch: [(read id, raw int16)].  sig(raw, q_lo, q_hi, **kw) -> SigmapResult is Backend.sigmap or sigmap_host bound to the panel and the
-    model.  -> one dict per read: id, status, n, t_lo and, from pass 1 on, m2, d4, T1, T2, s1, s2 (the chosen candidate's scores), j (target), S, E, score, score2
+    model; seg (--events): see event_arrays.  -> one dict per read: id, status, n, t_lo and, from pass 1 on, m2, d4, T1, T2, s1, s2 (the chosen candidate's scores), j (target), S, E, score, score2
     (the best sum on another target or -1), n_cand, n_tied"""
-    Q = args.query_samples
+    Q = args.query_events if seg is not None else args.query_samples
     off = np.zeros(len(batch) + 1, dtype=np.int64)
     off[1:] = np.cumsum([len(r[1]) for r in batch])
     flat = np.concatenate([np.asarray(r[1], dtype=np.int16) for r in batch]) if off[-1] else np.zeros(1, np.int16)
@@ -102,15 +124,22 @@ def map_batch(sig, batch, panel, bounds, args):
     base = np.array([off[i] for i in todo], dtype=np.int64)
     n = np.array([rows[i]["n"] for i in todo], dtype=np.int64)
     lo = np.array([rows[i]["t_lo"] for i in todo], dtype=np.int64)
-    p1 = sig(flat, base + lo, base + np.minimum(n, lo + Q), sc_lo=base + lo, sc_hi=base + n, n_best=args.max_cand)
+    if seg is None:      # the rows are the samples [first, first + cnt) of flat
+        arr, first, cnt = flat, base + lo, n - lo
+        p1 = sig(flat, base + lo, base + np.minimum(n, lo + Q), sc_lo=base + lo, sc_hi=base + n, n_best=args.max_cand)
+    else:                # ... the events [first, first + cnt) of arr
+        arr, first, cnt, ev = event_arrays(seg, [flat[base[k] + lo[k]:base[k] + n[k]] for k in range(len(todo))])
+        p1 = sig(arr, first, first + np.minimum(cnt, Q), m2=ev.m2, d4=ev.d4, n_best=args.max_cand)
     second = []       # (index into todo, target, origin state, pass-1 score)
     for k, i in enumerate(todo):
         row, st = rows[i], int(p1.status[k])
         row.update(m2=int(p1.m2[k]), d4=int(p1.d4[k]))
+        if seg is not None:
+            row.update(m2=int(ev.m2[k]), d4=int(ev.d4[k]), n_events=int(ev.n_events[k]))
         if st != SIGMAP_OK:
-            row["status"] = _SM_STATUS[st]
+            row["status"] = "too-large" if seg is not None and int(ev.status[k]) == SEGMENT_TOO_LARGE else _SM_STATUS[st]
             continue
-        T1 = int(min(n[k], lo[k] + Q) - lo[k])
+        T1 = int(min(cnt[k], Q))
         row["T1"] = T1
         for r in range(args.max_cand):
             if p1.tgt[k, r] >= 0 and p1.score[k, r] <= p1.score[k, 0] + args.cand_slack * T1:
@@ -118,14 +147,14 @@ def map_batch(sig, batch, panel, bounds, args):
     if second:
         ks = np.array([s[0] for s in second])
         tg = np.array([s[1] for s in second])
-        p2 = sig(flat, base[ks] + np.maximum(lo[ks], n[ks] - Q), base[ks] + n[ks], m2=p1.m2[ks], d4=p1.d4[ks],
+        p2 = sig(arr, first[ks] + np.maximum(0, cnt[ks] - Q), first[ks] + cnt[ks], m2=p1.m2[ks], d4=p1.d4[ks],
                  s_lo=panel.off[tg] + np.array([s[2] for s in second]), s_hi=panel.off[tg + 1], n_best=1)
     per = {}
     for c, (k, j, org, s1) in enumerate(second):
         per.setdefault(k, []).append((c, j, org, s1))
     for k, cands in per.items():
         row = rows[todo[k]]
-        T2 = int(n[k] - max(lo[k], n[k] - Q))
+        T2 = int(min(cnt[k], Q))
         done = sorted((s1 + int(p2.score[c, 0]), j, org, int(p2.end[c, 0]), s1, int(p2.score[c, 0])) for c, j, org, s1 in cands if int(p2.status[c]) == SIGMAP_OK)
         if not done:
             row["status"] = "too-large"
@@ -158,21 +187,25 @@ def summary_row(row, panel):
                  row["n_cand"], row["n_tied"]]
     else:
         cols += ["-"] * 7
+    if "n_events" in row:
+        cols.append(row["n_events"])
     return "\t".join(str(c) for c in cols) + "\n"
 
 
-def run(args, sig, reads, panel, bounds):
+def run(args, sig, reads, panel, bounds, seg=None):
     """reads: iterable of (file stem, read id, raw int16 samples) in input order.  Writes the files, returns the counters."""
     st = {"reads": 0, "multi": 0, "tied": 0, "per_sample": [], "margin": [], **{s: 0 for s in STATUSES}}
     outs = [open(args.output, "w"), open(args.paf, "w") if args.paf else None, open(args.summary, "w") if args.summary else None]
     try:
         outs[0].write(TSV_HEADER)
         if outs[2]:
-            outs[2].write("\t".join(SUMMARY_COLUMNS) + "\n")
+            outs[2].write("\t".join(SUMMARY_COLUMNS + (("n_events",) if seg is not None else ())) + "\n")
         for batch in _batches(reads, args.batch_reads):
             st["reads"] += len(batch)
-            for row in map_batch(sig, [(rid, raw) for _, rid, raw in batch], panel, bounds, args):
+            for row in map_batch(sig, [(rid, raw) for _, rid, raw in batch], panel, bounds, args, seg):
                 st[row["status"]] += 1
+                if seg is not None and "n_events" not in row:
+                    row["n_events"] = "-"
                 if outs[2]:
                     outs[2].write(summary_row(row, panel))
                 if row["status"] != "ok":
@@ -216,6 +249,9 @@ def build_parser():
     ap.add_argument("--bounds", required=True, help="TSV with read_id and tail_end columns (polya.tsv, truth.tsv): where the transcript body starts")
     ap.add_argument("--start-slack", default=32, type=int, help="samples before tail_end the first query may start at")
     ap.add_argument("--query-samples", default=2048, type=int, help="samples of either query (1..16384)")
+    ap.add_argument("--events", action="store_true", help="the rows are events (rd_segment), not samples; --query-events of them per pass")
+    add_detector_arguments(ap)
+    ap.add_argument("--query-events", default=256, type=int, help="with --events: events of either query (1..16384)")
     ap.add_argument("--tail-pad", default=8, type=int, help="A's in front of every target")
     ap.add_argument("--max-cand", default=8, type=int, help="targets pass 1 keeps (1..8)")
     ap.add_argument("--cand-slack", default=2.0, type=float, help="a candidate scores within this x rows of the best (1/32 nat per sample; uncalibrated)")
@@ -249,6 +285,9 @@ def check_args(args):
             or not 1 <= args.max_cand <= 8 or args.cand_slack < 0 or args.max_cost < 0 or not 0.01 <= args.bg_sd <= 32):
         raise SystemExit("sigmap: --batch-reads at least 1; --budget-bytes, --start-slack, --cand-slack and --max-cost at least 0; --query-samples "
                          "1..16384; --tail-pad 0..64; --max-cand 1..8; --bg-sd 0.01..32")
+    check_detector_arguments(args, "sigmap")
+    if not 1 <= args.query_events <= SIGMAP_MAX_T:
+        raise SystemExit("sigmap: --query-events must be 1..16384")
     outs = [p for p in (args.output, args.paf, args.summary) if p]
     if len(set(os.path.abspath(p) for p in outs)) != len(outs):
         raise SystemExit("sigmap: -o, --paf and --summary must name different files")
@@ -280,7 +319,11 @@ def main(argv=None):
     with Backend(args.device) as be:
         def sig(raw, q_lo, q_hi, **kw):
             return be.sigmap(raw, packed, model, q_lo, q_hi, budget_bytes=args.budget_bytes, allow_too_large=True, **kw)
-        st = run(args, sig, reads, panel, bounds)
+        seg = None
+        if args.events:
+            def seg(raws):
+                return be.segment(raws, params_of(args), [(0, len(x)) for x in raws], budget_bytes=args.budget_bytes, allow_too_large=True)
+        st = run(args, sig, reads, panel, bounds, seg)
     sys.stdout.write(summary(panel, st))
     sys.stdout.flush()
     return st
