@@ -333,43 +333,41 @@ int rd_align_batch_run(rd_ctx* ctx, const char* who, const char* too_large_name,
     std::vector<uint8_t> ops_h;
     for (auto [k0, k1] : plan.launches) {
         const int nb = (int)(k1 - k0);
-        const size_t res_at = align_up((size_t)nb * sizeof(AlnPair), 256);
-        size_t at = res_at + align_up((size_t)nb * ALN_RES * 4, 256);
+        Carve c;   // (dry: the descriptors hold offsets into ws_align; the head of the block is staged on the host and copied whole)
+        c.take<AlnPair>((size_t)nb);
+        const size_t res_at = c.mark();
+        c.take<int32_t>((size_t)nb * ALN_RES);
         desc.resize(nb);
         for (int k = 0; k < nb; k++) {   // sequences first (one upload with the descriptors), then the device-only regions
             const int p = run[k0 + k];
             AlnPair& d = desc[k];
             d.n = (int32_t)(ref_off[p + 1] - ref_off[p]);
             d.m = (int32_t)(read_off[p + 1] - read_off[p]);
-            d.ref = (int64_t)at;
+            d.ref = (int64_t)c.mark();
             d.read = d.ref + d.n;
-            at += align_up((size_t)(d.n + d.m), 256);
+            c.take<uint8_t>((size_t)(d.n + d.m));
         }
-        const size_t up_bytes = at;
-        for (int k = 0; k < nb; k++) {   // op slots side by side (one copy back)
-            desc[k].ops = (int64_t)at;
-            at += (size_t)(desc[k].n + desc[k].m);
+        const size_t up_bytes = c.mark();
+        for (int k = 0; k < nb; k++) {   // op slots side by side, unrounded (one copy back)
+            desc[k].ops = (int64_t)c.mark();
+            c.take<uint8_t>((size_t)(desc[k].n + desc[k].m), 0, 1);
         }
-        const size_t ops_lo = up_bytes, ops_hi = at;
-        at = align_up(at, 256);
+        const size_t ops_lo = up_bytes, ops_hi = c.mark();
+        c.round();
         for (int k = 0; k < nb; k++) {
             AlnPair& d = desc[k];
             if (d.n > 0 && d.m > 0) {
-                d.bnd = (int64_t)(at / 4);
-                at += align_up((size_t)8 * (d.m + 1), 256);
-                d.dir = (int64_t)(at / 4);
-                at += align_up((size_t)((d.n + 63) / 64) * ((d.m + 126) / 64) * 8 * 64 * 4, 256);
+                d.bnd = (int64_t)(c.mark() / 4);
+                c.take<int32_t>(2 * ((size_t)d.m + 1));
+                d.dir = (int64_t)(c.mark() / 4);
+                c.take<uint32_t>((size_t)((d.n + 63) / 64) * ((d.m + 126) / 64) * 8 * 64);
             } else {
                 d.bnd = d.dir = 0;
             }
         }
-        at = align_up(at, 256);
-        const size_t extra_at = at;
-        at += (size_t)nb * extra;
-        if (at > ctx->ws_align.cap) {
-            rd_set_error("%s: internal workspace accounting (%zu > %zu)", who, at, ctx->ws_align.cap);
-            return RD_ERR_STATE;
-        }
+        const size_t extra_at = c.mark();
+        c.take<uint8_t>((size_t)nb * extra, 0, 1);
+        if (int rc = rd_carve_check(who, c, ctx->ws_align.cap)) return rc;
         stage.assign(up_bytes, 0);
         memcpy(stage.data(), desc.data(), (size_t)nb * sizeof(AlnPair));
         for (int k = 0; k < nb; k++) {

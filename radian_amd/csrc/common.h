@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "carve.h"
 #include "polya_rules.h"
 
 #define RD_OK 0
@@ -43,6 +44,28 @@ struct DevBuf {
     void release();
     template <typename T> T* as() const { return (T*)p; }
 };
+// A launch's members gathered from the host array src (elements of elem_bytes; member i: src_off[members[i]] .. src_off[members[i] + 1]) into
+// the dense device array dst, member i at element off[i] (rd_gather_offsets, carve.h): one copy per run of members that are contiguous in
+// the source (rd_gather_runs), none for a run without elements.  Queues on st; the caller keeps src alive until the stream has run.
+int rd_gather_h2d(hipStream_t st, void* dst, const void* src, size_t elem_bytes, const int64_t* src_off, const int32_t* members, int n,
+                  const int64_t* off);
+// a stage's block (carve.h): a dry pass of the stage's layout sizes buf, a second pass carves it
+template <typename Layout> inline int rd_carve(DevBuf& buf, Layout layout)
+{
+    Carve dry;
+    layout(dry);
+    if (buf.reserve(dry.at)) return RD_ERR_NOMEM;
+    Carve c(buf.p);
+    layout(c);
+    return RD_OK;
+}
+// a launch carved into ws_align (whose size comes from the entry point's byte formulas, not from the layout) must have stayed inside it
+inline int rd_carve_check(const char* who, const Carve& c, size_t cap)
+{
+    if (c.fits(cap)) return RD_OK;
+    rd_set_error("%s: internal workspace accounting (%zu > %zu)", who, c.at, cap);
+    return RD_ERR_STATE;
+}
 
 // Model geometry: radian/models/sig2seq.yaml:34-49
 constexpr int RD_C = 256;      // tcn.nb_filters
@@ -229,21 +252,22 @@ struct rd_ctx {
     DevBuf ws_in, ws_probs, ws_mat, ws_seq, ws_nodes_child, ws_nodes_back, ws_labels, ws_misc;
     DevBuf ws_queue;                // the work-queue counter of beam_search_queue_kernel (decode.hip)
     DevBuf ws_wide, ws_wide_slot;   // beam widths above 51 (decode_wide.hip): per-sequence scratch block, per-trie-node slot map
-    DevBuf ws_align;                // the budgeted workspace of rd_align_batch, rd_fit_batch, rd_ctc_align_*, rd_map_batch and rd_map_diag_chain: one
-                                    // launch at a time, sized exactly to the largest launch under the caller's budget (budget.h, reserve_exact)
-    DevBuf ws_ctc;                  // rd_ctc_* (ctc.hip): window descriptors, labels, per-window results, greedy labels
-    DevBuf ws_calign;               // rd_ctc_align_* (ctcalign.hip): a launch's descriptors and results (its DP workspace is ws_align, under the budget)
-    DevBuf ws_events, ws_events_io; // rd_event_stats* (events.hip): a launch's group descriptors; the step and event arrays of a host-pointer call
-    DevBuf ws_polya, ws_polya_io;   // rd_polya_* (polya.hip): a launch's descriptors, scales and window arrays; the per-read results of a host-pointer call
-    DevBuf ws_segment;              // rd_segment* (segment.hip): a launch's descriptors, flags, scan and dense event arrays
-    DevBuf ws_sim;                  // rd_sim_* (sim.hip): the model tables, then a launch's bases, dwells, positions and samples
-    DevBuf ws_eval, ws_eval_model;  // rd_eventalign (eventalign.hip): a launch's descriptors, scales and results (its DP workspace is ws_align, under the budget); the pore-model tables
-    DevBuf ws_site;                 // rd_site_* (sitecmp.hip): a launch's events, keys, segments and per-site results
+    // The stages' device blocks.  Each is described once, by its stage's layout function (carve.h), which sizes it dry and then carves it.
+    DevBuf ws_align;                // the budgeted entry points (align, fit, ctc_align, map, eventalign, sigmap): one launch at a time, sized exactly to the
+                                    // largest launch under the caller's budget (budget.h, reserve_exact); carved per launch, checked by rd_carve_check
+    DevBuf ws_ctc;                  // rd_ctc_* (ctc.hip): ctc_layout
+    DevBuf ws_calign;               // rd_ctc_align_* (ctcalign.hip): ca_io_layout
+    DevBuf ws_events, ws_events_io; // rd_event_stats* (events.hip): a launch's group descriptors; ev_io_layout
+    DevBuf ws_polya, ws_polya_io;   // rd_polya_* (polya.hip): pa_layout; the per-read results of a host-pointer call
+    DevBuf ws_segment;              // rd_segment* (segment.hip): sg_layout
+    DevBuf ws_sim;                  // rd_sim_* (sim.hip): sim_layout
+    DevBuf ws_eval, ws_eval_model;  // rd_eventalign, rd_sigmap and signal_dev.h: ea_io_layout, sm_io_layout, signal_scales; signal_upload_tables, sm_panel_layout
+    DevBuf ws_site;                 // rd_site_* (sitecmp.hip): sc_layout
     DevBuf ws_quant;                // rd_quant_em (quant.hip): the packed candidates, the counts and the shares of one call, resident over its iterations
     // rd_pileup_* (pileup.hip): the accumulator lives from rd_pileup_open to rd_pileup_close, across calls (as the seed index of rd_map_index does)
     DevBuf pileup_sites;            // [pileup_n_sites][8] uint32: A C G T other del ins starts
     DevBuf pileup_profile;          // [RD_PILEUP_PROFILE_LEN] uint64
-    DevBuf ws_pileup;               // a launch of rd_pileup_add_ops (descriptors, sequences, ops, results); the flags, scan and rows of rd_pileup_read
+    DevBuf ws_pileup;               // rd_pileup_add_ops and rd_pileup_read (pileup.hip): pu_ops_layout, pu_read_layout
     int64_t pileup_n_sites = -1;    // -1: not open
     int64_t pileup_pairs = 0;       // pairs added since rd_pileup_open (at most 2^31 - 1: no 32-bit site counter can overflow)
     int64_t trie_budget = (int64_t)24 << 30;   // bytes of beam-search workspace one launch may ask for (rd_plan_trie_runs; rd_set_trie_budget)

@@ -93,6 +93,19 @@ void DevBuf::release()
     cap = 0;
 }
 
+int rd_gather_h2d(hipStream_t st, void* dst, const void* src, size_t elem_bytes, const int64_t* src_off, const int32_t* members, int n,
+                  const int64_t* off)
+{
+    hipError_t e = hipSuccess;
+    rd_gather_runs(members, n, src_off, [&](int64_t i, int64_t k) {
+        if (off[k] > off[i] && e == hipSuccess)
+            e = hipMemcpyAsync((char*)dst + (size_t)off[i] * elem_bytes, (const char*)src + (size_t)src_off[members[i]] * elem_bytes,
+                               (size_t)(off[k] - off[i]) * elem_bytes, hipMemcpyHostToDevice, st);
+    });
+    RD_HIP(e);
+    return RD_OK;
+}
+
 extern "C" int rd_device_count(int* n)
 {
     RD_REQUIRE(n != nullptr, "rd_device_count: null argument");

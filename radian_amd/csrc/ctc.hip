@@ -232,6 +232,23 @@ int ctc_check(const char* fn, int n, const int32_t* input_len, const uint8_t* la
     return RD_OK;
 }
 
+// ws_ctc: window descriptors | labels | loss [n] f64 | greedy_len + distance [n][2] i32 | greedy labels [n][1024] u8
+struct CtcWs {
+    CtcWin* win;
+    uint8_t* lab;
+    double* loss;
+    int32_t* ed;
+    uint8_t* greedy;
+};
+void ctc_layout(Carve& c, int n, int64_t nl, bool greedy, CtcWs* W)
+{
+    W->win = c.take<CtcWin>((size_t)n);
+    W->lab = c.take<uint8_t>((size_t)nl + 1);
+    W->loss = c.take<double>((size_t)n);
+    W->ed = c.take<int32_t>((size_t)n * 2);
+    W->greedy = c.take<uint8_t>(greedy ? (size_t)n * CTC_T : 0, 0, 1);
+}
+
 // Stages the (checked) metadata into the context's CTC workspace and runs both kernels on d_probs.
 int ctc_run(rd_ctx* ctx, const float* d_probs, int n, const int32_t* input_len, const uint8_t* labels, const int64_t* label_off,
             const int32_t* label_len, double* loss, int32_t* status, int32_t* greedy_len, int32_t* edit_distance, uint8_t* greedy_out)
@@ -239,12 +256,10 @@ int ctc_run(rd_ctx* ctx, const float* d_probs, int n, const int32_t* input_len, 
     int64_t nl = 0;
     for (int i = 0; i < n; i++) nl += label_len[i];
     if (n == 0) return RD_OK;
-    // workspace: window descriptors | labels | loss [n] f64 | greedy_len + distance [n][2] i32 | greedy labels [n][1024] u8
-    const size_t a_win = align_up((size_t)n * sizeof(CtcWin), 256), a_lab = align_up((size_t)nl + 1, 256);
-    const size_t a_loss = align_up((size_t)n * 8, 256), a_ed = align_up((size_t)n * 8, 256);
-    const size_t a_g = greedy_out ? (size_t)n * CTC_T : 0;
-    if (ctx->ws_ctc.reserve(a_win + a_lab + a_loss + a_ed + a_g)) return RD_ERR_NOMEM;
-    std::vector<uint8_t> stage(a_win + a_lab);
+    CtcWs W;
+    if (rd_carve(ctx->ws_ctc, [&](Carve& c) { ctc_layout(c, n, nl, greedy_out != nullptr, &W); })) return RD_ERR_NOMEM;
+    const size_t a_win = (size_t)((uint8_t*)W.lab - (uint8_t*)W.win), a_g = greedy_out ? (size_t)n * CTC_T : 0;
+    std::vector<uint8_t> stage((size_t)((uint8_t*)W.loss - (uint8_t*)W.win));   // descriptors and labels go up in one copy
     CtcWin* w = (CtcWin*)stage.data();
     int64_t at = 0;
     for (int i = 0; i < n; i++) {
@@ -252,20 +267,15 @@ int ctc_run(rd_ctx* ctx, const float* d_probs, int n, const int32_t* input_len, 
         if (label_len[i]) memcpy(stage.data() + a_win + at, labels + label_off[i], (size_t)label_len[i]);
         at += label_len[i];
     }
-    uint8_t* ws = ctx->ws_ctc.as<uint8_t>();
-    const CtcWin* d_win = (const CtcWin*)ws;
-    const uint8_t* d_lab = ws + a_win;
-    double* d_loss = (double*)(ws + a_win + a_lab);
-    int32_t* d_ed = (int32_t*)(ws + a_win + a_lab + a_loss);
-    uint8_t* d_g = greedy_out ? ws + a_win + a_lab + a_loss + a_ed : nullptr;
-    RD_HIP(hipMemcpyAsync(ws, stage.data(), stage.size(), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(ctc_alpha_kernel, dim3(n), dim3(64), 0, ctx->stream, d_probs, d_win, d_lab, d_loss);
+    uint8_t* d_g = greedy_out ? W.greedy : nullptr;
+    RD_HIP(hipMemcpyAsync(W.win, stage.data(), stage.size(), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(ctc_alpha_kernel, dim3(n), dim3(64), 0, ctx->stream, d_probs, W.win, W.lab, W.loss);
     RD_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ctc_greedy_ed_kernel, dim3(n), dim3(64), 0, ctx->stream, d_probs, d_win, d_lab, d_ed, d_g);
+    hipLaunchKernelGGL(ctc_greedy_ed_kernel, dim3(n), dim3(64), 0, ctx->stream, d_probs, W.win, W.lab, W.ed, d_g);
     RD_HIP(hipGetLastError());
     std::vector<int32_t> ed((size_t)n * 2);
-    RD_HIP(hipMemcpyAsync(loss, d_loss, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    RD_HIP(hipMemcpyAsync(ed.data(), d_ed, ed.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RD_HIP(hipMemcpyAsync(loss, W.loss, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    RD_HIP(hipMemcpyAsync(ed.data(), W.ed, ed.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (greedy_out) RD_HIP(hipMemcpyAsync(greedy_out, d_g, a_g, hipMemcpyDeviceToHost, ctx->stream));
     RD_HIP(hipStreamSynchronize(ctx->stream));
     for (int i = 0; i < n; i++) {

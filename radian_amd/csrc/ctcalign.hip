@@ -288,6 +288,29 @@ extern "C" int64_t rd_ctc_align_workspace_bytes(int64_t n_rows, int64_t n_labels
     return (int64_t)ca_seq_bytes(n_rows, n_labels);
 }
 
+namespace {
+
+// a launch's io block (ws_calign) for nb sequences whose label offsets span nlab: descriptors | end values [2] | score | status | first |
+// last | qual
+struct CaIo {
+    CaSeq* seqs;
+    double *fin, *score;
+    int32_t *status, *first, *last;
+    uint8_t* qual;
+};
+void ca_io_layout(Carve& c, int nb, size_t nlab, CaIo* io)
+{
+    io->seqs = c.take<CaSeq>((size_t)nb);
+    io->fin = c.take<double>((size_t)nb * 2);
+    io->score = c.take<double>((size_t)nb);
+    io->status = c.take<int32_t>((size_t)nb);
+    io->first = c.take<int32_t>(nlab);
+    io->last = c.take<int32_t>(nlab);
+    io->qual = c.take<uint8_t>(nlab, 256, 1);
+}
+
+}  // namespace
+
 int rd_ctc_align_dev(rd_ctx* ctx, hipStream_t st, const void* d_probs, int ptype, const int64_t* seq_off, const int32_t* seq_len, int n_seq,
                      const uint8_t* d_labels, const int64_t* dlab_off, const int32_t* label_len, int64_t budget_bytes, int32_t* first_step,
                      int32_t* last_step, uint8_t* qual, const int64_t* out_off, double* score, int32_t* status)
@@ -327,7 +350,7 @@ int rd_ctc_align_dev(rd_ctx* ctx, hipStream_t st, const void* d_probs, int ptype
     for (auto [k0, k1] : plan.launches) {
         const int nb = (int)(k1 - k0);
         desc.resize(nb);
-        size_t at = 0;
+        Carve ws;   // (dry: the descriptors hold offsets into ws_align)
         int64_t lab_lo = INT64_MAX, lab_hi = 0, max_T = 0, max_L = 0;
         for (int k = 0; k < nb; k++) {
             const int i = run[k0 + k];
@@ -336,12 +359,12 @@ int rd_ctc_align_dev(rd_ctx* ctx, hipStream_t st, const void* d_probs, int ptype
             d.lab = dlab_off[i];
             d.T = seq_len[i];
             d.L = label_len[i];
-            d.lp = (int64_t)at;
-            at += ca_lp_bytes(d.T);
-            d.bp = (int64_t)at;
-            at += ca_bp_bytes(d.T, d.L);
-            d.col = (int64_t)at;
-            at += ca_col_bytes(d.T);
+            d.lp = (int64_t)ws.mark();
+            ws.take<char>(ca_lp_bytes(d.T), 0, 1);
+            d.bp = (int64_t)ws.mark();
+            ws.take<char>(ca_bp_bytes(d.T, d.L), 0, 1);
+            d.col = (int64_t)ws.mark();
+            ws.take<char>(ca_col_bytes(d.T), 0, 1);
             if (d.L) {
                 lab_lo = std::min(lab_lo, d.lab);
                 lab_hi = std::max(lab_hi, d.lab + d.L);
@@ -349,28 +372,19 @@ int rd_ctc_align_dev(rd_ctx* ctx, hipStream_t st, const void* d_probs, int ptype
             max_T = std::max<int64_t>(max_T, d.T);
             max_L = std::max<int64_t>(max_L, d.L);
         }
-        if (at > ctx->ws_align.cap) {
-            rd_set_error("ctc_align: internal workspace accounting (%zu > %zu)", at, ctx->ws_align.cap);
-            return RD_ERR_STATE;
-        }
+        if (int rc = rd_carve_check("ctc_align", ws, ctx->ws_align.cap)) return rc;
         if (lab_hi <= lab_lo) lab_lo = lab_hi = 0;
         const size_t nlab = (size_t)(lab_hi - lab_lo);   // the per-base results of the launch: the span of its label offsets
-        // descriptors | end values [2] | score | status | first | last | qual
-        const size_t o_fin = align_up((size_t)nb * sizeof(CaSeq), 256), o_score = o_fin + align_up((size_t)nb * 16, 256);
-        const size_t o_status = o_score + align_up((size_t)nb * 8, 256), o_first = o_status + align_up((size_t)nb * 4, 256);
-        const size_t o_last = o_first + align_up(nlab * 4, 256), o_qual = o_last + align_up(nlab * 4, 256);
-        if (ctx->ws_calign.reserve(o_qual + nlab + 256)) return RD_ERR_NOMEM;
-        uint8_t* io = ctx->ws_calign.as<uint8_t>();
+        CaIo io;
+        if (rd_carve(ctx->ws_calign, [&](Carve& c) { ca_io_layout(c, nb, nlab, &io); })) return RD_ERR_NOMEM;
         uint8_t* dws = ctx->ws_align.as<uint8_t>();
-        const CaSeq* d_seqs = (const CaSeq*)io;
-        double* d_fin = (double*)(io + o_fin);
-        double* d_score = (double*)(io + o_score);
-        int32_t* d_status = (int32_t*)(io + o_status);
+        const CaSeq* d_seqs = io.seqs;
+        double *d_fin = io.fin, *d_score = io.score;
+        int32_t* d_status = io.status;
         // per-base buffers are indexed by the label offsets: shift them so that the launch's lowest offset is element 0
-        int32_t* d_first = (int32_t*)(io + o_first) - lab_lo;
-        int32_t* d_last = (int32_t*)(io + o_last) - lab_lo;
-        uint8_t* d_qual = io + o_qual - lab_lo;
-        RD_HIP(hipMemcpyAsync(io, desc.data(), (size_t)nb * sizeof(CaSeq), hipMemcpyHostToDevice, st));
+        int32_t *d_first = io.first - lab_lo, *d_last = io.last - lab_lo;
+        uint8_t* d_qual = io.qual - lab_lo;
+        RD_HIP(hipMemcpyAsync(io.seqs, desc.data(), (size_t)nb * sizeof(CaSeq), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(ca_log_kernel, dim3((unsigned)((max_T + 31) / 32), nb), dim3(256), 0, st, d_seqs, d_probs, ptype, dws, d_fin);
         RD_HIP(hipGetLastError());
         hipLaunchKernelGGL(ca_dp_kernel, dim3(nb), dim3(BS_NT), 0, st, d_seqs, d_labels, dws, d_fin);
@@ -390,9 +404,9 @@ int rd_ctc_align_dev(rd_ctx* ctx, hipStream_t st, const void* d_probs, int ptype
         RD_HIP(hipMemcpyAsync(h_score.data(), d_score, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
         RD_HIP(hipMemcpyAsync(h_status.data(), d_status, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
         if (nlab) {
-            RD_HIP(hipMemcpyAsync(h_first.data(), io + o_first, nlab * 4, hipMemcpyDeviceToHost, st));
-            RD_HIP(hipMemcpyAsync(h_last.data(), io + o_last, nlab * 4, hipMemcpyDeviceToHost, st));
-            RD_HIP(hipMemcpyAsync(h_qual.data(), io + o_qual, nlab, hipMemcpyDeviceToHost, st));
+            RD_HIP(hipMemcpyAsync(h_first.data(), io.first, nlab * 4, hipMemcpyDeviceToHost, st));
+            RD_HIP(hipMemcpyAsync(h_last.data(), io.last, nlab * 4, hipMemcpyDeviceToHost, st));
+            RD_HIP(hipMemcpyAsync(h_qual.data(), io.qual, nlab, hipMemcpyDeviceToHost, st));
         }
         RD_HIP(hipStreamSynchronize(st));
         for (int k = 0; k < nb; k++) {

@@ -412,6 +412,32 @@ __global__ __launch_bounds__(256) void ea_sums_kernel(const EaSeq* __restrict__ 
     if (tid < 5) out[blockIdx.x].sums[tid] = sh[0][tid] + sh[1][tid] + sh[2][tid] + sh[3][tid];
 }
 
+// a launch's io block (ws_eval) for nb reads of nlab bases: descriptors | end values [2] | score and sums | first, last, start, end | sum,
+// sumsq | min, max.  Arrays of one type follow each other at one stride, so the host fetches each type in one copy.
+struct EaIo {
+    EaSeq* seqs;
+    int32_t* fin;
+    EaOut* out;
+    int32_t *first, *last, *start, *end;
+    int64_t *sum, *sumsq;
+    int16_t *mn, *mx;
+};
+void ea_io_layout(Carve& c, int nb, int64_t nlab, EaIo* io)
+{
+    const size_t n = (size_t)nlab;
+    io->seqs = c.take<EaSeq>((size_t)nb);
+    io->fin = c.take<int32_t>((size_t)nb * 2);
+    io->out = c.take<EaOut>((size_t)nb);
+    io->first = c.take<int32_t>(n, 16);
+    io->last = c.take<int32_t>(n, 16);
+    io->start = c.take<int32_t>(n, 16);
+    io->end = c.take<int32_t>(n, 16);
+    io->sum = c.take<int64_t>(n, 16);
+    io->sumsq = c.take<int64_t>(n, 16);
+    io->mn = c.take<int16_t>(n, 16);
+    io->mx = c.take<int16_t>(n, 16);
+}
+
 }  // namespace
 
 extern "C" int rd_eventalign(rd_ctx* ctx, const int16_t* raw, const int64_t* read_off, int n_reads, const int64_t* t_lo, const int64_t* t_hi,
@@ -473,7 +499,7 @@ extern "C" int rd_eventalign(rd_ctx* ctx, const int16_t* raw, const int64_t* rea
         ev_len.assign(r_hi - r_lo, 0);
         ev_lab.assign(r_hi - r_lo, 0);
         ev_status.assign(r_hi - r_lo, 0);
-        size_t at = 0;
+        Carve ws;   // (dry: the descriptors hold offsets into ws_align)
         int64_t nlab = 0, max_T = 0;
         for (int i = 0; i < nb; i++) {
             const int r = members[i];
@@ -487,56 +513,43 @@ extern "C" int rd_eventalign(rd_ctx* ctx, const int16_t* raw, const int64_t* rea
             d.d4 = d4[r];
             d.t_lo = (int32_t)t_lo[r];
             d.pad_ = 0;
-            d.zq = (int64_t)at;
-            at += ea_zq_bytes(d.T);
-            d.bp = (int64_t)at;
-            at += ea_bp_bytes(d.T, d.L);
-            d.col = (int64_t)at;
-            at += ea_col_bytes(d.T, d.L);
+            d.zq = (int64_t)ws.mark();
+            ws.take<char>(ea_zq_bytes(d.T), 0, 1);
+            d.bp = (int64_t)ws.mark();
+            ws.take<char>(ea_bp_bytes(d.T, d.L), 0, 1);
+            d.col = (int64_t)ws.mark();
+            ws.take<char>(ea_col_bytes(d.T, d.L), 0, 1);
             ev_len[r - r_lo] = d.L;   // (a read between two members that is not one has no labels in this launch)
             ev_lab[r - r_lo] = d.lab;
             nlab += d.L;
             max_T = std::max<int64_t>(max_T, d.T);
         }
-        if (at > ctx->ws_align.cap) {
-            rd_set_error("rd_eventalign: internal workspace accounting (%zu > %zu)", at, ctx->ws_align.cap);
-            return RD_ERR_STATE;
-        }
-        // descriptors | end values [2] | score and sums | first, last, start, end | sum, sumsq | min, max
-        const size_t n = (size_t)nlab, a4 = align_up(n * 4 + 16, 256), a8 = align_up(n * 8 + 16, 256), a2 = align_up(n * 2 + 16, 256);
-        const size_t o_fin = align_up((size_t)nb * sizeof(EaSeq), 256), o_out = o_fin + align_up((size_t)nb * 8, 256);
-        const size_t o_i32 = o_out + align_up((size_t)nb * sizeof(EaOut), 256), o_i64 = o_i32 + 4 * a4, o_i16 = o_i64 + 2 * a8;
-        if (ctx->ws_eval.reserve(o_i16 + 2 * a2)) return RD_ERR_NOMEM;
-        uint8_t* io = ctx->ws_eval.as<uint8_t>();
+        if ((rc = rd_carve_check("rd_eventalign", ws, ctx->ws_align.cap))) return rc;
+        EaIo io;
+        if (rd_carve(ctx->ws_eval, [&](Carve& c) { ea_io_layout(c, nb, nlab, &io); })) return RD_ERR_NOMEM;
         uint8_t* dws = ctx->ws_align.as<uint8_t>();
-        const EaSeq* d_seqs = (const EaSeq*)io;
-        int32_t* d_fin = (int32_t*)(io + o_fin);
-        EaOut* d_out = (EaOut*)(io + o_out);
-        int32_t *d_first = (int32_t*)(io + o_i32), *d_last = (int32_t*)(io + o_i32 + a4), *d_start = (int32_t*)(io + o_i32 + 2 * a4),
-                *d_end = (int32_t*)(io + o_i32 + 3 * a4);
-        int64_t *d_sum = (int64_t*)(io + o_i64), *d_sumsq = (int64_t*)(io + o_i64 + a8);
-        int16_t *d_min = (int16_t*)(io + o_i16), *d_max = (int16_t*)(io + o_i16 + a2);
-        RD_HIP(hipMemcpyAsync(io, desc.data(), (size_t)nb * sizeof(EaSeq), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(ea_quant_kernel, dim3((unsigned)((max_T + 255) / 256), nb), dim3(256), 0, st, d_seqs, d_raw, dws, d_fin);
+        RD_HIP(hipMemcpyAsync(io.seqs, desc.data(), (size_t)nb * sizeof(EaSeq), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(ea_quant_kernel, dim3((unsigned)((max_T + 255) / 256), nb), dim3(256), 0, st, io.seqs, d_raw, dws, io.fin);
         RD_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ea_dp_kernel, dim3(nb), dim3(BS_NT), 0, st, d_seqs, d_codes, d_lvl, d_w, d_bias, c.m.bg, k, dws, d_fin);
+        hipLaunchKernelGGL(ea_dp_kernel, dim3(nb), dim3(BS_NT), 0, st, io.seqs, d_codes, d_lvl, d_w, d_bias, c.m.bg, k, dws, io.fin);
         RD_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ea_tb_kernel, dim3(nb), dim3(64), 0, st, d_seqs, dws, d_fin, d_out, d_first, d_last);
+        hipLaunchKernelGGL(ea_tb_kernel, dim3(nb), dim3(64), 0, st, io.seqs, dws, io.fin, io.out, io.first, io.last);
         RD_HIP(hipGetLastError());
-        if ((rc = rd_event_stats_dev(ctx, st, d_raw, off.data() + r_lo, r_hi - r_lo, d_first, d_last, ev_lab.data(), ev_len.data(), ev_status.data(),
-                                     d_start, d_end, d_sum, d_sumsq, d_min, d_max)))
+        if ((rc = rd_event_stats_dev(ctx, st, d_raw, off.data() + r_lo, r_hi - r_lo, io.first, io.last, ev_lab.data(), ev_len.data(), ev_status.data(),
+                                     io.start, io.end, io.sum, io.sumsq, io.mn, io.mx)))
             return rc;
-        hipLaunchKernelGGL(ea_sums_kernel, dim3(nb), dim3(256), 0, st, d_seqs, d_codes, d_lvl, k, d_start, d_end, d_sum, d_out);
+        hipLaunchKernelGGL(ea_sums_kernel, dim3(nb), dim3(256), 0, st, io.seqs, d_codes, d_lvl, k, io.start, io.end, io.sum, io.out);
         RD_HIP(hipGetLastError());
         h_out.resize(nb);
-        h_i32.resize(4 * a4 / 4);
-        h_i64.resize(2 * a8 / 8);
-        h_i16.resize(2 * a2 / 2);
-        RD_HIP(hipMemcpyAsync(h_out.data(), d_out, (size_t)nb * sizeof(EaOut), hipMemcpyDeviceToHost, st));
-        if (n) {
-            RD_HIP(hipMemcpyAsync(h_i32.data(), io + o_i32, 4 * a4, hipMemcpyDeviceToHost, st));
-            RD_HIP(hipMemcpyAsync(h_i64.data(), io + o_i64, 2 * a8, hipMemcpyDeviceToHost, st));
-            RD_HIP(hipMemcpyAsync(h_i16.data(), io + o_i16, 2 * a2, hipMemcpyDeviceToHost, st));
+        const size_t s4 = io.last - io.first, s8 = io.sumsq - io.sum, s2 = io.mx - io.mn;   // the arrays' strides, in elements
+        h_i32.resize(4 * s4);
+        h_i64.resize(2 * s8);
+        h_i16.resize(2 * s2);
+        RD_HIP(hipMemcpyAsync(h_out.data(), io.out, (size_t)nb * sizeof(EaOut), hipMemcpyDeviceToHost, st));
+        if (nlab) {
+            RD_HIP(hipMemcpyAsync(h_i32.data(), io.first, 4 * s4 * 4, hipMemcpyDeviceToHost, st));
+            RD_HIP(hipMemcpyAsync(h_i64.data(), io.sum, 2 * s8 * 8, hipMemcpyDeviceToHost, st));
+            RD_HIP(hipMemcpyAsync(h_i16.data(), io.mn, 2 * s2 * 2, hipMemcpyDeviceToHost, st));
         }
         RD_HIP(hipStreamSynchronize(st));
         for (int i = 0; i < nb; i++) {
@@ -548,13 +561,13 @@ extern "C" int rd_eventalign(rd_ctx* ctx, const int16_t* raw, const int64_t* rea
             memcpy(fit_sums + 5 * (int64_t)r, h_out[i].sums, 40);
             if (!L) continue;
             memcpy(first_step + o, h_i32.data() + s, L * 4);
-            memcpy(last_step + o, h_i32.data() + a4 / 4 + s, L * 4);
-            memcpy(ev_start + o, h_i32.data() + 2 * (a4 / 4) + s, L * 4);
-            memcpy(ev_end + o, h_i32.data() + 3 * (a4 / 4) + s, L * 4);
+            memcpy(last_step + o, h_i32.data() + s4 + s, L * 4);
+            memcpy(ev_start + o, h_i32.data() + 2 * s4 + s, L * 4);
+            memcpy(ev_end + o, h_i32.data() + 3 * s4 + s, L * 4);
             memcpy(ev_sum + o, h_i64.data() + s, L * 8);
-            memcpy(ev_sumsq + o, h_i64.data() + a8 / 8 + s, L * 8);
+            memcpy(ev_sumsq + o, h_i64.data() + s8 + s, L * 8);
             memcpy(ev_min + o, h_i16.data() + s, L * 2);
-            memcpy(ev_max + o, h_i16.data() + a2 / 2 + s, L * 2);
+            memcpy(ev_max + o, h_i16.data() + s2 + s, L * 2);
         }
     }
     if (too_large) {

@@ -116,6 +116,29 @@ extern "C" int rd_event_stats_host(const int16_t* raw, const int64_t* read_off, 
     return RD_OK;
 }
 
+namespace {
+
+// the step and event arrays of n labels in one device block (ws_events_io)
+struct EvIo {
+    int32_t *first, *last, *start, *end;
+    int64_t *sum, *sumsq;
+    int16_t *mn, *mx;
+};
+void ev_io_layout(Carve& c, int64_t n_labels, EvIo* io)
+{
+    const size_t n = (size_t)n_labels;
+    io->first = c.take<int32_t>(n, 16);
+    io->last = c.take<int32_t>(n, 16);
+    io->start = c.take<int32_t>(n, 16);
+    io->end = c.take<int32_t>(n, 16);
+    io->sum = c.take<int64_t>(n, 16);
+    io->sumsq = c.take<int64_t>(n, 16);
+    io->mn = c.take<int16_t>(n, 16);
+    io->mx = c.take<int16_t>(n, 16);
+}
+
+}  // namespace
+
 #if defined(__HIPCC__)
 // ------------------------------------------------------------------------------------------------------------------ device half
 namespace {
@@ -233,41 +256,14 @@ int rd_event_stats_dev(rd_ctx* ctx, hipStream_t st, const int16_t* d_raw, const 
     return RD_OK;
 }
 
-namespace {
-
-// the step and event arrays of n labels in one device block
-struct EvIo {
-    int32_t *first, *last, *start, *end;
-    int64_t *sum, *sumsq;
-    int16_t *mn, *mx;
-};
-
-int ev_io_layout(rd_ctx* ctx, int64_t n_labels, EvIo* io)
-{
-    const size_t n = (size_t)n_labels, a4 = align_up(n * 4 + 16, 256), a8 = align_up(n * 8 + 16, 256), a2 = align_up(n * 2 + 16, 256);
-    if (ctx->ws_events_io.reserve(4 * a4 + 2 * a8 + 2 * a2)) return RD_ERR_NOMEM;
-    char* p = (char*)ctx->ws_events_io.p;
-    io->first = (int32_t*)p; p += a4;
-    io->last = (int32_t*)p; p += a4;
-    io->start = (int32_t*)p; p += a4;
-    io->end = (int32_t*)p; p += a4;
-    io->sum = (int64_t*)p; p += a8;
-    io->sumsq = (int64_t*)p; p += a8;
-    io->mn = (int16_t*)p; p += a2;
-    io->mx = (int16_t*)p;
-    return RD_OK;
-}
-
-}  // namespace
-
 int rd_event_stats_steps(rd_ctx* ctx, hipStream_t st, const int16_t* d_raw, const int64_t* read_off, int n_reads, const int32_t* first_step,
                          const int32_t* last_step, const int64_t* label_off, const int32_t* label_len, const int32_t* align_status, int64_t n_labels,
                          int32_t* ev_start, int32_t* ev_end, int64_t* ev_sum, int64_t* ev_sumsq, int16_t* ev_min, int16_t* ev_max)
 {
     if (n_labels == 0) return RD_OK;
     EvIo io;
-    int rc = ev_io_layout(ctx, n_labels, &io);
-    if (rc) return rc;
+    int rc;
+    if (rd_carve(ctx->ws_events_io, [&](Carve& c) { ev_io_layout(c, n_labels, &io); })) return RD_ERR_NOMEM;
     const size_t n = (size_t)n_labels;
     RD_HIP(hipMemcpyAsync(io.first, first_step, n * 4, hipMemcpyHostToDevice, st));
     RD_HIP(hipMemcpyAsync(io.last, last_step, n * 4, hipMemcpyHostToDevice, st));

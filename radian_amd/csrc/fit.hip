@@ -270,8 +270,10 @@ extern "C" int rd_fit_batch(rd_ctx* ctx, const uint8_t* refs, const int64_t* ref
     for (auto [k0, k1] : plan.launches) {
         const size_t nb = (size_t)(k1 - k0);
         // layout: descriptors (sorted by class) | results | references, 4-aligned each | queries
-        const size_t res_at = align_up(nb * sizeof(FitQuery), 256);
-        size_t at = res_at + align_up(nb * FIT_RES * 4, 256);
+        Carve ws;   // (dry: the descriptors hold offsets into ws_align; the whole block is staged on the host and copied)
+        ws.take<FitQuery>(nb);
+        const size_t res_at = ws.mark();
+        ws.take<int32_t>(nb * FIT_RES);
         desc.resize(nb);
         int32_t cur_ref = -1;
         int64_t cur_ref_at = 0;
@@ -280,9 +282,9 @@ extern "C" int rd_fit_batch(rd_ctx* ctx, const uint8_t* refs, const int64_t* ref
             const int32_t p = order[k0 + k], r = query_ref[p];
             if (r != cur_ref) {
                 cur_ref = r;
-                cur_ref_at = (int64_t)at;
+                cur_ref_at = (int64_t)ws.mark();
                 ref_at.push_back({r, cur_ref_at});
-                at += fit_ref_bytes(ref_off[r + 1] - ref_off[r]);
+                ws.take<uint8_t>(fit_ref_bytes(ref_off[r + 1] - ref_off[r]), 0, 1);
             }
             FitQuery& d = desc[k];
             d.ref = cur_ref_at;
@@ -292,14 +294,11 @@ extern "C" int rd_fit_batch(rd_ctx* ctx, const uint8_t* refs, const int64_t* ref
             d.pad = 0;
         }
         for (size_t k = 0; k < nb; k++) {
-            desc[k].query = (int64_t)at;
-            at += (size_t)desc[k].m;
+            desc[k].query = (int64_t)ws.mark();
+            ws.take<uint8_t>((size_t)desc[k].m, 0, 1);
         }
-        const size_t up_bytes = at;
-        if (up_bytes > ctx->ws_align.cap) {
-            rd_set_error("rd_fit_batch: internal workspace accounting (%zu > %zu)", up_bytes, ctx->ws_align.cap);
-            return RD_ERR_STATE;
-        }
+        const size_t up_bytes = ws.mark();
+        if (int rc = rd_carve_check("rd_fit_batch", ws, ctx->ws_align.cap)) return rc;
         stage.assign(up_bytes, 0);
         for (auto [r, where] : ref_at)
             if (ref_off[r + 1] > ref_off[r]) memcpy(stage.data() + where, refs + ref_off[r], (size_t)(ref_off[r + 1] - ref_off[r]));

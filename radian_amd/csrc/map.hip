@@ -573,34 +573,24 @@ struct LaunchWs {
 
 int carve_launch_ws(rd_ctx* ctx, const char* who, int64_t A, int end_bit, LaunchWs& W)
 {
-    uint8_t* base = ctx->ws_align.as<uint8_t>();
-    size_t at = 0;
-    auto take = [&](size_t bytes) {
-        uint8_t* p = base + at;
-        at += align_up(bytes, 256);
-        return p;
-    };
-    W.ka = (uint64_t*)take((size_t)A * 8);
-    W.kb = (uint64_t*)take((size_t)A * 8);
-    W.qa = (uint32_t*)take((size_t)A * 4);
-    W.qb = (uint32_t*)take((size_t)A * 4);
-    W.seg_start = (uint32_t*)take((size_t)A * 4);
-    W.seg_res = (int4*)take((size_t)A * 16);
-    W.head = take((size_t)A);
+    Carve c(ctx->ws_align.p);
+    W.ka = c.take<uint64_t>((size_t)A);
+    W.kb = c.take<uint64_t>((size_t)A);
+    W.qa = c.take<uint32_t>((size_t)A);
+    W.qb = c.take<uint32_t>((size_t)A);
+    W.seg_start = c.take<uint32_t>((size_t)A);
+    W.seg_res = c.take<int4>((size_t)A);
+    W.head = c.take<uint8_t>((size_t)A);
     W.nb = (uint32_t)((A + CP_PER - 1) / CP_PER);
-    W.bcnt = (uint32_t*)take((size_t)(W.nb + 1) * 4);
-    W.boff = (uint32_t*)take((size_t)(W.nb + 1) * 4);
+    W.bcnt = c.take<uint32_t>((size_t)W.nb + 1);
+    W.boff = c.take<uint32_t>((size_t)W.nb + 1);
     rocprim::double_buffer<uint64_t> dk(W.ka, W.kb);
     rocprim::double_buffer<uint32_t> dq(W.qa, W.qb);
     W.sort_bytes = W.scan_bytes = 0;
     RD_HIP(rocprim::radix_sort_pairs(nullptr, W.sort_bytes, dk, dq, (size_t)A, 0u, (unsigned)end_bit, ctx->stream));
     RD_HIP(rocprim::exclusive_scan(nullptr, W.scan_bytes, W.bcnt, W.boff, 0u, (size_t)W.nb + 1, rocprim::plus<uint32_t>(), ctx->stream));
-    W.tmp = take(std::max(W.sort_bytes, W.scan_bytes));
-    if (at > ctx->ws_align.cap) {
-        rd_set_error("%s: internal workspace accounting (%zu > %zu for %lld anchors)", who, at, ctx->ws_align.cap, (long long)A);
-        return RD_ERR_STATE;
-    }
-    return RD_OK;
+    W.tmp = c.take<char>(std::max(W.sort_bytes, W.scan_bytes));
+    return rd_carve_check(who, c, ctx->ws_align.cap);   // (A anchors: the size came from MAP_ANCHOR_BYTES and MAP_LAUNCH_BYTES)
 }
 
 // sorted anchors (keys, qs) -> segment starts and one chain result per segment in W; *n_seg on the host

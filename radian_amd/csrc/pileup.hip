@@ -20,6 +20,7 @@
 //   workgroup has seen since its last flush reach 2^30 (a round adds fewer than 4 * 2^28), so no 32-bit counter wraps.
 // Integer adds only: the tables do not depend on the launch order, the budget, the batching or the run.
 #include "common.h"
+#include "align_batch.h"
 #include "pileup_rules.h"
 #include "../../include/radian_hip.h"
 
@@ -97,9 +98,53 @@ extern "C" int rd_pileup_host(const uint8_t* ops, const int64_t* ops_off, const 
     return RD_OK;
 }
 
+// ------------------------------------------------------------------------------------------------------------------ the device blocks
+namespace {
+
+// A launch of rd_pileup_add_ops, nb pairs.  It is staged on the host and copied whole, so its blocks are offsets: descriptors | results as
+// align_tb_kernel leaves them | site0 | this kernel's results | then every pair's sequences and ops, unrounded (pu_ops_pair)
+struct PuOpsAt {
+    size_t res, site, out;
+};
+void pu_ops_layout(Carve& c, int nb, PuOpsAt* o)
+{
+    c.take<AlnPair>((size_t)nb);
+    o->res = c.mark();
+    c.take<int32_t>((size_t)nb * ALN_RES);
+    o->site = c.mark();
+    c.take<int64_t>((size_t)nb);
+    o->out = c.mark();
+    c.take<int32_t>((size_t)nb * PILEUP_RES);
+}
+void pu_ops_pair(Carve& c, int64_t n, int64_t m, int64_t L, AlnPair* d)
+{
+    d->n = (int32_t)n;
+    d->m = (int32_t)m;
+    d->ref = (int64_t)c.mark();
+    d->read = d->ref + n;
+    d->ops = d->read + m;
+    d->bnd = d->dir = 0;
+    c.take<uint8_t>((size_t)(n + m + L), 0, 1);
+}
+
+// rd_pileup_read over S sites: flags | positions | the scan's own | then the rows, `need` of them once their number is known (0 before)
+struct PuReadWs {
+    uint32_t *flag, *pos, *site, *counts;
+    void* tmp;
+};
+void pu_read_layout(Carve& c, int64_t S, size_t scan_bytes, int64_t need, PuReadWs* w)
+{
+    w->flag = c.take<uint32_t>((size_t)S);
+    w->pos = c.take<uint32_t>((size_t)S);
+    w->tmp = c.take<char>(scan_bytes);
+    w->site = c.take<uint32_t>((size_t)need);
+    w->counts = c.take<uint32_t>((size_t)need * PILEUP_CH, 0, 1);
+}
+
+}  // namespace
+
 #if defined(__HIPCC__)
 // ------------------------------------------------------------------------------------------------------------------ device half
-#include "align_batch.h"
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -402,22 +447,15 @@ extern "C" int rd_pileup_add_ops(rd_ctx* ctx, const uint8_t* ops, const int64_t*
             p1++;
         }
         const int nb = p1 - p0;
-        // descriptors | results as align_tb_kernel leaves them | site0 | this kernel's results | sequences and ops
-        const size_t res_at = align_up((size_t)nb * sizeof(AlnPair), 256), site_at = res_at + align_up((size_t)nb * ALN_RES * 4, 256);
-        const size_t out_at = site_at + align_up((size_t)nb * 8, 256);
-        size_t at = out_at + align_up((size_t)nb * PILEUP_RES * 4, 256);
+        Carve c;   // (dry: the offsets go into the descriptors and the host's staging buffer)
+        PuOpsAt o;
+        pu_ops_layout(c, nb, &o);
         std::vector<AlnPair> desc(nb);
         for (int k = 0; k < nb; k++) {
             const int p = p0 + k;
-            AlnPair& d = desc[k];
-            d.n = (int32_t)(ref_off[p + 1] - ref_off[p]);
-            d.m = (int32_t)(read_off[p + 1] - read_off[p]);
-            d.ref = (int64_t)at;
-            d.read = d.ref + d.n;
-            d.ops = d.read + d.m;
-            d.bnd = d.dir = 0;
-            at += (size_t)d.n + d.m + (size_t)(ops_off[p + 1] - ops_off[p]);
+            pu_ops_pair(c, ref_off[p + 1] - ref_off[p], read_off[p + 1] - read_off[p], ops_off[p + 1] - ops_off[p], &desc[k]);
         }
+        const size_t at = c.at, res_at = o.res, site_at = o.site, out_at = o.out;
         stage.assign(at, 0);
         memcpy(stage.data(), desc.data(), (size_t)nb * sizeof(AlnPair));
         for (int k = 0; k < nb; k++) {
@@ -459,41 +497,32 @@ extern "C" int rd_pileup_read(rd_ctx* ctx, uint32_t min_depth, int64_t capacity,
     if (S == 0) return RD_OK;
     size_t scan_bytes = 0;
     RD_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)S, rocprim::plus<uint32_t>(), st));
-    // flags | positions | the scan's own | then the rows, once their number is known
-    const size_t pos_at = align_up((size_t)S * 4, 256), tmp_at = pos_at + align_up((size_t)S * 4, 256), rows_at = tmp_at + align_up(scan_bytes, 256);
-    if (ctx->ws_pileup.reserve(rows_at)) return RD_ERR_NOMEM;
-    uint8_t* w = ctx->ws_pileup.as<uint8_t>();
-    uint32_t* d_flag = (uint32_t*)w;
-    uint32_t* d_pos = (uint32_t*)(w + pos_at);
+    PuReadWs w;
+    if (rd_carve(ctx->ws_pileup, [&](Carve& c) { pu_read_layout(c, S, scan_bytes, 0, &w); })) return RD_ERR_NOMEM;
     const unsigned grid = (unsigned)((S + 255) / 256);
-    hipLaunchKernelGGL(pileup_flag_kernel, dim3(grid), dim3(256), 0, st, ctx->pileup_sites.as<uint32_t>(), S, min_depth, d_flag);
+    hipLaunchKernelGGL(pileup_flag_kernel, dim3(grid), dim3(256), 0, st, ctx->pileup_sites.as<uint32_t>(), S, min_depth, w.flag);
     RD_HIP(hipGetLastError());
-    RD_HIP(rocprim::exclusive_scan(w + tmp_at, scan_bytes, d_flag, d_pos, 0u, (size_t)S, rocprim::plus<uint32_t>(), st));
+    RD_HIP(rocprim::exclusive_scan(w.tmp, scan_bytes, w.flag, w.pos, 0u, (size_t)S, rocprim::plus<uint32_t>(), st));
     uint32_t tail[2] = {0, 0};
-    RD_HIP(hipMemcpyAsync(&tail[0], d_flag + (S - 1), 4, hipMemcpyDeviceToHost, st));
-    RD_HIP(hipMemcpyAsync(&tail[1], d_pos + (S - 1), 4, hipMemcpyDeviceToHost, st));
+    RD_HIP(hipMemcpyAsync(&tail[0], w.flag + (S - 1), 4, hipMemcpyDeviceToHost, st));
+    RD_HIP(hipMemcpyAsync(&tail[1], w.pos + (S - 1), 4, hipMemcpyDeviceToHost, st));
     RD_HIP(hipStreamSynchronize(st));
     const int64_t need = (int64_t)tail[0] + tail[1];
     *n_out = need;
     RD_REQUIRE(capacity >= need, "%s: %lld sites at depth %u or more, the outputs hold %lld", who, (long long)need, min_depth, (long long)capacity);
     if (need == 0) return RD_OK;
     // (growing the workspace would drop the flags: the rows get a block of their own size only when the first one is too small)
-    const size_t counts_at = rows_at + align_up((size_t)need * 4, 256), total = counts_at + (size_t)need * PILEUP_CH * 4;
-    if (total > ctx->ws_pileup.cap) {
-        if (ctx->ws_pileup.reserve(total)) return RD_ERR_NOMEM;
-        w = ctx->ws_pileup.as<uint8_t>();
-        d_flag = (uint32_t*)w;
-        d_pos = (uint32_t*)(w + pos_at);
-        hipLaunchKernelGGL(pileup_flag_kernel, dim3(grid), dim3(256), 0, st, ctx->pileup_sites.as<uint32_t>(), S, min_depth, d_flag);
+    const size_t cap0 = ctx->ws_pileup.cap;
+    if (rd_carve(ctx->ws_pileup, [&](Carve& c) { pu_read_layout(c, S, scan_bytes, need, &w); })) return RD_ERR_NOMEM;
+    if (ctx->ws_pileup.cap != cap0) {
+        hipLaunchKernelGGL(pileup_flag_kernel, dim3(grid), dim3(256), 0, st, ctx->pileup_sites.as<uint32_t>(), S, min_depth, w.flag);
         RD_HIP(hipGetLastError());
-        RD_HIP(rocprim::exclusive_scan(w + tmp_at, scan_bytes, d_flag, d_pos, 0u, (size_t)S, rocprim::plus<uint32_t>(), st));
+        RD_HIP(rocprim::exclusive_scan(w.tmp, scan_bytes, w.flag, w.pos, 0u, (size_t)S, rocprim::plus<uint32_t>(), st));
     }
-    uint32_t* d_site = (uint32_t*)(w + rows_at);
-    uint32_t* d_counts = (uint32_t*)(w + counts_at);
-    hipLaunchKernelGGL(pileup_gather_kernel, dim3(grid), dim3(256), 0, st, ctx->pileup_sites.as<uint32_t>(), S, d_flag, d_pos, d_site, d_counts);
+    hipLaunchKernelGGL(pileup_gather_kernel, dim3(grid), dim3(256), 0, st, ctx->pileup_sites.as<uint32_t>(), S, w.flag, w.pos, w.site, w.counts);
     RD_HIP(hipGetLastError());
-    RD_HIP(hipMemcpyAsync(site, d_site, (size_t)need * 4, hipMemcpyDeviceToHost, st));
-    RD_HIP(hipMemcpyAsync(counts, d_counts, (size_t)need * PILEUP_CH * 4, hipMemcpyDeviceToHost, st));
+    RD_HIP(hipMemcpyAsync(site, w.site, (size_t)need * 4, hipMemcpyDeviceToHost, st));
+    RD_HIP(hipMemcpyAsync(counts, w.counts, (size_t)need * PILEUP_CH * 4, hipMemcpyDeviceToHost, st));
     RD_HIP(hipStreamSynchronize(st));
     return RD_OK;
 }

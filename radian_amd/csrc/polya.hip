@@ -30,6 +30,7 @@
 // No floating point, no atomics but the select's LDS histogram, no inline assembly.  A result does not depend on the launch's other reads.
 #include "common.h"
 #include "budget.h"
+#include "carve.h"
 #include "polya_rules.h"
 #include "../../include/radian_hip.h"
 
@@ -165,14 +166,8 @@ extern "C" int rd_polya_segment_host(const int16_t* raw, const int64_t* read_off
     return RD_OK;
 }
 
-#if defined(__HIPCC__)
-// ------------------------------------------------------------------------------------------------------------------ device half
-#include "select.h"
-
+// ------------------------------------------------------------------------------------------------------------------ a launch's device block
 namespace {
-
-constexpr int PA_WPB = 64;   // windows per workgroup of the window kernel
-constexpr int PA_SEG = 256;  // threads of the segment kernel = windows per chunk of its sweep
 
 struct PaRead {
     int64_t raw0;   // the read's sample 0 in the raw buffer
@@ -186,6 +181,39 @@ struct PaScale {
 struct PaBlock {
     int32_t read, j0;   // windows [j0, j0 + PA_WPB) of the read
 };
+
+// descriptors, scales and the window arrays
+struct PaWs {
+    PaRead* reads;
+    PaScale* scale;
+    PaBlock* blocks;
+    uint8_t* flag;
+    int32_t* S;
+    int64_t* Q;
+    int64_t n_windows;
+};
+
+void pa_layout(Carve& c, size_t n_reads, size_t n_blocks, int64_t nwin, PaWs* ws)
+{
+    ws->reads = c.take<PaRead>(n_reads);
+    ws->scale = c.take<PaScale>(n_reads);
+    ws->blocks = c.take<PaBlock>(n_blocks, 8);
+    ws->Q = c.take<int64_t>((size_t)nwin, 8);
+    ws->S = c.take<int32_t>((size_t)nwin, 8);
+    ws->flag = c.take<uint8_t>((size_t)nwin, 8);
+    ws->n_windows = nwin;
+}
+
+}  // namespace
+
+#if defined(__HIPCC__)
+// ------------------------------------------------------------------------------------------------------------------ device half
+#include "select.h"
+
+namespace {
+
+constexpr int PA_WPB = 64;   // windows per workgroup of the window kernel
+constexpr int PA_SEG = 256;  // threads of the segment kernel = windows per chunk of its sweep
 
 __global__ __launch_bounds__(256) void pa_scale_kernel(const PaRead* __restrict__ reads, const int16_t* __restrict__ raw, PaParams p,
                                                        PaScale* __restrict__ scale)
@@ -370,17 +398,6 @@ __global__ __launch_bounds__(PA_SEG) void pa_segment_kernel(const PaRead* __rest
     }
 }
 
-// a launch's device block: descriptors, scales and the window arrays
-struct PaWs {
-    PaRead* reads;
-    PaScale* scale;
-    PaBlock* blocks;
-    uint8_t* flag;
-    int32_t* S;
-    int64_t* Q;
-    int64_t n_windows;
-};
-
 // scale and window kernels (and, with d_out, the segment kernel) for reads whose samples are on the device; read_off is a host array
 int pa_run(rd_ctx* ctx, hipStream_t st, const int16_t* d_raw, const int64_t* read_off, int n_reads, const PaParams& p, PaOut* d_out, PaWs* ws)
 {
@@ -393,18 +410,7 @@ int pa_run(rd_ctx* ctx, hipStream_t st, const int16_t* d_raw, const int64_t* rea
         for (int32_t j0 = 0; j0 < reads[r].nw; j0 += PA_WPB) blocks.push_back(PaBlock{r, j0});
         nwin += reads[r].nw;
     }
-    const size_t b_reads = align_up(reads.size() * sizeof(PaRead), 256), b_scale = align_up((size_t)n_reads * sizeof(PaScale), 256),
-                 b_blocks = align_up(blocks.size() * sizeof(PaBlock) + 8, 256), b_flag = align_up((size_t)nwin + 8, 256),
-                 b_S = align_up((size_t)nwin * 4 + 8, 256), b_Q = align_up((size_t)nwin * 8 + 8, 256);
-    if (ctx->ws_polya.reserve(b_reads + b_scale + b_blocks + b_flag + b_S + b_Q)) return RD_ERR_NOMEM;
-    char* c = (char*)ctx->ws_polya.p;
-    ws->reads = (PaRead*)c; c += b_reads;
-    ws->scale = (PaScale*)c; c += b_scale;
-    ws->blocks = (PaBlock*)c; c += b_blocks;
-    ws->Q = (int64_t*)c; c += b_Q;
-    ws->S = (int32_t*)c; c += b_S;
-    ws->flag = (uint8_t*)c;
-    ws->n_windows = nwin;
+    if (rd_carve(ctx->ws_polya, [&](Carve& c) { pa_layout(c, reads.size(), blocks.size(), nwin, ws); })) return RD_ERR_NOMEM;
     RD_HIP(hipMemcpyAsync(ws->reads, reads.data(), reads.size() * sizeof(PaRead), hipMemcpyHostToDevice, st));
     if (!blocks.empty()) RD_HIP(hipMemcpyAsync(ws->blocks, blocks.data(), blocks.size() * sizeof(PaBlock), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(pa_scale_kernel, dim3(n_reads), dim3(256), 0, st, ws->reads, d_raw, p, ws->scale);
@@ -459,14 +465,9 @@ extern "C" int rd_polya_segment(rd_ctx* ctx, const int16_t* raw, const int64_t* 
     for (auto [k0, k1] : plan.launches) {
         const int n = (int)(k1 - k0);
         const int32_t* members = plan.run.data() + k0;
-        off.assign(1, 0);
-        for (int i = 0; i < n; i++) off.push_back(off.back() + read_off[members[i] + 1] - read_off[members[i]]);
+        rd_gather_offsets(read_off, members, n, off);
         if (ctx->ws_raw.reserve((size_t)off[n] * 2 + 16) || ctx->ws_polya_io.reserve((size_t)n * sizeof(PaOut))) return RD_ERR_NOMEM;
-        for (int i = 0, k; i < n; i = k) {   // one copy per run of consecutive reads (their samples are contiguous on both sides)
-            for (k = i + 1; k < n && members[k] == members[k - 1] + 1; k++) {}
-            const int64_t T = off[k] - off[i];
-            if (T) RD_HIP(hipMemcpyAsync(ctx->ws_raw.as<int16_t>() + off[i], raw + read_off[members[i]], (size_t)T * 2, hipMemcpyHostToDevice, st));
-        }
+        if ((rc = rd_gather_h2d(st, ctx->ws_raw.p, raw, 2, read_off, members, n, off.data()))) return rc;
         if ((rc = rd_polya_segment_dev(ctx, st, ctx->ws_raw.as<int16_t>(), off.data(), n, p, ctx->ws_polya_io.as<PaOut>()))) return rc;
         got.resize(n);
         RD_HIP(hipMemcpyAsync(got.data(), ctx->ws_polya_io.p, (size_t)n * sizeof(PaOut), hipMemcpyDeviceToHost, st));

@@ -194,6 +194,55 @@ extern "C" int rd_segment_host(const int16_t* raw, const int64_t* read_off, int 
     return RD_OK;
 }
 
+// ------------------------------------------------------------------------------------------------------------------ a launch's device block
+namespace {
+
+struct SgRead {
+    int64_t raw0;   // the read's sample 0 in the launch's sample buffer
+    int32_t T, pad_;
+};
+struct SgTile {
+    int32_t read, t0;   // samples [t0, t0 + SG_TILE) of the read
+};
+struct SgWs {
+    SgRead* reads;
+    SgTile* tiles;
+    uint8_t *flags, *bnd, *ev_src;
+    uint32_t* pos;
+    int64_t *ev_g, *ev_sum, *ev_sumsq;
+    int16_t *ev_min, *ev_max;
+    uint64_t *tN, *tD;
+    void* tmp;
+    size_t tmp_bytes;
+    int64_t n, cap;
+    unsigned n_tiles;
+};
+
+// n samples, room for cap events, tmp_bytes of scan storage; diag: the two statistics of every sample and detector as well
+void sg_layout(Carve& c, size_t n_reads, size_t n_tiles, int64_t n, int64_t cap, size_t tmp_bytes, bool diag, SgWs* ws)
+{
+    ws->reads = c.take<SgRead>(n_reads);
+    ws->tiles = c.take<SgTile>(n_tiles, 8);
+    ws->ev_g = c.take<int64_t>((size_t)cap);
+    ws->ev_sum = c.take<int64_t>((size_t)cap);
+    ws->ev_sumsq = c.take<int64_t>((size_t)cap);
+    ws->tN = c.take<uint64_t>(diag ? (size_t)n * 2 : 0, diag ? 8 : 0);
+    ws->tD = c.take<uint64_t>(diag ? (size_t)n * 2 : 0, diag ? 8 : 0);
+    ws->tmp = c.take<char>(tmp_bytes, 8);
+    ws->pos = c.take<uint32_t>((size_t)n + 1);
+    ws->ev_min = c.take<int16_t>((size_t)cap);
+    ws->ev_max = c.take<int16_t>((size_t)cap);
+    ws->flags = c.take<uint8_t>((size_t)n + 1);
+    ws->bnd = c.take<uint8_t>((size_t)n + 1);
+    ws->ev_src = c.take<uint8_t>((size_t)cap);
+    ws->tmp_bytes = tmp_bytes;
+    ws->n = n;
+    ws->cap = cap;
+    ws->n_tiles = (unsigned)n_tiles;
+}
+
+}  // namespace
+
 #if defined(__HIPCC__)
 // ------------------------------------------------------------------------------------------------------------------ device half
 #include "signal_dev.h"
@@ -209,13 +258,6 @@ constexpr int SG_MAX_ST = SG_TILE + 4 * SG_MAX_W;            // staged samples: 
 constexpr int SG_MAX_POS = SG_TILE + 2 * SG_MAX_W + 1;       // positions with N, D: the tile and W to either side
 constexpr int64_t SG_MAX_LAUNCH_BYTES = (int64_t)1 << 35;    // a launch's workspace: its samples (under 2^35 / 8) give under 2^32 events
 
-struct SgRead {
-    int64_t raw0;   // the read's sample 0 in the launch's sample buffer
-    int32_t T, pad_;
-};
-struct SgTile {
-    int32_t read, t0;   // samples [t0, t0 + SG_TILE) of the read
-};
 struct SgNonZero {
     __host__ __device__ uint32_t operator()(uint8_t v) const { return v != 0 ? 1u : 0u; }
 };
@@ -415,21 +457,6 @@ __global__ __launch_bounds__(SG_NT) void sg_event_kernel(const int16_t* __restri
     }
 }
 
-// a launch's device block
-struct SgWs {
-    SgRead* reads;
-    SgTile* tiles;
-    uint8_t *flags, *bnd, *ev_src;
-    uint32_t* pos;
-    int64_t *ev_g, *ev_sum, *ev_sumsq;
-    int16_t *ev_min, *ev_max;
-    uint64_t *tN, *tD;
-    void* tmp;
-    size_t tmp_bytes;
-    int64_t n, cap;
-    unsigned n_tiles;
-};
-
 // lays the launch out in ctx->ws_segment, uploads its descriptors and runs the peak kernel; off: the reads' offsets in the sample buffer
 int sg_peaks(rd_ctx* ctx, hipStream_t st, const int16_t* d_raw, const int64_t* off, int nb, const SgParams& p, bool diag, SgWs* ws,
              std::vector<SgRead>& reads, std::vector<SgTile>& tiles)
@@ -447,30 +474,7 @@ int sg_peaks(rd_ctx* ctx, hipStream_t st, const int16_t* d_raw, const int64_t* o
     size_t tmp_bytes = 0;
     RD_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, rocprim::make_transform_iterator((const uint8_t*)nullptr, SgNonZero()), (uint32_t*)nullptr, 0u,
                                    (size_t)n + 1, rocprim::plus<uint32_t>(), st));
-    const size_t b_reads = align_up(reads.size() * sizeof(SgRead), 256), b_tiles = align_up(tiles.size() * sizeof(SgTile) + 8, 256),
-                 b_byte = align_up((size_t)n + 1, 256), b_pos = align_up(((size_t)n + 1) * 4, 256), b_e8 = align_up((size_t)cap * 8, 256),
-                 b_e2 = align_up((size_t)cap * 2, 256), b_e1 = align_up((size_t)cap, 256), b_tmp = align_up(tmp_bytes + 8, 256),
-                 b_t = diag ? align_up((size_t)n * 16 + 8, 256) : 0;
-    if (ctx->ws_segment.reserve(b_reads + b_tiles + 2 * b_byte + b_pos + 3 * b_e8 + 2 * b_e2 + b_e1 + b_tmp + 2 * b_t)) return RD_ERR_NOMEM;
-    char* c = (char*)ctx->ws_segment.p;
-    ws->reads = (SgRead*)c; c += b_reads;
-    ws->tiles = (SgTile*)c; c += b_tiles;
-    ws->ev_g = (int64_t*)c; c += b_e8;
-    ws->ev_sum = (int64_t*)c; c += b_e8;
-    ws->ev_sumsq = (int64_t*)c; c += b_e8;
-    ws->tN = (uint64_t*)c; c += b_t;
-    ws->tD = (uint64_t*)c; c += b_t;
-    ws->tmp = c; c += b_tmp;
-    ws->pos = (uint32_t*)c; c += b_pos;
-    ws->ev_min = (int16_t*)c; c += b_e2;
-    ws->ev_max = (int16_t*)c; c += b_e2;
-    ws->flags = (uint8_t*)c; c += b_byte;
-    ws->bnd = (uint8_t*)c; c += b_byte;
-    ws->ev_src = (uint8_t*)c;
-    ws->tmp_bytes = tmp_bytes;
-    ws->n = n;
-    ws->cap = cap;
-    ws->n_tiles = (unsigned)tiles.size();
+    if (rd_carve(ctx->ws_segment, [&](Carve& c) { sg_layout(c, reads.size(), tiles.size(), n, cap, tmp_bytes, diag, ws); })) return RD_ERR_NOMEM;
     RD_HIP(hipMemcpyAsync(ws->reads, reads.data(), reads.size() * sizeof(SgRead), hipMemcpyHostToDevice, st));
     RD_HIP(hipMemcpyAsync(ws->tiles, tiles.data(), tiles.size() * sizeof(SgTile), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(sg_peak_kernel, dim3(ws->n_tiles), dim3(SG_NT), 0, st, ws->tiles, ws->reads, d_raw, p, ws->flags, diag ? ws->tN : nullptr,
@@ -592,13 +596,9 @@ extern "C" int rd_segment(rd_ctx* ctx, const int16_t* raw, const int64_t* read_o
     for (auto [k0, k1] : plan.launches) {
         const int nb = (int)(k1 - k0);
         const int32_t* members = plan.run.data() + k0;
-        off.assign(1, 0);
-        for (int i = 0; i < nb; i++) off.push_back(off.back() + read_off[members[i] + 1] - read_off[members[i]]);
+        rd_gather_offsets(read_off, members, nb, off);
         if (ctx->ws_raw.reserve((size_t)off[nb] * 2 + 16)) return RD_ERR_NOMEM;
-        for (int i = 0, k; i < nb; i = k) {   // one copy per run of reads whose samples are contiguous on both sides
-            for (k = i + 1; k < nb && read_off[members[k]] == read_off[members[k - 1] + 1]; k++) {}
-            RD_HIP(hipMemcpyAsync(ctx->ws_raw.as<int16_t>() + off[i], raw + read_off[members[i]], (size_t)(off[k] - off[i]) * 2, hipMemcpyHostToDevice, st));
-        }
+        if ((rc = rd_gather_h2d(st, ctx->ws_raw.p, raw, 2, read_off, members, nb, off.data()))) return rc;
         if ((rc = sg_launch(ctx, st, c, members, nb, off.data(), reads, tiles, h_g, h_sum, h_sq, h_min, h_max, h_src))) return rc;
     }
     if (plan.too_large) {

@@ -204,15 +204,8 @@ extern "C" int rd_sigmap_host(const int16_t* raw, int64_t n_raw, int n_q, const 
     return RD_OK;
 }
 
-#if defined(__HIPCC__)
-// ------------------------------------------------------------------------------------------------------------------ device half
-#include "band_sweep.h"
-#include "signal_dev.h"
-
+// ------------------------------------------------------------------------------------------------------------------ the device blocks
 namespace {
-
-constexpr int SM_MAX_LAUNCH = 4096;        // queries of one launch
-static_assert(SM_BAND == BS_BAND, "a band is a workgroup pass");
 
 struct SmQuery {
     int64_t raw0;            // the query window's sample 0 in the raw buffer
@@ -226,6 +219,44 @@ struct SmStripe {
 struct SmOut {
     int32_t tgt[SM_MAX_BEST], score[SM_MAX_BEST], end[SM_MAX_BEST], org[SM_MAX_BEST];
 };
+
+// behind the k-mer tables in ws_eval_model: the panel's target offsets, and per state its k-mer (bit 31: a target's first) and its target
+struct SmPanel {
+    int64_t* off;
+    uint32_t* kid;
+    int32_t* tg;
+};
+void sm_panel_layout(Carve& c, int n_tgt, int64_t R, SmPanel* p)
+{
+    p->off = c.take<int64_t>((size_t)n_tgt + 1);
+    p->kid = c.take<uint32_t>((size_t)R, 16);
+    p->tg = c.take<int32_t>((size_t)R, 16);
+}
+
+// a launch's io block (ws_eval): descriptors | stripes | results
+struct SmIo {
+    SmQuery* qs;
+    SmStripe* str;
+    SmOut* out;
+};
+void sm_io_layout(Carve& c, int nb, size_t n_stripes, SmIo* io)
+{
+    io->qs = c.take<SmQuery>((size_t)nb);
+    io->str = c.take<SmStripe>(n_stripes);
+    io->out = c.take<SmOut>((size_t)nb, 0, 1);
+}
+
+}  // namespace
+
+#if defined(__HIPCC__)
+// ------------------------------------------------------------------------------------------------------------------ device half
+#include "band_sweep.h"
+#include "signal_dev.h"
+
+namespace {
+
+constexpr int SM_MAX_LAUNCH = 4096;        // queries of one launch
+static_assert(SM_BAND == BS_BAND, "a band is a workgroup pass");
 
 __global__ __launch_bounds__(256) void sm_state_kernel(const int64_t* __restrict__ tgt_off, int n_tgt, const uint8_t* __restrict__ codes, int k,
                                                        int64_t R, uint32_t* __restrict__ kid, int32_t* __restrict__ tg)
@@ -442,22 +473,23 @@ extern "C" int rd_sigmap(rd_ctx* ctx, const int16_t* raw, int64_t n_raw, int n_q
         hi = std::max(hi, std::max(q_hi[q], sc_hi[q]));
     }
     const int64_t n_samples = hi > lo ? hi - lo : 0, R = tgt_off[n_tgt];
-    const size_t b_off = align_up((size_t)(n_tgt + 1) * 8, 256), b_st = align_up((size_t)R * 4 + 16, 256);
     if (ctx->ws_raw.reserve((size_t)n_samples * 2 + 16) || ctx->ws_labels.reserve((size_t)R + 16)) return RD_ERR_NOMEM;
     const int16_t* d_raw = ctx->ws_raw.as<int16_t>();
     const uint8_t* d_codes = ctx->ws_labels.as<uint8_t>();
     if (n_samples) RD_HIP(hipMemcpyAsync(ctx->ws_raw.p, raw + lo, (size_t)n_samples * 2, hipMemcpyHostToDevice, st));
     if (R) RD_HIP(hipMemcpyAsync(ctx->ws_labels.p, codes, (size_t)R, hipMemcpyHostToDevice, st));
     KmerTables tab;
-    if ((rc = signal_upload_tables(ctx, st, k, lvl, w, bias, b_off + 2 * b_st, &tab))) return rc;
+    SmPanel panel;
+    Carve panel_dry;
+    sm_panel_layout(panel_dry, n_tgt, R, &panel);
+    if ((rc = signal_upload_tables(ctx, st, k, lvl, w, bias, panel_dry.at, &tab))) return rc;
+    Carve panel_wet(tab.extra);
+    sm_panel_layout(panel_wet, n_tgt, R, &panel);
     const int32_t *d_lvl = tab.lvl, *d_bias = tab.bias;
     const uint32_t* d_w = tab.w;
-    const int64_t* d_off = (const int64_t*)tab.extra;
-    uint32_t* d_kid = (uint32_t*)(tab.extra + b_off);
-    int32_t* d_tg = (int32_t*)(tab.extra + b_off + b_st);
-    RD_HIP(hipMemcpyAsync((void*)d_off, tgt_off, (size_t)(n_tgt + 1) * 8, hipMemcpyHostToDevice, st));
+    RD_HIP(hipMemcpyAsync(panel.off, tgt_off, (size_t)(n_tgt + 1) * 8, hipMemcpyHostToDevice, st));
     if (R) {
-        hipLaunchKernelGGL(sm_state_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, d_off, n_tgt, d_codes, k, R, d_kid, d_tg);
+        hipLaunchKernelGGL(sm_state_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, panel.off, n_tgt, d_codes, k, R, panel.kid, panel.tg);
         RD_HIP(hipGetLastError());
     }
     // every query's scale: a property of the query alone, whatever the budget does with it afterwards
@@ -484,7 +516,7 @@ extern "C" int rd_sigmap(rd_ctx* ctx, const int16_t* raw, int64_t n_raw, int n_q
         const int32_t* members = plan.run.data() + k0;
         desc.resize(nb);
         stripes.clear();
-        size_t at = 0;
+        Carve ws;   // (dry: the descriptors hold offsets into ws_align)
         int64_t max_T = 0;
         for (int i = 0; i < nb; i++) {
             const int q = members[i];
@@ -493,41 +525,33 @@ extern "C" int rd_sigmap(rd_ctx* ctx, const int16_t* raw, int64_t n_raw, int n_q
             int32_t j_lo;
             const int64_t n_j = sm_target_span(c, q, &j_lo);
             d = SmQuery{q_lo[q] - lo, 0, 0, 0, (int32_t)T, m2[q], d4[q], (int32_t)s_lo[q], j_lo, (int32_t)n_j, {0, 0}};
-            d.zq = (int64_t)at;
-            at += (size_t)sm_round256(4 * T);
-            d.org = (int64_t)at;
-            at += (size_t)sm_round256(4 * n);
-            d.key = (int64_t)at;
-            at += (size_t)sm_round256(8 * n_j);
+            d.zq = (int64_t)ws.mark();
+            ws.take<int32_t>((size_t)T);
+            d.org = (int64_t)ws.mark();
+            ws.take<int32_t>((size_t)n);
+            d.key = (int64_t)ws.mark();
+            ws.take<int64_t>((size_t)n_j);
             const bool cols = std::min<int64_t>(n, SM_PAYLOAD + T - 1) > SM_BAND;
             for (int64_t a = s_lo[q]; a < s_hi[q]; a += SM_PAYLOAD) {
-                stripes.push_back(SmStripe{(int64_t)at, i, (int32_t)sm_stripe_left(a, T, s_lo[q]), (int32_t)a, (int32_t)std::min<int64_t>(a + SM_PAYLOAD, s_hi[q])});
-                if (cols) at += (size_t)sm_round256(16 * T);
+                stripes.push_back(SmStripe{(int64_t)ws.mark(), i, (int32_t)sm_stripe_left(a, T, s_lo[q]), (int32_t)a, (int32_t)std::min<int64_t>(a + SM_PAYLOAD, s_hi[q])});
+                if (cols) ws.take<int64_t>(2 * (size_t)T);
             }
             max_T = std::max(max_T, T);
         }
-        if (at > ctx->ws_align.cap) {
-            rd_set_error("rd_sigmap: internal workspace accounting (%zu > %zu)", at, ctx->ws_align.cap);
-            return RD_ERR_STATE;
-        }
-        // descriptors | stripes | results
-        const size_t o_str = align_up((size_t)nb * sizeof(SmQuery), 256), o_out = o_str + align_up(stripes.size() * sizeof(SmStripe), 256);
-        if (ctx->ws_eval.reserve(o_out + (size_t)nb * sizeof(SmOut))) return RD_ERR_NOMEM;
-        uint8_t* io = ctx->ws_eval.as<uint8_t>();
+        if ((rc = rd_carve_check("rd_sigmap", ws, ctx->ws_align.cap))) return rc;
+        SmIo io;
+        if (rd_carve(ctx->ws_eval, [&](Carve& c) { sm_io_layout(c, nb, stripes.size(), &io); })) return RD_ERR_NOMEM;
         uint8_t* dws = ctx->ws_align.as<uint8_t>();
-        const SmQuery* d_qs = (const SmQuery*)io;
-        const SmStripe* d_str = (const SmStripe*)(io + o_str);
-        SmOut* d_out = (SmOut*)(io + o_out);
-        RD_HIP(hipMemcpyAsync(io, desc.data(), (size_t)nb * sizeof(SmQuery), hipMemcpyHostToDevice, st));
-        RD_HIP(hipMemcpyAsync(io + o_str, stripes.data(), stripes.size() * sizeof(SmStripe), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(sm_quant_kernel, dim3((unsigned)((max_T + 255) / 256), nb), dim3(256), 0, st, d_qs, d_raw, dws);
+        RD_HIP(hipMemcpyAsync(io.qs, desc.data(), (size_t)nb * sizeof(SmQuery), hipMemcpyHostToDevice, st));
+        RD_HIP(hipMemcpyAsync(io.str, stripes.data(), stripes.size() * sizeof(SmStripe), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(sm_quant_kernel, dim3((unsigned)((max_T + 255) / 256), nb), dim3(256), 0, st, io.qs, d_raw, dws);
         RD_HIP(hipGetLastError());
-        hipLaunchKernelGGL(sm_dp_kernel, dim3((unsigned)stripes.size()), dim3(BS_NT), 0, st, d_qs, d_str, d_kid, d_tg, d_lvl, d_w, d_bias, dws);
+        hipLaunchKernelGGL(sm_dp_kernel, dim3((unsigned)stripes.size()), dim3(BS_NT), 0, st, io.qs, io.str, panel.kid, panel.tg, d_lvl, d_w, d_bias, dws);
         RD_HIP(hipGetLastError());
-        hipLaunchKernelGGL(sm_select_kernel, dim3(nb), dim3(64), 0, st, d_qs, d_off, dws, n_best, d_out);
+        hipLaunchKernelGGL(sm_select_kernel, dim3(nb), dim3(64), 0, st, io.qs, panel.off, dws, n_best, io.out);
         RD_HIP(hipGetLastError());
         h_out.resize(nb);
-        RD_HIP(hipMemcpyAsync(h_out.data(), d_out, (size_t)nb * sizeof(SmOut), hipMemcpyDeviceToHost, st));
+        RD_HIP(hipMemcpyAsync(h_out.data(), io.out, (size_t)nb * sizeof(SmOut), hipMemcpyDeviceToHost, st));
         RD_HIP(hipStreamSynchronize(st));
         for (int i = 0; i < nb; i++) {
             const int q = members[i];

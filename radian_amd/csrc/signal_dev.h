@@ -41,12 +41,17 @@ inline SignalScaleIn signal_scale_in(int64_t raw0, int64_t n, int64_t T, int64_t
 inline int signal_scales(rd_ctx* ctx, hipStream_t st, const int16_t* d_raw, const std::vector<SignalScaleIn>& in, int64_t max_T,
                          std::vector<int32_t>& scale)
 {
-    const size_t n = in.size(), b_in = align_up(n * sizeof(SignalScaleIn), 256);
+    const size_t n = in.size();
     scale.resize(2 * n);
-    if (ctx->ws_eval.reserve(b_in + n * 8 + 256)) return RD_ERR_NOMEM;
-    int32_t* d_scale = (int32_t*)(ctx->ws_eval.as<uint8_t>() + b_in);
-    RD_HIP(hipMemcpyAsync(ctx->ws_eval.p, in.data(), n * sizeof(SignalScaleIn), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(signal_scale_kernel, dim3((unsigned)n), dim3(256), 0, st, (const SignalScaleIn*)ctx->ws_eval.p, d_raw, (int)max_T, d_scale);
+    SignalScaleIn* d_in = nullptr;
+    int32_t* d_scale = nullptr;
+    const auto layout = [&](Carve& c) {
+        d_in = c.take<SignalScaleIn>(n);
+        d_scale = c.take<int32_t>(2 * n, 256, 1);
+    };
+    if (rd_carve(ctx->ws_eval, layout)) return RD_ERR_NOMEM;
+    RD_HIP(hipMemcpyAsync(d_in, in.data(), n * sizeof(SignalScaleIn), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(signal_scale_kernel, dim3((unsigned)n), dim3(256), 0, st, d_in, d_raw, (int)max_T, d_scale);
     RD_HIP(hipGetLastError());
     RD_HIP(hipMemcpyAsync(scale.data(), d_scale, n * 8, hipMemcpyDeviceToHost, st));
     RD_HIP(hipStreamSynchronize(st));
@@ -64,13 +69,17 @@ struct KmerTables {
 inline int signal_upload_tables(rd_ctx* ctx, hipStream_t st, int k, const int32_t* lvl, const uint32_t* w, const int32_t* bias, size_t extra_bytes,
                                 KmerTables* d)
 {
-    const size_t bytes = (size_t)4 << (2 * k), b_tab = align_up(bytes, 256);
-    if (ctx->ws_eval_model.reserve(3 * b_tab + extra_bytes)) return RD_ERR_NOMEM;
-    uint8_t* mb = ctx->ws_eval_model.as<uint8_t>();
-    *d = KmerTables{(const int32_t*)mb, (const uint32_t*)(mb + b_tab), (const int32_t*)(mb + 2 * b_tab), mb + 3 * b_tab};
-    RD_HIP(hipMemcpyAsync(mb, lvl, bytes, hipMemcpyHostToDevice, st));
-    RD_HIP(hipMemcpyAsync(mb + b_tab, w, bytes, hipMemcpyHostToDevice, st));
-    RD_HIP(hipMemcpyAsync(mb + 2 * b_tab, bias, bytes, hipMemcpyHostToDevice, st));
+    const size_t nk = (size_t)1 << (2 * k);
+    const auto layout = [&](Carve& c) {
+        d->lvl = c.take<int32_t>(nk);
+        d->w = c.take<uint32_t>(nk);
+        d->bias = c.take<int32_t>(nk);
+        d->extra = c.take<uint8_t>(extra_bytes, 0, 1);
+    };
+    if (rd_carve(ctx->ws_eval_model, layout)) return RD_ERR_NOMEM;
+    RD_HIP(hipMemcpyAsync((void*)d->lvl, lvl, nk * 4, hipMemcpyHostToDevice, st));
+    RD_HIP(hipMemcpyAsync((void*)d->w, w, nk * 4, hipMemcpyHostToDevice, st));
+    RD_HIP(hipMemcpyAsync((void*)d->bias, bias, nk * 4, hipMemcpyHostToDevice, st));
     return RD_OK;
 }
 

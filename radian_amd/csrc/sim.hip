@@ -192,14 +192,8 @@ extern "C" int rd_sim_signal_host(const uint8_t* codes, const int64_t* seq_off, 
     return RD_OK;
 }
 
-#if defined(__HIPCC__)
-// ------------------------------------------------------------------------------------------------------------------ device half
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/iterator/transform_iterator.hpp>
-
+// ------------------------------------------------------------------------------------------------------------------ a launch's device block
 namespace {
-
-constexpr int64_t SIM_LAUNCH_OVERHEAD = 12288;   // alignment of a launch's arrays and the scan's temporary storage
 
 // a read of a launch
 struct SimRead {
@@ -211,6 +205,55 @@ struct SimRead {
     int32_t pad_;
 };
 static_assert(sizeof(SimRead) == 64, "SimRead is copied as 64 bytes");
+
+// The model sits at the head of ws_sim for the whole call.
+struct SimWs {
+    SimRead* reads;
+    uint8_t* codes;
+    int16_t* shift;
+    uint16_t* dscale;
+    int32_t* dwell;
+    int64_t* cum;
+    int32_t* bfirst;
+    int2* lvsd;
+    int64_t* len;
+    int16_t* raw;
+    void* tmp;
+    size_t tmp_bytes, total;
+};
+
+size_t sim_model_bytes(int k) { return align_up(((size_t)12 << (2 * k)) + 4096, 256); }
+
+// a launch of n reads, B bases and R padded samples behind the model, with tmp_bytes of scan storage.  What stage A leaves for the sample
+// kernel (reads, lvsd, bfirst) lies before the samples: its place does not depend on R, which is known only after stage A
+void sim_layout(Carve& c, int k, int n, int64_t B, int64_t R, bool with_shift, bool with_dscale, size_t tmp_bytes, SimWs* W)
+{
+    c.take<char>(sim_model_bytes(k));
+    W->reads = c.take<SimRead>((size_t)n, 8);
+    W->cum = c.take<int64_t>((size_t)B + 1, 8);
+    W->len = c.take<int64_t>((size_t)n, 8);
+    W->lvsd = c.take<int2>((size_t)B, 8);
+    W->dwell = c.take<int32_t>((size_t)B + 1, 8);
+    W->bfirst = c.take<int32_t>((size_t)B, 8);
+    W->raw = c.take<int16_t>((size_t)R, 8);
+    W->shift = c.take<int16_t>(with_shift ? (size_t)B : 0, 8);
+    W->dscale = c.take<uint16_t>(with_dscale ? (size_t)B : 0, 8);
+    W->codes = c.take<uint8_t>((size_t)B, 8);
+    W->tmp = c.take<char>(tmp_bytes, 8);
+    W->tmp_bytes = tmp_bytes;
+    W->total = c.at;
+}
+
+}  // namespace
+
+#if defined(__HIPCC__)
+// ------------------------------------------------------------------------------------------------------------------ device half
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
+
+namespace {
+
+constexpr int64_t SIM_LAUNCH_OVERHEAD = 12288;   // alignment of a launch's arrays and the scan's temporary storage
 
 struct SimModelDev {
     const int32_t *level, *sd, *dwell;
@@ -336,50 +379,14 @@ __global__ __launch_bounds__(256) void sim_sample_kernel(const SimRead* __restri
     *(uint4*)(raw + rd.raw0 + s0) = make_uint4(out[0], out[1], out[2], out[3]);   // (raw0 and s0 are multiples of 8)
 }
 
-// a launch's device block.  The model sits at the head of ws_sim for the whole call.
-struct SimWs {
-    SimRead* reads;
-    uint8_t* codes;
-    int16_t* shift;
-    uint16_t* dscale;
-    int32_t* dwell;
-    int64_t* cum;
-    int32_t* bfirst;
-    int2* lvsd;
-    int64_t* len;
-    int16_t* raw;
-    void* tmp;
-    size_t tmp_bytes, total;
-};
-
-size_t sim_model_bytes(int k) { return align_up(((size_t)12 << (2 * k)) + 4096, 256); }
-
-// carve a launch of n reads, B bases and R padded samples behind the model.  What stage A leaves for the sample kernel (reads, lvsd, bfirst)
-// lies before the samples: its place does not depend on R, which is known only after stage A
+// the scan's storage asked of rocprim, then sim_layout: dry with base == nullptr (W->total: the bytes)
 int sim_carve(int k, int n, int64_t B, int64_t R, bool with_shift, bool with_dscale, hipStream_t st, char* base, SimWs* W)
 {
     size_t tb = 0;
     RD_HIP(rocprim::exclusive_scan(nullptr, tb, rocprim::make_transform_iterator((const int32_t*)nullptr, ToI64()), (int64_t*)nullptr, (int64_t)0,
                                    (size_t)B + 1, rocprim::plus<int64_t>(), st));
-    W->tmp_bytes = tb;
-    size_t at = sim_model_bytes(k);
-    const auto take = [&](size_t bytes) {
-        char* p = base ? base + at : nullptr;
-        at += align_up(bytes + 8, 256);
-        return p;
-    };
-    W->reads = (SimRead*)take((size_t)n * sizeof(SimRead));
-    W->cum = (int64_t*)take((size_t)(B + 1) * 8);
-    W->len = (int64_t*)take((size_t)n * 8);
-    W->lvsd = (int2*)take((size_t)B * 8);
-    W->dwell = (int32_t*)take((size_t)(B + 1) * 4);
-    W->bfirst = (int32_t*)take((size_t)B * 4);
-    W->raw = (int16_t*)take((size_t)R * 2);
-    W->shift = (int16_t*)take(with_shift ? (size_t)B * 2 : 0);
-    W->dscale = (uint16_t*)take(with_dscale ? (size_t)B * 2 : 0);
-    W->codes = (uint8_t*)take((size_t)B);
-    W->tmp = take(tb);
-    W->total = at;
+    Carve c(base);
+    sim_layout(c, k, n, B, R, with_shift, with_dscale, tb, W);
     return RD_OK;
 }
 
@@ -387,6 +394,7 @@ struct SimLaunch {
     const int32_t* members;
     int n;
     std::vector<SimRead> reads;
+    std::vector<int64_t> off;   // the members' first bases in the launch's base arrays, and B
     int64_t B = 0, R = 0, tiles = 0;
 };
 
@@ -395,6 +403,7 @@ void sim_describe(const SimIn& in, const int32_t* members, int n, const int64_t*
     Lc->members = members;
     Lc->n = n;
     Lc->reads.resize(n);
+    rd_gather_offsets(in.seq_off, members, n, Lc->off);
     Lc->B = Lc->R = Lc->tiles = 0;
     for (int i = 0; i < n; i++) {
         const int r = members[i];
@@ -413,14 +422,10 @@ int sim_stage_a(hipStream_t st, const SimIn& in, const SimModelDev& m, const Sim
 {
     const int n = Lc.n;
     RD_HIP(hipMemcpyAsync(W.reads, Lc.reads.data(), (size_t)n * sizeof(SimRead), hipMemcpyHostToDevice, st));
-    for (int i = 0, k; i < n; i = k) {   // one copy per run of consecutive reads (their bases are contiguous on both sides)
-        for (k = i + 1; k < n && Lc.members[k] == Lc.members[k - 1] + 1; k++) {}
-        const int64_t src = in.seq_off[Lc.members[i]], dst = Lc.reads[i].seq0, nb = in.seq_off[Lc.members[k - 1] + 1] - src;
-        if (!nb) continue;
-        RD_HIP(hipMemcpyAsync(W.codes + dst, in.codes + src, (size_t)nb, hipMemcpyHostToDevice, st));
-        if (in.shift) RD_HIP(hipMemcpyAsync(W.shift + dst, in.shift + src, (size_t)nb * 2, hipMemcpyHostToDevice, st));
-        if (in.dscale) RD_HIP(hipMemcpyAsync(W.dscale + dst, in.dscale + src, (size_t)nb * 2, hipMemcpyHostToDevice, st));
-    }
+    int rc = rd_gather_h2d(st, W.codes, in.codes, 1, in.seq_off, Lc.members, n, Lc.off.data());   // (off[i] == reads[i].seq0)
+    if (!rc && in.shift) rc = rd_gather_h2d(st, W.shift, in.shift, 2, in.seq_off, Lc.members, n, Lc.off.data());
+    if (!rc && in.dscale) rc = rd_gather_h2d(st, W.dscale, in.dscale, 2, in.seq_off, Lc.members, n, Lc.off.data());
+    if (rc) return rc;
     const unsigned gb = (unsigned)((Lc.B + 1 + 255) / 256);
     hipLaunchKernelGGL(sim_dwell_kernel, dim3(gb), dim3(256), 0, st, W.reads, n, Lc.B, m, W.codes, in.shift ? W.shift : nullptr,
                        in.dscale ? W.dscale : nullptr, W.dwell, W.lvsd);

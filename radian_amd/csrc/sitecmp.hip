@@ -30,6 +30,7 @@
 //   ss_pick_kernel     one wave per site: the best over the site's slots under the same order, then lane 0 writes the entry (ss_entry:
 //                      totals and the low cluster's n, sum and sumsq as differences of the two prefix arrays)
 #include "common.h"
+#include "carve.h"
 #include "site_rules.h"
 #include "../../include/radian_hip.h"
 
@@ -217,6 +218,66 @@ extern "C" int rd_site_split_host(const uint32_t* site, const uint8_t* cond, con
     return RD_OK;
 }
 
+// ------------------------------------------------------------------------------------------------------------------ a launch's device block
+namespace {
+
+struct ScSeg {
+    uint32_t start, split, end, pad_;
+};
+// a work item's best candidate (n_lo == 0: none); n_hi is the site's count less n_lo
+struct SsSlot {
+    uint64_t d;
+    uint32_t n_lo;
+    int32_t cut;
+};
+
+struct ScWs {
+    uint32_t* in_site;
+    uint8_t* in_cond;
+    int16_t* in_value;
+    uint64_t *ka, *kb;
+    uint32_t *flag, *pos, *seg_start, *n_chunk, *item_off, *n_seg;
+    ScSeg* seg;
+    ScOut* out;
+    void* tmp;
+    int64_t *psum, *psq;   // the split's: the two prefix arrays, the slots, the admissible-cut counts and the entries
+    SsSlot* slot;
+    int32_t* cnt;
+    SsOut* split_out;
+    size_t tmp_bytes;
+    const uint64_t* sorted;
+    size_t min_tmp = 0;         // set by the caller before sc_run: the least tmp_bytes
+    int64_t split_items = -1;   // ... and, for a split, its work items (-1: a comparison, without the split's arrays)
+};
+
+// n events expected to fall into S sites, tmp_bytes of sort and scan storage
+void sc_layout(Carve& c, int64_t n, int64_t S, size_t tmp_bytes, int64_t split_items, ScWs* W)
+{
+    W->in_site = c.take<uint32_t>((size_t)n, 8);
+    W->in_cond = c.take<uint8_t>((size_t)n, 8);
+    W->in_value = c.take<int16_t>((size_t)n, 8);
+    W->ka = c.take<uint64_t>((size_t)n, 8);
+    W->kb = c.take<uint64_t>((size_t)n, 8);
+    W->flag = c.take<uint32_t>((size_t)n, 8);
+    W->pos = c.take<uint32_t>((size_t)n, 8);
+    W->seg_start = c.take<uint32_t>((size_t)S + 1, 8);
+    W->n_chunk = c.take<uint32_t>((size_t)S + 1, 8);
+    W->item_off = c.take<uint32_t>((size_t)S + 1, 8);
+    W->n_seg = c.take<uint32_t>(1, 8);
+    W->seg = c.take<ScSeg>((size_t)S, 8);
+    W->out = c.take<ScOut>((size_t)S, 8);
+    W->tmp = c.take<char>(tmp_bytes, 8);
+    const bool split = split_items >= 0;   // (a comparison keeps the 8 bytes behind its last array)
+    W->psum = c.take<int64_t>(split ? (size_t)n : 0);
+    W->psq = c.take<int64_t>(split ? (size_t)n : 0);
+    W->slot = c.take<SsSlot>(split ? (size_t)split_items : 0);
+    W->cnt = c.take<int32_t>(split ? (size_t)S : 0);
+    W->split_out = c.take<SsOut>(split ? (size_t)S : 0, 8);
+    W->tmp_bytes = tmp_bytes;
+}
+
+}  // namespace
+
 #if defined(__HIPCC__)
 // ------------------------------------------------------------------------------------------------------------------ device half
 #include <rocprim/device/device_radix_sort.hpp>
@@ -226,10 +287,6 @@ extern "C" int rd_site_split_host(const uint32_t* site, const uint8_t* cond, con
 namespace {
 
 constexpr int SC_WAVES = 4;   // waves (work items) per workgroup of the site kernel
-
-struct ScSeg {
-    uint32_t start, split, end, pad_;
-};
 
 __global__ __launch_bounds__(256) void sc_pack_kernel(const uint32_t* __restrict__ site, const uint8_t* __restrict__ cond,
                                                       const int16_t* __restrict__ value, uint32_t n, uint64_t* __restrict__ keys)
@@ -324,22 +381,6 @@ __global__ __launch_bounds__(64 * SC_WAVES) void sc_site_kernel(const uint64_t* 
     if (t.ks) atomicMax((unsigned long long*)&o->ks, (unsigned long long)t.ks);
 }
 
-// a launch's device block
-struct ScWs {
-    uint32_t* in_site;
-    uint8_t* in_cond;
-    int16_t* in_value;
-    uint64_t *ka, *kb;
-    uint32_t *flag, *pos, *seg_start, *n_chunk, *item_off, *n_seg;
-    ScSeg* seg;
-    ScOut* out;
-    void* tmp;
-    size_t tmp_bytes;
-    const uint64_t* sorted;
-    size_t extra_bytes = 0, min_tmp = 0;   // set by the caller before sc_run: bytes of its own after the block's arrays, the least tmp_bytes
-    char* extra = nullptr;
-};
-
 // pack, sort and segment n events expected to fall into S sites; with n_items > 0 the head and site kernels too.  Leaves the stream running
 int sc_run(rd_ctx* ctx, hipStream_t st, const uint32_t* site, const uint8_t* cond, const int16_t* value, int64_t n, int64_t S, int64_t n_items,
            int end_bit, ScWs& W)
@@ -349,34 +390,8 @@ int sc_run(rd_ctx* ctx, hipStream_t st, const uint32_t* site, const uint8_t* con
     RD_HIP(rocprim::radix_sort_keys(nullptr, sort_bytes, probe, (size_t)n, 0u, (unsigned)end_bit, st));
     RD_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
     RD_HIP(rocprim::exclusive_scan(nullptr, scan2_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)S + 1, rocprim::plus<uint32_t>(), st));
-    W.tmp_bytes = std::max(std::max(sort_bytes, W.min_tmp), std::max(scan_bytes, scan2_bytes));
-    size_t at = 0;
-    const auto take = [&](size_t bytes) {
-        const size_t o = at;
-        at += align_up(bytes + 8, 256);
-        return o;
-    };
-    const size_t o_site = take((size_t)n * 4), o_cond = take((size_t)n), o_value = take((size_t)n * 2), o_ka = take((size_t)n * 8),
-                 o_kb = take((size_t)n * 8), o_flag = take((size_t)n * 4), o_pos = take((size_t)n * 4), o_start = take((size_t)(S + 1) * 4),
-                 o_chunk = take((size_t)(S + 1) * 4), o_item = take((size_t)(S + 1) * 4), o_nseg = take(4), o_seg = take((size_t)S * sizeof(ScSeg)),
-                 o_out = take((size_t)S * sizeof(ScOut)), o_tmp = take(W.tmp_bytes), o_extra = take(W.extra_bytes);
-    if (ctx->ws_site.reserve(at)) return RD_ERR_NOMEM;
-    char* base = (char*)ctx->ws_site.p;
-    W.in_site = (uint32_t*)(base + o_site);
-    W.in_cond = (uint8_t*)(base + o_cond);
-    W.in_value = (int16_t*)(base + o_value);
-    W.ka = (uint64_t*)(base + o_ka);
-    W.kb = (uint64_t*)(base + o_kb);
-    W.flag = (uint32_t*)(base + o_flag);
-    W.pos = (uint32_t*)(base + o_pos);
-    W.seg_start = (uint32_t*)(base + o_start);
-    W.n_chunk = (uint32_t*)(base + o_chunk);
-    W.item_off = (uint32_t*)(base + o_item);
-    W.n_seg = (uint32_t*)(base + o_nseg);
-    W.seg = (ScSeg*)(base + o_seg);
-    W.out = (ScOut*)(base + o_out);
-    W.tmp = base + o_tmp;
-    W.extra = base + o_extra;
+    const size_t tmp_bytes = std::max(std::max(sort_bytes, W.min_tmp), std::max(scan_bytes, scan2_bytes));
+    if (rd_carve(ctx->ws_site, [&](Carve& c) { sc_layout(c, n, S, tmp_bytes, W.split_items, &W); })) return RD_ERR_NOMEM;
     RD_HIP(hipMemcpyAsync(W.in_site, site, (size_t)n * 4, hipMemcpyHostToDevice, st));
     RD_HIP(hipMemcpyAsync(W.in_cond, cond, (size_t)n, hipMemcpyHostToDevice, st));
     RD_HIP(hipMemcpyAsync(W.in_value, value, (size_t)n * 2, hipMemcpyHostToDevice, st));
@@ -527,13 +542,6 @@ struct SsSquare {
     __host__ __device__ int64_t operator()(uint64_t key) const { return (int64_t)sc_key_value(key) * sc_key_value(key); }
 };
 
-// a work item's best candidate (n_lo == 0: none); n_hi is the site's count less n_lo
-struct SsSlot {
-    uint64_t d;
-    uint32_t n_lo;
-    int32_t cut;
-};
-
 // the wave's best under ss_better (a total order over the candidates of a site: their cuts differ), in every lane
 __device__ inline SsCand ss_wave_best(SsCand b)
 {
@@ -648,40 +656,34 @@ extern "C" int rd_site_split(rd_ctx* ctx, const uint32_t* site, const uint8_t* c
             items += sc_site_chunks(sites[plan.run[k]]);
         }
         const int64_t e0 = whole ? 0 : off[l];
-        // after the block's arrays: the two prefix arrays, the slots, the admissible-cut counts and the entries
-        const size_t b_pre = align_up((size_t)nl * 8, 256), b_slot = align_up((size_t)items * sizeof(SsSlot), 256), b_cnt = align_up((size_t)S * 4, 256);
         size_t scan_bytes = 0;
         RD_HIP(rocprim::inclusive_scan(nullptr, scan_bytes, rocprim::make_transform_iterator((const uint64_t*)nullptr, SsValue()), (int64_t*)nullptr,
                                        (size_t)nl, rocprim::plus<int64_t>(), st));
         ScWs W;
-        W.extra_bytes = 2 * b_pre + b_slot + b_cnt + (size_t)S * sizeof(SsOut);
         W.min_tmp = scan_bytes;
+        W.split_items = items;
         if ((rc = sc_run(ctx, st, (whole ? site : g_site.data()) + e0, (whole ? cond : g_cond.data()) + e0, (whole ? value : g_value.data()) + e0, nl, S,
                          0, end_bit, W)))
             return rc;
-        int64_t *psum = (int64_t*)W.extra, *psq = (int64_t*)(W.extra + b_pre);
-        SsSlot* slot = (SsSlot*)(W.extra + 2 * b_pre);
-        int32_t* cnt = (int32_t*)(W.extra + 2 * b_pre + b_slot);
-        SsOut* out = (SsOut*)(W.extra + 2 * b_pre + b_slot + b_cnt);
         size_t tb = W.tmp_bytes;
         RD_HIP(rocprim::exclusive_scan(W.tmp, tb, W.n_chunk, W.item_off, 0u, (size_t)S + 1, rocprim::plus<uint32_t>(), st));
         tb = W.tmp_bytes;
-        RD_HIP(rocprim::inclusive_scan(W.tmp, tb, rocprim::make_transform_iterator(W.sorted, SsValue()), psum, (size_t)nl, rocprim::plus<int64_t>(), st));
+        RD_HIP(rocprim::inclusive_scan(W.tmp, tb, rocprim::make_transform_iterator(W.sorted, SsValue()), W.psum, (size_t)nl, rocprim::plus<int64_t>(), st));
         tb = W.tmp_bytes;
-        RD_HIP(rocprim::inclusive_scan(W.tmp, tb, rocprim::make_transform_iterator(W.sorted, SsSquare()), psq, (size_t)nl, rocprim::plus<int64_t>(), st));
-        RD_HIP(hipMemsetAsync(cnt, 0, (size_t)S * 4, st));
-        RD_HIP(hipMemsetAsync(out, 0, (size_t)S * sizeof(SsOut), st));
-        hipLaunchKernelGGL(ss_item_kernel, dim3((unsigned)((items + SC_WAVES - 1) / SC_WAVES)), dim3(64 * SC_WAVES), 0, st, W.sorted, psum, W.seg, W.item_off,
-                           (uint32_t)S, (uint32_t)items, W.n_seg, min_frac_q16, slot, cnt);
+        RD_HIP(rocprim::inclusive_scan(W.tmp, tb, rocprim::make_transform_iterator(W.sorted, SsSquare()), W.psq, (size_t)nl, rocprim::plus<int64_t>(), st));
+        RD_HIP(hipMemsetAsync(W.cnt, 0, (size_t)S * 4, st));
+        RD_HIP(hipMemsetAsync(W.split_out, 0, (size_t)S * sizeof(SsOut), st));
+        hipLaunchKernelGGL(ss_item_kernel, dim3((unsigned)((items + SC_WAVES - 1) / SC_WAVES)), dim3(64 * SC_WAVES), 0, st, W.sorted, W.psum, W.seg, W.item_off,
+                           (uint32_t)S, (uint32_t)items, W.n_seg, min_frac_q16, W.slot, W.cnt);
         RD_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ss_pick_kernel, dim3((unsigned)((S + SC_WAVES - 1) / SC_WAVES)), dim3(64 * SC_WAVES), 0, st, W.sorted, psum, psq, W.seg, W.item_off,
-                           (uint32_t)S, (uint32_t)items, W.n_seg, slot, cnt, out);
+        hipLaunchKernelGGL(ss_pick_kernel, dim3((unsigned)((S + SC_WAVES - 1) / SC_WAVES)), dim3(64 * SC_WAVES), 0, st, W.sorted, W.psum, W.psq, W.seg, W.item_off,
+                           (uint32_t)S, (uint32_t)items, W.n_seg, W.slot, W.cnt, W.split_out);
         RD_HIP(hipGetLastError());
         got.resize((size_t)S);
         uint32_t n_seg = 0, n_it = 0;
         RD_HIP(hipMemcpyAsync(&n_seg, W.n_seg, 4, hipMemcpyDeviceToHost, st));
         RD_HIP(hipMemcpyAsync(&n_it, W.item_off + S, 4, hipMemcpyDeviceToHost, st));
-        RD_HIP(hipMemcpyAsync(got.data(), out, (size_t)S * sizeof(SsOut), hipMemcpyDeviceToHost, st));
+        RD_HIP(hipMemcpyAsync(got.data(), W.split_out, (size_t)S * sizeof(SsOut), hipMemcpyDeviceToHost, st));
         RD_HIP(hipStreamSynchronize(st));
         if ((int64_t)n_seg != S || (int64_t)n_it != items) {
             rd_set_error("rd_site_split: internal: the device found %u sites and %u chunks in a launch of %lld and %lld", n_seg, n_it, (long long)S,

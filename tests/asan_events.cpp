@@ -13,6 +13,8 @@
 extern "C" int rd_event_stats_host(const int16_t* raw, const int64_t* read_off, int n_reads, const int32_t* first_step, const int32_t* last_step,
                                    const int64_t* label_off, const int32_t* label_len, const int32_t* align_status, int32_t* ev_start,
                                    int32_t* ev_end, int64_t* ev_sum, int64_t* ev_sumsq, int16_t* ev_min, int16_t* ev_max);
+#include "../radian_amd/csrc/events.hip"   // the host half (this is no HIP build): the device blocks' layout functions live in its unnamed namespace
+
 void rd_set_error(const char* fmt, ...) { (void)fmt; }
 
 static long g_accepted = 0, g_refused = 0;
@@ -53,10 +55,42 @@ struct Outs {
     }
 };
 
+// The yardstick of ev_io_layout: the size expressions and the pointer chain it held before it took a Carve, written out literally; on
+// seeded random label counts (0 and 1 among them) the total and every array's offset must be equal.
+static void check_layout()
+{
+    std::mt19937_64 rng(7);
+    const size_t dims[] = {0, 1, 2, 31, 32, 33, 255, 256, 257};
+    auto dim = [&](size_t big) { return rng() % 3 ? dims[rng() % 9] : (size_t)(rng() % big); };
+    char* const base = (char*)((uintptr_t)1 << 32);
+    for (int it = 0; it < 4000; it++) {
+        const size_t n = dim(3000000), a4 = align_up(n * 4 + 16, 256), a8 = align_up(n * 8 + 16, 256), a2 = align_up(n * 2 + 16, 256);
+        const size_t total = 4 * a4 + 2 * a8 + 2 * a2;
+        char* p = base;
+        EvIo old;
+        old.first = (int32_t*)p; p += a4;
+        old.last = (int32_t*)p; p += a4;
+        old.start = (int32_t*)p; p += a4;
+        old.end = (int32_t*)p; p += a4;
+        old.sum = (int64_t*)p; p += a8;
+        old.sumsq = (int64_t*)p; p += a8;
+        old.mn = (int16_t*)p; p += a2;
+        old.mx = (int16_t*)p;
+        EvIo io;
+        Carve dry, wet(base);
+        ev_io_layout(dry, (int64_t)n, &io);
+        CHECK(dry.at == total && !io.first && !io.mx);
+        ev_io_layout(wet, (int64_t)n, &io);
+        CHECK(wet.at == total && io.first == old.first && io.last == old.last && io.start == old.start && io.end == old.end && io.sum == old.sum &&
+              io.sumsq == old.sumsq && io.mn == old.mn && io.mx == old.mx);
+    }
+}
+
 int main(int argc, char** argv)
 {
     if (argc < 2) return 2;
     const int iters = atoi(argv[1]);
+    check_layout();
     std::mt19937_64 rng(2024);
     auto below = [&](uint64_t n) { return (int64_t)(rng() % n); };
     for (int it = 0; it < iters; it++) {

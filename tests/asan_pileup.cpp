@@ -15,7 +15,7 @@
 #include <string>
 #include <vector>
 
-#include "../radian_amd/csrc/pileup_rules.h"
+#include "../radian_amd/csrc/pileup.hip"   // the host half (this is no HIP build): the device blocks' layout functions live in its unnamed namespace
 
 extern "C" int rd_pileup_host(const uint8_t* ops, const int64_t* ops_off, const uint8_t* refs, const int64_t* ref_off, const uint8_t* reads,
                               const int64_t* read_off, int n_pairs, const int64_t* site0, int64_t n_sites, uint32_t* sites, uint64_t* profile,
@@ -101,9 +101,59 @@ static void own_pair(const std::string& o, const std::string& A, const std::stri
     res[5] = (int32_t)((int64_t)B.size() - qj[hi] - 1);
 }
 
+// The yardsticks of pu_ops_layout / pu_ops_pair and pu_read_layout: the offset expressions that rd_pileup_add_ops and the two phases of
+// rd_pileup_read held before the layout functions replaced them, written out literally; on seeded random dimensions (0 and 1 of each among
+// them) the totals and every offset must be equal.
+static void check_layout()
+{
+    std::mt19937_64 rng(7);
+    const size_t dims[] = {0, 1, 2, 31, 32, 33, 255, 256, 257};
+    auto dim = [&](size_t big) { return rng() % 3 ? dims[rng() % 9] : (size_t)(rng() % big); };
+    char* const base = (char*)((uintptr_t)1 << 32);
+    for (int it = 0; it < 4000; it++) {
+        const int nb = (int)dim(300);
+        std::vector<int64_t> n(nb), m(nb), L(nb);
+        for (int k = 0; k < nb; k++) n[k] = (int64_t)dim(3000), m[k] = (int64_t)dim(3000), L[k] = (int64_t)dim(6000);
+        const size_t res_at = align_up((size_t)nb * sizeof(AlnPair), 256), site_at = res_at + align_up((size_t)nb * ALN_RES * 4, 256);
+        const size_t out_at = site_at + align_up((size_t)nb * 8, 256);
+        size_t at = out_at + align_up((size_t)nb * PILEUP_RES * 4, 256);
+        Carve c;
+        PuOpsAt o;
+        pu_ops_layout(c, nb, &o);
+        CHECK(o.res == res_at && o.site == site_at && o.out == out_at && c.at == at);
+        for (int k = 0; k < nb; k++) {
+            AlnPair d, e;
+            d.n = (int32_t)n[k];
+            d.m = (int32_t)m[k];
+            d.ref = (int64_t)at;
+            d.read = d.ref + d.n;
+            d.ops = d.read + d.m;
+            d.bnd = d.dir = 0;
+            at += (size_t)d.n + d.m + (size_t)L[k];
+            pu_ops_pair(c, n[k], m[k], L[k], &e);
+            CHECK(e.n == d.n && e.m == d.m && e.ref == d.ref && e.read == d.read && e.ops == d.ops && e.bnd == 0 && e.dir == 0 && c.at == at);
+        }
+        // rd_pileup_read: the first phase reserves up to the rows, the second the rows as well
+        const int64_t S = (int64_t)dim(3000000), need = (int64_t)dim(1000000);
+        const size_t scan_bytes = dim(100000);
+        const size_t pos_at = align_up((size_t)S * 4, 256), tmp_at = pos_at + align_up((size_t)S * 4, 256), rows_at = tmp_at + align_up(scan_bytes, 256);
+        const size_t counts_at = rows_at + align_up((size_t)need * 4, 256), total = counts_at + (size_t)need * PILEUP_CH * 4;
+        PuReadWs w;
+        Carve dry0, dry1, wet(base);
+        pu_read_layout(dry0, S, scan_bytes, 0, &w);
+        CHECK(dry0.at == rows_at && !w.flag && !w.site);
+        pu_read_layout(dry1, S, scan_bytes, need, &w);
+        CHECK(dry1.at == total);
+        pu_read_layout(wet, S, scan_bytes, need, &w);
+        CHECK(wet.at == total && (char*)w.flag == base && (char*)w.pos == base + pos_at && (char*)w.tmp == base + tmp_at && (char*)w.site == base + rows_at &&
+              (char*)w.counts == base + counts_at);
+    }
+}
+
 int main(int argc, char** argv)
 {
     const long iters = argc > 1 ? atol(argv[1]) : 20;
+    check_layout();
     // the rules at their limits
     CHECK(pileup_code('A') == 0 && pileup_code('C') == 1 && pileup_code('G') == 2 && pileup_code('T') == 3 && pileup_code('N') == 4 && pileup_code('a') == 4 &&
           pileup_code('U') == 4 && pileup_code(0) == 4 && pileup_code(255) == 4);

@@ -13,7 +13,7 @@
 #include <random>
 #include <vector>
 
-#include "../radian_amd/csrc/polya_rules.h"
+#include "../radian_amd/csrc/polya.hip"   // the host half (this is no HIP build): the launch's layout function lives in its unnamed namespace
 
 extern "C" int rd_polya_segment_host(const int16_t* raw, const int64_t* read_off, int n_reads, int win, int flat_q, int use_level, int lo_q, int hi_q,
                                      int max_gap, int64_t min_samples, int64_t search_limit, int32_t* status, int64_t* tail_start,
@@ -66,10 +66,45 @@ static int call(const int16_t* raw, const int64_t* off, int n, const PaParams& p
                                  o.end, o.n_flat, o.sum, o.sumsq, o.m2, o.d4, o.ncand);
 }
 
+// The yardstick of pa_layout: the size expressions and the pointer chain that pa_run held before the layout function replaced them, written
+// out literally; on seeded random dimensions (0 and 1 of each among them) the total and every block's offset must be equal.
+static void check_layout()
+{
+    std::mt19937_64 rng(7);
+    const size_t dims[] = {0, 1, 2, 31, 32, 33, 255, 256, 257};
+    auto dim = [&](size_t big) { return rng() % 3 ? dims[rng() % 9] : (size_t)(rng() % big); };
+    for (int it = 0; it < 4000; it++) {
+        const size_t n_reads = dim(5000), n_blocks = dim(20000);
+        const int64_t nwin = (int64_t)dim(2000000);
+        const size_t b_reads = align_up(n_reads * sizeof(PaRead), 256), b_scale = align_up((size_t)n_reads * sizeof(PaScale), 256),
+                     b_blocks = align_up(n_blocks * sizeof(PaBlock) + 8, 256), b_flag = align_up((size_t)nwin + 8, 256),
+                     b_S = align_up((size_t)nwin * 4 + 8, 256), b_Q = align_up((size_t)nwin * 8 + 8, 256);
+        const size_t total = b_reads + b_scale + b_blocks + b_flag + b_S + b_Q;
+        char* const base = (char*)((uintptr_t)1 << 32);
+        char* c = base;
+        PaWs old;
+        old.reads = (PaRead*)c; c += b_reads;
+        old.scale = (PaScale*)c; c += b_scale;
+        old.blocks = (PaBlock*)c; c += b_blocks;
+        old.Q = (int64_t*)c; c += b_Q;
+        old.S = (int32_t*)c; c += b_S;
+        old.flag = (uint8_t*)c;
+        PaWs ws;
+        Carve dry, wet(base);
+        pa_layout(dry, n_reads, n_blocks, nwin, &ws);
+        CHECK(dry.at == total && !ws.reads && !ws.scale && !ws.blocks && !ws.Q && !ws.S && !ws.flag);
+        pa_layout(wet, n_reads, n_blocks, nwin, &ws);
+        CHECK(wet.at == total && ws.reads == old.reads && ws.scale == old.scale && ws.blocks == old.blocks && ws.Q == old.Q && ws.S == old.S &&
+              ws.flag == old.flag && ws.n_windows == nwin);
+        CHECK((size_t)((char*)ws.flag - base) + b_flag == total);   // (the last block's size stood in the sum only)
+    }
+}
+
 int main(int argc, char** argv)
 {
     if (argc < 2) return 2;
     const int iters = atoi(argv[1]);
+    check_layout();
     std::mt19937_64 rng(2025);
     auto uni = [&](int64_t lo, int64_t hi) { return (int64_t)(lo + rng() % (uint64_t)(hi - lo + 1)); };
 

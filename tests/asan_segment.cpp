@@ -13,7 +13,7 @@
 #include <random>
 #include <vector>
 
-#include "../radian_amd/csrc/segment_rules.h"
+#include "../radian_amd/csrc/segment.hip"   // the host half (this is no HIP build): the device blocks' layout functions live in its unnamed namespace
 
 extern "C" int rd_segment_host(const int16_t* raw, const int64_t* read_off, int n_reads, int w1, int w2, uint32_t th1, uint32_t th2, int v0,
                                const int64_t* sc_lo, const int64_t* sc_hi, const int64_t* ev_off, int32_t* status, int32_t* n_events, int32_t* m2,
@@ -88,9 +88,56 @@ static void rules_at_their_limits()
     CHECK(rd_segment_workspace_bytes(SG_MAX_T, 2) > 0 && rd_segment_workspace_bytes(-1, 4) == -1 && rd_segment_workspace_bytes(1, 33) == -1);
 }
 
+// The yardstick of sg_layout: the size expressions and the pointer chain that sg_peaks held before the layout function replaced them,
+// written out literally; on seeded random dimensions (0 and 1 of each among them) the total and every block's offset must be equal.
+static void check_layout()
+{
+    std::mt19937_64 rng(7);
+    const size_t dims[] = {0, 1, 2, 31, 32, 33, 255, 256, 257};
+    auto dim = [&](size_t big) { return rng() % 3 ? dims[rng() % 9] : (size_t)(rng() % big); };
+    char* const base = (char*)((uintptr_t)1 << 32);
+    for (int it = 0; it < 4000; it++) {
+        const size_t n_reads = dim(3000), n_tiles = dim(30000), tmp_bytes = dim(100000);
+        const int64_t n = (int64_t)dim(3000000), cap = (int64_t)dim(1500000);
+        const bool diag = it % 2;
+        const size_t b_reads = align_up(n_reads * sizeof(SgRead), 256), b_tiles = align_up(n_tiles * sizeof(SgTile) + 8, 256),
+                     b_byte = align_up((size_t)n + 1, 256), b_pos = align_up(((size_t)n + 1) * 4, 256), b_e8 = align_up((size_t)cap * 8, 256),
+                     b_e2 = align_up((size_t)cap * 2, 256), b_e1 = align_up((size_t)cap, 256), b_tmp = align_up(tmp_bytes + 8, 256),
+                     b_t = diag ? align_up((size_t)n * 16 + 8, 256) : 0;
+        const size_t total = b_reads + b_tiles + 2 * b_byte + b_pos + 3 * b_e8 + 2 * b_e2 + b_e1 + b_tmp + 2 * b_t;
+        char* c = base;
+        SgWs old;
+        old.reads = (SgRead*)c; c += b_reads;
+        old.tiles = (SgTile*)c; c += b_tiles;
+        old.ev_g = (int64_t*)c; c += b_e8;
+        old.ev_sum = (int64_t*)c; c += b_e8;
+        old.ev_sumsq = (int64_t*)c; c += b_e8;
+        old.tN = (uint64_t*)c; c += b_t;
+        old.tD = (uint64_t*)c; c += b_t;
+        old.tmp = c; c += b_tmp;
+        old.pos = (uint32_t*)c; c += b_pos;
+        old.ev_min = (int16_t*)c; c += b_e2;
+        old.ev_max = (int16_t*)c; c += b_e2;
+        old.flags = (uint8_t*)c; c += b_byte;
+        old.bnd = (uint8_t*)c; c += b_byte;
+        old.ev_src = (uint8_t*)c;
+        SgWs ws;
+        Carve dry, wet(base);
+        sg_layout(dry, n_reads, n_tiles, n, cap, tmp_bytes, diag, &ws);
+        CHECK(dry.at == total && !ws.reads && !ws.ev_src && !ws.tmp);
+        sg_layout(wet, n_reads, n_tiles, n, cap, tmp_bytes, diag, &ws);
+        CHECK(wet.at == total && ws.reads == old.reads && ws.tiles == old.tiles && ws.ev_g == old.ev_g && ws.ev_sum == old.ev_sum &&
+              ws.ev_sumsq == old.ev_sumsq && ws.tN == old.tN && ws.tD == old.tD && ws.tmp == old.tmp && ws.pos == old.pos &&
+              ws.ev_min == old.ev_min && ws.ev_max == old.ev_max && ws.flags == old.flags && ws.bnd == old.bnd && ws.ev_src == old.ev_src);
+        CHECK(ws.tmp_bytes == tmp_bytes && ws.n == n && ws.cap == cap && ws.n_tiles == (unsigned)n_tiles);
+        CHECK((size_t)((char*)ws.ev_src - base) + b_e1 == total);   // (the last block's size stood in the sum only)
+    }
+}
+
 int main(int argc, char** argv)
 {
     const int iters = argc > 1 ? atoi(argv[1]) : 20;
+    check_layout();
     rules_at_their_limits();
     std::mt19937_64 rng(2727);
     auto U = [&](int64_t a, int64_t b) { return (int64_t)(a + (int64_t)(rng() % (uint64_t)(b - a + 1))); };

@@ -13,7 +13,7 @@
 #include <random>
 #include <vector>
 
-#include "../radian_amd/csrc/sigmap_rules.h"
+#include "../radian_amd/csrc/sigmap.hip"   // the host half (this is no HIP build): the device blocks' layout functions live in its unnamed namespace
 
 extern "C" int rd_sigmap_host(const int16_t* raw, int64_t n_raw, int n_q, const int64_t* q_lo, const int64_t* q_hi, const int64_t* sc_lo,
                               const int64_t* sc_hi, const int32_t* m2_in, const int32_t* d4_in, const int64_t* s_lo, const int64_t* s_hi,
@@ -103,9 +103,40 @@ static void rules_at_their_limits()
     CHECK(rd_sigmap_workspace_bytes(SM_MAX_T, INT32_MAX, INT32_MAX) > 0);   // no overflow at the contract's largest query
 }
 
+// The yardsticks of sm_panel_layout and sm_io_layout: the size and offset expressions that rd_sigmap held before the layout functions
+// replaced them, written out literally; on seeded random dimensions (0 and 1 of each among them) the totals and every offset must be equal.
+static void check_layout()
+{
+    std::mt19937_64 rng(7);
+    const size_t dims[] = {0, 1, 2, 31, 32, 33, 255, 256, 257};
+    auto dim = [&](size_t big) { return rng() % 3 ? dims[rng() % 9] : (size_t)(rng() % big); };
+    char* const base = (char*)((uintptr_t)1 << 32);
+    for (int it = 0; it < 4000; it++) {
+        const int n_tgt = (int)dim(50000), nb = (int)dim(4096);
+        const int64_t R = (int64_t)dim(5000000);
+        const size_t n_stripes = dim(100000);
+        const size_t b_off = align_up((size_t)(n_tgt + 1) * 8, 256), b_st = align_up((size_t)R * 4 + 16, 256);
+        SmPanel p;
+        Carve pd, pw(base);
+        sm_panel_layout(pd, n_tgt, R, &p);
+        CHECK(pd.at == b_off + 2 * b_st && !p.off && !p.kid && !p.tg);
+        sm_panel_layout(pw, n_tgt, R, &p);
+        CHECK(pw.at == b_off + 2 * b_st && (char*)p.off == base && (char*)p.kid == base + b_off && (char*)p.tg == base + b_off + b_st);
+        const size_t o_str = align_up((size_t)nb * sizeof(SmQuery), 256), o_out = o_str + align_up(n_stripes * sizeof(SmStripe), 256);
+        const size_t total = o_out + (size_t)nb * sizeof(SmOut);
+        SmIo io;
+        Carve dry, wet(base);
+        sm_io_layout(dry, nb, n_stripes, &io);
+        CHECK(dry.at == total && !io.qs && !io.str && !io.out);
+        sm_io_layout(wet, nb, n_stripes, &io);
+        CHECK(wet.at == total && (char*)io.qs == base && (char*)io.str == base + o_str && (char*)io.out == base + o_out);
+    }
+}
+
 int main(int argc, char** argv)
 {
     const int iters = argc > 1 ? atoi(argv[1]) : 20;
+    check_layout();
     rules_at_their_limits();
     std::mt19937_64 rng(2525);
     auto U = [&](int64_t a, int64_t b) { return (int64_t)(a + (int64_t)(rng() % (uint64_t)(b - a + 1))); };

@@ -14,7 +14,7 @@
 #include <vector>
 
 #include "../radian_amd/csrc/budget.h"
-#include "../radian_amd/csrc/sim_rules.h"
+#include "../radian_amd/csrc/sim.hip"   // the host half (this is no HIP build): the device blocks' layout functions live in its unnamed namespace
 
 extern "C" int rd_sim_lengths_host(const uint8_t* codes, const int64_t* seq_off, int n_reads, const int16_t* level_shift_q10,
                                    const uint16_t* dwell_scale_q8, const int32_t* lead, const int32_t* lead_level_q10, const int32_t* lead_sd_q10,
@@ -70,9 +70,55 @@ static int signal(const In& a, int16_t* raw, int32_t* bf, int32_t* st)
                               a.sd, a.dwell, a.cdf, a.raw_off, raw, bf, st);
 }
 
+// The yardstick of sim_layout: the take lambda and the block list that sim_carve held before the layout function replaced them, written
+// out literally; on seeded random dimensions (0 and 1 of each among them) the total and every block's offset must be equal, dry and wet.
+static void check_layout()
+{
+    std::mt19937_64 rng(7);
+    const size_t dims[] = {0, 1, 2, 31, 32, 33, 255, 256, 257};
+    auto dim = [&](size_t big) { return rng() % 3 ? dims[rng() % 9] : (size_t)(rng() % big); };
+    char* const base = (char*)((uintptr_t)1 << 32);
+    for (int it = 0; it < 4000; it++) {
+        const int k = 1 + (int)(rng() % 9), n = (int)dim(4000);
+        const int64_t B = (int64_t)dim(2000000), R = (int64_t)dim(20000000);
+        const bool with_shift = rng() % 2, with_dscale = rng() % 2;
+        const size_t tb = dim(200000);
+        for (int wet = 0; wet < 2; wet++) {
+            char* const b = wet ? base : nullptr;
+            SimWs old;
+            size_t at = sim_model_bytes(k);
+            const auto take = [&](size_t bytes) {
+                char* p = b ? b + at : nullptr;
+                at += align_up(bytes + 8, 256);
+                return p;
+            };
+            old.reads = (SimRead*)take((size_t)n * sizeof(SimRead));
+            old.cum = (int64_t*)take((size_t)(B + 1) * 8);
+            old.len = (int64_t*)take((size_t)n * 8);
+            old.lvsd = (int2*)take((size_t)B * 8);
+            old.dwell = (int32_t*)take((size_t)(B + 1) * 4);
+            old.bfirst = (int32_t*)take((size_t)B * 4);
+            old.raw = (int16_t*)take((size_t)R * 2);
+            old.shift = (int16_t*)take(with_shift ? (size_t)B * 2 : 0);
+            old.dscale = (uint16_t*)take(with_dscale ? (size_t)B * 2 : 0);
+            old.codes = (uint8_t*)take((size_t)B);
+            old.tmp = take(tb);
+            old.total = at;
+            SimWs W;
+            Carve c(b);
+            sim_layout(c, k, n, B, R, with_shift, with_dscale, tb, &W);
+            CHECK(W.total == old.total && c.at == old.total && W.tmp_bytes == tb);
+            CHECK(W.reads == old.reads && W.cum == old.cum && W.len == old.len && W.lvsd == old.lvsd && W.dwell == old.dwell && W.bfirst == old.bfirst &&
+                  W.raw == old.raw && W.shift == old.shift && W.dscale == old.dscale && W.codes == old.codes && W.tmp == old.tmp);
+            CHECK(wet ? (char*)W.reads == base + sim_model_bytes(k) : W.reads == nullptr);
+        }
+    }
+}
+
 int main(int argc, char** argv)
 {
     const long iters = argc > 1 ? atol(argv[1]) : 20;
+    check_layout();
     // Philox4x32-10: the known answers
     {
         uint32_t w[4];

@@ -15,7 +15,7 @@
 #include <random>
 #include <vector>
 
-#include "../radian_amd/csrc/site_rules.h"
+#include "../radian_amd/csrc/sitecmp.hip"   // the host half (this is no HIP build): the device blocks' layout functions live in its unnamed namespace
 
 extern "C" int rd_site_compare_host(const uint32_t* site, const uint8_t* cond, const int16_t* value, int64_t n_events, uint32_t n_sites,
                                     int64_t capacity, uint32_t* out_site, int32_t* status, int64_t* n, int64_t* sum, int64_t* sumsq, int32_t* vmin,
@@ -76,9 +76,45 @@ struct Outs {
     }
 };
 
+// The yardstick of sc_layout for a comparison: the take lambda and the offset list that sc_run held before the layout function replaced
+// them, written out literally (extra_bytes = 0: a comparison asked for none); on seeded random dimensions (0 and 1 of each among them) the
+// total and every block's offset must be equal.
+static void check_layout()
+{
+    std::mt19937_64 rng(7);
+    const size_t dims[] = {0, 1, 2, 31, 32, 33, 255, 256, 257};
+    auto dim = [&](size_t big) { return rng() % 3 ? dims[rng() % 9] : (size_t)(rng() % big); };
+    char* const base = (char*)((uintptr_t)1 << 32);
+    for (int it = 0; it < 4000; it++) {
+        const int64_t n = (int64_t)dim(3000000), S = (int64_t)dim(100000);
+        const size_t tmp_bytes = dim(3000000), extra_bytes = 0;
+        size_t at = 0;
+        const auto take = [&](size_t bytes) {
+            const size_t o = at;
+            at += align_up(bytes + 8, 256);
+            return o;
+        };
+        const size_t o_site = take((size_t)n * 4), o_cond = take((size_t)n), o_value = take((size_t)n * 2), o_ka = take((size_t)n * 8),
+                     o_kb = take((size_t)n * 8), o_flag = take((size_t)n * 4), o_pos = take((size_t)n * 4), o_start = take((size_t)(S + 1) * 4),
+                     o_chunk = take((size_t)(S + 1) * 4), o_item = take((size_t)(S + 1) * 4), o_nseg = take(4), o_seg = take((size_t)S * sizeof(ScSeg)),
+                     o_out = take((size_t)S * sizeof(ScOut)), o_tmp = take(tmp_bytes), o_extra = take(extra_bytes);
+        ScWs W;
+        Carve dry, wet(base);
+        sc_layout(dry, n, S, tmp_bytes, -1, &W);
+        CHECK(!W.in_site && !W.tmp && !W.psum);
+        sc_layout(wet, n, S, tmp_bytes, -1, &W);
+        CHECK(wet.at == at && dry.at == at && W.tmp_bytes == tmp_bytes);
+        CHECK((char*)W.in_site == base + o_site && (char*)W.in_cond == base + o_cond && (char*)W.in_value == base + o_value && (char*)W.ka == base + o_ka &&
+              (char*)W.kb == base + o_kb && (char*)W.flag == base + o_flag && (char*)W.pos == base + o_pos && (char*)W.seg_start == base + o_start &&
+              (char*)W.n_chunk == base + o_chunk && (char*)W.item_off == base + o_item && (char*)W.n_seg == base + o_nseg && (char*)W.seg == base + o_seg &&
+              (char*)W.out == base + o_out && (char*)W.tmp == base + o_tmp && (char*)W.psum == base + o_extra);
+    }
+}
+
 int main(int argc, char** argv)
 {
     const int iters = argc > 1 ? atoi(argv[1]) : 50;
+    check_layout();
     std::mt19937_64 rng(20);
     // the key and the packed maximum at their extremes
     CHECK(sc_key(0xfffffffeu, 1, 32767) == (((uint64_t)0xfffffffeu << 17) | 0x1ffff) && sc_key_site(sc_key(0xfffffffeu, 1, -32768)) == 0xfffffffeu);

@@ -16,7 +16,7 @@
 #include <set>
 #include <vector>
 
-#include "../radian_amd/csrc/site_rules.h"
+#include "../radian_amd/csrc/sitecmp.hip"   // the host half (this is no HIP build): the device blocks' layout functions live in its unnamed namespace
 
 extern "C" int rd_site_split_host(const uint32_t* site, const uint8_t* cond, const int16_t* value, int64_t n_events, uint32_t n_sites,
                                   int64_t capacity, int min_frac_q16, uint32_t* out_site, int32_t* status, int64_t* n, int64_t* sum, int64_t* sumsq,
@@ -77,9 +77,50 @@ struct Outs {
     }
 };
 
+// The yardstick of sc_layout for a split: the take lambda and the offset list that sc_run held, and the sizes and pointers of the split's
+// own arrays behind them that rd_site_split held, before the layout function replaced them -- written out literally; on seeded random
+// dimensions (0 and 1 of each among them) the total and every block's offset must be equal.
+static void check_layout()
+{
+    std::mt19937_64 rng(7);
+    const size_t dims[] = {0, 1, 2, 31, 32, 33, 255, 256, 257};
+    auto dim = [&](size_t big) { return rng() % 3 ? dims[rng() % 9] : (size_t)(rng() % big); };
+    char* const base = (char*)((uintptr_t)1 << 32);
+    for (int it = 0; it < 4000; it++) {
+        const int64_t n = (int64_t)dim(3000000), S = (int64_t)dim(100000), items = (int64_t)dim(200000), nl = n;
+        const size_t tmp_bytes = dim(3000000);
+        const size_t b_pre = align_up((size_t)nl * 8, 256), b_slot = align_up((size_t)items * sizeof(SsSlot), 256), b_cnt = align_up((size_t)S * 4, 256);
+        const size_t extra_bytes = 2 * b_pre + b_slot + b_cnt + (size_t)S * sizeof(SsOut);
+        size_t at = 0;
+        const auto take = [&](size_t bytes) {
+            const size_t o = at;
+            at += align_up(bytes + 8, 256);
+            return o;
+        };
+        const size_t o_site = take((size_t)n * 4), o_cond = take((size_t)n), o_value = take((size_t)n * 2), o_ka = take((size_t)n * 8),
+                     o_kb = take((size_t)n * 8), o_flag = take((size_t)n * 4), o_pos = take((size_t)n * 4), o_start = take((size_t)(S + 1) * 4),
+                     o_chunk = take((size_t)(S + 1) * 4), o_item = take((size_t)(S + 1) * 4), o_nseg = take(4), o_seg = take((size_t)S * sizeof(ScSeg)),
+                     o_out = take((size_t)S * sizeof(ScOut)), o_tmp = take(tmp_bytes), o_extra = take(extra_bytes);
+        ScWs W;
+        Carve dry, wet(base);
+        sc_layout(dry, n, S, tmp_bytes, items, &W);
+        CHECK(!W.in_site && !W.tmp && !W.psum && !W.split_out);
+        sc_layout(wet, n, S, tmp_bytes, items, &W);
+        CHECK(wet.at == at && dry.at == at && W.tmp_bytes == tmp_bytes);
+        CHECK((char*)W.in_site == base + o_site && (char*)W.in_cond == base + o_cond && (char*)W.in_value == base + o_value && (char*)W.ka == base + o_ka &&
+              (char*)W.kb == base + o_kb && (char*)W.flag == base + o_flag && (char*)W.pos == base + o_pos && (char*)W.seg_start == base + o_start &&
+              (char*)W.n_chunk == base + o_chunk && (char*)W.item_off == base + o_item && (char*)W.n_seg == base + o_nseg && (char*)W.seg == base + o_seg &&
+              (char*)W.out == base + o_out && (char*)W.tmp == base + o_tmp && (char*)W.psum == base + o_extra);
+        char* const extra = base + o_extra;
+        CHECK((char*)W.psum == extra && (char*)W.psq == extra + b_pre && (char*)W.slot == extra + 2 * b_pre && (char*)W.cnt == extra + 2 * b_pre + b_slot &&
+              (char*)W.split_out == extra + 2 * b_pre + b_slot + b_cnt);
+    }
+}
+
 int main(int argc, char** argv)
 {
     const int iters = argc > 1 ? atoi(argv[1]) : 50;
+    check_layout();
     std::mt19937_64 rng(26);
     // the order of two candidates at the extremes: |D| = 2^46 at n_lo = n_hi = 2^15 against one unit less
     {
