@@ -389,9 +389,11 @@ int rd_stitch_chunk(const uint8_t* labels, const int32_t* label_len, int chunk_l
  *   refs / reads   concatenated bytes; pair p is refs[ref_off[p] .. ref_off[p+1]) against reads[read_off[p] .. read_off[p+1])
  *                  (offsets have n_pairs + 1 entries and start at 0).  Characters are compared as bytes (no U -> T here).
  *   Affine-gap global alignment (Gotoh), int32 scores: a gap of length L costs gap_open + (L-1) * gap_extend, end gaps are
- *   penalised.  Of the co-optimal alignments the traceback takes the one of a FIXED tie-break (the reference draws one at
- *   random, align.py:89): diagonal before deletion (ref base against a read gap) before insertion, and inside a gap run
- *   extending before closing.
+ *   penalised.  Every |score| < 2^16, and gap_open <= gap_extend (equal: linear gaps), else RD_ERR_ARG before anything is staged
+ *   or launched: with open > extend the recurrence reopens adjacent gaps, so the score is not the stated gap cost.  A pair with
+ *   max|score| * (n + m + 1) >= 2^28 is RD_ERR_ARG too (int32 scores).  Of the co-optimal alignments the traceback takes
+ *   the one of a FIXED tie-break (the reference draws one at random, align.py:89): diagonal before deletion (ref base
+ *   against a read gap) before insertion, and inside a gap run extending before closing.
  *   score[p]       the optimal score
  *   counts[4p..]   n_match, n_sub, n_ins, n_del after analyse_alignment's soft clip (its return order)
  *   status[p]      RD_ALIGN_OK, RD_ALIGN_CLIP_INDEX_ERROR (analyse_alignment raises IndexError), RD_ALIGN_EMPTY_AFTER_CLIP
@@ -913,7 +915,9 @@ int rd_tfrecord_write(const char* path, const float* signals, const int32_t* inp
  *                  whose reference and query alone exceed it is not aligned: status RD_FIT_TOO_LARGE, and the call returns
  *                  RD_ERR_NOMEM naming it after aligning the others.  Results do not depend on the batches.
  * A code outside its range, a query longer than 1024 or a reference index outside 0..n_refs-1 is RD_ERR_ARG before anything is
- * launched.  Synchronous; uses the context's stream. */
+ * launched.  So are a |score| >= 2^16, a reference with max|score| * (n + 1025) >= 2^28 (int32 scores), and gap_open > gap_extend
+ * (equal, linear gaps, is legal): with open > extend the recurrence reopens adjacent gaps, so the score is not the stated gap cost.
+ * Synchronous; uses the context's stream. */
 #define RD_FIT_OK 0
 #define RD_FIT_EMPTY 1
 #define RD_FIT_TOO_LARGE 2
@@ -1047,7 +1051,9 @@ int64_t rd_quant_workspace_bytes(int64_t slots, int64_t n_reads, int64_t n_tx);
  *   rd_pileup_open      allocates and zeroes the tables of n_sites (0 .. 2^30) sites in the context; a second open starts again from zero
  *   rd_pileup_close     frees them
  *   rd_pileup_add       aligns exactly as rd_align_batch does (scores, tie-break, optional ops, budget) and accumulates.  Requires
- *                       site0[p] + n <= n_sites.  A pair that alone exceeds the budget is not aligned and adds nothing: status
+ *                       site0[p] + n <= n_sites, and gap_open <= gap_extend as rd_align_batch does (RD_ERR_ARG, nothing added and
+ *                       `out` not written: with open > extend the recurrence reopens adjacent gaps, so the score is not the
+ *                       stated gap cost).  A pair that alone exceeds the budget is not aligned and adds nothing: status
  *                       RD_PILEUP_TOO_LARGE, and the call returns RD_ERR_NOMEM naming it after the others ran.  A pair takes
  *                       rd_pileup_workspace_bytes(n, m) = rd_align_workspace_bytes(n, m) + 48 + 256.
  *   rd_pileup_add_ops   the same accumulation from columns the caller has (ops + ops_off[p] .. ops_off[p+1]); no alignment runs.

@@ -1534,7 +1534,9 @@ class Backend:
     # ------------------------------------------------------------------ read-accuracy evaluation (radian/align.py)
     def align(self, refs, reads, scores=ALIGN_SCORES, budget_bytes=0, with_ops=False, allow_too_large=False):
         """Global affine-gap alignment of reads[p] against refs[p] (str or bytes, compared byte by byte) and analyse_alignment's
-        clip + counts, on the GPU (rd_align_batch).  budget_bytes: device workspace per batch, 0 = a quarter of free memory.
+        clip + counts, on the GPU (rd_align_batch).  scores: match, mismatch, gap_open, gap_extend with gap_open <= gap_extend (the
+        library refuses open > extend: the recurrence would reopen adjacent gaps).  budget_bytes: device workspace per batch,
+        0 = a quarter of free memory.
         A pair that does not fit the budget raises, unless allow_too_large: it then comes back with status ALIGN_TOO_LARGE."""
         if len(refs) != len(reads):
             raise ValueError(f"{len(refs)} refs for {len(reads)} reads")

@@ -293,6 +293,9 @@ int rd_align_batch_run(rd_ctx* ctx, const char* who, const char* too_large_name,
     RD_REQUIRE(budget_bytes >= 0, "%s: negative budget", who);
     const int lim = 1 << 16;
     RD_REQUIRE(abs(match) < lim && abs(mismatch) < lim && abs(gap_open) < lim && abs(gap_extend) < lim, "%s: score out of range", who);
+    // with open > extend the recurrence closes a gap and reopens it in the next column: its optimum is not the stated gap cost
+    RD_REQUIRE(gap_open <= gap_extend, "%s: gap_open %d is above gap_extend %d (gap_open <= gap_extend is required: otherwise adjacent gaps "
+               "reopen and the score is not open + (L-1) * extend per gap)", who, gap_open, gap_extend);
     RD_REQUIRE(ref_off[0] == 0 && read_off[0] == 0, "%s: offsets must start at 0", who);
     std::vector<int64_t> cells(n_pairs), bytes(n_pairs);
     const size_t extra = hook.extra_pair_bytes, batch_bytes = ALN_BATCH_BYTES + (extra ? 256 : 0);
@@ -325,6 +328,7 @@ int rd_align_batch_run(rd_ctx* ctx, const char* who, const char* too_large_name,
         for (int c = 0; c < 4; c++) counts[4 * (int64_t)p + c] = 0;
         if (ops_len) ops_len[p] = 0;
     }
+    hook.accepted(n_pairs);
     if (ctx->ws_align.reserve_exact((size_t)plan.max_bytes, who)) return RD_ERR_NOMEM;
     const AlnScores sc{match, mismatch, gap_open, gap_extend};
     std::vector<uint8_t> stage;

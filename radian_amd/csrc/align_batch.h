@@ -25,6 +25,7 @@ struct AlnLaunch {
 };
 struct AlnHook {
     size_t extra_pair_bytes = 0;   // workspace the hook wants per slot, inside the budget (a batch then takes 256 bytes more)
+    virtual void accepted(int n_pairs) {}                      // every argument check passed: set the hook's own outputs to "not aligned yet"
     virtual int launched(const AlnLaunch&) { return RD_OK; }   // queue work behind the traceback; must not wait
     virtual int finished(const AlnLaunch&) { return RD_OK; }   // the stream has been synchronised
     virtual ~AlnHook() {}

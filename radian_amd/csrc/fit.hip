@@ -220,6 +220,9 @@ extern "C" int rd_fit_batch(rd_ctx* ctx, const uint8_t* refs, const int64_t* ref
     RD_REQUIRE(budget_bytes >= 0, "rd_fit_batch: negative budget");
     const int lim = 1 << 16;
     RD_REQUIRE(abs(match) < lim && abs(mismatch) < lim && abs(gap_open) < lim && abs(gap_extend) < lim, "rd_fit_batch: score out of range");
+    // with open > extend the recurrence closes a gap and reopens it in the next column: its optimum is not the stated gap cost
+    RD_REQUIRE(gap_open <= gap_extend, "rd_fit_batch: gap_open %d is above gap_extend %d (gap_open <= gap_extend is required: otherwise adjacent "
+               "gaps reopen and the score is not open + (L-1) * extend per gap)", gap_open, gap_extend);
     RD_REQUIRE(ref_off[0] == 0 && query_off[0] == 0, "rd_fit_batch: offsets must start at 0");
     const int64_t smax = std::max(std::max(abs(match), abs(mismatch)), std::max(abs(gap_open), abs(gap_extend)));
     for (int64_t r = 0; r < n_refs; r++) {

@@ -348,6 +348,10 @@ struct PileupHook : AlnHook {
     std::vector<int64_t> h_site0;
     std::vector<int32_t> h_out;
     PileupHook(rd_ctx* c, const int64_t* s, int32_t* o) : ctx(c), site0(s), out(o) { extra_pair_bytes = PU_EXTRA; }
+    void accepted(int n_pairs) override   // behind the routine's argument checks: a refused call leaves `out` as it was
+    {
+        for (int64_t k = 0; k < (int64_t)n_pairs * PILEUP_RES; k++) out[k] = k % PILEUP_RES == 0 ? PILEUP_TOO_LARGE : 0;   // until its batch has run
+    }
     int launched(const AlnLaunch& l) override
     {
         h_site0.resize(l.n_slots);
@@ -414,7 +418,6 @@ extern "C" int rd_pileup_add(rd_ctx* ctx, const uint8_t* refs, const int64_t* re
     RD_REQUIRE(ref_off && read_off && ((site0 && out) || n_pairs == 0), "%s: null argument", who);
     if (int rc = pileup_check_pairs(who, ref_off, read_off, n_pairs, site0, ctx->pileup_n_sites)) return rc;
     std::vector<int32_t> score((size_t)n_pairs + 1), counts(4 * (size_t)n_pairs + 1), status((size_t)n_pairs + 1);
-    for (int64_t k = 0; k < (int64_t)n_pairs * PILEUP_RES; k++) out[k] = k % PILEUP_RES == 0 ? PILEUP_TOO_LARGE : 0;   // until its batch has run
     PileupHook hook(ctx, site0, out);
     const int rc = rd_align_batch_run(ctx, who, "RD_PILEUP_TOO_LARGE", refs, ref_off, reads, read_off, n_pairs, match, mismatch, gap_open, gap_extend,
                                       budget_bytes, score.data(), counts.data(), status.data(), ops_out, ops_off, ops_len, hook);

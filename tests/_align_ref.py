@@ -131,6 +131,119 @@ def rescore(ops, ref, read, sc=SCORES):
     return tot
 
 
+# ---- score sets other than the default (match, mismatch, gap open, gap extend) ----
+# accepted: gap_open <= gap_extend.  Linear gaps (open == extend: every "opened" comparison is a tie), a zero match score, a mismatch
+# score of zero and a positive one, free extension, an expensive opening.
+SMALL_SETS = (SCORES, (1, -1, -1, -1), (2, -3, -2, -2), (2, -4, 0, 0), (0, -1, -1, -1), (1, 0, -1, -1), (3, 1, -5, -2), (2, -4, -4, 0),
+              (5, -4, -10, -1))
+BOUND_SETS = ((65535, -65535, -65535, -65535), (1, -65535, -3, -1))   # the largest |score| the entry points take
+ACCEPTED_SETS = SMALL_SETS + BOUND_SETS
+REFUSED_SET = (1, -2, -1, -3)   # open > extend: the recurrence reopens adjacent gaps (tests/test_align_cpu.py keeps the counter-example)
+
+
+def can_substitute(sc):
+    """whether an optimal alignment can hold an X column at all: a D column followed by an I column (two openings) replaces it"""
+    return sc[1] >= 2 * sc[2]
+
+
+def three_state(ref, read, sc=SCORES):
+    """The optimal global score under "a gap of length L costs open + (L - 1) * extend", by a model that is not Gotoh's recurrence:
+    three matrices of alignments that END in a pair column (M), a deletion (X) or an insertion (Y), and a gap is ENTERED only from one
+    of the other two states -- so two gaps of one kind are never adjacent, whatever the scores.  Plain Python ints, byte equality."""
+    match, mis, go, ge = sc
+    n, m = len(ref), len(read)
+    none = -(1 << 62)
+    M = [[none] * (m + 1) for _ in range(n + 1)]
+    X = [[none] * (m + 1) for _ in range(n + 1)]
+    Y = [[none] * (m + 1) for _ in range(n + 1)]
+    M[0][0] = 0
+    for i in range(1, n + 1):
+        X[i][0] = go + (i - 1) * ge
+    for j in range(1, m + 1):
+        Y[0][j] = go + (j - 1) * ge
+    for i in range(1, n + 1):
+        a = ref[i - 1]
+        Mi, Xi, Yi, Mu, Xu, Yu = M[i], X[i], Y[i], M[i - 1], X[i - 1], Y[i - 1]
+        for j in range(1, m + 1):
+            Mi[j] = max(Mu[j - 1], Xu[j - 1], Yu[j - 1]) + (match if a == read[j - 1] else mis)
+            Xi[j] = max(max(Mu[j], Yu[j]) + go, Xu[j] + ge)
+            Yi[j] = max(max(Mi[j - 1], Xi[j - 1]) + go, Yi[j - 1] + ge)
+    return max(M[n][m], X[n][m], Y[n][m])
+
+
+def _mutate(rng, s, letters, p=0.12):
+    out = bytearray()
+    for c in s:
+        r = rng.random()
+        if r < p / 3:
+            continue
+        out.append(c if r > p else int(rng.choice(list(letters))))
+        if rng.random() < p / 3:
+            out.append(int(rng.choice(list(letters))))
+    return bytes(out)
+
+
+def tie_pairs(rng):
+    """pairs with very many co-optimal alignments, a pair with N (a byte like any other here), and the three empty cases"""
+    def rnd(n, letters=b"AC"):
+        return bytes(rng.choice(list(letters), n).astype(np.uint8))
+
+    x = rnd(90)
+    return [(b"A" * 70, b"A" * 40), (b"A" * 40, b"A" * 66), (b"AC" * 35, b"CA" * 33), (b"AAC" * 30, b"AC" * 40), (rnd(100), rnd(80)),
+            (x, _mutate(rng, x, b"AC", 0.2)), (b"ACGTN" * 20, b"ACGT" * 26), (b"ACNNGT" * 11, b"ACNGT" * 13), (b"", rnd(10)), (rnd(10), b""),
+            (b"", b"")]
+
+
+def edge_pairs(rng, lengths_n=(1, 2, 3, 63, 64, 65, 127, 128, 129), lengths_m=(1, 2, 3, 63, 64, 65, 127, 128, 129)):
+    """lengths around the forward kernel's 64-row tile and 64-column chunk on both sides: a mutated copy (its length moves a little) and
+    an unrelated read of the exact length for every (n, m)"""
+    def rnd(n):
+        return bytes(rng.choice(list(b"ACGT"), n).astype(np.uint8))
+
+    pairs = []
+    for n in lengths_n:
+        for m in lengths_m:
+            a = rnd(n)
+            pairs.append((a, _mutate(rng, a, b"ACGT") if n > 8 and abs(n - m) <= 2 else rnd(m)))
+            pairs.append((rnd(n), rnd(m)))
+    return pairs
+
+
+def score_set_pairs():
+    """the pairs the GPU tests align under every score set of SMALL_SETS (seeded: the same everywhere)"""
+    rng = np.random.default_rng(41)
+    return edge_pairs(rng) + tie_pairs(rng)
+
+
+def small_pairs():
+    """20 pairs of 1..140 bases for the pure-Python model: edges at 63 / 64 / 65, homopolymer and dinucleotide pairs"""
+    rng = np.random.default_rng(42)
+
+    def rnd(n, letters=b"ACGT"):
+        return bytes(rng.choice(list(letters), n).astype(np.uint8))
+
+    pairs = [(b"A", b"C"), (b"A", b"AAAA"), (rnd(5), rnd(2)), (b"A" * 64, b"A" * 40), (b"A" * 30, b"A" * 65), (b"AC" * 32, b"CA" * 30),
+             (b"AAC" * 21, b"AC" * 32), (rnd(63, b"AC"), rnd(65, b"AC")), (b"ACGTN" * 13, b"ACGT" * 16)]
+    for n, m in ((63, 64), (64, 63), (65, 65), (64, 20), (20, 64), (140, 100), (100, 140)):
+        pairs.append((rnd(n), rnd(m)))
+    for n in (63, 64, 65, 140):
+        a = rnd(n)
+        pairs.append((a, _mutate(rng, a, b"ACGT", 0.15)))
+    assert len(pairs) == 20 and all(1 <= len(a) <= 140 and 1 <= len(b) <= 140 for a, b in pairs)
+    return pairs
+
+
+def longest_run(ops, c):
+    """length of the longest run of byte c in any of the op strings"""
+    best = 0
+    for o in ops:
+        run = 0
+        for x in o:
+            run = run + 1 if x == c else 0
+            best = max(best, run)
+    return best
+
+
 def align_cpu(refs, reads, sc=SCORES, cells_per_batch=48 << 20):
     """score, n_optimal and tie-broken ops of every pair (batches of similar sizes, largest first)"""
     refs = [r.encode() if isinstance(r, str) else bytes(r) for r in refs]

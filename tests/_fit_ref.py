@@ -10,6 +10,8 @@ brute(ref, query, scores)      every (start, end) span against the whole query w
 Codes: queries 0..3, references 0..4; code 4 equals nothing, itself included."""
 import numpy as np
 
+from _align_ref import ACCEPTED_SETS, BOUND_SETS, REFUSED_SET, SMALL_SETS   # the score sets the tests run besides the default
+
 NEG = -(1 << 40)
 NEG32 = -(1 << 29)   # fit_rows' stored -inf: far below any score, and NEG32 + a gap score still fits
 SCORES = (2, -4, -4, -2)   # match, mismatch, gap open, gap extend

@@ -118,6 +118,55 @@ def test_cpu_tie_break_order():
     assert nopt[0] == 2 and ops[0] == b"DM"   # at (2, 1) the diagonal ties with the deletion and wins: the gap goes first
 
 
+@pytest.fixture(scope="module")
+def small_pairs():
+    return aref.small_pairs()
+
+
+@pytest.mark.parametrize("sc", aref.ACCEPTED_SETS, ids=lambda sc: "_".join(str(v) for v in sc))
+def test_restatement_equals_the_three_state_model_under_every_accepted_score_set(small_pairs, sc):
+    """gap_open <= gap_extend: Gotoh's recurrence (the restatement, the kernels) is the stated gap cost.  The model is written
+    independently (a gap is entered only from another state); the traceback's columns add up to the score; the pairs tie heavily."""
+    refs, reads = [p[0] for p in small_pairs], [p[1] for p in small_pairs]
+    score, nopt, ops = aref.align_cpu(refs, reads, sc)
+    for k, (a, b) in enumerate(small_pairs):
+        assert int(score[k]) == aref.three_state(a, b, sc), (k, sc)
+        assert aref.rescore(ops[k], a, b, sc) == score[k], (k, sc)
+    assert 2 * int((nopt >= 2).sum()) >= len(small_pairs), (sc, nopt.tolist())
+
+
+def test_open_above_extend_is_not_the_stated_gap_cost(small_pairs):
+    """Why the entry points refuse gap_open > gap_extend (include/radian_hip.h): at (1, -2, -1, -3) the recurrence closes a gap and
+    reopens it in the next column for 2 * open, where one gap of length 2 costs open + extend.  Its score is then above the optimum of
+    the stated cost model, and the traced columns do not add up to it.  Relaxing the refusal brings this back."""
+    sc = aref.REFUSED_SET
+    assert sc[2] > sc[3]
+    refs, reads = [p[0] for p in small_pairs], [p[1] for p in small_pairs]
+    score, _, ops = aref.align_cpu(refs, reads, sc)
+    model = [aref.three_state(a, b, sc) for a, b in small_pairs]
+    differ = [k for k in range(len(small_pairs)) if int(score[k]) != model[k]]
+    assert differ, "the recurrence and the cost model agree on every pair: the counter-example is gone"
+    assert all(int(score[k]) > model[k] for k in differ)        # never below: every alignment of the model is a path of the recurrence
+    assert any(aref.rescore(ops[k], refs[k], reads[k], sc) != score[k] for k in range(len(small_pairs)))
+    # equality (linear gaps) has no such case
+    for k, (a, b) in enumerate(small_pairs[:8]):
+        assert int(aref.gotoh_batch([a], [b], (1, -2, -3, -3))[0][0]) == aref.three_state(a, b, (1, -2, -3, -3)), k
+
+
+def test_score_set_pairs_cover_every_branch_under_every_set():
+    """what tests/test_gpu_align.py asserts of the device's ops holds for the restatement's: under every set the tie-broken alignments
+    of its pairs hold a run of two or more D, a run of two or more I, and an X wherever an optimal alignment can hold one"""
+    pairs = aref.score_set_pairs()
+    refs, reads = [p[0] for p in pairs], [p[1] for p in pairs]
+    assert {len(r) for r in refs} >= {0, 1, 2, 3, 63, 64, 65, 127, 128, 129} and max(len(s) for s in refs + reads) <= 140
+    for sc in aref.SMALL_SETS:
+        _, nopt, ops = aref.align_cpu(refs, reads, sc)
+        assert aref.longest_run(ops, ord("D")) >= 2 and aref.longest_run(ops, ord("I")) >= 2, sc
+        assert (aref.longest_run(ops, ord("X")) >= 1) == aref.can_substitute(sc), sc
+        assert 2 * int((nopt >= 2).sum()) >= len(pairs), sc
+    assert [sc for sc in aref.SMALL_SETS if not aref.can_substitute(sc)] == [(2, -4, 0, 0)]
+
+
 def test_fasta_and_tsv_parsing(tmp_path):
     from radian_amd import align
     fa = tmp_path / "x.fasta"

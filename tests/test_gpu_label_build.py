@@ -1,5 +1,6 @@
 """GPU checks of training-shard building: rd_fit_batch (fit.hip) against the restatement of its contract (tests/_fit_ref.py) on every
-output field, and python -m radian_amd.label_build end to end -- the windows, spans and labels the restatement plus the selection
+output field (under the default scores and under every score set of tests/_align_ref.py, the int32 bound and the refusal of
+gap_open > gap_extend among them), and python -m radian_amd.label_build end to end -- the windows, spans and labels the restatement plus the selection
 rules give, shards that read back exactly, bytes that do not depend on the batch size, and `evaluate` / `train` running on the result."""
 import os
 import subprocess
@@ -9,6 +10,7 @@ import time
 import numpy as np
 import pytest
 
+import _fit_cases as fc
 import _fit_ref as fr
 
 pytestmark = pytest.mark.gpu
@@ -169,6 +171,88 @@ def test_fit_batch_too_large_leaves_the_others_aligned(be, fit_cases):
         with pytest.raises(RadianHipError):
             be.fit_batch(bad_refs, bad_q, bad_r)
     assert len(be.fit_batch([], [], []).score) == 0
+
+
+# ---------------------------------------------------------------- scores other than 2 / -4 / -4 / -2
+_SET_ID = lambda sc: "_".join(str(v) for v in sc)
+
+
+@pytest.fixture(scope="module")
+def small_cases():
+    refs, queries, qref = fc.fit_cases_small()
+    ms = sorted({len(q) for q in queries})
+    for lo, hi in ((1, 16), (17, 32), (33, 64), (65, 128), (129, 256), (257, 512), (513, 1024)):   # fit.hip's launch classes
+        assert any(lo <= m <= hi for m in ms), (lo, hi)
+    assert any(len(q) > len(refs[r]) for q, r in zip(queries, qref))
+    return refs, queries, qref
+
+
+@pytest.mark.parametrize("sc", fr.SMALL_SETS, ids=_SET_ID)
+def test_fit_batch_under_every_score_set(be, small_cases, sc):
+    """Linear gaps (every `ee >= eo` / `fe >= fo` select of fit_kernel decided on a tie), a zero match score, a zero and a positive
+    mismatch score, free extension, an expensive opening: every field equals the row-wise restatement's; the same after a permutation
+    and under a budget that cuts the queries into several launches"""
+    refs, queries, qref = small_cases
+    want = [fr.fit_rows(refs[r], q, sc) for q, r in zip(queries, qref)]
+    _check(be.fit_batch(refs, queries, qref, scores=sc), want)
+    perm = np.random.default_rng(2).permutation(len(queries))
+    _check(be.fit_batch(refs, [queries[p] for p in perm], qref[perm], scores=sc), [want[p] for p in perm])
+    budget = 4096   # the 1500-code reference and a 1024-label query fit (1500 + 1024 + 64 + 1024 bytes)
+    assert sum(len(r) for r in refs) + sum(len(q) for q in queries) > 2 * budget
+    _check(be.fit_batch(refs, queries, qref, scores=sc, budget_bytes=budget), want)
+    # the set's results hold gaps of both kinds, so both selects ran on a path that counts
+    assert any(w["counts"][2] >= 2 for w in want) and any(w["counts"][3] >= 2 for w in want), sc
+
+
+def _raw_fit(be, refs, queries, qref, sc, fill=-7):
+    """rd_fit_batch on pre-filled outputs: (rc, error text, whether every output still holds the fill)"""
+    from radian_amd.backend import _concat_codes, _p
+    rbuf, roff = _concat_codes(refs)
+    qbuf, qoff = _concat_codes(queries)
+    n = len(queries)
+    qr = np.ascontiguousarray(qref, dtype=np.int32)
+    score, start, end, status = (np.full(n, fill, dtype=np.int32) for _ in range(4))
+    counts = np.full((n, 4), fill, dtype=np.int32)
+    rc = be._L.rd_fit_batch(be._h, _p(rbuf), _p(roff), len(roff) - 1, _p(qbuf), _p(qoff), _p(qr), n, *(int(v) for v in sc), 0, _p(score),
+                            _p(start), _p(end), _p(counts), _p(status))
+    return rc, be._L.rd_last_error().decode(), all((x == fill).all() for x in (score, start, end, status, counts))
+
+
+def test_fit_batch_at_the_int32_bound(be, small_cases):
+    """|score| = 65535: a reference of 3071 codes is the longest the argument check admits (65535 * (3071 + 1025) < 2^28); queries of 1, 64
+    and 1024 against it and some of the small cases are exact against the restatement, whose stored -inf lies below every reachable value
+    at these scores (tests/test_label_build_cpu.py).  3072 codes are refused before any output is written."""
+    rng = np.random.default_rng(22)
+    assert 65535 * (3071 + 1025) < 1 << 28 <= 65535 * (3072 + 1025)
+    big = rng.integers(0, 4, size=3072).astype(np.uint8)
+    big[rng.integers(0, 3071, size=20)] = 4
+    qs = [_mutate(rng, np.where(big[lo: lo + m + 40] == 4, 0, big[lo: lo + m + 40]), 0.1)[:m] for lo, m in ((100, 1), (2000, 64), (1500, 1024))]
+    assert [len(q) for q in qs] == [1, 64, 1024]
+    qs.append(rng.integers(0, 4, size=1024).astype(np.uint8))                        # unrelated: the most negative scores
+    refs, queries, qref = small_cases
+    few = [p for p in range(len(queries)) if len(refs[qref[p]]) <= 300][:30]
+    all_refs = list(refs) + [big[:3071]]
+    all_q, all_r = [queries[p] for p in few] + qs, np.array([qref[p] for p in few] + [len(refs)] * len(qs), dtype=np.int32)
+    for sc in fr.BOUND_SETS:
+        want = [fr.fit_rows(all_refs[r], q, sc) for q, r in zip(all_q, all_r)]
+        _check(be.fit_batch(all_refs, all_q, all_r, scores=sc), want)
+        rc, msg, untouched = _raw_fit(be, list(refs) + [big], all_q, all_r, sc)
+        assert rc == -1 and untouched and f"reference {len(refs)} (3072 codes)" in msg and "too long for int32 scores" in msg, (sc, rc, msg)
+
+
+def test_fit_batch_refuses_gap_open_above_gap_extend_before_any_output(be, small_cases):
+    """with open > extend the recurrence reopens adjacent gaps: its score is not the stated gap cost (tests/test_label_build_cpu.py)"""
+    from radian_amd import RadianHipError
+    refs, queries, qref = small_cases
+    for sc in (fr.REFUSED_SET, (2, -4, -2, -4)):
+        rc, msg, untouched = _raw_fit(be, refs, queries[:20], qref[:20], sc)
+        assert rc == -1 and untouched and msg.startswith("rd_fit_batch: gap_open") and "gap_open <= gap_extend" in msg, (sc, rc, msg)
+        with pytest.raises(RadianHipError, match="gap_open <= gap_extend"):
+            be.fit_batch(refs, queries[:20], qref[:20], scores=sc)
+    sc = (2, -4, -3, -3)                                                             # equality, linear gaps, is legal
+    rc, msg, untouched = _raw_fit(be, refs, queries[:20], qref[:20], sc)
+    assert rc == 0 and not untouched, (rc, msg)
+    _check(be.fit_batch(refs, queries[:20], qref[:20], scores=sc), [fr.fit_rows(refs[r], q, sc) for q, r in zip(queries[:20], qref[:20])])
 
 
 # ---------------------------------------------------------------- python -m radian_amd.label_build, end to end

@@ -227,6 +227,56 @@ def test_scores_and_ops_are_aligns(be, cases):
     assert a.ops == c["ops"] and [int(s) for s in a.score] == c["scores"]
 
 
+@pytest.mark.parametrize("sc", [(2, -3, -2, -2), (5, -4, -10, -1)], ids=["linear_2_-3_-2_-2", "affine_5_-4_-10_-1"])
+def test_add_under_other_scores_equals_add_ops_of_the_restatements_ops(be, cases, sc):
+    """rd_pileup_add hands its scores to the alignment: under linear gaps and under an expensive opening it leaves the site counts, the
+    profile and the per-pair fields that rd_pileup_add_ops leaves when fed the restatement's ops for those scores, and returns those ops"""
+    import _align_ref as ar
+    for name in ("length_grid", "hot"):
+        c = cases[name]
+        score, _, ops = ar.align_cpu(c["spans"], c["reads"], sc)
+        ops = [bytes(o) for o in ops]
+        assert ops != c["ops"], name                                     # not the default scores' alignments
+        be.pileup_open(c["n_sites"])
+        exp = be.pileup_add_ops(ops, c["spans"], c["reads"], c["site0"])
+        exp_sites, exp_prof = _table(be, c["n_sites"])
+        be.pileup_open(c["n_sites"])
+        res = be.pileup_add(c["spans"], c["reads"], c["site0"], scores=sc, with_ops=True)
+        sites, prof = _table(be, c["n_sites"])
+        be.pileup_close()
+        assert res.ops == ops, name
+        want = exp.out.copy()
+        want[:, 1] = score                                               # rd_pileup_add_ops ran no alignment: its score column is 0
+        assert np.array_equal(res.out, want), name
+        assert np.array_equal(sites, exp_sites) and np.array_equal(prof, exp_prof), name
+        assert exp_sites.any() and exp_prof.any()
+        # and the restatement of the pileup itself on those ops
+        r_sites, r_prof, r_out = ref.pileup(ops, c["spans"], c["reads"], c["site0"], c["n_sites"], [int(s) for s in score])
+        assert np.array_equal(res.out, r_out) and np.array_equal(prof, r_prof), name
+
+
+def test_add_refuses_gap_open_above_gap_extend_under_its_own_name(be):
+    from radian_amd import RadianHipError
+    one = np.zeros(4, dtype=np.int64)
+    one[1] = 2
+    seq = np.frombuffer(b"ACAC", dtype=np.uint8).copy()
+    out = np.full(16, -7, dtype=np.int32)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    be.pileup_open(10)
+    be.pileup_add_ops([b"M"], [b"A"], [b"A"], [0])
+    for sc in ((1, -2, -1, -3), (2, -4, -2, -4)):
+        rc = be._L.rd_pileup_add(be._h, p(seq), p(one), p(seq), p(one), 1, p(one[2:]), *sc, 0, p(out), None, None, None)
+        msg = be._L.rd_last_error().decode()
+        assert rc == -1 and msg.startswith("rd_pileup_add: gap_open") and "gap_open <= gap_extend" in msg and "rd_align_batch" not in msg, (rc, msg)
+        assert (out == -7).all()                                                                   # the refusal precedes every write to `out`
+        with pytest.raises(RadianHipError, match="rd_pileup_add: gap_open"):
+            be.pileup_add([b"AC"], [b"AC"], [0], scores=sc)
+    assert be.pileup_read().counts.tolist() == [[1, 0, 0, 0, 0, 0, 0, 1]]                           # nothing was added by the refused calls
+    be.pileup_add([b"AC"], [b"AC"], [0], scores=(2, -4, -3, -3))                                   # equality is legal
+    assert be.pileup_read().site.tolist() == [0, 1]
+    be.pileup_close()
+
+
 # ---------------------------------------------------------------------------------------------- the command line
 def test_command_line_files_byte_for_byte(tmp_path):
     names, seqs, reads, paf, alt = pc.cli_case()

@@ -8,6 +8,7 @@ import struct
 import numpy as np
 import pytest
 
+import _fit_cases as fc
 import _fit_ref as fr
 import _tfrecord_writer as tw
 
@@ -61,6 +62,85 @@ def test_row_wise_restatement_equals_the_cell_wise_one():
             ref[rng.integers(0, n, size=3)] = 4
         q = rng.integers(0, alpha, size=m)
         assert fr.fit_rows(ref, q) == fr.fit(ref, q)
+
+
+_SET_IDS = lambda sc: "_".join(str(v) for v in sc)
+
+
+@pytest.mark.parametrize("sc", fr.ACCEPTED_SETS, ids=_SET_IDS)
+def test_restatement_against_brute_force_under_every_accepted_score_set(sc):
+    """gap_open <= gap_extend: the contract's recurrence is the stated gap cost (brute: every span, a three-matrix global alignment)"""
+    rng = np.random.default_rng(16)
+    for k in range(25):
+        n, m = int(rng.integers(0, 14)), int(rng.integers(1, 9))
+        alpha = 1 + k % 4
+        ref = [int(c) for c in rng.integers(0, alpha, size=n)]
+        if k % 5 == 0:
+            ref = [4 if rng.random() < 0.25 else c for c in ref]
+        q = [int(c) for c in rng.integers(0, alpha, size=m)]
+        got = fr.fit(ref, q, sc)
+        assert (got["score"], got["ref_end"]) == fr.brute(ref, q, sc), (ref, q, sc)
+        nm, ns, ni, nd = got["counts"]
+        assert nm + ns + ni == len(q) and nm + ns + nd == got["ref_end"] - got["ref_start"] and 0 <= got["ref_start"] <= got["ref_end"]
+
+
+@pytest.mark.parametrize("sc", fr.ACCEPTED_SETS, ids=_SET_IDS)
+def test_row_wise_restatement_equals_the_cell_wise_one_under_every_accepted_score_set(sc):
+    rng = np.random.default_rng(17)
+    for k in range(12):
+        n, m = ((130, 70), (0, 5), (1, 70), (64, 64))[k] if k < 4 else (int(rng.integers(0, 131)), int(rng.integers(1, 71)))
+        alpha = 1 if k % 6 == 4 else 2 if k % 6 == 5 else 4
+        ref = rng.integers(0, alpha, size=n)
+        if k % 3 == 0 and n:
+            ref[rng.integers(0, n, size=3)] = 4
+        q = rng.integers(0, alpha, size=m)
+        assert fr.fit_rows(ref, q, sc) == fr.fit(ref, q, sc), (k, n, m, sc)
+
+
+def test_open_above_extend_is_not_the_stated_gap_cost():
+    """why rd_fit_batch refuses gap_open > gap_extend: the recurrence then differs from brute force over the stated cost model"""
+    rng = np.random.default_rng(16)
+    differ = 0
+    for k in range(25):
+        ref = [int(c) for c in rng.integers(0, 1 + k % 4, size=int(rng.integers(0, 14)))]
+        q = [int(c) for c in rng.integers(0, 1 + k % 4, size=int(rng.integers(1, 9)))]
+        got, want = fr.fit(ref, q, fr.REFUSED_SET)["score"], fr.brute(ref, q, fr.REFUSED_SET)[0]
+        assert got >= want
+        differ += got != want
+    assert differ >= 1
+    with pytest.raises(AssertionError):
+        fr.fit_rows([0, 1], [0], fr.REFUSED_SET)
+
+
+def test_gpu_cases_tell_a_flipped_tie_select_apart_under_every_score_set():
+    """the cases tests/test_gpu_label_build.py runs under every score set: with the tie of extend and close inside a deletion run (E) or
+    an insertion run (F) decided the other way, the restatement's result changes on at least one of them under every set -- so a kernel
+    with `ee >= eo` or `fe >= fo` written `>` fails that test under every set, not only under some"""
+    refs, queries, qref = fc.fit_cases_small()
+    cases = [([int(c) for c in refs[r]], [int(c) for c in q]) for q, r in zip(queries, qref) if len(q) <= 130]   # (the long ones: seconds each)
+    for sc in fr.SMALL_SETS:
+        seen = set()
+        for ref, q in cases:
+            mats = fr._matrices_rows(ref, q, sc)
+            want = fr._trace(*mats, ref, q, sc)
+            seen |= {flip for flip in "EF" if fc.trace_tie_flipped(*mats, ref, q, sc, flip) != want}
+        assert seen == {"E", "F"}, (sc, seen)
+
+
+def test_row_wise_sentinel_lies_below_every_value_at_the_largest_scores():
+    """fit_rows stores -inf as NEG32 = -2^29 in int32.  H(i, j) >= H(i, 0) + open + (j - 1) * extend >= -65535 * 1024 and E, F >= an H
+    + open, so nothing reachable is below -65535 * 1026 > -2^27: the sentinel, and the sentinel plus a gap score, stay apart from every
+    value.  Checked on the stored matrices and against the cell-wise restatement (whose -inf is -2^40) with the longest query."""
+    sc = fr.ACCEPTED_SETS[-2]
+    assert sc == (65535, -65535, -65535, -65535)
+    rng = np.random.default_rng(18)
+    for ref, q in ((rng.integers(0, 4, size=40), rng.integers(0, 4, size=1024)), (np.full(30, 4), rng.integers(0, 4, size=1024)),
+                   (rng.integers(0, 2, size=300), rng.integers(2, 4, size=200))):
+        H, E, F = fr._matrices_rows([int(c) for c in ref], [int(c) for c in q], sc)
+        for X in (H, E[1:, 1:], F[:, 1:]):
+            assert X.min() >= -65535 * 1026 > fr.NEG32 // 4
+        assert (E[0] == fr.NEG32).all() and (E[:, 0] == fr.NEG32).all() and (F[:, 0] == fr.NEG32).all()
+        assert fr.fit_rows(ref, q, sc) == fr.fit(ref, q, sc)
 
 
 def test_code_4_matches_nothing_itself_included():
