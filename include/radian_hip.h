@@ -758,6 +758,56 @@ int rd_eventalign_host(const int16_t* raw, const int64_t* read_off, int n_reads,
                        int64_t* ev_sumsq, int16_t* ev_min, int16_t* ev_max, int64_t* fit_sums);
 int64_t rd_eventalign_workspace_bytes(int64_t n_rows, int64_t n_bases);
 
+/* ---- eventalign on event rows: weighted rows and base skips (eventalign.hip) ------------------------------
+ * NO reference behaviour.  rd_eventalign's Viterbi over lead, base 1 .. base L, trail, with rows that are a detector's EVENTS, each
+ * weighted by its sample count, and a third predecessor that skips one base.  Integer arithmetic only; met exactly.  With one event per
+ * sample and skips off it is rd_eventalign on a given scale.  Model, states, ea_quant and the cell's cost are rd_eventalign's.
+ *   read      n_samples[r] = T, the window's length, which closes the last event; sample_off[r] (>= 0, sample_off + T <= 2^31 - 1) is
+ *             added to every reported sample index.  E = n_events[r] events at ev_off[r] + e of in_start, in_sum, in_sumsq, in_min, in_max,
+ *             exactly as rd_segment returns them (in_start relative to the window); no raw sample is read.  codes / ref_off / ref_len and
+ *             the model as rd_eventalign.  The scale (m2_in, d4_in) is always given (rd_segment's, or a refit); d4_in == 0 is
+ *             RD_EVAL_MAD_ZERO.  skip_pen: -1 no skip edge, otherwise 0..256 in 1/32 nat
+ *   rows      n_e = in_start[e+1] - in_start[e], T - in_start[E-1] for the last; x_e = floor((2 in_sum[e] + n_e) / (2 n_e)), the mean rounded
+ *             half up; zq_e = rd_eventalign's sample rule on x_e
+ *   cell      c(e, s) = n_e * cost(zq_e, s).  V[0][0] = c(0, 0), V[0][1] = c(0, 1); V[e][s] = c(e, s) + the best of three: stay
+ *             V[e-1][s]; advance V[e-1][s-1], taken only if STRICTLY smaller than stay; skip V[e-1][s-2] + skip_pen (2 <= s <= L + 1), taken
+ *             only if STRICTLY smaller than the best of the other two.  On ties: stay, advance, skip.  Lead to base 2 skips base 1; base
+ *             L - 1 to the trail skips base L.  The path ends in L + 1, or in L if the trail is not strictly smaller
+ *   bounds    T <= 2^19 and sum n_e = T: the weighted costs of a path sum to less than 2^19 * 1280; at most one skip per row, E <= T and
+ *             skip_pen <= 256: finite values stay below 2^19 * 1536 = 0.75 * 2^30.  An unreachable cell (s > 2 e + 1; s > e + 1 without
+ *             skips) starts at 2^30, stays above 2^30 - 2^19 * 256 = 0.875 * 2^30 and below 2^31, so computed unmasked it never wins.
+ *             n_e < 2^23 and |cost| <= 1280: n_e * cost is exact as a 24-bit multiply
+ *   status    in this order: T == 0 or E == 0 RD_EVAL_EMPTY; T > 2^19 RD_EVAL_TOO_LONG; d4_in == 0 RD_EVAL_MAD_ZERO; E < L without
+ *             skips, 2 E - 1 < L with them RD_EVAL_NO_PATH; over the budget alone RD_EVAL_TOO_LARGE; otherwise RD_EVAL_OK
+ *   outputs   per read status, score, n_skipped, fit_sums (rd_eventalign's, a skipped base adding nothing).  Per base at ref_off[r] + b:
+ *             row_first / row_last, indices into the read's events (-1, -1 for a skipped base); ev_start / ev_end in read coordinates
+ *             (sample_off added), for a skipped base both the start of the row at which the path jumped over it; ev_sum, ev_sumsq,
+ *             ev_min, ev_max accumulated from the records of the base's rows, zeros for a skipped base.  A read that is not OK has score
+ *             0, n_skipped 0, zero sums, -1 in row_first, row_last, ev_start, ev_end and zeros elsewhere; it never affects its neighbours
+ * A result does not depend on the batch, the order, the budget or the launches.  RD_ERR_ARG before anything is launched: whatever
+ * rd_eventalign refuses; E > 0 with in_start[0] != 0, starts that do not strictly increase or a start >= T; an event whose mean does not fit
+ * int16; skip_pen outside -1..256.  n_reads == 0 is RD_OK.
+ *   rd_eventalign_events        on the GPU; synchronous, uses the context's stream; budget_bytes and RD_ERR_NOMEM as rd_eventalign
+ *   rd_eventalign_events_host   host, no GPU: the same rules (csrc/eventalign_rules.h) in a plain loop
+ *   rd_eventalign_events_workspace_bytes   of n_rows events and n_bases bases, each term rounded up to 256: 8 n_rows (zq and n per row)
+ *                        + 4 n_rows ceil((n_bases + 2) / 16) (back-pointers, two bits per cell) + 16 n_rows (two band columns of two
+ *                        cells per row) when n_bases + 2 > 4096 */
+int rd_eventalign_events(rd_ctx* ctx, int n_reads, const int64_t* n_samples, const int64_t* sample_off, const int64_t* ev_off,
+                         const int32_t* n_events, const int32_t* in_start, const int64_t* in_sum, const int64_t* in_sumsq, const int16_t* in_min,
+                         const int16_t* in_max, const uint8_t* codes, const int64_t* ref_off, const int32_t* ref_len, const int32_t* m2_in,
+                         const int32_t* d4_in, int k, const int32_t* lvl, const uint32_t* w, const int32_t* bias, int32_t lvl_bg, uint32_t w_bg,
+                         int32_t bias_bg, int skip_pen, int64_t budget_bytes, int32_t* status, int64_t* score, int32_t* n_skipped,
+                         int32_t* row_first, int32_t* row_last, int32_t* ev_start, int32_t* ev_end, int64_t* ev_sum, int64_t* ev_sumsq,
+                         int16_t* ev_min, int16_t* ev_max, int64_t* fit_sums);
+int rd_eventalign_events_host(int n_reads, const int64_t* n_samples, const int64_t* sample_off, const int64_t* ev_off, const int32_t* n_events,
+                              const int32_t* in_start, const int64_t* in_sum, const int64_t* in_sumsq, const int16_t* in_min, const int16_t* in_max,
+                              const uint8_t* codes, const int64_t* ref_off, const int32_t* ref_len, const int32_t* m2_in, const int32_t* d4_in,
+                              int k, const int32_t* lvl, const uint32_t* w, const int32_t* bias, int32_t lvl_bg, uint32_t w_bg, int32_t bias_bg,
+                              int skip_pen, int32_t* status, int64_t* score, int32_t* n_skipped, int32_t* row_first, int32_t* row_last,
+                              int32_t* ev_start, int32_t* ev_end, int64_t* ev_sum, int64_t* ev_sumsq, int16_t* ev_min, int16_t* ev_max,
+                              int64_t* fit_sums);
+int64_t rd_eventalign_events_workspace_bytes(int64_t n_rows, int64_t n_bases);
+
 /* ---- sigmap: raw samples against a panel of targets, subsequence Viterbi with a free start and end (sigmap.hip)
  * NO reference behaviour.  Which targets of a panel a window of samples fits best, where the fit ends in each and where it began.  No
  * basecall and no neural network take part.  Integer arithmetic only; met exactly.  Sample, cell and the three model tables are

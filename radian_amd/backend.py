@@ -528,6 +528,63 @@ def eventalign_workspace_bytes(n_rows, n_bases):
     return int(_lib.load().rd_eventalign_workspace_bytes(int(n_rows), int(n_bases)))
 
 
+class EvalRowsResult:
+    """rd_eventalign_events: per read status (int32, EVAL_*), score (int64), n_skipped (int32), m2 / d4 (int32: the scale as given), fit_sums
+    (int64 [reads, 5]); per read and base: row_first / row_last (int32 arrays, indices into the read's events; -1 for a skipped base) and
+    events (an EventsResult in read sample coordinates; start == end for a skipped base)"""
+    __slots__ = ("status", "score", "n_skipped", "m2", "d4", "fit_sums", "row_first", "row_last", "events")
+
+
+def _eval_rows_args(events, n_samples, seqs, model, m2, d4, sample_off, skip_pen):
+    """-> (the arrays, kept alive by the caller; the arguments up to the budget; the output buffers; the per-base cut)"""
+    n = len(events)
+    if not (len(seqs) == len(n_samples) == len(m2) == len(d4) == n) or (sample_off is not None and len(sample_off) != n):
+        raise ValueError(f"per-read arguments that do not hold one entry for each of {n} reads")
+    codes, coff = _concat_codes(seqs)
+    ref_len = np.diff(coff).astype(np.int32)
+    ref_off = np.ascontiguousarray(coff[:-1] if n else np.zeros(1), dtype=np.int64)
+    cnt = np.array([len(e["start"]) for e in events] + [0], dtype=np.int32)
+    ev_off = np.zeros(n + 1, dtype=np.int64)
+    ev_off[1:] = np.cumsum(cnt[:n])
+    ev = [np.concatenate([np.asarray(e[name], dtype=dt).ravel() for e in events] + [np.zeros(1, dt)])
+          for name, dt in SEGMENT_EVENT_FIELDS if name != "src"]
+    pad = lambda a, dt: np.concatenate([np.ascontiguousarray(a, dtype=dt).ravel(), np.zeros(1, dt)])   # (a pointer the library can check when n = 0)
+    ns, so = pad(n_samples, np.int64), pad(np.zeros(n) if sample_off is None else sample_off, np.int64)
+    m2, d4 = pad(m2, np.int32), pad(d4, np.int32)
+    tot = int(coff[-1])
+    outs = [np.zeros(n + 1, np.int32), np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int32), np.full(tot + 1, -1, np.int32),
+            np.full(tot + 1, -1, np.int32), *_event_buffers(tot), np.zeros((n + 1, 5), np.int64)]
+    keep = (codes, ref_off, ref_len, cnt, ev_off, ev, ns, so, m2, d4, model)
+    head = (n, _p(ns), _p(so), _p(ev_off), _p(cnt), *[_p(a) for a in ev], _p(codes), _p(ref_off), _p(ref_len), _p(m2), _p(d4), *model.args(),
+            int(skip_pen))
+    cut = [(int(coff[i]), int(coff[i + 1])) for i in range(n)]
+    return keep, head, outs, cut
+
+
+def _eval_rows_result(keep, outs, cut, n):
+    res = EvalRowsResult()
+    res.status, res.score, res.n_skipped = outs[0][:n], outs[1][:n], outs[2][:n]
+    res.m2, res.d4 = keep[8][:n], keep[9][:n]
+    res.row_first, res.row_last = [outs[3][a:b].copy() for a, b in cut], [outs[4][a:b].copy() for a, b in cut]
+    res.events = _events_of(outs[5:11], cut)
+    res.fit_sums = outs[11][:n]
+    return res
+
+
+def eventalign_events_host(events, n_samples, seqs, model, m2, d4, sample_off=None, skip_pen=96):
+    """Backend.eventalign_events on the host (rd_eventalign_events_host: the same rules in a plain loop; no GPU, no context)"""
+    L = _lib.load()
+    keep, head, outs, cut = _eval_rows_args(events, n_samples, seqs, model, m2, d4, sample_off, skip_pen)
+    if L.rd_eventalign_events_host(*head, *[_p(b) for b in outs]) != 0:
+        raise RadianHipError(L.rd_last_error().decode())
+    return _eval_rows_result(keep, outs, cut, len(events))
+
+
+def eventalign_events_workspace_bytes(n_rows, n_bases):
+    """device workspace Backend.eventalign_events needs for one read of n_rows events and n_bases bases (rd_eventalign_events_workspace_bytes)"""
+    return int(_lib.load().rd_eventalign_events_workspace_bytes(int(n_rows), int(n_bases)))
+
+
 # rd_sigmap per-query status (include/radian_hip.h RD_SIGMAP_*)
 SIGMAP_OK, SIGMAP_EMPTY, SIGMAP_TOO_LONG, SIGMAP_MAD_ZERO, SIGMAP_NO_TARGET, SIGMAP_TOO_LARGE = 0, 1, 2, 3, 4, 5
 SIGMAP_STATUS_NAMES = ("ok", "empty", "too-long", "mad-zero", "no-target", "too-large")
@@ -1784,6 +1841,21 @@ class Backend:
         return _eval_result(outs, cut, len(raws))
 
     eventalign_host = staticmethod(eventalign_host)
+
+    def eventalign_events(self, events, n_samples, seqs, model, m2, d4, sample_off=None, skip_pen=96, budget_bytes=0, allow_too_large=False):
+        """The Viterbi path of every read's bases through its EVENTS, each weighted by its sample count, with skips of one base
+        (rd_eventalign_events, on the GPU): events -- per read the dict of arrays a SegmentResult holds (start, sum,
+        sumsq, min, max); n_samples -- the length of the window the events cut; seqs, model -- as eventalign; m2 / d4 -- the scale of every
+        read, always given; sample_off -- added to every sample index reported; skip_pen -- -1: no skips, otherwise 0..256 in 1/32 nat.
+        budget_bytes and allow_too_large as eventalign.  -> EvalRowsResult."""
+        keep, head, outs, cut = _eval_rows_args(events, n_samples, seqs, model, m2, d4, sample_off, skip_pen)
+        rc = self._L.rd_eventalign_events(self._h, *head, int(budget_bytes), *[_p(b) for b in outs])
+        if rc != 0 and not (allow_too_large and rc == -4 and (outs[0][:len(events)] == EVAL_TOO_LARGE).any()):
+            self._check(rc)
+        return _eval_rows_result(keep, outs, cut, len(events))
+
+    eventalign_events_host = staticmethod(eventalign_events_host)
+    eventalign_events_workspace_bytes = staticmethod(eventalign_events_workspace_bytes)
 
     # ------------------------------------------------------------------ signal against a panel of targets (DESIGN.md section 25)
     def sigmap(self, raw, targets, model, q_lo, q_hi, sc_lo=None, sc_hi=None, m2=None, d4=None, s_lo=None, s_hi=None, n_best=1,

@@ -1,5 +1,5 @@
 // band_sweep.h -- device only: the row-by-row sweep of a left-to-right dynamic programme that ea_dp_kernel (eventalign.hip), sm_dp_kernel
-// (sigmap.hip) and ca_dp_kernel (ctcalign.hip) share, and its primitives.  DESIGN.md section 16.
+// (sigmap.hip), ca_dp_kernel (ctcalign.hip) and ear_dp_kernel (eventalign.hip, event rows) share, and its primitives.  DESIGN.md section 16.
 //
 // One workgroup of 256 threads sweeps one sequence of n states over the rows t < T.  A thread owns 16 consecutive states in registers, a
 // workgroup pass a BAND of 4096 states; a sequence of more states is swept band after band, the last state of a band at every row going
@@ -41,6 +41,12 @@ constexpr int BS_WAVE_STATES = 64 * BS_K;  // at most this many states: the firs
 // lane l receives v of lane l - 1; lane 0 keeps its own (DPP wave_shr:1, bound_ctrl off)
 __device__ __forceinline__ int32_t lane_shr1(int32_t v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false); }
 __device__ __forceinline__ double lane_shr1(double v) { return __hiloint2double(lane_shr1(__double2hiint(v)), lane_shr1(__double2loint(v))); }
+// a thread's last TWO states, for a DP whose cell also reads two states to the left (ear_dp_kernel, eventalign.hip): b is the last state and
+// a the one before it.  Two DPP moves; xch and the band column then carry 8 bytes a cell
+struct Cell2 {
+    int32_t a, b;
+};
+__device__ __forceinline__ Cell2 lane_shr1(Cell2 v) { return Cell2{lane_shr1(v.a), lane_shr1(v.b)}; }
 
 // the single-wave path's ordering of LDS writes before other lanes' reads: a wavefront-scope fence, then the scheduling barrier
 __device__ __forceinline__ void wave_lds_sync()

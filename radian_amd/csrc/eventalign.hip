@@ -27,6 +27,13 @@
 //   ev_stats_kernel   events.hip's, on the steps while the samples are on the device
 //   ea_sums_kernel    one workgroup per read: N, sum l, sum l^2, sum x, sum x l over its events (int64 adds: any order gives the same)
 // No floating point, no atomics but the select's LDS histogram, no scratch.  A read's result does not depend on its launch's other reads.
+//
+// rd_eventalign_events is the same Viterbi over event rows: a row is one of rd_segment's events, weighted by its
+// sample count, and a third predecessor skips one base.  Per launch: ear_row_kernel (n, mean and zq per event), ear_dp_kernel (a fourth
+// policy of band_sweep.h: the cell that crosses a thread boundary is the thread's last TWO states, Cell2; two bits per back-pointer, a
+// thread's 16 cells = one uint32, a wave's 64 stores = 256 consecutive bytes; band b > 0 starts at row 2048 b), ear_tb_kernel (one wave
+// per read, 64 rows of back-pointer words staged in LDS, a row a step), ear_reduce_kernel (one lane per base over its rows' records) and
+// ea_sums_kernel as it is.
 #include "common.h"
 #include "budget.h"
 #include "eventalign_rules.h"
@@ -63,18 +70,23 @@ struct EaCall {
     int64_t* fit_sums;
 };
 
+int ea_check_model(const char* who, const EaModel& m)
+{
+    RD_REQUIRE(sim_k_ok(m.k), "%s: k = %d, not odd and 1..9", who, m.k);
+    RD_REQUIRE(m.lvl && m.w && m.bias, "%s: null model table", who);
+    const int64_t n_kmers = (int64_t)1 << (2 * m.k);
+    for (int64_t i = 0; i < n_kmers; i++)
+        RD_REQUIRE(ea_entry_ok(m.lvl[i], m.bias[i]), "%s: model entry %lld (lvl %d, bias %d) is outside |lvl| < 2^14, |bias| <= 256", who,
+                   (long long)i, m.lvl[i], m.bias[i]);
+    RD_REQUIRE(ea_entry_ok(m.bg.lvl, m.bg.bias), "%s: the background (lvl %d, bias %d) is outside |lvl| < 2^14, |bias| <= 256", who, m.bg.lvl, m.bg.bias);
+    return RD_OK;
+}
+
 int ea_check_args(const char* who, const EaCall& c, int64_t* n_bases)
 {
     *n_bases = 0;
     RD_REQUIRE(c.n_reads >= 0, "%s: negative n_reads", who);
-    RD_REQUIRE(sim_k_ok(c.m.k), "%s: k = %d, not odd and 1..9", who, c.m.k);
-    RD_REQUIRE(c.m.lvl && c.m.w && c.m.bias, "%s: null model table", who);
-    const int64_t n_kmers = (int64_t)1 << (2 * c.m.k);
-    for (int64_t i = 0; i < n_kmers; i++)
-        RD_REQUIRE(ea_entry_ok(c.m.lvl[i], c.m.bias[i]), "%s: model entry %lld (lvl %d, bias %d) is outside |lvl| < 2^14, |bias| <= 256", who,
-                   (long long)i, c.m.lvl[i], c.m.bias[i]);
-    RD_REQUIRE(ea_entry_ok(c.m.bg.lvl, c.m.bg.bias), "%s: the background (lvl %d, bias %d) is outside |lvl| < 2^14, |bias| <= 256", who, c.m.bg.lvl,
-               c.m.bg.bias);
+    if (int rc = ea_check_model(who, c.m)) return rc;
     if (c.n_reads == 0) return RD_OK;
     RD_REQUIRE(c.raw && c.read_off && c.t_lo && c.t_hi && c.ref_off && c.ref_len && c.m2_in && c.d4_in, "%s: null argument", who);
     RD_REQUIRE(c.status && c.score && c.m2 && c.d4 && c.fit_sums, "%s: null output", who);
@@ -218,6 +230,199 @@ extern "C" int rd_eventalign_host(const int16_t* raw, const int64_t* read_off, i
     return RD_OK;
 }
 
+// ------------------------------------------------------------------------------------------------------------------ event rows
+// rd_eventalign_events (include/radian_hip.h): the same Viterbi, but a row is one of the detector's events (rd_segment's
+// records as they are; no raw sample is read), weighted by its sample count, and a third predecessor skips one base:
+//   n_e = start[e+1] - start[e] (the window's T closes the last), x_e = floor((2 sum_e + n_e) / (2 n_e)), zq_e = ea_quant(x_e, m2, d4)
+//   c(e, s) = n_e * ea_cost(zq_e, s);  V[e][s] = c(e, s) + ear_best(V[e-1][s], V[e-1][s-1], V[e-1][s-2] + skip_pen): two bits per cell
+namespace {
+
+struct EarCall {
+    int n_reads;
+    const int64_t *n_samples, *sample_off, *ev_off;
+    const int32_t* n_events;
+    const int32_t* in_start;
+    const int64_t *in_sum, *in_sumsq;
+    const int16_t *in_min, *in_max;
+    const uint8_t* codes;
+    const int64_t* ref_off;
+    const int32_t *ref_len, *m2_in, *d4_in;
+    EaModel m;
+    int skip_pen;
+    int32_t* status;
+    int64_t* score;
+    int32_t *n_skipped, *row_first, *row_last, *ev_start, *ev_end;
+    int64_t *ev_sum, *ev_sumsq;
+    int16_t *ev_min, *ev_max;
+    int64_t* fit_sums;
+};
+
+int ear_check_args(const char* who, const EarCall& c, int64_t* n_bases)
+{
+    *n_bases = 0;
+    RD_REQUIRE(c.n_reads >= 0, "%s: negative n_reads", who);
+    if (int rc = ea_check_model(who, c.m)) return rc;
+    RD_REQUIRE(ear_pen_ok(c.skip_pen), "%s: skip_pen = %d, not -1 (no skips) or 0..256", who, c.skip_pen);
+    if (c.n_reads == 0) return RD_OK;
+    RD_REQUIRE(c.n_samples && c.sample_off && c.ev_off && c.n_events && c.ref_off && c.ref_len && c.m2_in && c.d4_in, "%s: null argument", who);
+    RD_REQUIRE(c.status && c.score && c.n_skipped && c.fit_sums, "%s: null output", who);
+    int64_t end = 0;
+    for (int r = 0; r < c.n_reads; r++) {
+        const int64_t T = c.n_samples[r], E = c.n_events[r];
+        RD_REQUIRE(T >= 0 && c.sample_off[r] >= 0 && T <= INT32_MAX && c.sample_off[r] <= INT32_MAX - T,
+                   "%s: read %d: %lld samples from %lld on do not fit 0 .. 2^31 - 1", who, r, (long long)T, (long long)c.sample_off[r]);
+        RD_REQUIRE(E >= 0 && c.ev_off[r] >= 0, "%s: read %d: negative event count or offset", who, r);
+        RD_REQUIRE(c.ref_len[r] >= 0 && c.ref_len[r] < (1 << 29), "%s: read %d has %d bases", who, r, c.ref_len[r]);
+        RD_REQUIRE(c.ref_off[r] >= end, "%s: base offsets must be non-decreasing and the reads' bases must not overlap (read %d)", who, r);
+        RD_REQUIRE(ea_scale_ok(c.m2_in[r], c.d4_in[r]), "%s: read %d: the scale (m2 %d, d4 %d) is outside |m2| <= 2^17, 0 <= d4 <= 2^20", who, r,
+                   c.m2_in[r], c.d4_in[r]);
+        end = c.ref_off[r] + c.ref_len[r];
+        if (E == 0) continue;
+        RD_REQUIRE(c.in_start && c.in_sum && c.in_sumsq && c.in_min && c.in_max, "%s: null event array", who);
+        const int32_t* s = c.in_start + c.ev_off[r];
+        RD_REQUIRE(s[0] == 0, "%s: read %d: event 0 starts at sample %d, not 0", who, r, s[0]);
+        for (int64_t e = 0; e < E; e++) {
+            RD_REQUIRE(s[e] < T && (e == 0 || s[e] > s[e - 1]), "%s: read %d: event %lld starts at sample %d: not after the event before it, or not inside the %lld samples",
+                       who, r, (long long)e, s[e], (long long)T);
+            const int64_t n = (e + 1 < E ? (int64_t)s[e + 1] : T) - s[e], sum = c.in_sum[c.ev_off[r] + e];   // (n <= 0 is refused at e + 1)
+            if (n <= 0) continue;
+            RD_REQUIRE(sum >= -32768 * n && sum <= 32767 * n && ear_mean(sum, n) <= 32767, "%s: read %d: the mean of event %lld (sum %lld over %lld samples) does not fit int16",
+                       who, r, (long long)e, (long long)sum, (long long)n);
+        }
+    }
+    *n_bases = end;
+    if (end) {
+        RD_REQUIRE(c.codes && c.row_first && c.row_last && c.ev_start && c.ev_end && c.ev_sum && c.ev_sumsq && c.ev_min && c.ev_max,
+                   "%s: null code or per-base buffer", who);
+        for (int r = 0; r < c.n_reads; r++)
+            for (int b = 0; b < c.ref_len[r]; b++)
+                RD_REQUIRE(c.codes[c.ref_off[r] + b] < 4, "%s: base %d of read %d is %d, not in 0..3", who, b, r, c.codes[c.ref_off[r] + b]);
+    }
+    return RD_OK;
+}
+
+void ear_blank(const EarCall& c, int r, int status)
+{
+    c.status[r] = status;
+    c.score[r] = 0;
+    c.n_skipped[r] = 0;
+    for (int i = 0; i < 5; i++) c.fit_sums[5 * (int64_t)r + i] = 0;
+    const int64_t o = c.ref_off[r];
+    for (int b = 0; b < c.ref_len[r]; b++) {
+        c.row_first[o + b] = c.row_last[o + b] = c.ev_start[o + b] = c.ev_end[o + b] = -1;
+        c.ev_sum[o + b] = c.ev_sumsq[o + b] = 0;
+        c.ev_min[o + b] = c.ev_max[o + b] = 0;
+    }
+}
+
+size_t ear_row_bytes(int64_t E) { return align_up((size_t)E * 8, 256); }
+size_t ear_bp_bytes(int64_t E, int64_t L) { return align_up((size_t)E * (size_t)((L + 2 + 15) / 16) * 4, 256); }
+size_t ear_col_bytes(int64_t E, int64_t L) { return L + 2 > 4096 ? align_up((size_t)E * 16, 256) : 0; }
+size_t ear_read_bytes(int64_t E, int64_t L) { return ear_row_bytes(E) + ear_bp_bytes(E, L) + ear_col_bytes(E, L); }
+
+}  // namespace
+
+extern "C" int64_t rd_eventalign_events_workspace_bytes(int64_t n_rows, int64_t n_bases)
+{
+    if (n_rows < 0 || n_bases < 0) return -1;
+    return (int64_t)ear_read_bytes(n_rows, n_bases);
+}
+
+extern "C" int rd_eventalign_events_host(int n_reads, const int64_t* n_samples, const int64_t* sample_off, const int64_t* ev_off, const int32_t* n_events,
+                                         const int32_t* in_start, const int64_t* in_sum, const int64_t* in_sumsq, const int16_t* in_min,
+                                         const int16_t* in_max, const uint8_t* codes, const int64_t* ref_off, const int32_t* ref_len,
+                                         const int32_t* m2_in, const int32_t* d4_in, int k, const int32_t* lvl, const uint32_t* w, const int32_t* bias,
+                                         int32_t lvl_bg, uint32_t w_bg, int32_t bias_bg, int skip_pen, int32_t* status, int64_t* score,
+                                         int32_t* n_skipped, int32_t* row_first, int32_t* row_last, int32_t* ev_start, int32_t* ev_end, int64_t* ev_sum,
+                                         int64_t* ev_sumsq, int16_t* ev_min, int16_t* ev_max, int64_t* fit_sums)
+{
+    const EarCall c{n_reads, n_samples, sample_off, ev_off, n_events, in_start, in_sum, in_sumsq, in_min, in_max, codes, ref_off, ref_len, m2_in, d4_in,
+                    EaModel{k, lvl, w, bias, EaState{lvl_bg, w_bg, bias_bg}}, skip_pen, status, score, n_skipped, row_first, row_last, ev_start, ev_end,
+                    ev_sum, ev_sumsq, ev_min, ev_max, fit_sums};
+    int64_t n_bases = 0;
+    const int rc = ear_check_args("rd_eventalign_events_host", c, &n_bases);
+    if (rc || n_reads == 0) return rc;
+    const bool skips = skip_pen >= 0;
+    std::vector<int32_t> zq, nn, V;
+    std::vector<EaState> st;
+    std::vector<uint32_t> bp;
+    for (int r = 0; r < n_reads; r++) {
+        const int64_t T = n_samples[r], E = n_events[r], L = ref_len[r], S = L + 2, o = ref_off[r], eo = ev_off[r], wpr = (S + 15) / 16;
+        const int stat = ear_status(T, E, L, d4_in[r], skip_pen);
+        ear_blank(c, r, stat);
+        if (stat != EA_OK) continue;
+        const int32_t off = (int32_t)sample_off[r];
+        const auto row_end = [&](int64_t e) { return e + 1 < E ? in_start[eo + e + 1] : (int32_t)T; };   // the sample behind row e
+        zq.resize(E);
+        nn.resize(E);
+        for (int64_t e = 0; e < E; e++) {
+            nn[e] = row_end(e) - in_start[eo + e];
+            zq[e] = ea_quant((int32_t)ear_mean(in_sum[eo + e], nn[e]), m2_in[r], d4_in[r]);
+        }
+        st.resize(S);
+        for (int64_t s = 0; s < S; s++) st[s] = ea_state((int32_t)s, (int32_t)L, codes + o, k, lvl, w, bias, c.m.bg);
+        V.assign(S, EA_INF);
+        bp.assign((size_t)(E * wpr), 0);
+        V[0] = ear_cost(zq[0], nn[0], st[0].lvl, st[0].w, st[0].bias);
+        V[1] = ear_cost(zq[0], nn[0], st[1].lvl, st[1].w, st[1].bias);
+        for (int64_t e = 1; e < E; e++) {
+            const int64_t reach = skips ? 2 * e + 1 : e + 1, top = reach < S - 1 ? reach : S - 1;   // the cells above stay unreachable
+            for (int64_t s = top; s >= 0; s--) {
+                int code;
+                const int32_t best = ear_best(V[s], s >= 1 ? V[s - 1] : EA_INF, (s >= 2 ? V[s - 2] : EA_INF) + (skips ? skip_pen : 0), skips, &code);
+                bp[(size_t)(e * wpr + (s >> 4))] |= (uint32_t)code << (2 * (s & 15));
+                V[s] = ear_cost(zq[e], nn[e], st[s].lvl, st[s].w, st[s].bias) + best;
+            }
+        }
+        int64_t s = ea_ends_in_trail(V[L + 1], V[L]) ? L + 1 : L;
+        score[r] = V[s];
+        // the walk: row_first of a skipped base holds -2 - (the row at which the path jumped over it) until the reduce below
+        if (s >= 1 && s <= L) row_last[o + s - 1] = (int32_t)(E - 1);
+        for (int64_t e = E - 1; e > 0 && s > 0; e--) {
+            const int code = (int)((bp[(size_t)(e * wpr + (s >> 4))] >> (2 * (s & 15))) & 3);
+            if (code == EAR_STAY) continue;
+            if (s <= L) row_first[o + s - 1] = (int32_t)e;
+            if (code == EAR_SKIP) {
+                row_first[o + s - 2] = (int32_t)(-2 - e);
+                n_skipped[r]++;
+            }
+            if (s - code >= 1) row_last[o + s - code - 1] = (int32_t)(e - 1);
+            s -= code;
+        }
+        if (s == 1 && L >= 1) row_first[o] = 0;
+        int64_t* fs = fit_sums + 5 * (int64_t)r;
+        for (int64_t b = 0; b < L; b++) {
+            const int32_t f = row_first[o + b], l = row_last[o + b];
+            if (f <= -2) {
+                ev_start[o + b] = ev_end[o + b] = in_start[eo + (-2 - f)] + off;
+                row_first[o + b] = row_last[o + b] = -1;
+                continue;
+            }
+            int64_t sum = 0, sq = 0;
+            int16_t mn = in_min[eo + f], mx = in_max[eo + f];
+            for (int64_t e = f; e <= l; e++) {
+                sum += in_sum[eo + e];
+                sq += in_sumsq[eo + e];
+                mn = std::min(mn, in_min[eo + e]);
+                mx = std::max(mx, in_max[eo + e]);
+            }
+            ev_start[o + b] = in_start[eo + f] + off;
+            ev_end[o + b] = row_end(l) + off;
+            ev_sum[o + b] = sum;
+            ev_sumsq[o + b] = sq;
+            ev_min[o + b] = mn;
+            ev_max[o + b] = mx;
+            const int64_t lv = lvl[sim_kmer(codes + o, (int32_t)L, (int32_t)b, k)], n = ev_end[o + b] - ev_start[o + b];
+            fs[0] += n;
+            fs[1] += n * lv;
+            fs[2] += n * lv * lv;
+            fs[3] += sum;
+            fs[4] += sum * lv;
+        }
+    }
+    return RD_OK;
+}
+
 #if defined(__HIPCC__)
 // ------------------------------------------------------------------------------------------------------------------ device half
 #include "band_sweep.h"
@@ -232,7 +437,7 @@ struct EaSeq {
     int64_t codes;   // the read's base 0 in the code buffer
     int64_t lab;     // its base 0 in the launch's per-base arrays
     int64_t zq, bp, col;   // byte offsets into the workspace
-    int32_t T, L, m2, d4, t_lo, pad_;
+    int32_t T, L, m2, d4, t_lo, n_win;   // (n_win: the samples of the window when the rows are events, T of them; 0 otherwise)
 };
 struct EaOut {
     int64_t score, sums[5];
@@ -438,6 +643,269 @@ void ea_io_layout(Carve& c, int nb, int64_t nlab, EaIo* io)
     io->mx = c.take<int16_t>(n, 16);
 }
 
+// ---- event rows (rd_eventalign_events).  An EaSeq of these kernels: raw0 = the read's event 0 in the launch's event arrays, T = its rows
+// (events), n_win = its window's samples, t_lo = what is added to a sample index; zq = the rows' block, E zq then E sample counts.
+struct EarEvents {
+    int32_t* start;
+    int64_t *sum, *sumsq;
+    int16_t *mn, *mx;
+};
+void ear_events_layout(Carve& c, int64_t n_ev, EarEvents* ev)
+{
+    const size_t n = (size_t)n_ev;
+    ev->start = c.take<int32_t>(n);
+    ev->sum = c.take<int64_t>(n);
+    ev->sumsq = c.take<int64_t>(n);
+    ev->mn = c.take<int16_t>(n);
+    ev->mx = c.take<int16_t>(n);
+}
+
+// grid (ceil(max E / 256), reads): n_e, x_e and zq_e of every event
+__global__ __launch_bounds__(256) void ear_row_kernel(const EaSeq* __restrict__ seqs, const int32_t* __restrict__ ev_start, const int64_t* __restrict__ ev_sum,
+                                                      uint8_t* __restrict__ ws, int32_t* __restrict__ fin)
+{
+    const EaSeq q = seqs[blockIdx.y];
+    if (blockIdx.x == 0 && threadIdx.x < 2) fin[2 * (int64_t)blockIdx.y + threadIdx.x] = EA_INF;
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= q.T) return;
+    const int32_t s = ev_start[q.raw0 + e], n = (e + 1 < q.T ? ev_start[q.raw0 + e + 1] : q.n_win) - s;
+    int32_t* rows = (int32_t*)(ws + q.zq);
+    rows[e] = ea_quant((int32_t)ear_mean(ev_sum[q.raw0 + e], n), q.m2, q.d4);
+    rows[q.T + e] = n;
+}
+
+// band_sweep.h's policy of eventalign on event rows: the cell that crosses a thread boundary is the thread's last TWO states
+template <bool SKIPS>
+struct EarSweep {
+    using Cell = Cell2;
+    using Elem = int32_t;
+    static constexpr bool AHEAD_CLAMPED = true;
+    static constexpr int TR = 128, SLOTS = 4;   // a tile: [0: zq, 1: n, 2 and 3: the band's incoming pair V[e-1][s_lo-2], V[e-1][s_lo-1]][row]
+    struct Row {
+        int32_t z, n;
+        Cell2 c;
+    };
+    // the read
+    const int32_t* __restrict__ zq;
+    const int32_t* __restrict__ nn;
+    uint32_t* __restrict__ bp;
+    const uint8_t* cod;
+    const int32_t* __restrict__ lvl_t;
+    const uint32_t* __restrict__ w_t;
+    const int32_t* __restrict__ bias_t;
+    EaState bg;
+    int32_t* fin;   // the read's two end values
+    int k, L, S, wpr, pen;   // wpr: 32-bit words of a back-pointer row
+    // the thread's states of the band
+    int s0;
+    int32_t lv[BS_K], bi[BS_K], v[BS_K];
+    uint32_t wt[BS_K];
+
+    // Row e reaches the states up to 2 e + 1 (two per row from state 1 at row 0), so the band's first state 4096 b is first reachable at
+    // row 2048 b, from states 4096 b - 1 and 4096 b - 2 of row 2048 b - 1: that is the first row whose incoming column is read, and band
+    // b - 1, which starts at 2048 (b - 1), has written it.  At row 2048 b - 1 every state of the band is still unreachable: begin_band's
+    // 2^30.  Without skips the same row is early (state 4096 b is reached at row 4096 b - 1), which costs rows of unreachable cells, no more.
+    static __device__ __forceinline__ int first_row(int b) { return b * (BS_BAND / 2); }
+    static __device__ __forceinline__ Cell none() { return Cell2{EA_INF, EA_INF}; }
+    static __device__ __forceinline__ Cell incoming(const Row& in) { return in.c; }
+    __device__ __forceinline__ Cell last() const { return Cell2{v[BS_K - 2], v[BS_K - 1]}; }
+
+    __device__ __forceinline__ void begin_band(int b)
+    {
+        s0 = b * BS_BAND + (int)threadIdx.x * BS_K;
+#pragma unroll
+        for (int j = 0; j < BS_K; j++) {
+            EaState st{0, 0, 0};   // a state past the read: it costs nothing, its value never rises above its neighbours'
+            if (s0 + j < S) st = ea_state(s0 + j, L, cod, k, lvl_t, w_t, bias_t, bg);
+            lv[j] = st.lvl;
+            wt[j] = st.w;
+            bi[j] = st.bias;
+            v[j] = EA_INF;
+        }
+        // row -1 of band 0: V = 0 in state 0 and unreachable elsewhere makes row 0 the contract's start, state 1 by the advance.  A skip
+        // from that 0 would reach state 2 and beat its 2^30, so row 0 takes no skip edge (row())
+        if (s0 == 0) v[0] = 0;
+    }
+    __device__ __forceinline__ Elem tile_elem(int e, int tbase, int T, int b, const Cell* cin) const
+    {
+        const int which = e / TR, t = tbase + (e % TR);
+        Elem x = EA_INF;
+        if (t < T) {
+            if (which == 0) x = zq[t];
+            else if (which == 1) x = nn[t];
+            else if (b > 0) x = which == 2 ? cin[t - 1].a : cin[t - 1].b;   // t >= first_row(b) >= 1
+        }
+        return x;
+    }
+    __device__ __forceinline__ Row read_row(const Elem* tile, int r) const { return Row{tile[r], tile[TR + r], Cell2{tile[2 * TR + r], tile[3 * TR + r]}}; }
+    __device__ __forceinline__ void row(int t, const Row& in, Cell left)
+    {
+        uint32_t bits = 0;
+        const bool skips = SKIPS && t > 0;   // (wave-uniform)
+#pragma unroll
+        for (int j = BS_K - 1; j >= 0; j--) {
+            const int32_t adv = j >= 1 ? v[j - 1] : left.b;
+            const int32_t two = j >= 2 ? v[j - 2] : j == 1 ? left.b : left.a;
+            int code;
+            const int32_t best = ear_best(v[j], adv, two + pen, skips, &code);
+            v[j] = ear_cost(in.z, in.n, lv[j], wt[j], bi[j]) + best;
+            bits |= (uint32_t)code << (2 * j);
+        }
+        if (s0 < S) bp[(size_t)t * wpr + (s0 >> 4)] = bits;
+    }
+    // the two states the path may end in
+    __device__ __forceinline__ void end_band() const
+    {
+#pragma unroll
+        for (int j = 0; j < BS_K; j++) {
+            if (s0 + j == L + 1) fin[0] = v[j];
+            if (s0 + j == L) fin[1] = v[j];
+        }
+    }
+};
+
+template <bool SKIPS>
+__global__ __launch_bounds__(BS_NT) void ear_dp_kernel(const EaSeq* __restrict__ seqs, const uint8_t* __restrict__ codes, const int32_t* __restrict__ lvl_t,
+                                                       const uint32_t* __restrict__ w_t, const int32_t* __restrict__ bias_t, EaState bg, int k, int pen,
+                                                       uint8_t* __restrict__ ws, int32_t* __restrict__ fin)
+{
+    const EaSeq q = seqs[blockIdx.x];
+    const int S = q.L + 2;
+    const int32_t* rows = (const int32_t*)(ws + q.zq);
+    EarSweep<SKIPS> p{rows, rows + q.T, (uint32_t*)(ws + q.bp), codes + q.codes, lvl_t, w_t, bias_t, bg, fin + 2 * (int64_t)blockIdx.x,
+                      k, q.L, S, (S + 15) / 16, pen};
+    band_sweep(p, S, q.T, (Cell2*)(ws + q.col));
+}
+
+// One wave per read: end state, score, then the walk.  With 1.7 rows per base nearly every row is a transition, so ea_tb_kernel's ballot
+// (which jumps over the rows a state dwells in) has little to jump over; here the wave stages 64 rows of the words the path can be in --
+// it moves down at most two states a row, 126 states over the block, 9 words of 16 -- into LDS with independent loads, and the walk reads
+// LDS, a row a step, the same in every lane.  first[] of a skipped base holds -2 - (the row at which the path jumped over it) for
+// ear_reduce_kernel.
+constexpr int EAR_TB_ROWS = 64, EAR_TB_WORDS = 9;
+__global__ __launch_bounds__(64) void ear_tb_kernel(const EaSeq* __restrict__ seqs, const uint8_t* __restrict__ ws, const int32_t* __restrict__ fin,
+                                                    EaOut* __restrict__ out, int32_t* __restrict__ nskip, int32_t* __restrict__ first,
+                                                    int32_t* __restrict__ last)
+{
+    __shared__ uint32_t blk[EAR_TB_ROWS][EAR_TB_WORDS];
+    const int p = blockIdx.x, lane = threadIdx.x;
+    const EaSeq q = seqs[p];
+    const int L = q.L;
+    const int32_t v_trail = fin[2 * (int64_t)p], v_last = fin[2 * (int64_t)p + 1];
+    // s, e and the walk below are the same in every lane; read through the first lane they are the compiler's scalars, and the walk branches
+    // on scalar compares instead of masking lanes
+    int s = __builtin_amdgcn_readfirstlane(ea_ends_in_trail(v_trail, v_last) ? L + 1 : L);
+    const uint32_t* __restrict__ bp = (const uint32_t*)(ws + q.bp);
+    const int64_t wpr = (L + 2 + 15) / 16;
+    int32_t* fs = first + q.lab;
+    int32_t* ls = last + q.lab;
+    int e = q.T - 1, skipped = 0;
+    if (lane == 0) {
+        out[p].score = s == L + 1 ? v_trail : v_last;
+        if (s >= 1 && s <= L) ls[s - 1] = e;
+    }
+    while (e > 0 && s > 0) {
+        const int n = e < EAR_TB_ROWS ? e : EAR_TB_ROWS;   // rows e .. e - n + 1
+        const int w_hi = s >> 4, w_lo = w_hi >= EAR_TB_WORDS - 1 ? w_hi - (EAR_TB_WORDS - 1) : 0;
+        // a lane's nine words of the block: every load is issued before the first is stored (a loop that loads and stores a word a turn
+        // waits for each load in turn: nine latencies a block instead of one)
+        uint32_t word[EAR_TB_WORDS];
+#pragma unroll
+        for (int j = 0; j < EAR_TB_WORDS; j++) {
+            const int i = lane + 64 * j, r = i / EAR_TB_WORDS, w = w_lo + i % EAR_TB_WORDS;
+            word[j] = r < n && w <= w_hi ? bp[(int64_t)(e - r) * wpr + w] : 0u;
+        }
+#pragma unroll
+        for (int j = 0; j < EAR_TB_WORDS; j++) (&blk[0][0])[lane + 64 * j] = word[j];
+        __syncthreads();
+        int r = 0;
+        for (; r < n && s > 0; r++) {
+            int code = __builtin_amdgcn_readfirstlane((int)((blk[r][(s >> 4) - w_lo] >> (2 * (s & 15))) & 3u));
+            if (code == EAR_STAY) continue;
+            if (code > s) code = s;   // (no reachable cell has such a code: the state never leaves the read)
+            const int row = e - r;
+            if (lane == 0) {
+                if (s <= L) fs[s - 1] = row;
+                if (code == EAR_SKIP) fs[s - 2] = -2 - row;
+                if (s - code >= 1) ls[s - code - 1] = row - 1;
+            }
+            skipped += code == EAR_SKIP;
+            s -= code;
+        }
+        e -= r;
+        __syncthreads();
+    }
+    if (lane == 0) {
+        if (s == 1 && L >= 1) fs[0] = 0;
+        nskip[p] = skipped;
+    }
+}
+
+// grid (ceil(max L / 256), reads), one lane per base: the records of the base's rows (1.7 on average) summed.  A base the path stalls in for
+// thousands of rows is one lane reading 28 bytes a row while its wave waits; at 2^19 rows that is tens of milliseconds, and a detector
+// that cuts an event per 17 samples leaves no such base in practice.
+__global__ __launch_bounds__(256) void ear_reduce_kernel(const EaSeq* __restrict__ seqs, const int32_t* __restrict__ in_start, const int64_t* __restrict__ in_sum,
+                                                         const int64_t* __restrict__ in_sumsq, const int16_t* __restrict__ in_min,
+                                                         const int16_t* __restrict__ in_max, int32_t* __restrict__ first, int32_t* __restrict__ last,
+                                                         int32_t* __restrict__ start, int32_t* __restrict__ end, int64_t* __restrict__ sum,
+                                                         int64_t* __restrict__ sumsq, int16_t* __restrict__ mn, int16_t* __restrict__ mx)
+{
+    const EaSeq q = seqs[blockIdx.y];
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= q.L) return;
+    const int64_t o = q.lab + b;
+    int32_t f = first[o], l = last[o];
+    if (f <= -2) {
+        start[o] = end[o] = in_start[q.raw0 + min(-2 - f, q.T - 1)] + q.t_lo;
+        first[o] = last[o] = -1;
+        sum[o] = sumsq[o] = 0;
+        mn[o] = mx[o] = 0;
+        return;
+    }
+    f = min(max(f, 0), q.T - 1);   // (a walked path leaves 0 <= f <= l < T; no index leaves the read's events whatever the words held)
+    l = min(max(l, f), q.T - 1);
+    int64_t a = 0, a2 = 0;
+    int lo = 32767, hi = -32768;
+    for (int e = f; e <= l; e++) {
+        a += in_sum[q.raw0 + e];
+        a2 += in_sumsq[q.raw0 + e];
+        lo = min(lo, (int)in_min[q.raw0 + e]);
+        hi = max(hi, (int)in_max[q.raw0 + e]);
+    }
+    start[o] = in_start[q.raw0 + f] + q.t_lo;
+    end[o] = (l + 1 < q.T ? in_start[q.raw0 + l + 1] : q.n_win) + q.t_lo;
+    sum[o] = a;
+    sumsq[o] = a2;
+    mn[o] = (int16_t)lo;
+    mx[o] = (int16_t)hi;
+}
+
+// a launch's io block (ws_eval), as EaIo with the skip counts
+struct EarIo {
+    EaSeq* seqs;
+    int32_t *fin, *nskip;
+    EaOut* out;
+    int32_t *first, *last, *start, *end;
+    int64_t *sum, *sumsq;
+    int16_t *mn, *mx;
+};
+void ear_io_layout(Carve& c, int nb, int64_t nlab, EarIo* io)
+{
+    const size_t n = (size_t)nlab;
+    io->seqs = c.take<EaSeq>((size_t)nb);
+    io->fin = c.take<int32_t>((size_t)nb * 2);
+    io->nskip = c.take<int32_t>((size_t)nb);
+    io->out = c.take<EaOut>((size_t)nb);
+    io->first = c.take<int32_t>(n, 16);
+    io->last = c.take<int32_t>(n, 16);
+    io->start = c.take<int32_t>(n, 16);
+    io->end = c.take<int32_t>(n, 16);
+    io->sum = c.take<int64_t>(n, 16);
+    io->sumsq = c.take<int64_t>(n, 16);
+    io->mn = c.take<int16_t>(n, 16);
+    io->mx = c.take<int16_t>(n, 16);
+}
+
 }  // namespace
 
 extern "C" int rd_eventalign(rd_ctx* ctx, const int16_t* raw, const int64_t* read_off, int n_reads, const int64_t* t_lo, const int64_t* t_hi,
@@ -512,7 +980,7 @@ extern "C" int rd_eventalign(rd_ctx* ctx, const int16_t* raw, const int64_t* rea
             d.m2 = m2[r];
             d.d4 = d4[r];
             d.t_lo = (int32_t)t_lo[r];
-            d.pad_ = 0;
+            d.n_win = 0;
             d.zq = (int64_t)ws.mark();
             ws.take<char>(ea_zq_bytes(d.T), 0, 1);
             d.bp = (int64_t)ws.mark();
@@ -575,6 +1043,156 @@ extern "C" int rd_eventalign(rd_ctx* ctx, const int16_t* raw, const int64_t* rea
         rd_set_error("rd_eventalign: read %d (%lld samples x %d bases) needs %lld bytes of workspace, over the budget of %lld; %d read(s) not "
                      "aligned (status RD_EVAL_TOO_LARGE), the others were", r, (long long)(t_hi[r] - t_lo[r]), ref_len[r],
                      (long long)ea_read_bytes(t_hi[r] - t_lo[r], ref_len[r]), (long long)budget_bytes, too_large);
+        return RD_ERR_NOMEM;
+    }
+    return RD_OK;
+}
+
+extern "C" int rd_eventalign_events(rd_ctx* ctx, int n_reads, const int64_t* n_samples, const int64_t* sample_off, const int64_t* ev_off,
+                                    const int32_t* n_events, const int32_t* in_start, const int64_t* in_sum, const int64_t* in_sumsq,
+                                    const int16_t* in_min, const int16_t* in_max, const uint8_t* codes, const int64_t* ref_off, const int32_t* ref_len,
+                                    const int32_t* m2_in, const int32_t* d4_in, int k, const int32_t* lvl, const uint32_t* w, const int32_t* bias,
+                                    int32_t lvl_bg, uint32_t w_bg, int32_t bias_bg, int skip_pen, int64_t budget_bytes, int32_t* status, int64_t* score,
+                                    int32_t* n_skipped, int32_t* row_first, int32_t* row_last, int32_t* ev_start, int32_t* ev_end, int64_t* ev_sum,
+                                    int64_t* ev_sumsq, int16_t* ev_min, int16_t* ev_max, int64_t* fit_sums)
+{
+    RD_REQUIRE(ctx, "rd_eventalign_events: null context");
+    RD_REQUIRE(budget_bytes >= 0, "rd_eventalign_events: negative budget");
+    const EarCall c{n_reads, n_samples, sample_off, ev_off, n_events, in_start, in_sum, in_sumsq, in_min, in_max, codes, ref_off, ref_len, m2_in, d4_in,
+                    EaModel{k, lvl, w, bias, EaState{lvl_bg, w_bg, bias_bg}}, skip_pen, status, score, n_skipped, row_first, row_last, ev_start, ev_end,
+                    ev_sum, ev_sumsq, ev_min, ev_max, fit_sums};
+    int64_t n_bases = 0;
+    int rc = ear_check_args("rd_eventalign_events", c, &n_bases);
+    if (rc || n_reads == 0) return rc;
+    RD_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    if (ctx->ws_labels.reserve((size_t)n_bases + 16)) return RD_ERR_NOMEM;
+    const uint8_t* d_codes = ctx->ws_labels.as<uint8_t>();
+    if (n_bases) RD_HIP(hipMemcpyAsync(ctx->ws_labels.p, codes, (size_t)n_bases, hipMemcpyHostToDevice, st));
+    KmerTables tab;
+    if ((rc = signal_upload_tables(ctx, st, k, lvl, w, bias, 0, &tab))) return rc;
+    // statuses that need no alignment, then the launches: the other reads in the caller's order, as many as fit the budget; a read that
+    // alone exceeds it is reported, not launched
+    for (int r = 0; r < n_reads; r++) {
+        const int stat = ear_status(n_samples[r], n_events[r], ref_len[r], d4_in[r], skip_pen);
+        ear_blank(c, r, stat == EA_OK ? EA_TOO_LARGE : stat);   // OK: until its launch has run
+    }
+    if ((rc = rd_resolve_budget(&budget_bytes, ctx->ws_align.cap))) return rc;
+    const BudgetPlan plan = rd_plan_budget(n_reads, nullptr, budget_bytes, 0, false,
+                                           [&](int r, int) { return status[r] == EA_TOO_LARGE ? (int64_t)ear_read_bytes(n_events[r], ref_len[r]) : (int64_t)-1; },
+                                           [](int, int, int64_t count, int64_t) { return count >= EA_MAX_LAUNCH; });
+    if (plan.max_bytes && ctx->ws_align.reserve_exact((size_t)plan.max_bytes, "rd_eventalign_events")) return RD_ERR_NOMEM;
+    std::vector<EaSeq> desc;
+    std::vector<EaOut> h_out;
+    std::vector<int32_t> h_i32, h_skip, p_start;
+    std::vector<int64_t> h_i64, p_sum, p_sumsq;
+    std::vector<int16_t> h_i16, p_min, p_max;
+    for (auto [k0, k1] : plan.launches) {
+        const int nb = (int)(k1 - k0);
+        const int32_t* members = plan.run.data() + k0;
+        desc.resize(nb);
+        p_start.clear();
+        p_sum.clear();
+        p_sumsq.clear();
+        p_min.clear();
+        p_max.clear();
+        Carve ws;   // (dry: the descriptors hold offsets into ws_align)
+        int64_t nlab = 0, max_E = 0, max_L = 0;
+        for (int i = 0; i < nb; i++) {
+            const int r = members[i];
+            const int64_t E = n_events[r], eo = ev_off[r];
+            EaSeq& d = desc[i];
+            d.raw0 = (int64_t)p_start.size();   // the launch's events, the members' back to back
+            p_start.insert(p_start.end(), in_start + eo, in_start + eo + E);
+            p_sum.insert(p_sum.end(), in_sum + eo, in_sum + eo + E);
+            p_sumsq.insert(p_sumsq.end(), in_sumsq + eo, in_sumsq + eo + E);
+            p_min.insert(p_min.end(), in_min + eo, in_min + eo + E);
+            p_max.insert(p_max.end(), in_max + eo, in_max + eo + E);
+            d.codes = ref_off[r];
+            d.lab = nlab;
+            d.T = (int32_t)E;
+            d.L = ref_len[r];
+            d.m2 = m2_in[r];
+            d.d4 = d4_in[r];
+            d.t_lo = (int32_t)sample_off[r];
+            d.n_win = (int32_t)n_samples[r];
+            d.zq = (int64_t)ws.mark();
+            ws.take<char>(ear_row_bytes(E), 0, 1);
+            d.bp = (int64_t)ws.mark();
+            ws.take<char>(ear_bp_bytes(E, d.L), 0, 1);
+            d.col = (int64_t)ws.mark();
+            ws.take<char>(ear_col_bytes(E, d.L), 0, 1);
+            nlab += d.L;
+            max_E = std::max<int64_t>(max_E, E);
+            max_L = std::max<int64_t>(max_L, d.L);
+        }
+        if ((rc = rd_carve_check("rd_eventalign_events", ws, ctx->ws_align.cap))) return rc;
+        const int64_t n_ev = (int64_t)p_start.size();
+        EarEvents ev;
+        EarIo io;
+        if (rd_carve(ctx->ws_raw, [&](Carve& cv) { ear_events_layout(cv, n_ev, &ev); })) return RD_ERR_NOMEM;
+        if (rd_carve(ctx->ws_eval, [&](Carve& cv) { ear_io_layout(cv, nb, nlab, &io); })) return RD_ERR_NOMEM;
+        uint8_t* dws = ctx->ws_align.as<uint8_t>();
+        RD_HIP(hipMemcpyAsync(io.seqs, desc.data(), (size_t)nb * sizeof(EaSeq), hipMemcpyHostToDevice, st));
+        RD_HIP(hipMemcpyAsync(ev.start, p_start.data(), (size_t)n_ev * 4, hipMemcpyHostToDevice, st));
+        RD_HIP(hipMemcpyAsync(ev.sum, p_sum.data(), (size_t)n_ev * 8, hipMemcpyHostToDevice, st));
+        RD_HIP(hipMemcpyAsync(ev.sumsq, p_sumsq.data(), (size_t)n_ev * 8, hipMemcpyHostToDevice, st));
+        RD_HIP(hipMemcpyAsync(ev.mn, p_min.data(), (size_t)n_ev * 2, hipMemcpyHostToDevice, st));
+        RD_HIP(hipMemcpyAsync(ev.mx, p_max.data(), (size_t)n_ev * 2, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(ear_row_kernel, dim3((unsigned)((max_E + 255) / 256), nb), dim3(256), 0, st, io.seqs, ev.start, ev.sum, dws, io.fin);
+        RD_HIP(hipGetLastError());
+        if (skip_pen >= 0)
+            hipLaunchKernelGGL(ear_dp_kernel<true>, dim3(nb), dim3(BS_NT), 0, st, io.seqs, d_codes, tab.lvl, tab.w, tab.bias, c.m.bg, k, skip_pen, dws, io.fin);
+        else
+            hipLaunchKernelGGL(ear_dp_kernel<false>, dim3(nb), dim3(BS_NT), 0, st, io.seqs, d_codes, tab.lvl, tab.w, tab.bias, c.m.bg, k, 0, dws, io.fin);
+        RD_HIP(hipGetLastError());
+        hipLaunchKernelGGL(ear_tb_kernel, dim3(nb), dim3(64), 0, st, io.seqs, dws, io.fin, io.out, io.nskip, io.first, io.last);
+        RD_HIP(hipGetLastError());
+        if (max_L) {
+            hipLaunchKernelGGL(ear_reduce_kernel, dim3((unsigned)((max_L + 255) / 256), nb), dim3(256), 0, st, io.seqs, ev.start, ev.sum, ev.sumsq, ev.mn,
+                               ev.mx, io.first, io.last, io.start, io.end, io.sum, io.sumsq, io.mn, io.mx);
+            RD_HIP(hipGetLastError());
+        }
+        hipLaunchKernelGGL(ea_sums_kernel, dim3(nb), dim3(256), 0, st, io.seqs, d_codes, tab.lvl, k, io.start, io.end, io.sum, io.out);
+        RD_HIP(hipGetLastError());
+        h_out.resize(nb);
+        h_skip.resize(nb);
+        const size_t s4 = io.last - io.first, s8 = io.sumsq - io.sum, s2 = io.mx - io.mn;   // the arrays' strides, in elements
+        h_i32.resize(4 * s4);
+        h_i64.resize(2 * s8);
+        h_i16.resize(2 * s2);
+        RD_HIP(hipMemcpyAsync(h_out.data(), io.out, (size_t)nb * sizeof(EaOut), hipMemcpyDeviceToHost, st));
+        RD_HIP(hipMemcpyAsync(h_skip.data(), io.nskip, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+        if (nlab) {
+            RD_HIP(hipMemcpyAsync(h_i32.data(), io.first, 4 * s4 * 4, hipMemcpyDeviceToHost, st));
+            RD_HIP(hipMemcpyAsync(h_i64.data(), io.sum, 2 * s8 * 8, hipMemcpyDeviceToHost, st));
+            RD_HIP(hipMemcpyAsync(h_i16.data(), io.mn, 2 * s2 * 2, hipMemcpyDeviceToHost, st));
+        }
+        RD_HIP(hipStreamSynchronize(st));
+        for (int i = 0; i < nb; i++) {
+            const int r = members[i];
+            const EaSeq& d = desc[i];
+            const size_t L = (size_t)d.L, o = (size_t)ref_off[r], s = (size_t)d.lab;
+            status[r] = EA_OK;
+            score[r] = h_out[i].score;
+            n_skipped[r] = h_skip[i];
+            memcpy(fit_sums + 5 * (int64_t)r, h_out[i].sums, 40);
+            if (!L) continue;
+            memcpy(row_first + o, h_i32.data() + s, L * 4);
+            memcpy(row_last + o, h_i32.data() + s4 + s, L * 4);
+            memcpy(ev_start + o, h_i32.data() + 2 * s4 + s, L * 4);
+            memcpy(ev_end + o, h_i32.data() + 3 * s4 + s, L * 4);
+            memcpy(ev_sum + o, h_i64.data() + s, L * 8);
+            memcpy(ev_sumsq + o, h_i64.data() + s8 + s, L * 8);
+            memcpy(ev_min + o, h_i16.data() + s, L * 2);
+            memcpy(ev_max + o, h_i16.data() + s2 + s, L * 2);
+        }
+    }
+    if (plan.too_large) {
+        const int r = (int)plan.first_too_large;
+        rd_set_error("rd_eventalign_events: read %d (%d events x %d bases) needs %lld bytes of workspace, over the budget of %lld; %d read(s) not "
+                     "aligned (status RD_EVAL_TOO_LARGE), the others were", r, n_events[r], ref_len[r],
+                     (long long)ear_read_bytes(n_events[r], ref_len[r]), (long long)budget_bytes, (int)plan.too_large);
         return RD_ERR_NOMEM;
     }
     return RD_OK;

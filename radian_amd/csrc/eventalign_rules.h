@@ -73,3 +73,50 @@ EA_HD inline bool ea_advance(int32_t stay, int32_t adv) { return adv < stay; }
 
 // the path ends in L + 1, or in L if V[T-1][L+1] is not strictly smaller
 EA_HD inline bool ea_ends_in_trail(int32_t v_trail, int32_t v_last) { return v_trail < v_last; }
+
+// ---- event rows (include/radian_hip.h, rd_eventalign_events): the rows are a detector's events, each weighted by
+// its sample count, and a third predecessor skips one base
+constexpr int32_t EA_SKIP_MAX = 256;      // the largest skip penalty, in 1/32 nat; -1: no skip edge
+constexpr int EAR_STAY = 0, EAR_ADV = 1, EAR_SKIP = 2;   // the two-bit back-pointer codes
+
+EA_HD inline bool ear_pen_ok(int32_t skip_pen) { return skip_pen >= -1 && skip_pen <= EA_SKIP_MAX; }
+
+// the status of a window of T samples cut into E events against L bases, before anything is aligned.  Row e reaches the states up to
+// e + 1 without skips and up to 2 e + 1 with them; the path must reach state L in row E - 1
+EA_HD inline int ear_status(int64_t T, int64_t E, int64_t L, int32_t d4, int32_t skip_pen)
+{
+    if (T <= 0 || E <= 0) return EA_EMPTY;
+    if (T > EA_MAX_T) return EA_TOO_LONG;
+    if (d4 == 0) return EA_MAD_ZERO;
+    return (skip_pen < 0 ? E : 2 * E - 1) < L ? EA_NO_PATH : EA_OK;
+}
+
+// the row of an event of n >= 1 samples that sum to `sum`: its mean, rounded half up
+EA_HD inline int64_t ear_mean(int64_t sum, int64_t n)
+{
+    const int64_t num = 2 * sum + n, den = 2 * n;
+    int64_t q = num / den;
+    if (num % den < 0) q--;   // floor: den > 0
+    return q;
+}
+
+// c(e, s) = n_e * ea_cost: n < 2^23 and |cost| <= 1280, the 24-bit multiply is exact; with n <= T <= 2^19 the product stays below 2^30
+EA_HD inline int32_t ear_cost(int32_t zq, int32_t n, int32_t lvl, uint32_t w, int32_t bias)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __mul24(ea_cost(zq, lvl, w, bias), n);
+#else
+    return ea_cost(zq, lvl, w, bias) * n;
+#endif
+}
+
+// the best of the three predecessors and its code: stay; the advance only if STRICTLY smaller; the skip (skp = V[e-1][s-2] + skip_pen)
+// only if STRICTLY smaller than the best of the other two.  On ties: stay, advance, skip
+EA_HD inline int32_t ear_best(int32_t stay, int32_t adv, int32_t skp, bool skips, int* code)
+{
+    const bool a = ea_advance(stay, adv);
+    const int32_t b2 = a ? adv : stay;
+    const bool k = skips && skp < b2;
+    *code = k ? EAR_SKIP : a ? EAR_ADV : EAR_STAY;
+    return k ? skp : b2;
+}

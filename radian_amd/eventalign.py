@@ -5,6 +5,7 @@ weights take part.  fast5, `map`'s read_ref.tsv and a pore-model table in, one e
     python -m radian_amd.eventalign fast5_dir read_ref.tsv -o out_dir (--kmer-table T.tsv [--fill-missing] | --model-seed S --kmer 5)
            [--bounds PATH] [--start-slack 32] [--rescale-rounds 2] [--bg-sd 1.0]
            [--summary PATH] [--kmer-table-out PATH] [--device N] [--batch-reads R] [--budget-bytes B]
+           [--events [--w1 4 --t1 2.5 --w2 12 --t2 5.0 --var-floor 1] [--skip-penalty 96 | --no-skips]]
 
 NO reference behaviour.  The read's span -- column 3 of read_ref.tsv, reversed into decode order, U = T -- is aligned to the samples by a
 Viterbi pass over the states lead, base 1 .. base L, trail (rd_eventalign; the contract is in include/radian_hip.h):
@@ -31,7 +32,16 @@ A read is `ok`, or is counted and left out: `no-reference`, `has-N`, `signal` (e
 `resquiggle`; `no-path` (fewer samples than bases), `too-long` (more than 2^19 samples in the window), `too-large` (does not fit
 --budget-bytes).  Every file is bit-identical across --batch-reads, --budget-bytes and runs.  One GPU; there is no CPU path.
 
-Out of scope: event detection before the alignment, skips and dwell priors (an HSMM), banding, pooling the rescaling across reads,
+--events [--w1 4 --t1 2.5 --w2 12 --t2 5.0 --var-floor 1] [--skip-penalty 96 | --no-skips]
+                    the rows are EVENTS, not samples (rd_eventalign_events): rd_segment (`segment`'s options) cuts
+                    the window from t_lo on once, with that window as its scale window, as `sigmap --events` does; round 0 runs on that
+                    scale and the refits change the scale alone.  A row is weighted by its event's samples, and the path may jump over
+                    one base at a time for --skip-penalty (1/32 nat; 96 = 3 nats).  A skipped base writes no row and is left out of
+                    --kmer-table-out; --summary gains the columns rows and skipped; the printed summary adds the events per base and the
+                    share of bases skipped.  `no-path` then means fewer than (L + 1) / 2 events (L with --no-skips).  THE STAND-IN IS NO
+                    PORE AND THE DEFAULTS COME FROM SIMULATED READS: no sequencer's read took part.  Without --events nothing changes.
+
+Out of scope: dwell priors (an HSMM), skips of more than one base, banding (from the events or otherwise), pooling the rescaling across reads,
 conversion to pA, adapter and leader models, per-read modification calls against the table, the pipelined route, several GPUs."""
 import argparse
 import math
@@ -51,6 +61,7 @@ from .simulate import read_kmer_table, standin_tables
 
 STATUSES = ("ok", "no-reference", "has-N", "no-path", "too-long", "too-large", "signal")
 SUMMARY_COLUMNS = RESQUIGGLE_SUMMARY + ("score_per_sample", "m2", "d4", "rounds")
+EVENTS_SUMMARY_COLUMNS = ("rows", "skipped")       # --events: the read's events and the bases its path jumped over
 _EVAL_STATUS = {EVAL_EMPTY: "signal", EVAL_MAD_ZERO: "signal", EVAL_NO_PATH: "no-path", EVAL_TOO_LONG: "too-long", EVAL_TOO_LARGE: "too-large"}
 MAD_UNIT = 1.4826 * 256     # model units (MAD / 256) per z
 SD_FLOOR = 8                # the least model sd, in MAD / 256
@@ -146,34 +157,70 @@ def kmer_indices(codes, k):
 
 
 def read_rows(rid, name, span, raw, codes, res, r, model, sd_m):
-    """the event rows of OK read r of an EvalResult -> (rows, levels, dwells) as resquiggle.event_rows gives them"""
+    """the event rows of OK read r of an EvalResult (or, --events, an EvalRowsResult: a skipped base has no samples and writes no row) ->
+    (rows, levels, dwells) as resquiggle.event_rows gives them"""
     ev = res.events
     m2, d4 = int(res.m2[r]), int(res.d4[r])
     start, end, s = ev.start[r], ev.end[r], ev.sum[r]
     idx = kmer_indices(codes, model.k)
     qual = np.zeros(len(codes), dtype=np.int64)
+    skipped = (end == start) if hasattr(res, "n_skipped") else None
     for b in range(len(codes)):
+        if skipped is not None and skipped[b]:
+            continue
         mean = float(int(s[b])) / float(int(end[b]) - int(start[b]))
         qual[b] = base_quality((mean - m2 / 2.0) * 1024.0 / d4, int(model.lvl[idx[b]]), int(sd_m[idx[b]]))
-    return event_rows(rid, name, span, raw, (start, end, s, ev.sumsq[r], ev.min[r], ev.max[r]), qual, scale=(m2 / 2.0, d4 / 4.0))
+    return event_rows(rid, name, span, raw, (start, end, s, ev.sumsq[r], ev.min[r], ev.max[r]), qual, scale=(m2 / 2.0, d4 / 4.0), skipped=skipped)
+
+
+def events_aligner(seg, align, skip_pen):
+    """--events: the be_align of align_rounds over event rows.  seg(windows) -> SegmentResult (segment.window_segmenter) cuts every read's
+    window from t_lo on ONCE, at round 0, which runs on that window's own scale; the refits change the scale alone.  align is
+    Backend.eventalign_events or eventalign_events_host bound to the budget.  A read the detector could not take keeps that status.
+    -> (be_align, cut): cut["ev"] is the batch's SegmentResult once round 0 has run"""
+    from .backend import SEGMENT_TOO_LARGE, SEGMENT_TOO_LONG
+    cut = {}
+
+    def be_align(raws, codes, mdl, t_lo, m2, d4):
+        if "ev" not in cut:
+            cut["ev"] = seg([x[t:] for x, t in zip(raws, t_lo)])
+        ev = cut["ev"]
+        if m2 is None:
+            m2, d4 = ev.m2, ev.d4
+        else:       # a read that is not OK is asked again as it was: on the window's scale
+            m2, d4 = np.where(d4 == 0, ev.m2, m2), np.where(d4 == 0, ev.d4, d4)
+        res = align(ev.events, [len(x) - t for x, t in zip(raws, t_lo)], codes, mdl, m2, d4, sample_off=t_lo, skip_pen=skip_pen)
+        res.status[ev.status == SEGMENT_TOO_LONG] = EVAL_TOO_LONG
+        res.status[ev.status == SEGMENT_TOO_LARGE] = EVAL_TOO_LARGE
+        return res
+
+    return be_align, cut
 
 
 def run(args, be, reads, refs, names, bounds, model, sd_m, open_out):
     """reads: iterable of (file stem, read id, raw int16 samples) in input order; refs / names: {read id: span} / {read id: transcript name};
     bounds: {read id: tail_end} or None.  Returns the counters."""
+    from .segment import params_of, window_segmenter      # (segment imports this module's bounds)
+    events = getattr(args, "events", False)
     st = {"reads": 0, "written": 0, "bases": 0, "unbounded": 0, "dwell": {}, "score_per_sample": [], **{s: 0 for s in STATUSES}}
+    if events:
+        st.update(rows=0, skipped=0, span_bases=0)
+        seg = window_segmenter(be.segment, params_of(args), budget_bytes=args.budget_bytes, allow_too_large=True)
     kt = KmerTable(model.k) if args.kmer_table_out else None
     summ = open(args.summary, "w") if args.summary else None
     if summ:
-        summ.write("\t".join(SUMMARY_COLUMNS) + "\n")
+        summ.write("\t".join(SUMMARY_COLUMNS + (EVENTS_SUMMARY_COLUMNS if events else ())) + "\n")
 
-    def done(rid, status, n_samples, ref_len, extra=("-",) * 9):
+    def done(rid, status, n_samples, ref_len, extra=("-",) * (11 if events else 9)):
         st[status] += 1
         if summ:
             summ.write("\t".join((rid, status, str(n_samples), str(ref_len)) + tuple(extra)) + "\n")
 
     def be_align(raws, codes, mdl, **kw):
         return be.eventalign(raws, codes, mdl, budget_bytes=args.budget_bytes, allow_too_large=True, **kw)
+
+    def be_align_rows(*a, **kw):
+        return be.eventalign_events(*a, budget_bytes=args.budget_bytes, allow_too_large=True, **kw)
 
     try:
         for batch in _batches(reads, args.batch_reads):
@@ -189,6 +236,9 @@ def run(args, be, reads, refs, names, bounds, model, sd_m, open_out):
                     lo, bounded = window_start(rid, len(raw), bounds, args.start_slack)
                     st["unbounded"] += 0 if bounded else 1
                     todo.append((raw, codes, lo))
+            cut = {}
+            if events:      # the batch's events are cut once; only the scale changes between rounds
+                be_align, cut = events_aligner(seg, be_align_rows, args.skip_penalty)
             res = align_rounds(be_align, [t[0] for t in todo], [t[1] for t in todo], model, [t[2] for t in todo], args.rescale_rounds) if todo else None
             r = -1
             for stem, rid, raw, status in verdict:
@@ -215,12 +265,24 @@ def run(args, be, reads, refs, names, bounds, model, sd_m, open_out):
                 st["score_per_sample"].append(sps)
                 if kt:
                     kt.add(span, levels, dwells)
+                if events:
+                    dwells = [d for d, lv in zip(dwells, levels) if lv is not None]
                 spb = f"{score / len(rows):.6f}" if rows else "nan"
                 md = f"{float(np.median(dwells)):.1f}" if dwells else "nan"
-                first = int(res.first_step[r][0]) if rows else -1
-                last = int(res.last_step[r][-1]) if rows else -1
+                more = ()
+                if events:      # the span's first and last sample are those of its first and last base with a row
+                    first = min(int(row[4]) for row in rows) if rows else -1
+                    last = max(int(row[5]) for row in rows) - 1 if rows else -1
+                    n_rows, n_skip = int(cut["ev"].n_events[r]), int(res.n_skipped[r])
+                    st["rows"] += n_rows
+                    st["skipped"] += n_skip
+                    st["span_bases"] += len(codes)
+                    more = (str(n_rows), str(n_skip))
+                else:
+                    first = int(res.first_step[r][0]) if rows else -1
+                    last = int(res.last_step[r][-1]) if rows else -1
                 done(rid, "ok", len(raw), ref_len, (str(score), spb, md, str(first), str(last), f"{sps:.6f}", str(int(res.m2[r])), str(int(res.d4[r])),
-                                                    str(args.rescale_rounds)))
+                                                    str(args.rescale_rounds)) + more)
     finally:
         if summ:
             summ.close()
@@ -236,10 +298,13 @@ def summary(st):
             f"bases: {st['bases']}\n"
             + (f"median dwell: {md:.1f} samples\n" if md is not None else "median dwell: -\n")
             + (f"median score per sample: {float(np.median(sps)):.4f}\n" if sps else "median score per sample: -\n")
+            + ((f"events per base: {st['rows'] / st['span_bases']:.3f}; bases skipped: {100.0 * st['skipped'] / st['span_bases']:.2f} %\n"
+                if st["span_bases"] else "events per base: -; bases skipped: -\n") if "rows" in st else "")
             + "status: " + "; ".join(f"{s}: {st[s]}" for s in STATUSES) + "\n")
 
 
 def build_parser():
+    from .segment import add_detector_arguments
     ap = argparse.ArgumentParser(prog="eventalign", description="Align every read's reference span to its raw signal against a k-mer pore model "
                                  "on one GPU and write the per-base event table.  Without --kmer-table the pore model is a stand-in and NO pore.")
     ap.add_argument("fast5_dir", help="Directory of single/multi fast5 files.")
@@ -258,6 +323,11 @@ def build_parser():
     ap.add_argument("--device", default=0, type=int, help="GPU index")
     ap.add_argument("--batch-reads", default=512, type=int, help="reads per device batch (the output does not depend on it)")
     ap.add_argument("--budget-bytes", default=0, type=int, help="device workspace per alignment launch (0: a quarter of free memory)")
+    ap.add_argument("--events", action="store_true", help="the rows are events (rd_segment), each weighted by its samples, and a base may be "
+                    "skipped (rd_eventalign_events); the stand-in is no pore, and no sequencer's read took part in choosing the defaults")
+    add_detector_arguments(ap)
+    ap.add_argument("--skip-penalty", default=96, type=int, help="--events: the cost of skipping one base, in 1/32 nat (0..256)")
+    ap.add_argument("--no-skips", action="store_true", help="--events: no base is skipped")
     return ap
 
 
@@ -282,6 +352,13 @@ def main(argv=None):
         raise SystemExit("eventalign: --batch-reads at least 1; --budget-bytes and --start-slack at least 0; --rescale-rounds 0..16; --bg-sd 0.01..32")
     if not os.path.isdir(args.fast5_dir):
         raise SystemExit(f"eventalign: {args.fast5_dir}: no such directory")
+    if args.events:
+        from .segment import check_detector_arguments
+        check_detector_arguments(args, "eventalign")
+        if not 0 <= args.skip_penalty <= 256:
+            raise SystemExit("eventalign: --skip-penalty must be 0..256")
+        if args.no_skips:
+            args.skip_penalty = -1
     refs, names = read_ref_tsv(args.read_ref), read_ref_names(args.read_ref)
     bounds = read_bounds(args.bounds) if args.bounds else None
     model, sd_m = build_model(args)

@@ -83,10 +83,11 @@ def event_level(mean, median, mad):
     return (mean - median) / (1.4826 * mad)
 
 
-def event_rows(read_id, ref_name, span, raw, ev, qual, scale=None):
+def event_rows(read_id, ref_name, span, raw, ev, qual, scale=None, skipped=None):
     """the rows of one `ok` read: span as written (5'->3'); ev = (start, end, sum, sumsq, min, max) and qual in decode order (label k is
-    span position L - 1 - k); scale: the (median, MAD) the levels are taken on (default: the read's own).  -> [(columns as strings)], levels,
-    dwells in span order"""
+    span position L - 1 - k); scale: the (median, MAD) the levels are taken on (default: the read's own); skipped (`eventalign --events`):
+    per label, true for a base the path jumped over -- it writes no row, its level is None and its dwell 0.  -> [(columns as strings)],
+    levels, dwells in span order"""
     L = len(span)
     median, mad = scale if scale is not None else read_scale(raw)
     start, end, s, sq, mn, mx = ev
@@ -94,6 +95,10 @@ def event_rows(read_id, ref_name, span, raw, ev, qual, scale=None):
     for p in range(L):
         k = L - 1 - p
         n = int(end[k]) - int(start[k])
+        if skipped is not None and skipped[k]:
+            levels.append(None)
+            dwells.append(0)
+            continue
         mean, stdv = event_moments(n, int(s[k]), int(sq[k]))
         level = event_level(mean, median, mad)
         rows.append((read_id, ref_name, str(p), span[p].upper(), str(int(start[k])), str(int(end[k])), str(n), f"{mean:.4f}", f"{stdv:.4f}",
@@ -115,6 +120,8 @@ class KmerTable:
         k, h = self.k, self.k // 2
         seq = span.upper().replace("U", "T")
         for p in range(h, len(seq) - h):
+            if levels[p] is None:      # a skipped base (eventalign --events)
+                continue
             a = self.acc.setdefault(seq[p - h: p + h + 1], [0, 0.0, 0.0, 0])
             a[0] += 1
             a[1] += levels[p]

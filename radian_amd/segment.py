@@ -53,6 +53,12 @@ def event_ends(start, n_samples):
     return np.concatenate([start[1:], [n_samples]]).astype(np.int64)
 
 
+def window_segmenter(segment, params, **kw):
+    """seg(windows) -> SegmentResult: `segment` (Backend.segment or segment_host) bound to the detector's parameters, with every window as
+    its own scale window -- what `sigmap --events` and `eventalign --events` cut their rows with"""
+    return lambda windows: segment(windows, params, [(0, len(x)) for x in windows], **kw)
+
+
 def read_rows(rid, t_lo, n_window, ev):
     """the rows of one `ok` read whose detection started at sample t_lo"""
     start = ev["start"].astype(np.int64)

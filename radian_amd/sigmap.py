@@ -51,7 +51,7 @@ from .backend import (Backend, SigmapPanel, SEGMENT_OK, SEGMENT_TOO_LARGE, SIGMA
 from .eventalign import model_tables, read_bounds, window_start
 from .fastq import _batches
 from .map import TSV_HEADER, Transcripts
-from .segment import add_detector_arguments, check_detector_arguments, event_ends, event_rows, params_of
+from .segment import add_detector_arguments, check_detector_arguments, event_ends, event_rows, params_of, window_segmenter
 from .simulate import read_kmer_table, standin_tables
 
 STATUSES = ("ok", "no-bound", "signal", "too-large", "unmapped")
@@ -319,10 +319,7 @@ def main(argv=None):
     with Backend(args.device) as be:
         def sig(raw, q_lo, q_hi, **kw):
             return be.sigmap(raw, packed, model, q_lo, q_hi, budget_bytes=args.budget_bytes, allow_too_large=True, **kw)
-        seg = None
-        if args.events:
-            def seg(raws):
-                return be.segment(raws, params_of(args), [(0, len(x)) for x in raws], budget_bytes=args.budget_bytes, allow_too_large=True)
+        seg = window_segmenter(be.segment, params_of(args), budget_bytes=args.budget_bytes, allow_too_large=True) if args.events else None
         st = run(args, sig, reads, panel, bounds, seg)
     sys.stdout.write(summary(panel, st))
     sys.stdout.flush()
