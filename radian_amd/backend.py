@@ -482,15 +482,23 @@ class EvalResult:
         self.first_step, self.last_step, self.events = first_step, last_step, events
 
 
+def _eval_bases(seqs, n, per_read):
+    """the bases side of both eventalign calls -> (codes, ref_off, ref_len, the per-base cut, the outputs: per_read's, first, last, events', fit sums)"""
+    codes, coff = _concat_codes(seqs)
+    tot = int(coff[-1])
+    outs = [*[np.zeros(n + 1, dt) for dt in per_read], np.full(tot + 1, -1, np.int32), np.full(tot + 1, -1, np.int32), *_event_buffers(tot),
+            np.zeros((n + 1, 5), np.int64)]
+    ref_off = np.ascontiguousarray(coff[:-1] if n else np.zeros(1), dtype=np.int64)
+    return codes, ref_off, np.diff(coff).astype(np.int32), [(int(coff[i]), int(coff[i + 1])) for i in range(n)], outs
+
+
 def _eval_args(raws, seqs, model, t_lo, t_hi, m2, d4):
     """-> (the arrays, kept alive by the caller; the arguments up to the budget; the output buffers; the per-base cut)"""
     flat, off = Backend._pack_raw(raws)
     n = len(raws)
     if len(seqs) != n:
         raise ValueError(f"{len(seqs)} sequences for {n} reads")
-    codes, coff = _concat_codes(seqs)
-    ref_len = np.diff(coff).astype(np.int32)
-    ref_off = np.ascontiguousarray(coff[:-1] if n else np.zeros(1), dtype=np.int64)
+    codes, ref_off, ref_len, cut, outs = _eval_bases(seqs, n, (np.int32, np.int64, np.int32, np.int32))
     lens = np.diff(off)
     lo = np.zeros(n, dtype=np.int64) if t_lo is None else np.ascontiguousarray(t_lo, dtype=np.int64).ravel()
     hi = lens.astype(np.int64) if t_hi is None else np.ascontiguousarray(t_hi, dtype=np.int64).ravel()
@@ -499,12 +507,8 @@ def _eval_args(raws, seqs, model, t_lo, t_hi, m2, d4):
     if not (lo.size == hi.size == m2.size == d4.size == n):
         raise ValueError(f"per-read arguments that do not hold one entry for each of {n} reads")
     lo, hi, m2, d4 = (np.concatenate([a, np.zeros(1, a.dtype)]) for a in (lo, hi, m2, d4))   # (a pointer the library can check when n = 0)
-    tot = int(coff[-1])
-    outs = [np.zeros(n + 1, np.int32), np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int32), np.zeros(n + 1, np.int32),
-            np.full(tot + 1, -1, np.int32), np.full(tot + 1, -1, np.int32), *_event_buffers(tot), np.zeros((n + 1, 5), np.int64)]
     keep = (flat, off, codes, ref_off, ref_len, lo, hi, m2, d4, model)
     head = (_p(flat), _p(off), n, _p(lo), _p(hi), _p(codes), _p(ref_off), _p(ref_len), _p(m2), _p(d4), *model.args())
-    cut = [(int(coff[i]), int(coff[i + 1])) for i in range(n)]
     return keep, head, outs, cut
 
 
@@ -540,9 +544,7 @@ def _eval_rows_args(events, n_samples, seqs, model, m2, d4, sample_off, skip_pen
     n = len(events)
     if not (len(seqs) == len(n_samples) == len(m2) == len(d4) == n) or (sample_off is not None and len(sample_off) != n):
         raise ValueError(f"per-read arguments that do not hold one entry for each of {n} reads")
-    codes, coff = _concat_codes(seqs)
-    ref_len = np.diff(coff).astype(np.int32)
-    ref_off = np.ascontiguousarray(coff[:-1] if n else np.zeros(1), dtype=np.int64)
+    codes, ref_off, ref_len, cut, outs = _eval_bases(seqs, n, (np.int32, np.int64, np.int32))
     cnt = np.array([len(e["start"]) for e in events] + [0], dtype=np.int32)
     ev_off = np.zeros(n + 1, dtype=np.int64)
     ev_off[1:] = np.cumsum(cnt[:n])
@@ -551,13 +553,9 @@ def _eval_rows_args(events, n_samples, seqs, model, m2, d4, sample_off, skip_pen
     pad = lambda a, dt: np.concatenate([np.ascontiguousarray(a, dtype=dt).ravel(), np.zeros(1, dt)])   # (a pointer the library can check when n = 0)
     ns, so = pad(n_samples, np.int64), pad(np.zeros(n) if sample_off is None else sample_off, np.int64)
     m2, d4 = pad(m2, np.int32), pad(d4, np.int32)
-    tot = int(coff[-1])
-    outs = [np.zeros(n + 1, np.int32), np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int32), np.full(tot + 1, -1, np.int32),
-            np.full(tot + 1, -1, np.int32), *_event_buffers(tot), np.zeros((n + 1, 5), np.int64)]
     keep = (codes, ref_off, ref_len, cnt, ev_off, ev, ns, so, m2, d4, model)
     head = (n, _p(ns), _p(so), _p(ev_off), _p(cnt), *[_p(a) for a in ev], _p(codes), _p(ref_off), _p(ref_len), _p(m2), _p(d4), *model.args(),
             int(skip_pen))
-    cut = [(int(coff[i]), int(coff[i + 1])) for i in range(n)]
     return keep, head, outs, cut
 
 

@@ -34,6 +34,12 @@
 // thread's 16 cells = one uint32, a wave's 64 stores = 256 consecutive bytes; band b > 0 starts at row 2048 b), ear_tb_kernel (one wave
 // per read, 64 rows of back-pointer words staged in LDS, a row a step), ear_reduce_kernel (one lane per base over its rows' records) and
 // ea_sums_kernel as it is.
+//
+// The two row kinds differ in their DP (one predecessor or two, one back-pointer bit or two) and in their traceback (a ballot walk or an
+// LDS walk); DESIGN.md section 28 says why.  What surrounds the DPs exists once (section 29): EaBases, the bases side of a call with its
+// checks, blank outputs and host fit sums; EaBand, the read fields and thread registers of both sweep policies; EaIo, the launch's io
+// block; and the helpers the two launch loops call to place a read's workspace, fetch the block, scatter a member and report a read
+// over the budget.
 #include "common.h"
 #include "budget.h"
 #include "eventalign_rules.h"
@@ -54,20 +60,26 @@ struct EaModel {
     EaState bg;
 };
 
-struct EaCall {
-    const int16_t* raw;
-    const int64_t *read_off, *t_lo, *t_hi;
-    int n_reads;
+// the bases side of a call, the same for sample rows and event rows: first / last are steps (samples) or rows (events)
+struct EaBases {
     const uint8_t* codes;
     const int64_t* ref_off;
     const int32_t *ref_len, *m2_in, *d4_in;
     EaModel m;
     int32_t* status;
     int64_t* score;
-    int32_t *m2, *d4, *first_step, *last_step, *ev_start, *ev_end;
+    int32_t *first, *last, *ev_start, *ev_end;
     int64_t *ev_sum, *ev_sumsq;
     int16_t *ev_min, *ev_max;
     int64_t* fit_sums;
+};
+
+struct EaCall {
+    const int16_t* raw;
+    const int64_t *read_off, *t_lo, *t_hi;
+    int n_reads;
+    EaBases b;
+    int32_t *m2, *d4;
 };
 
 int ea_check_model(const char* who, const EaModel& m)
@@ -82,57 +94,71 @@ int ea_check_model(const char* who, const EaModel& m)
     return RD_OK;
 }
 
+// read r's bases and scale; *end: where the bases of the reads before it end, then where its own do
+int ea_check_read_bases(const char* who, const EaBases& b, int r, int64_t* end)
+{
+    RD_REQUIRE(b.ref_len[r] >= 0 && b.ref_len[r] < (1 << 29), "%s: read %d has %d bases", who, r, b.ref_len[r]);
+    RD_REQUIRE(b.ref_off[r] >= *end, "%s: base offsets must be non-decreasing and the reads' bases must not overlap (read %d)", who, r);
+    RD_REQUIRE(ea_scale_ok(b.m2_in[r], b.d4_in[r]), "%s: read %d: the scale (m2 %d, d4 %d) is outside |m2| <= 2^17, 0 <= d4 <= 2^20", who, r,
+               b.m2_in[r], b.d4_in[r]);
+    *end = b.ref_off[r] + b.ref_len[r];
+    return RD_OK;
+}
+
+// the per-base buffers and the codes of a call with n_bases bases, after every read has passed
+int ea_check_codes(const char* who, const EaBases& b, int n_reads, int64_t n_bases)
+{
+    if (!n_bases) return RD_OK;
+    RD_REQUIRE(b.codes && b.first && b.last && b.ev_start && b.ev_end && b.ev_sum && b.ev_sumsq && b.ev_min && b.ev_max,
+               "%s: null code or per-base buffer", who);
+    for (int r = 0; r < n_reads; r++)
+        for (int i = 0; i < b.ref_len[r]; i++)
+            RD_REQUIRE(b.codes[b.ref_off[r] + i] < 4, "%s: base %d of read %d is %d, not in 0..3", who, i, r, b.codes[b.ref_off[r] + i]);
+    return RD_OK;
+}
+
 int ea_check_args(const char* who, const EaCall& c, int64_t* n_bases)
 {
     *n_bases = 0;
     RD_REQUIRE(c.n_reads >= 0, "%s: negative n_reads", who);
-    if (int rc = ea_check_model(who, c.m)) return rc;
+    if (int rc = ea_check_model(who, c.b.m)) return rc;
     if (c.n_reads == 0) return RD_OK;
-    RD_REQUIRE(c.raw && c.read_off && c.t_lo && c.t_hi && c.ref_off && c.ref_len && c.m2_in && c.d4_in, "%s: null argument", who);
-    RD_REQUIRE(c.status && c.score && c.m2 && c.d4 && c.fit_sums, "%s: null output", who);
+    RD_REQUIRE(c.raw && c.read_off && c.t_lo && c.t_hi && c.b.ref_off && c.b.ref_len && c.b.m2_in && c.b.d4_in, "%s: null argument", who);
+    RD_REQUIRE(c.b.status && c.b.score && c.m2 && c.d4 && c.b.fit_sums, "%s: null output", who);
     RD_REQUIRE(c.read_off[0] >= 0, "%s: negative read offset", who);
-    int64_t end = 0;
     for (int r = 0; r < c.n_reads; r++) {
         const int64_t n = c.read_off[r + 1] - c.read_off[r];
         RD_REQUIRE(n >= 0, "%s: read offsets must be non-decreasing (read %d)", who, r);
         RD_REQUIRE(n <= INT32_MAX, "%s: read %d has more than 2^31 - 1 samples", who, r);
         RD_REQUIRE(0 <= c.t_lo[r] && c.t_lo[r] <= c.t_hi[r] && c.t_hi[r] <= n, "%s: read %d: the window [%lld, %lld) is outside its %lld samples", who,
                    r, (long long)c.t_lo[r], (long long)c.t_hi[r], (long long)n);
-        RD_REQUIRE(c.ref_len[r] >= 0 && c.ref_len[r] < (1 << 29), "%s: read %d has %d bases", who, r, c.ref_len[r]);
-        RD_REQUIRE(c.ref_off[r] >= end, "%s: base offsets must be non-decreasing and the reads' bases must not overlap (read %d)", who, r);
-        RD_REQUIRE(ea_scale_ok(c.m2_in[r], c.d4_in[r]), "%s: read %d: the scale (m2 %d, d4 %d) is outside |m2| <= 2^17, 0 <= d4 <= 2^20", who, r,
-                   c.m2_in[r], c.d4_in[r]);
-        end = c.ref_off[r] + c.ref_len[r];
+        if (int rc = ea_check_read_bases(who, c.b, r, n_bases)) return rc;
     }
-    *n_bases = end;
-    if (end) {
-        RD_REQUIRE(c.codes && c.first_step && c.last_step && c.ev_start && c.ev_end && c.ev_sum && c.ev_sumsq && c.ev_min && c.ev_max,
-                   "%s: null code or per-base buffer", who);
-        for (int r = 0; r < c.n_reads; r++)
-            for (int b = 0; b < c.ref_len[r]; b++)
-                RD_REQUIRE(c.codes[c.ref_off[r] + b] < 4, "%s: base %d of read %d is %d, not in 0..3", who, b, r, c.codes[c.ref_off[r] + b]);
-    }
-    return RD_OK;
+    return ea_check_codes(who, c.b, c.n_reads, *n_bases);
 }
 
-// the "no path" outputs of read r with this status and scale
+// the "no path" outputs of read r with this status; the caller adds its row kind's own fields
+void ea_blank(const EaBases& b, int r, int status)
+{
+    b.status[r] = status;
+    b.score[r] = 0;
+    for (int i = 0; i < 5; i++) b.fit_sums[5 * (int64_t)r + i] = 0;
+    const int64_t o = b.ref_off[r];
+    for (int i = 0; i < b.ref_len[r]; i++) {
+        b.first[o + i] = b.last[o + i] = b.ev_start[o + i] = b.ev_end[o + i] = -1;
+        b.ev_sum[o + i] = b.ev_sumsq[o + i] = 0;
+        b.ev_min[o + i] = b.ev_max[o + i] = 0;
+    }
+}
 void ea_blank(const EaCall& c, int r, int status, int32_t m2, int32_t d4)
 {
-    c.status[r] = status;
-    c.score[r] = 0;
+    ea_blank(c.b, r, status);
     c.m2[r] = m2;
     c.d4[r] = d4;
-    for (int i = 0; i < 5; i++) c.fit_sums[5 * (int64_t)r + i] = 0;
-    const int64_t o = c.ref_off[r];
-    for (int b = 0; b < c.ref_len[r]; b++) {
-        c.first_step[o + b] = c.last_step[o + b] = c.ev_start[o + b] = c.ev_end[o + b] = -1;
-        c.ev_sum[o + b] = c.ev_sumsq[o + b] = 0;
-        c.ev_min[o + b] = c.ev_max[o + b] = 0;
-    }
 }
 
-// the five fit sums of an OK read from its events
-void ea_host_sums(const EaCall& c, int r)
+// the five fit sums of an OK read from its events (a skipped base has no samples and no sum: it adds nothing)
+void ea_host_sums(const EaBases& c, int r)
 {
     const int64_t o = c.ref_off[r];
     const int32_t L = c.ref_len[r];
@@ -145,6 +171,14 @@ void ea_host_sums(const EaCall& c, int r)
         s[3] += x;
         s[4] += x * l;
     }
+}
+
+// the L + 2 states of read r
+void ea_host_states(const EaBases& b, int r, std::vector<EaState>& st)
+{
+    const int32_t L = b.ref_len[r];
+    st.resize((size_t)L + 2);
+    for (int32_t s = 0; s < L + 2; s++) st[s] = ea_state(s, L, b.codes + b.ref_off[r], b.m.k, b.m.lvl, b.m.w, b.m.bias, b.m.bg);
 }
 
 size_t ea_zq_bytes(int64_t T) { return align_up((size_t)T * 4, 256); }
@@ -167,8 +201,10 @@ extern "C" int rd_eventalign_host(const int16_t* raw, const int64_t* read_off, i
                                   int32_t* ev_start, int32_t* ev_end, int64_t* ev_sum, int64_t* ev_sumsq, int16_t* ev_min, int16_t* ev_max,
                                   int64_t* fit_sums)
 {
-    const EaCall c{raw, read_off, t_lo, t_hi, n_reads, codes, ref_off, ref_len, m2_in, d4_in, EaModel{k, lvl, w, bias, EaState{lvl_bg, w_bg, bias_bg}},
-                   status, score, m2, d4, first_step, last_step, ev_start, ev_end, ev_sum, ev_sumsq, ev_min, ev_max, fit_sums};
+    const EaCall c{raw, read_off, t_lo, t_hi, n_reads,
+                   EaBases{codes, ref_off, ref_len, m2_in, d4_in, EaModel{k, lvl, w, bias, EaState{lvl_bg, w_bg, bias_bg}}, status, score, first_step,
+                           last_step, ev_start, ev_end, ev_sum, ev_sumsq, ev_min, ev_max, fit_sums},
+                   m2, d4};
     int64_t n_bases = 0;
     int rc = ea_check_args("rd_eventalign_host", c, &n_bases);
     if (rc || n_reads == 0) return rc;
@@ -192,8 +228,7 @@ extern "C" int rd_eventalign_host(const int16_t* raw, const int64_t* read_off, i
         ev_status[r] = 0;
         zq.resize(T);
         for (int64_t t = 0; t < T; t++) zq[t] = ea_quant(x[t], um2, ud4);
-        st.resize(S);
-        for (int64_t s = 0; s < S; s++) st[s] = ea_state((int32_t)s, (int32_t)L, codes + o, k, lvl, w, bias, c.m.bg);
+        ea_host_states(c.b, r, st);
         V.assign(S, EA_INF);
         bp.assign((size_t)((T * S + 7) / 8), 0);
         V[0] = ea_cost(zq[0], st[0].lvl, st[0].w, st[0].bias);
@@ -226,7 +261,7 @@ extern "C" int rd_eventalign_host(const int16_t* raw, const int64_t* read_off, i
                                   ev_min, ev_max)))
         return rc;
     for (int r = 0; r < n_reads; r++)
-        if (status[r] == EA_OK) ea_host_sums(c, r);
+        if (status[r] == EA_OK) ea_host_sums(c.b, r);
     return RD_OK;
 }
 
@@ -235,6 +270,7 @@ extern "C" int rd_eventalign_host(const int16_t* raw, const int64_t* read_off, i
 // records as they are; no raw sample is read), weighted by its sample count, and a third predecessor skips one base:
 //   n_e = start[e+1] - start[e] (the window's T closes the last), x_e = floor((2 sum_e + n_e) / (2 n_e)), zq_e = ea_quant(x_e, m2, d4)
 //   c(e, s) = n_e * ea_cost(zq_e, s);  V[e][s] = c(e, s) + ear_best(V[e-1][s], V[e-1][s-1], V[e-1][s-2] + skip_pen): two bits per cell
+// Only the events side of the call and its checks are here: the bases side, the blank outputs, the state table and the fit sums are EaBases'.
 namespace {
 
 struct EarCall {
@@ -244,39 +280,26 @@ struct EarCall {
     const int32_t* in_start;
     const int64_t *in_sum, *in_sumsq;
     const int16_t *in_min, *in_max;
-    const uint8_t* codes;
-    const int64_t* ref_off;
-    const int32_t *ref_len, *m2_in, *d4_in;
-    EaModel m;
     int skip_pen;
-    int32_t* status;
-    int64_t* score;
-    int32_t *n_skipped, *row_first, *row_last, *ev_start, *ev_end;
-    int64_t *ev_sum, *ev_sumsq;
-    int16_t *ev_min, *ev_max;
-    int64_t* fit_sums;
+    EaBases b;
+    int32_t* n_skipped;
 };
 
 int ear_check_args(const char* who, const EarCall& c, int64_t* n_bases)
 {
     *n_bases = 0;
     RD_REQUIRE(c.n_reads >= 0, "%s: negative n_reads", who);
-    if (int rc = ea_check_model(who, c.m)) return rc;
+    if (int rc = ea_check_model(who, c.b.m)) return rc;
     RD_REQUIRE(ear_pen_ok(c.skip_pen), "%s: skip_pen = %d, not -1 (no skips) or 0..256", who, c.skip_pen);
     if (c.n_reads == 0) return RD_OK;
-    RD_REQUIRE(c.n_samples && c.sample_off && c.ev_off && c.n_events && c.ref_off && c.ref_len && c.m2_in && c.d4_in, "%s: null argument", who);
-    RD_REQUIRE(c.status && c.score && c.n_skipped && c.fit_sums, "%s: null output", who);
-    int64_t end = 0;
+    RD_REQUIRE(c.n_samples && c.sample_off && c.ev_off && c.n_events && c.b.ref_off && c.b.ref_len && c.b.m2_in && c.b.d4_in, "%s: null argument", who);
+    RD_REQUIRE(c.b.status && c.b.score && c.n_skipped && c.b.fit_sums, "%s: null output", who);
     for (int r = 0; r < c.n_reads; r++) {
         const int64_t T = c.n_samples[r], E = c.n_events[r];
         RD_REQUIRE(T >= 0 && c.sample_off[r] >= 0 && T <= INT32_MAX && c.sample_off[r] <= INT32_MAX - T,
                    "%s: read %d: %lld samples from %lld on do not fit 0 .. 2^31 - 1", who, r, (long long)T, (long long)c.sample_off[r]);
         RD_REQUIRE(E >= 0 && c.ev_off[r] >= 0, "%s: read %d: negative event count or offset", who, r);
-        RD_REQUIRE(c.ref_len[r] >= 0 && c.ref_len[r] < (1 << 29), "%s: read %d has %d bases", who, r, c.ref_len[r]);
-        RD_REQUIRE(c.ref_off[r] >= end, "%s: base offsets must be non-decreasing and the reads' bases must not overlap (read %d)", who, r);
-        RD_REQUIRE(ea_scale_ok(c.m2_in[r], c.d4_in[r]), "%s: read %d: the scale (m2 %d, d4 %d) is outside |m2| <= 2^17, 0 <= d4 <= 2^20", who, r,
-                   c.m2_in[r], c.d4_in[r]);
-        end = c.ref_off[r] + c.ref_len[r];
+        if (int rc = ea_check_read_bases(who, c.b, r, n_bases)) return rc;
         if (E == 0) continue;
         RD_REQUIRE(c.in_start && c.in_sum && c.in_sumsq && c.in_min && c.in_max, "%s: null event array", who);
         const int32_t* s = c.in_start + c.ev_off[r];
@@ -290,29 +313,13 @@ int ear_check_args(const char* who, const EarCall& c, int64_t* n_bases)
                        who, r, (long long)e, (long long)sum, (long long)n);
         }
     }
-    *n_bases = end;
-    if (end) {
-        RD_REQUIRE(c.codes && c.row_first && c.row_last && c.ev_start && c.ev_end && c.ev_sum && c.ev_sumsq && c.ev_min && c.ev_max,
-                   "%s: null code or per-base buffer", who);
-        for (int r = 0; r < c.n_reads; r++)
-            for (int b = 0; b < c.ref_len[r]; b++)
-                RD_REQUIRE(c.codes[c.ref_off[r] + b] < 4, "%s: base %d of read %d is %d, not in 0..3", who, b, r, c.codes[c.ref_off[r] + b]);
-    }
-    return RD_OK;
+    return ea_check_codes(who, c.b, c.n_reads, *n_bases);
 }
 
 void ear_blank(const EarCall& c, int r, int status)
 {
-    c.status[r] = status;
-    c.score[r] = 0;
+    ea_blank(c.b, r, status);
     c.n_skipped[r] = 0;
-    for (int i = 0; i < 5; i++) c.fit_sums[5 * (int64_t)r + i] = 0;
-    const int64_t o = c.ref_off[r];
-    for (int b = 0; b < c.ref_len[r]; b++) {
-        c.row_first[o + b] = c.row_last[o + b] = c.ev_start[o + b] = c.ev_end[o + b] = -1;
-        c.ev_sum[o + b] = c.ev_sumsq[o + b] = 0;
-        c.ev_min[o + b] = c.ev_max[o + b] = 0;
-    }
 }
 
 size_t ear_row_bytes(int64_t E) { return align_up((size_t)E * 8, 256); }
@@ -336,9 +343,10 @@ extern "C" int rd_eventalign_events_host(int n_reads, const int64_t* n_samples, 
                                          int32_t* n_skipped, int32_t* row_first, int32_t* row_last, int32_t* ev_start, int32_t* ev_end, int64_t* ev_sum,
                                          int64_t* ev_sumsq, int16_t* ev_min, int16_t* ev_max, int64_t* fit_sums)
 {
-    const EarCall c{n_reads, n_samples, sample_off, ev_off, n_events, in_start, in_sum, in_sumsq, in_min, in_max, codes, ref_off, ref_len, m2_in, d4_in,
-                    EaModel{k, lvl, w, bias, EaState{lvl_bg, w_bg, bias_bg}}, skip_pen, status, score, n_skipped, row_first, row_last, ev_start, ev_end,
-                    ev_sum, ev_sumsq, ev_min, ev_max, fit_sums};
+    const EarCall c{n_reads, n_samples, sample_off, ev_off, n_events, in_start, in_sum, in_sumsq, in_min, in_max, skip_pen,
+                    EaBases{codes, ref_off, ref_len, m2_in, d4_in, EaModel{k, lvl, w, bias, EaState{lvl_bg, w_bg, bias_bg}}, status, score, row_first,
+                            row_last, ev_start, ev_end, ev_sum, ev_sumsq, ev_min, ev_max, fit_sums},
+                    n_skipped};
     int64_t n_bases = 0;
     const int rc = ear_check_args("rd_eventalign_events_host", c, &n_bases);
     if (rc || n_reads == 0) return rc;
@@ -359,8 +367,7 @@ extern "C" int rd_eventalign_events_host(int n_reads, const int64_t* n_samples, 
             nn[e] = row_end(e) - in_start[eo + e];
             zq[e] = ea_quant((int32_t)ear_mean(in_sum[eo + e], nn[e]), m2_in[r], d4_in[r]);
         }
-        st.resize(S);
-        for (int64_t s = 0; s < S; s++) st[s] = ea_state((int32_t)s, (int32_t)L, codes + o, k, lvl, w, bias, c.m.bg);
+        ea_host_states(c.b, r, st);
         V.assign(S, EA_INF);
         bp.assign((size_t)(E * wpr), 0);
         V[0] = ear_cost(zq[0], nn[0], st[0].lvl, st[0].w, st[0].bias);
@@ -390,7 +397,6 @@ extern "C" int rd_eventalign_events_host(int n_reads, const int64_t* n_samples, 
             s -= code;
         }
         if (s == 1 && L >= 1) row_first[o] = 0;
-        int64_t* fs = fit_sums + 5 * (int64_t)r;
         for (int64_t b = 0; b < L; b++) {
             const int32_t f = row_first[o + b], l = row_last[o + b];
             if (f <= -2) {
@@ -412,13 +418,8 @@ extern "C" int rd_eventalign_events_host(int n_reads, const int64_t* n_samples, 
             ev_sumsq[o + b] = sq;
             ev_min[o + b] = mn;
             ev_max[o + b] = mx;
-            const int64_t lv = lvl[sim_kmer(codes + o, (int32_t)L, (int32_t)b, k)], n = ev_end[o + b] - ev_start[o + b];
-            fs[0] += n;
-            fs[1] += n * lv;
-            fs[2] += n * lv * lv;
-            fs[3] += sum;
-            fs[4] += sum * lv;
         }
+        ea_host_sums(c.b, r);
     }
     return RD_OK;
 }
@@ -454,8 +455,50 @@ __global__ __launch_bounds__(256) void ea_quant_kernel(const EaSeq* __restrict__
     ((int32_t*)(ws + q.zq))[t] = ea_quant(raw[q.raw0 + t], q.m2, q.d4);
 }
 
+// What both band_sweep.h policies of this file hold besides their rows and back-pointers: the read, the thread's 16 states of the band,
+// how a band starts and what it leaves
+struct EaBand {
+    // the read
+    const uint8_t* cod;
+    const int32_t* __restrict__ lvl_t;
+    const uint32_t* __restrict__ w_t;
+    const int32_t* __restrict__ bias_t;
+    EaState bg;
+    int32_t* fin;   // the read's two end values
+    int k, L, S;
+    // the thread's states of the band
+    int s0;
+    int32_t lv[BS_K], bi[BS_K], v[BS_K];
+    uint32_t wt[BS_K];
+
+    __device__ __forceinline__ void begin_band(int b)
+    {
+        s0 = b * BS_BAND + (int)threadIdx.x * BS_K;
+#pragma unroll
+        for (int j = 0; j < BS_K; j++) {
+            EaState st{0, 0, 0};   // a state past the read: it costs nothing, its value stays where it starts
+            if (s0 + j < S) st = ea_state(s0 + j, L, cod, k, lvl_t, w_t, bias_t, bg);
+            lv[j] = st.lvl;
+            wt[j] = st.w;
+            bi[j] = st.bias;
+            v[j] = EA_INF;
+        }
+        // row -1 of band 0: V = 0 in state 0 and unreachable elsewhere makes row 0 the contract's start, state 1 by the advance
+        if (s0 == 0) v[0] = 0;
+    }
+    // the two states the path may end in
+    __device__ __forceinline__ void end_band() const
+    {
+#pragma unroll
+        for (int j = 0; j < BS_K; j++) {
+            if (s0 + j == L + 1) fin[0] = v[j];
+            if (s0 + j == L) fin[1] = v[j];
+        }
+    }
+};
+
 // band_sweep.h's policy of eventalign
-struct EaSweep {
+struct EaSweep : EaBand {
     using Cell = int32_t;
     using Elem = int32_t;
     static constexpr bool AHEAD_CLAMPED = true;
@@ -463,41 +506,15 @@ struct EaSweep {
     struct Row {
         int32_t z, c;
     };
-    // the read
     const int32_t* __restrict__ zq;
     uint16_t* __restrict__ bp;
-    const uint8_t* cod;
-    const int32_t* __restrict__ lvl_t;
-    const uint32_t* __restrict__ w_t;
-    const int32_t* __restrict__ bias_t;
-    EaState bg;
-    int32_t* fin;   // the read's two end values
-    int k, L, S, hpr;   // hpr: 16-bit words of a back-pointer row
-    // the thread's states of the band
-    int s0;
-    int32_t lv[BS_K], bi[BS_K], v[BS_K];
-    uint32_t wt[BS_K];
+    int hpr;   // 16-bit words of a back-pointer row
 
     static __device__ __forceinline__ int first_row(int b) { return b ? b * BS_BAND - 1 : 0; }   // rows above have s > t + 1 in the whole band
     static __device__ __forceinline__ Cell none() { return EA_INF; }
     static __device__ __forceinline__ Cell incoming(const Row& in) { return in.c; }
     __device__ __forceinline__ Cell last() const { return v[BS_K - 1]; }
 
-    __device__ __forceinline__ void begin_band(int b)
-    {
-        s0 = b * BS_BAND + (int)threadIdx.x * BS_K;
-#pragma unroll
-        for (int j = 0; j < BS_K; j++) {
-            EaState st{0, 0, 0};   // a state past the read: its value stays where it starts
-            if (s0 + j < S) st = ea_state(s0 + j, L, cod, k, lvl_t, w_t, bias_t, bg);
-            lv[j] = st.lvl;
-            wt[j] = st.w;
-            bi[j] = st.bias;
-            v[j] = EA_INF;
-        }
-        // row -1 of band 0: V = 0 in state 0 and unreachable elsewhere makes row 0 the contract's start
-        if (s0 == 0) v[0] = 0;
-    }
     __device__ __forceinline__ Elem tile_elem(int e, int tbase, int T, int b, const Cell* cin) const
     {
         const int which = e / TR, t = tbase + (e % TR);
@@ -521,15 +538,6 @@ struct EaSweep {
         }
         if (s0 < S) bp[(size_t)t * hpr + (s0 >> 4)] = (uint16_t)bits;
     }
-    // the two states the path may end in
-    __device__ __forceinline__ void end_band() const
-    {
-#pragma unroll
-        for (int j = 0; j < BS_K; j++) {
-            if (s0 + j == L + 1) fin[0] = v[j];
-            if (s0 + j == L) fin[1] = v[j];
-        }
-    }
 };
 
 __global__ __launch_bounds__(BS_NT) void ea_dp_kernel(const EaSeq* __restrict__ seqs, const uint8_t* __restrict__ codes, const int32_t* __restrict__ lvl_t,
@@ -538,8 +546,8 @@ __global__ __launch_bounds__(BS_NT) void ea_dp_kernel(const EaSeq* __restrict__ 
 {
     const EaSeq q = seqs[blockIdx.x];
     const int S = q.L + 2;
-    EaSweep p{(const int32_t*)(ws + q.zq), (uint16_t*)(ws + q.bp), codes + q.codes, lvl_t, w_t, bias_t, bg, fin + 2 * (int64_t)blockIdx.x,
-              k, q.L, S, 2 * ((S + 31) / 32)};
+    EaSweep p{{codes + q.codes, lvl_t, w_t, bias_t, bg, fin + 2 * (int64_t)blockIdx.x, k, q.L, S},
+              (const int32_t*)(ws + q.zq), (uint16_t*)(ws + q.bp), 2 * ((S + 31) / 32)};
     band_sweep(p, S, q.T, (int32_t*)(ws + q.col));
 }
 
@@ -617,21 +625,23 @@ __global__ __launch_bounds__(256) void ea_sums_kernel(const EaSeq* __restrict__ 
     if (tid < 5) out[blockIdx.x].sums[tid] = sh[0][tid] + sh[1][tid] + sh[2][tid] + sh[3][tid];
 }
 
-// a launch's io block (ws_eval) for nb reads of nlab bases: descriptors | end values [2] | score and sums | first, last, start, end | sum,
-// sumsq | min, max.  Arrays of one type follow each other at one stride, so the host fetches each type in one copy.
+// a launch's io block (ws_eval) for nb reads of nlab bases: descriptors | end values [2] | skip counts (n_skip of them: nb for event rows,
+// none for sample rows, which moves nothing) | score and sums | first, last, start, end | sum, sumsq | min, max.  Arrays of one type
+// follow each other at one stride, so the host fetches each type in one copy.
 struct EaIo {
     EaSeq* seqs;
-    int32_t* fin;
+    int32_t *fin, *nskip;
     EaOut* out;
     int32_t *first, *last, *start, *end;
     int64_t *sum, *sumsq;
     int16_t *mn, *mx;
 };
-void ea_io_layout(Carve& c, int nb, int64_t nlab, EaIo* io)
+void ea_io_layout(Carve& c, int nb, int64_t nlab, int n_skip, EaIo* io)
 {
     const size_t n = (size_t)nlab;
     io->seqs = c.take<EaSeq>((size_t)nb);
     io->fin = c.take<int32_t>((size_t)nb * 2);
+    io->nskip = c.take<int32_t>((size_t)n_skip);
     io->out = c.take<EaOut>((size_t)nb);
     io->first = c.take<int32_t>(n, 16);
     io->last = c.take<int32_t>(n, 16);
@@ -645,6 +655,7 @@ void ea_io_layout(Carve& c, int nb, int64_t nlab, EaIo* io)
 
 // ---- event rows (rd_eventalign_events).  An EaSeq of these kernels: raw0 = the read's event 0 in the launch's event arrays, T = its rows
 // (events), n_win = its window's samples, t_lo = what is added to a sample index; zq = the rows' block, E zq then E sample counts.
+// Only what differs from sample rows is here: the event arrays, the four kernels and the sweep's rows.  Band state and io block are above.
 struct EarEvents {
     int32_t* start;
     int64_t *sum, *sumsq;
@@ -676,7 +687,7 @@ __global__ __launch_bounds__(256) void ear_row_kernel(const EaSeq* __restrict__ 
 
 // band_sweep.h's policy of eventalign on event rows: the cell that crosses a thread boundary is the thread's last TWO states
 template <bool SKIPS>
-struct EarSweep {
+struct EarSweep : EaBand {
     using Cell = Cell2;
     using Elem = int32_t;
     static constexpr bool AHEAD_CLAMPED = true;
@@ -685,21 +696,10 @@ struct EarSweep {
         int32_t z, n;
         Cell2 c;
     };
-    // the read
     const int32_t* __restrict__ zq;
     const int32_t* __restrict__ nn;
     uint32_t* __restrict__ bp;
-    const uint8_t* cod;
-    const int32_t* __restrict__ lvl_t;
-    const uint32_t* __restrict__ w_t;
-    const int32_t* __restrict__ bias_t;
-    EaState bg;
-    int32_t* fin;   // the read's two end values
-    int k, L, S, wpr, pen;   // wpr: 32-bit words of a back-pointer row
-    // the thread's states of the band
-    int s0;
-    int32_t lv[BS_K], bi[BS_K], v[BS_K];
-    uint32_t wt[BS_K];
+    int wpr, pen;   // wpr: 32-bit words of a back-pointer row
 
     // Row e reaches the states up to 2 e + 1 (two per row from state 1 at row 0), so the band's first state 4096 b is first reachable at
     // row 2048 b, from states 4096 b - 1 and 4096 b - 2 of row 2048 b - 1: that is the first row whose incoming column is read, and band
@@ -710,22 +710,6 @@ struct EarSweep {
     static __device__ __forceinline__ Cell incoming(const Row& in) { return in.c; }
     __device__ __forceinline__ Cell last() const { return Cell2{v[BS_K - 2], v[BS_K - 1]}; }
 
-    __device__ __forceinline__ void begin_band(int b)
-    {
-        s0 = b * BS_BAND + (int)threadIdx.x * BS_K;
-#pragma unroll
-        for (int j = 0; j < BS_K; j++) {
-            EaState st{0, 0, 0};   // a state past the read: it costs nothing, its value never rises above its neighbours'
-            if (s0 + j < S) st = ea_state(s0 + j, L, cod, k, lvl_t, w_t, bias_t, bg);
-            lv[j] = st.lvl;
-            wt[j] = st.w;
-            bi[j] = st.bias;
-            v[j] = EA_INF;
-        }
-        // row -1 of band 0: V = 0 in state 0 and unreachable elsewhere makes row 0 the contract's start, state 1 by the advance.  A skip
-        // from that 0 would reach state 2 and beat its 2^30, so row 0 takes no skip edge (row())
-        if (s0 == 0) v[0] = 0;
-    }
     __device__ __forceinline__ Elem tile_elem(int e, int tbase, int T, int b, const Cell* cin) const
     {
         const int which = e / TR, t = tbase + (e % TR);
@@ -741,6 +725,7 @@ struct EarSweep {
     __device__ __forceinline__ void row(int t, const Row& in, Cell left)
     {
         uint32_t bits = 0;
+        // begin_band's row -1 holds V = 0 in state 0.  A skip from that 0 would reach state 2 and beat its 2^30, so row 0 takes no skip edge
         const bool skips = SKIPS && t > 0;   // (wave-uniform)
 #pragma unroll
         for (int j = BS_K - 1; j >= 0; j--) {
@@ -753,15 +738,6 @@ struct EarSweep {
         }
         if (s0 < S) bp[(size_t)t * wpr + (s0 >> 4)] = bits;
     }
-    // the two states the path may end in
-    __device__ __forceinline__ void end_band() const
-    {
-#pragma unroll
-        for (int j = 0; j < BS_K; j++) {
-            if (s0 + j == L + 1) fin[0] = v[j];
-            if (s0 + j == L) fin[1] = v[j];
-        }
-    }
 };
 
 template <bool SKIPS>
@@ -772,8 +748,8 @@ __global__ __launch_bounds__(BS_NT) void ear_dp_kernel(const EaSeq* __restrict__
     const EaSeq q = seqs[blockIdx.x];
     const int S = q.L + 2;
     const int32_t* rows = (const int32_t*)(ws + q.zq);
-    EarSweep<SKIPS> p{rows, rows + q.T, (uint32_t*)(ws + q.bp), codes + q.codes, lvl_t, w_t, bias_t, bg, fin + 2 * (int64_t)blockIdx.x,
-                      k, q.L, S, (S + 15) / 16, pen};
+    EarSweep<SKIPS> p{{codes + q.codes, lvl_t, w_t, bias_t, bg, fin + 2 * (int64_t)blockIdx.x, k, q.L, S},
+                      rows, rows + q.T, (uint32_t*)(ws + q.bp), (S + 15) / 16, pen};
     band_sweep(p, S, q.T, (Cell2*)(ws + q.col));
 }
 
@@ -880,30 +856,70 @@ __global__ __launch_bounds__(256) void ear_reduce_kernel(const EaSeq* __restrict
     mx[o] = (int16_t)hi;
 }
 
-// a launch's io block (ws_eval), as EaIo with the skip counts
-struct EarIo {
-    EaSeq* seqs;
-    int32_t *fin, *nskip;
-    EaOut* out;
-    int32_t *first, *last, *start, *end;
-    int64_t *sum, *sumsq;
-    int16_t *mn, *mx;
-};
-void ear_io_layout(Carve& c, int nb, int64_t nlab, EarIo* io)
+// ---- what the two launch loops call
+// a read's three blocks of the launch's workspace (ws is dry: the descriptor holds offsets into ws_align)
+void ea_place(Carve& ws, EaSeq& d, size_t zq_bytes, size_t bp_bytes, size_t col_bytes)
 {
-    const size_t n = (size_t)nlab;
-    io->seqs = c.take<EaSeq>((size_t)nb);
-    io->fin = c.take<int32_t>((size_t)nb * 2);
-    io->nskip = c.take<int32_t>((size_t)nb);
-    io->out = c.take<EaOut>((size_t)nb);
-    io->first = c.take<int32_t>(n, 16);
-    io->last = c.take<int32_t>(n, 16);
-    io->start = c.take<int32_t>(n, 16);
-    io->end = c.take<int32_t>(n, 16);
-    io->sum = c.take<int64_t>(n, 16);
-    io->sumsq = c.take<int64_t>(n, 16);
-    io->mn = c.take<int16_t>(n, 16);
-    io->mx = c.take<int16_t>(n, 16);
+    d.zq = (int64_t)ws.mark();
+    ws.take<char>(zq_bytes, 0, 1);
+    d.bp = (int64_t)ws.mark();
+    ws.take<char>(bp_bytes, 0, 1);
+    d.col = (int64_t)ws.mark();
+    ws.take<char>(col_bytes, 0, 1);
+}
+
+// the host's copy of a launch's io block
+struct EaFetched {
+    std::vector<EaOut> out;
+    std::vector<int32_t> i32, skip;
+    std::vector<int64_t> i64;
+    std::vector<int16_t> i16;
+    size_t s4, s8, s2;   // the arrays' strides, in elements
+};
+// the device-to-host copies of the block (the skip counts where it holds them), and the wait for them
+int ea_fetch(hipStream_t st, const EaIo& io, int nb, int64_t nlab, bool skips, EaFetched& h)
+{
+    h.s4 = io.last - io.first, h.s8 = io.sumsq - io.sum, h.s2 = io.mx - io.mn;
+    h.out.resize(nb);
+    h.skip.resize(nb);
+    h.i32.resize(4 * h.s4);
+    h.i64.resize(2 * h.s8);
+    h.i16.resize(2 * h.s2);
+    RD_HIP(hipMemcpyAsync(h.out.data(), io.out, (size_t)nb * sizeof(EaOut), hipMemcpyDeviceToHost, st));
+    if (skips) RD_HIP(hipMemcpyAsync(h.skip.data(), io.nskip, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+    if (nlab) {
+        RD_HIP(hipMemcpyAsync(h.i32.data(), io.first, 4 * h.s4 * 4, hipMemcpyDeviceToHost, st));
+        RD_HIP(hipMemcpyAsync(h.i64.data(), io.sum, 2 * h.s8 * 8, hipMemcpyDeviceToHost, st));
+        RD_HIP(hipMemcpyAsync(h.i16.data(), io.mn, 2 * h.s2 * 2, hipMemcpyDeviceToHost, st));
+    }
+    RD_HIP(hipStreamSynchronize(st));
+    return RD_OK;
+}
+// member i of the launch, read r of the call with descriptor d, into the caller's arrays
+void ea_scatter(const EaBases& b, int r, const EaSeq& d, int i, const EaFetched& h)
+{
+    const size_t L = (size_t)d.L, o = (size_t)b.ref_off[r], s = (size_t)d.lab;
+    b.status[r] = EA_OK;
+    b.score[r] = h.out[i].score;
+    memcpy(b.fit_sums + 5 * (int64_t)r, h.out[i].sums, 40);
+    if (!L) return;
+    memcpy(b.first + o, h.i32.data() + s, L * 4);
+    memcpy(b.last + o, h.i32.data() + h.s4 + s, L * 4);
+    memcpy(b.ev_start + o, h.i32.data() + 2 * h.s4 + s, L * 4);
+    memcpy(b.ev_end + o, h.i32.data() + 3 * h.s4 + s, L * 4);
+    memcpy(b.ev_sum + o, h.i64.data() + s, L * 8);
+    memcpy(b.ev_sumsq + o, h.i64.data() + h.s8 + s, L * 8);
+    memcpy(b.ev_min + o, h.i16.data() + s, L * 2);
+    memcpy(b.ev_max + o, h.i16.data() + h.s2 + s, L * 2);
+}
+
+// the report of a call that left reads over the budget: the first of them, its rows ("samples" or "events"), what it needs
+int ea_too_large(const char* who, const BudgetPlan& plan, long long rows, const char* noun, int L, size_t bytes, int64_t budget_bytes)
+{
+    rd_set_error("%s: read %d (%lld %s x %d bases) needs %lld bytes of workspace, over the budget of %lld; %d read(s) not "
+                 "aligned (status RD_EVAL_TOO_LARGE), the others were", who, (int)plan.first_too_large, rows, noun, L, (long long)bytes,
+                 (long long)budget_bytes, (int)plan.too_large);
+    return RD_ERR_NOMEM;
 }
 
 }  // namespace
@@ -917,8 +933,10 @@ extern "C" int rd_eventalign(rd_ctx* ctx, const int16_t* raw, const int64_t* rea
 {
     RD_REQUIRE(ctx, "rd_eventalign: null context");
     RD_REQUIRE(budget_bytes >= 0, "rd_eventalign: negative budget");
-    const EaCall c{raw, read_off, t_lo, t_hi, n_reads, codes, ref_off, ref_len, m2_in, d4_in, EaModel{k, lvl, w, bias, EaState{lvl_bg, w_bg, bias_bg}},
-                   status, score, m2, d4, first_step, last_step, ev_start, ev_end, ev_sum, ev_sumsq, ev_min, ev_max, fit_sums};
+    const EaCall c{raw, read_off, t_lo, t_hi, n_reads,
+                   EaBases{codes, ref_off, ref_len, m2_in, d4_in, EaModel{k, lvl, w, bias, EaState{lvl_bg, w_bg, bias_bg}}, status, score, first_step,
+                           last_step, ev_start, ev_end, ev_sum, ev_sumsq, ev_min, ev_max, fit_sums},
+                   m2, d4};
     int64_t n_bases = 0;
     int rc = ea_check_args("rd_eventalign", c, &n_bases);
     if (rc || n_reads == 0) return rc;
@@ -952,13 +970,11 @@ extern "C" int rd_eventalign(rd_ctx* ctx, const int16_t* raw, const int64_t* rea
     const BudgetPlan plan = rd_plan_budget(n_reads, nullptr, budget_bytes, 0, false,
                                            [&](int r, int) { return status[r] == EA_TOO_LARGE ? (int64_t)ea_read_bytes(t_hi[r] - t_lo[r], ref_len[r]) : (int64_t)-1; },
                                            [](int, int, int64_t count, int64_t) { return count >= EA_MAX_LAUNCH; });
-    const int too_large = (int)plan.too_large, first_too_large = (int)plan.first_too_large;
     if (plan.max_bytes && ctx->ws_align.reserve_exact((size_t)plan.max_bytes, "rd_eventalign")) return RD_ERR_NOMEM;
     std::vector<EaSeq> desc;
-    std::vector<EaOut> h_out;
-    std::vector<int32_t> h_i32, ev_len, ev_status;
-    std::vector<int64_t> h_i64, ev_lab;
-    std::vector<int16_t> h_i16;
+    EaFetched h;
+    std::vector<int32_t> ev_len, ev_status;
+    std::vector<int64_t> ev_lab;
     for (auto [k0, k1] : plan.launches) {
         const int nb = (int)(k1 - k0);
         const int32_t* members = plan.run.data() + k0;
@@ -981,12 +997,7 @@ extern "C" int rd_eventalign(rd_ctx* ctx, const int16_t* raw, const int64_t* rea
             d.d4 = d4[r];
             d.t_lo = (int32_t)t_lo[r];
             d.n_win = 0;
-            d.zq = (int64_t)ws.mark();
-            ws.take<char>(ea_zq_bytes(d.T), 0, 1);
-            d.bp = (int64_t)ws.mark();
-            ws.take<char>(ea_bp_bytes(d.T, d.L), 0, 1);
-            d.col = (int64_t)ws.mark();
-            ws.take<char>(ea_col_bytes(d.T, d.L), 0, 1);
+            ea_place(ws, d, ea_zq_bytes(d.T), ea_bp_bytes(d.T, d.L), ea_col_bytes(d.T, d.L));
             ev_len[r - r_lo] = d.L;   // (a read between two members that is not one has no labels in this launch)
             ev_lab[r - r_lo] = d.lab;
             nlab += d.L;
@@ -994,12 +1005,12 @@ extern "C" int rd_eventalign(rd_ctx* ctx, const int16_t* raw, const int64_t* rea
         }
         if ((rc = rd_carve_check("rd_eventalign", ws, ctx->ws_align.cap))) return rc;
         EaIo io;
-        if (rd_carve(ctx->ws_eval, [&](Carve& c) { ea_io_layout(c, nb, nlab, &io); })) return RD_ERR_NOMEM;
+        if (rd_carve(ctx->ws_eval, [&](Carve& cv) { ea_io_layout(cv, nb, nlab, 0, &io); })) return RD_ERR_NOMEM;
         uint8_t* dws = ctx->ws_align.as<uint8_t>();
         RD_HIP(hipMemcpyAsync(io.seqs, desc.data(), (size_t)nb * sizeof(EaSeq), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(ea_quant_kernel, dim3((unsigned)((max_T + 255) / 256), nb), dim3(256), 0, st, io.seqs, d_raw, dws, io.fin);
         RD_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ea_dp_kernel, dim3(nb), dim3(BS_NT), 0, st, io.seqs, d_codes, d_lvl, d_w, d_bias, c.m.bg, k, dws, io.fin);
+        hipLaunchKernelGGL(ea_dp_kernel, dim3(nb), dim3(BS_NT), 0, st, io.seqs, d_codes, d_lvl, d_w, d_bias, c.b.m.bg, k, dws, io.fin);
         RD_HIP(hipGetLastError());
         hipLaunchKernelGGL(ea_tb_kernel, dim3(nb), dim3(64), 0, st, io.seqs, dws, io.fin, io.out, io.first, io.last);
         RD_HIP(hipGetLastError());
@@ -1008,42 +1019,13 @@ extern "C" int rd_eventalign(rd_ctx* ctx, const int16_t* raw, const int64_t* rea
             return rc;
         hipLaunchKernelGGL(ea_sums_kernel, dim3(nb), dim3(256), 0, st, io.seqs, d_codes, d_lvl, k, io.start, io.end, io.sum, io.out);
         RD_HIP(hipGetLastError());
-        h_out.resize(nb);
-        const size_t s4 = io.last - io.first, s8 = io.sumsq - io.sum, s2 = io.mx - io.mn;   // the arrays' strides, in elements
-        h_i32.resize(4 * s4);
-        h_i64.resize(2 * s8);
-        h_i16.resize(2 * s2);
-        RD_HIP(hipMemcpyAsync(h_out.data(), io.out, (size_t)nb * sizeof(EaOut), hipMemcpyDeviceToHost, st));
-        if (nlab) {
-            RD_HIP(hipMemcpyAsync(h_i32.data(), io.first, 4 * s4 * 4, hipMemcpyDeviceToHost, st));
-            RD_HIP(hipMemcpyAsync(h_i64.data(), io.sum, 2 * s8 * 8, hipMemcpyDeviceToHost, st));
-            RD_HIP(hipMemcpyAsync(h_i16.data(), io.mn, 2 * s2 * 2, hipMemcpyDeviceToHost, st));
-        }
-        RD_HIP(hipStreamSynchronize(st));
-        for (int i = 0; i < nb; i++) {
-            const int r = members[i];
-            const EaSeq& d = desc[i];
-            const size_t L = (size_t)d.L, o = (size_t)ref_off[r], s = (size_t)d.lab;
-            status[r] = EA_OK;
-            score[r] = h_out[i].score;
-            memcpy(fit_sums + 5 * (int64_t)r, h_out[i].sums, 40);
-            if (!L) continue;
-            memcpy(first_step + o, h_i32.data() + s, L * 4);
-            memcpy(last_step + o, h_i32.data() + s4 + s, L * 4);
-            memcpy(ev_start + o, h_i32.data() + 2 * s4 + s, L * 4);
-            memcpy(ev_end + o, h_i32.data() + 3 * s4 + s, L * 4);
-            memcpy(ev_sum + o, h_i64.data() + s, L * 8);
-            memcpy(ev_sumsq + o, h_i64.data() + s8 + s, L * 8);
-            memcpy(ev_min + o, h_i16.data() + s, L * 2);
-            memcpy(ev_max + o, h_i16.data() + s2 + s, L * 2);
-        }
+        if ((rc = ea_fetch(st, io, nb, nlab, false, h))) return rc;
+        for (int i = 0; i < nb; i++) ea_scatter(c.b, members[i], desc[i], i, h);
     }
-    if (too_large) {
-        const int r = first_too_large;
-        rd_set_error("rd_eventalign: read %d (%lld samples x %d bases) needs %lld bytes of workspace, over the budget of %lld; %d read(s) not "
-                     "aligned (status RD_EVAL_TOO_LARGE), the others were", r, (long long)(t_hi[r] - t_lo[r]), ref_len[r],
-                     (long long)ea_read_bytes(t_hi[r] - t_lo[r], ref_len[r]), (long long)budget_bytes, too_large);
-        return RD_ERR_NOMEM;
+    if (plan.too_large) {
+        const int r = (int)plan.first_too_large;
+        const int64_t T = t_hi[r] - t_lo[r];
+        return ea_too_large("rd_eventalign", plan, (long long)T, "samples", ref_len[r], ea_read_bytes(T, ref_len[r]), budget_bytes);
     }
     return RD_OK;
 }
@@ -1058,9 +1040,10 @@ extern "C" int rd_eventalign_events(rd_ctx* ctx, int n_reads, const int64_t* n_s
 {
     RD_REQUIRE(ctx, "rd_eventalign_events: null context");
     RD_REQUIRE(budget_bytes >= 0, "rd_eventalign_events: negative budget");
-    const EarCall c{n_reads, n_samples, sample_off, ev_off, n_events, in_start, in_sum, in_sumsq, in_min, in_max, codes, ref_off, ref_len, m2_in, d4_in,
-                    EaModel{k, lvl, w, bias, EaState{lvl_bg, w_bg, bias_bg}}, skip_pen, status, score, n_skipped, row_first, row_last, ev_start, ev_end,
-                    ev_sum, ev_sumsq, ev_min, ev_max, fit_sums};
+    const EarCall c{n_reads, n_samples, sample_off, ev_off, n_events, in_start, in_sum, in_sumsq, in_min, in_max, skip_pen,
+                    EaBases{codes, ref_off, ref_len, m2_in, d4_in, EaModel{k, lvl, w, bias, EaState{lvl_bg, w_bg, bias_bg}}, status, score, row_first,
+                            row_last, ev_start, ev_end, ev_sum, ev_sumsq, ev_min, ev_max, fit_sums},
+                    n_skipped};
     int64_t n_bases = 0;
     int rc = ear_check_args("rd_eventalign_events", c, &n_bases);
     if (rc || n_reads == 0) return rc;
@@ -1083,10 +1066,10 @@ extern "C" int rd_eventalign_events(rd_ctx* ctx, int n_reads, const int64_t* n_s
                                            [](int, int, int64_t count, int64_t) { return count >= EA_MAX_LAUNCH; });
     if (plan.max_bytes && ctx->ws_align.reserve_exact((size_t)plan.max_bytes, "rd_eventalign_events")) return RD_ERR_NOMEM;
     std::vector<EaSeq> desc;
-    std::vector<EaOut> h_out;
-    std::vector<int32_t> h_i32, h_skip, p_start;
-    std::vector<int64_t> h_i64, p_sum, p_sumsq;
-    std::vector<int16_t> h_i16, p_min, p_max;
+    EaFetched h;
+    std::vector<int32_t> p_start;
+    std::vector<int64_t> p_sum, p_sumsq;
+    std::vector<int16_t> p_min, p_max;
     for (auto [k0, k1] : plan.launches) {
         const int nb = (int)(k1 - k0);
         const int32_t* members = plan.run.data() + k0;
@@ -1116,12 +1099,7 @@ extern "C" int rd_eventalign_events(rd_ctx* ctx, int n_reads, const int64_t* n_s
             d.d4 = d4_in[r];
             d.t_lo = (int32_t)sample_off[r];
             d.n_win = (int32_t)n_samples[r];
-            d.zq = (int64_t)ws.mark();
-            ws.take<char>(ear_row_bytes(E), 0, 1);
-            d.bp = (int64_t)ws.mark();
-            ws.take<char>(ear_bp_bytes(E, d.L), 0, 1);
-            d.col = (int64_t)ws.mark();
-            ws.take<char>(ear_col_bytes(E, d.L), 0, 1);
+            ea_place(ws, d, ear_row_bytes(E), ear_bp_bytes(E, d.L), ear_col_bytes(E, d.L));
             nlab += d.L;
             max_E = std::max<int64_t>(max_E, E);
             max_L = std::max<int64_t>(max_L, d.L);
@@ -1129,9 +1107,9 @@ extern "C" int rd_eventalign_events(rd_ctx* ctx, int n_reads, const int64_t* n_s
         if ((rc = rd_carve_check("rd_eventalign_events", ws, ctx->ws_align.cap))) return rc;
         const int64_t n_ev = (int64_t)p_start.size();
         EarEvents ev;
-        EarIo io;
+        EaIo io;
         if (rd_carve(ctx->ws_raw, [&](Carve& cv) { ear_events_layout(cv, n_ev, &ev); })) return RD_ERR_NOMEM;
-        if (rd_carve(ctx->ws_eval, [&](Carve& cv) { ear_io_layout(cv, nb, nlab, &io); })) return RD_ERR_NOMEM;
+        if (rd_carve(ctx->ws_eval, [&](Carve& cv) { ea_io_layout(cv, nb, nlab, nb, &io); })) return RD_ERR_NOMEM;
         uint8_t* dws = ctx->ws_align.as<uint8_t>();
         RD_HIP(hipMemcpyAsync(io.seqs, desc.data(), (size_t)nb * sizeof(EaSeq), hipMemcpyHostToDevice, st));
         RD_HIP(hipMemcpyAsync(ev.start, p_start.data(), (size_t)n_ev * 4, hipMemcpyHostToDevice, st));
@@ -1142,9 +1120,9 @@ extern "C" int rd_eventalign_events(rd_ctx* ctx, int n_reads, const int64_t* n_s
         hipLaunchKernelGGL(ear_row_kernel, dim3((unsigned)((max_E + 255) / 256), nb), dim3(256), 0, st, io.seqs, ev.start, ev.sum, dws, io.fin);
         RD_HIP(hipGetLastError());
         if (skip_pen >= 0)
-            hipLaunchKernelGGL(ear_dp_kernel<true>, dim3(nb), dim3(BS_NT), 0, st, io.seqs, d_codes, tab.lvl, tab.w, tab.bias, c.m.bg, k, skip_pen, dws, io.fin);
+            hipLaunchKernelGGL(ear_dp_kernel<true>, dim3(nb), dim3(BS_NT), 0, st, io.seqs, d_codes, tab.lvl, tab.w, tab.bias, c.b.m.bg, k, skip_pen, dws, io.fin);
         else
-            hipLaunchKernelGGL(ear_dp_kernel<false>, dim3(nb), dim3(BS_NT), 0, st, io.seqs, d_codes, tab.lvl, tab.w, tab.bias, c.m.bg, k, 0, dws, io.fin);
+            hipLaunchKernelGGL(ear_dp_kernel<false>, dim3(nb), dim3(BS_NT), 0, st, io.seqs, d_codes, tab.lvl, tab.w, tab.bias, c.b.m.bg, k, 0, dws, io.fin);
         RD_HIP(hipGetLastError());
         hipLaunchKernelGGL(ear_tb_kernel, dim3(nb), dim3(64), 0, st, io.seqs, dws, io.fin, io.out, io.nskip, io.first, io.last);
         RD_HIP(hipGetLastError());
@@ -1155,45 +1133,15 @@ extern "C" int rd_eventalign_events(rd_ctx* ctx, int n_reads, const int64_t* n_s
         }
         hipLaunchKernelGGL(ea_sums_kernel, dim3(nb), dim3(256), 0, st, io.seqs, d_codes, tab.lvl, k, io.start, io.end, io.sum, io.out);
         RD_HIP(hipGetLastError());
-        h_out.resize(nb);
-        h_skip.resize(nb);
-        const size_t s4 = io.last - io.first, s8 = io.sumsq - io.sum, s2 = io.mx - io.mn;   // the arrays' strides, in elements
-        h_i32.resize(4 * s4);
-        h_i64.resize(2 * s8);
-        h_i16.resize(2 * s2);
-        RD_HIP(hipMemcpyAsync(h_out.data(), io.out, (size_t)nb * sizeof(EaOut), hipMemcpyDeviceToHost, st));
-        RD_HIP(hipMemcpyAsync(h_skip.data(), io.nskip, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
-        if (nlab) {
-            RD_HIP(hipMemcpyAsync(h_i32.data(), io.first, 4 * s4 * 4, hipMemcpyDeviceToHost, st));
-            RD_HIP(hipMemcpyAsync(h_i64.data(), io.sum, 2 * s8 * 8, hipMemcpyDeviceToHost, st));
-            RD_HIP(hipMemcpyAsync(h_i16.data(), io.mn, 2 * s2 * 2, hipMemcpyDeviceToHost, st));
-        }
-        RD_HIP(hipStreamSynchronize(st));
+        if ((rc = ea_fetch(st, io, nb, nlab, true, h))) return rc;
         for (int i = 0; i < nb; i++) {
-            const int r = members[i];
-            const EaSeq& d = desc[i];
-            const size_t L = (size_t)d.L, o = (size_t)ref_off[r], s = (size_t)d.lab;
-            status[r] = EA_OK;
-            score[r] = h_out[i].score;
-            n_skipped[r] = h_skip[i];
-            memcpy(fit_sums + 5 * (int64_t)r, h_out[i].sums, 40);
-            if (!L) continue;
-            memcpy(row_first + o, h_i32.data() + s, L * 4);
-            memcpy(row_last + o, h_i32.data() + s4 + s, L * 4);
-            memcpy(ev_start + o, h_i32.data() + 2 * s4 + s, L * 4);
-            memcpy(ev_end + o, h_i32.data() + 3 * s4 + s, L * 4);
-            memcpy(ev_sum + o, h_i64.data() + s, L * 8);
-            memcpy(ev_sumsq + o, h_i64.data() + s8 + s, L * 8);
-            memcpy(ev_min + o, h_i16.data() + s, L * 2);
-            memcpy(ev_max + o, h_i16.data() + s2 + s, L * 2);
+            ea_scatter(c.b, members[i], desc[i], i, h);
+            n_skipped[members[i]] = h.skip[i];
         }
     }
     if (plan.too_large) {
         const int r = (int)plan.first_too_large;
-        rd_set_error("rd_eventalign_events: read %d (%d events x %d bases) needs %lld bytes of workspace, over the budget of %lld; %d read(s) not "
-                     "aligned (status RD_EVAL_TOO_LARGE), the others were", r, n_events[r], ref_len[r],
-                     (long long)ear_read_bytes(n_events[r], ref_len[r]), (long long)budget_bytes, (int)plan.too_large);
-        return RD_ERR_NOMEM;
+        return ea_too_large("rd_eventalign_events", plan, n_events[r], "events", ref_len[r], ear_read_bytes(n_events[r], ref_len[r]), budget_bytes);
     }
     return RD_OK;
 }
