@@ -758,6 +758,53 @@ int rd_eventalign_host(const int16_t* raw, const int64_t* read_off, int n_reads,
                        int64_t* ev_sumsq, int16_t* ev_min, int16_t* ev_max, int64_t* fit_sums);
 int64_t rd_eventalign_workspace_bytes(int64_t n_rows, int64_t n_bases);
 
+/* ---- eventalign on sample rows in a band round a guide (eventalign.hip) ---------------------------------
+ * NO reference behaviour.  rd_eventalign over the states of a window of W = 64 (RD_EVAL_BAND_W) states that slides with a per-base guide:
+ * the accuracy of sample rows at a workspace of O(T + L) bytes a read.  Integer arithmetic only; met exactly.  Inputs, window [t_lo,
+ * t_hi), scale rule, model, zq, states 0 .. L + 1, the cell's cost, the strict tie-break, the end rule, the bounds and the outputs status,
+ * score, m2, d4, first_step, last_step, ev_*, fit_sums are rd_eventalign's.  What is new:
+ *   guide     guide[ref_off[r] + b], int32 in READ sample coordinates, one per base: the sample base b is expected to start at;
+ *             non-decreasing within a read (equal values and jumps are normal: it is what rd_eventalign_events returns as ev_start, where
+ *             a skipped base repeats a value)
+ *   window    g(t) = #{b : guide[b] <= t_lo + t};  lo(t) = min(max(g(t) - 31, 0), max(L + 2 - 64, 0)), non-decreasing;
+ *             win(t) = [lo(t), lo(t) + 63] within [0, L + 1]
+ *   path      V[0][s] = c(0, s) for s in {0, 1} and in win(0); every other state of the window starts at 2^30.  Row t >= 1, s in win(t):
+ *             stay = V[t-1][s] if s is in win(t-1), else 2^30; advance = V[t-1][s-1] if s - 1 >= lo(t) and s - 1 is in win(t-1), else
+ *             2^30 -- a state that has left the window is gone at once, the window's lowest state has no advance edge;
+ *             V = c + min(stay, advance), the advance only if STRICTLY smaller; one back-pointer bit.  Unreachable values may be computed
+ *             unmasked: one that started at 2^30 stays in (0.875 * 2^30, 2^31), a finite one below 0.625 * 2^30
+ *   end       rd_eventalign's rule over the states of {L, L + 1} that lie in win(T - 1), the other counting as 2^30.  If the chosen end
+ *             value is not finite (>= 3 * 2^28) the window lost the path: RD_EVAL_OFF_BAND, with the not-OK outputs of rd_eventalign
+ *   status    in this order: EMPTY, TOO_LONG, MAD_ZERO, NO_PATH (T < L), TOO_LARGE, OFF_BAND, OK
+ *   n_edge    per read: the bases b (state s = b + 1) whose rows touch the window's rim -- lo(last_step[b] - t_lo) == s (the lower rim)
+ *             or lo(first_step[b] - t_lo) + 63 == s (the upper rim); lo being monotone, that is "some row of the base sits on the rim".
+ *             0 for a read that is not OK
+ * IDENTITY.  If the path rd_eventalign finds on the same scale satisfies at every row t (lo(t) == 0 or s(t) > lo(t)) and s(t) <= lo(t) + 63,
+ * every output of this call equals rd_eventalign's: banded values are minima over a subset of the full DP's paths, they are equal along
+ * that path, and at every compare on it the edge that loses does not get better.  In particular L + 2 <= 64 gives rd_eventalign for
+ * any guide.  A result does not depend on the batch, the order, the budget or the launches.  RD_ERR_ARG before anything is launched:
+ * whatever rd_eventalign refuses; a null guide; a guide that decreases within a read.  n_reads == 0 is RD_OK.
+ *   rd_eventalign_banded        on the GPU; synchronous, uses the context's stream; budget_bytes and RD_ERR_NOMEM as rd_eventalign
+ *   rd_eventalign_banded_host   host, no GPU: the same rules (csrc/eventalign_rules.h) in a plain loop
+ *   rd_eventalign_banded_workspace_bytes   of a window of n_rows rows and n_bases bases, each term rounded up to 256: 4 n_rows (quantised
+ *                        samples) + 8 n_rows (back-pointers, one 64-bit word a row) + 4 n_rows (the window's lowest state per row)
+ *                        + 12 (n_bases + 2 + 128) (the states' constants) */
+#define RD_EVAL_OFF_BAND 6
+#define RD_EVAL_BAND_W 64
+int rd_eventalign_banded(rd_ctx* ctx, const int16_t* raw, const int64_t* read_off, int n_reads, const int64_t* t_lo, const int64_t* t_hi,
+                         const uint8_t* codes, const int64_t* ref_off, const int32_t* ref_len, const int32_t* guide, const int32_t* m2_in,
+                         const int32_t* d4_in, int k, const int32_t* lvl, const uint32_t* w, const int32_t* bias, int32_t lvl_bg, uint32_t w_bg,
+                         int32_t bias_bg, int64_t budget_bytes, int32_t* status, int64_t* score, int32_t* m2, int32_t* d4, int32_t* n_edge,
+                         int32_t* first_step, int32_t* last_step, int32_t* ev_start, int32_t* ev_end, int64_t* ev_sum, int64_t* ev_sumsq,
+                         int16_t* ev_min, int16_t* ev_max, int64_t* fit_sums);
+int rd_eventalign_banded_host(const int16_t* raw, const int64_t* read_off, int n_reads, const int64_t* t_lo, const int64_t* t_hi,
+                              const uint8_t* codes, const int64_t* ref_off, const int32_t* ref_len, const int32_t* guide, const int32_t* m2_in,
+                              const int32_t* d4_in, int k, const int32_t* lvl, const uint32_t* w, const int32_t* bias, int32_t lvl_bg, uint32_t w_bg,
+                              int32_t bias_bg, int32_t* status, int64_t* score, int32_t* m2, int32_t* d4, int32_t* n_edge, int32_t* first_step,
+                              int32_t* last_step, int32_t* ev_start, int32_t* ev_end, int64_t* ev_sum, int64_t* ev_sumsq, int16_t* ev_min,
+                              int16_t* ev_max, int64_t* fit_sums);
+int64_t rd_eventalign_banded_workspace_bytes(int64_t n_rows, int64_t n_bases);
+
 /* ---- eventalign on event rows: weighted rows and base skips (eventalign.hip) ------------------------------
  * NO reference behaviour.  rd_eventalign's Viterbi over lead, base 1 .. base L, trail, with rows that are a detector's EVENTS, each
  * weighted by its sample count, and a third predecessor that skips one base.  Integer arithmetic only; met exactly.  With one event per

@@ -116,6 +116,9 @@ SIGNATURES = {
     "rd_eventalign": (c_i, [c_vp, c_vp, c_vp, c_i] + [c_vp] * 7 + [c_i] + [c_vp] * 3 + [ctypes.c_int32, c_u32, ctypes.c_int32, c_i64] + [c_vp] * 13),
     "rd_eventalign_host": (c_i, [c_vp, c_vp, c_i] + [c_vp] * 7 + [c_i] + [c_vp] * 3 + [ctypes.c_int32, c_u32, ctypes.c_int32] + [c_vp] * 13),
     "rd_eventalign_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "rd_eventalign_banded": (c_i, [c_vp, c_vp, c_vp, c_i] + [c_vp] * 8 + [c_i] + [c_vp] * 3 + [ctypes.c_int32, c_u32, ctypes.c_int32, c_i64] + [c_vp] * 14),
+    "rd_eventalign_banded_host": (c_i, [c_vp, c_vp, c_i] + [c_vp] * 8 + [c_i] + [c_vp] * 3 + [ctypes.c_int32, c_u32, ctypes.c_int32] + [c_vp] * 14),
+    "rd_eventalign_banded_workspace_bytes": (c_i64, [c_i64, c_i64]),
     "rd_eventalign_events": (c_i, [c_vp, c_i] + [c_vp] * 14 + [c_i] + [c_vp] * 3 + [ctypes.c_int32, c_u32, ctypes.c_int32, c_i, c_i64] + [c_vp] * 12),
     "rd_eventalign_events_host": (c_i, [c_i] + [c_vp] * 14 + [c_i] + [c_vp] * 3 + [ctypes.c_int32, c_u32, ctypes.c_int32, c_i] + [c_vp] * 12),
     "rd_eventalign_events_workspace_bytes": (c_i64, [c_i64, c_i64]),

@@ -449,8 +449,9 @@ def sim_launch_bytes(k):
 
 
 # rd_eventalign per-read status (include/radian_hip.h RD_EVAL_*)
-EVAL_OK, EVAL_EMPTY, EVAL_TOO_LONG, EVAL_MAD_ZERO, EVAL_NO_PATH, EVAL_TOO_LARGE = 0, 1, 2, 3, 4, 5
-EVAL_STATUS_NAMES = ("ok", "empty", "too-long", "mad-zero", "no-path", "too-large")
+EVAL_OK, EVAL_EMPTY, EVAL_TOO_LONG, EVAL_MAD_ZERO, EVAL_NO_PATH, EVAL_TOO_LARGE, EVAL_OFF_BAND = 0, 1, 2, 3, 4, 5, 6
+EVAL_STATUS_NAMES = ("ok", "empty", "too-long", "mad-zero", "no-path", "too-large", "off-band")
+EVAL_BAND_W = 64   # states of rd_eventalign_banded's window (RD_EVAL_BAND_W)
 
 
 class EvalModel:
@@ -530,6 +531,43 @@ def eventalign_host(raws, seqs, model, t_lo=None, t_hi=None, m2=None, d4=None):
 def eventalign_workspace_bytes(n_rows, n_bases):
     """device workspace Backend.eventalign needs for one window of n_rows samples and n_bases bases (rd_eventalign_workspace_bytes)"""
     return int(_lib.load().rd_eventalign_workspace_bytes(int(n_rows), int(n_bases)))
+
+
+class EvalBandedResult(EvalResult):
+    """rd_eventalign_banded: an EvalResult (status may be EVAL_OFF_BAND) and n_edge (int32 per read: the bases whose rows touch the window's rim)"""
+    __slots__ = ("n_edge",)
+
+
+def _eval_banded_args(raws, seqs, guides, model, t_lo, t_hi, m2, d4):
+    """_eval_args with the guide (one int32 array per read, one value per base, read sample coordinates) behind ref_len and n_edge behind d4"""
+    keep, head, _, _ = _eval_args(raws, seqs, model, t_lo, t_hi, m2, d4)
+    n = len(raws)
+    if len(guides) != n or any(len(g) != len(q) for g, q in zip(guides, seqs)):
+        raise ValueError("a guide holds one value for every base of its read")
+    _, _, _, cut, outs = _eval_bases(seqs, n, (np.int32, np.int64, np.int32, np.int32, np.int32))
+    guide = np.concatenate([np.ascontiguousarray(g, dtype=np.int32).ravel() for g in guides] + [np.zeros(1, np.int32)])
+    return (keep, guide), (*head[:8], _p(guide), *head[8:]), outs, cut
+
+
+def _eval_banded_result(outs, cut, n):
+    base = _eval_result(outs[:4] + outs[5:], cut, n)
+    res = EvalBandedResult(base.status, base.score, base.m2, base.d4, base.fit_sums, base.first_step, base.last_step, base.events)
+    res.n_edge = outs[4][:n]
+    return res
+
+
+def eventalign_banded_host(raws, seqs, guides, model, t_lo=None, t_hi=None, m2=None, d4=None):
+    """Backend.eventalign_banded on the host (rd_eventalign_banded_host: the same rules in a plain loop; no GPU, no context)"""
+    L = _lib.load()
+    keep, head, outs, cut = _eval_banded_args(raws, seqs, guides, model, t_lo, t_hi, m2, d4)
+    if L.rd_eventalign_banded_host(*head, *[_p(b) for b in outs]) != 0:
+        raise RadianHipError(L.rd_last_error().decode())
+    return _eval_banded_result(outs, cut, len(raws))
+
+
+def eventalign_banded_workspace_bytes(n_rows, n_bases):
+    """device workspace Backend.eventalign_banded needs for one window of n_rows samples and n_bases bases (rd_eventalign_banded_workspace_bytes)"""
+    return int(_lib.load().rd_eventalign_banded_workspace_bytes(int(n_rows), int(n_bases)))
 
 
 class EvalRowsResult:
@@ -1854,6 +1892,20 @@ class Backend:
 
     eventalign_events_host = staticmethod(eventalign_events_host)
     eventalign_events_workspace_bytes = staticmethod(eventalign_events_workspace_bytes)
+
+    def eventalign_banded(self, raws, seqs, guides, model, t_lo=None, t_hi=None, m2=None, d4=None, budget_bytes=0, allow_too_large=False):
+        """eventalign over a window of EVAL_BAND_W states that slides with a guide (rd_eventalign_banded, on the GPU):
+        guides -- per read one int32 per base, the read sample the base is expected to start at, non-decreasing (what eventalign_events
+        returns as events[r]["start"]); everything else as eventalign.  Where eventalign's own path stays inside the window the result is
+        eventalign's; a read whose path the window lost has status EVAL_OFF_BAND.  -> EvalBandedResult."""
+        keep, head, outs, cut = _eval_banded_args(raws, seqs, guides, model, t_lo, t_hi, m2, d4)
+        rc = self._L.rd_eventalign_banded(self._h, *head, int(budget_bytes), *[_p(b) for b in outs])
+        if rc != 0 and not (allow_too_large and rc == -4 and (outs[0][:len(raws)] == EVAL_TOO_LARGE).any()):
+            self._check(rc)
+        return _eval_banded_result(outs, cut, len(raws))
+
+    eventalign_banded_host = staticmethod(eventalign_banded_host)
+    eventalign_banded_workspace_bytes = staticmethod(eventalign_banded_workspace_bytes)
 
     # ------------------------------------------------------------------ signal against a panel of targets (DESIGN.md section 25)
     def sigmap(self, raw, targets, model, q_lo, q_hi, sc_lo=None, sc_hi=None, m2=None, d4=None, s_lo=None, s_hi=None, n_best=1,

@@ -35,6 +35,11 @@
 // per read, 64 rows of back-pointer words staged in LDS, a row a step), ear_reduce_kernel (one lane per base over its rows' records) and
 // ea_sums_kernel as it is.
 //
+// rd_eventalign_banded is rd_eventalign over a window of 64 states that slides with a per-base guide: eab_rows_kernel
+// (zq, the window's lowest state per row, the states' constants), eab_dp_kernel (one wave per read, state s in lane s & 63, no band_sweep.h),
+// eab_tb_kernel (ea_tb_kernel's walk on one 64-bit word a row), eab_edge_kernel (the bases on the window's rim), then ev_stats_kernel and
+// ea_sums_kernel as they are.
+//
 // The two row kinds differ in their DP (one predecessor or two, one back-pointer bit or two) and in their traceback (a ballot walk or an
 // LDS walk); DESIGN.md section 28 says why.  What surrounds the DPs exists once (section 29): EaBases, the bases side of a call with its
 // checks, blank outputs and host fit sums; EaBand, the read fields and thread registers of both sweep policies; EaIo, the launch's io
@@ -421,6 +426,126 @@ extern "C" int rd_eventalign_events_host(int n_reads, const int64_t* n_samples, 
         }
         ea_host_sums(c.b, r);
     }
+    return RD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ sample rows in a band
+// rd_eventalign_banded (include/radian_hip.h): rd_eventalign's rows, cost and tie-break over the EAB_W states of a
+// window that slides with a per-base guide (eventalign_rules.h: eab_count, eab_lo).  A state outside the row's window does not exist: the
+// window's lowest state has no advance edge, a state that entered the window this row has no stay edge.  One 64-bit back-pointer word a
+// row, bit s & 63.  Only the guide, the window and the rim count are here: everything else is EaCall's.
+namespace {
+
+int eab_check_guide(const char* who, const EaCall& c, const int32_t* guide, int32_t* n_edge, int64_t n_bases)
+{
+    if (c.n_reads == 0) return RD_OK;
+    RD_REQUIRE(n_edge, "%s: null output", who);
+    RD_REQUIRE(guide || !n_bases, "%s: null guide", who);
+    for (int r = 0; r < c.n_reads; r++)
+        for (int i = 1; i < c.b.ref_len[r]; i++)
+            RD_REQUIRE(guide[c.b.ref_off[r] + i] >= guide[c.b.ref_off[r] + i - 1], "%s: the guide of read %d decreases at base %d", who, r, i);
+    return RD_OK;
+}
+
+size_t eab_lo_bytes(int64_t T) { return align_up((size_t)T * 4, 256); }
+size_t eab_bp_bytes(int64_t T) { return align_up((size_t)T * 8, 256); }
+int64_t eab_tab_entries(int64_t L) { return L + 2 + 2 * EAB_W; }   // a lane prefetches the constants of its state + 64
+size_t eab_tab_bytes(int64_t L) { return align_up((size_t)eab_tab_entries(L) * 12, 256); }
+size_t eab_read_bytes(int64_t T, int64_t L) { return ea_zq_bytes(T) + eab_bp_bytes(T) + eab_lo_bytes(T) + eab_tab_bytes(L); }
+
+}  // namespace
+
+extern "C" int64_t rd_eventalign_banded_workspace_bytes(int64_t n_rows, int64_t n_bases)
+{
+    if (n_rows < 0 || n_bases < 0) return -1;
+    return (int64_t)eab_read_bytes(n_rows, n_bases);
+}
+
+extern "C" int rd_eventalign_banded_host(const int16_t* raw, const int64_t* read_off, int n_reads, const int64_t* t_lo, const int64_t* t_hi,
+                                         const uint8_t* codes, const int64_t* ref_off, const int32_t* ref_len, const int32_t* guide,
+                                         const int32_t* m2_in, const int32_t* d4_in, int k, const int32_t* lvl, const uint32_t* w, const int32_t* bias,
+                                         int32_t lvl_bg, uint32_t w_bg, int32_t bias_bg, int32_t* status, int64_t* score, int32_t* m2, int32_t* d4,
+                                         int32_t* n_edge, int32_t* first_step, int32_t* last_step, int32_t* ev_start, int32_t* ev_end, int64_t* ev_sum,
+                                         int64_t* ev_sumsq, int16_t* ev_min, int16_t* ev_max, int64_t* fit_sums)
+{
+    const EaCall c{raw, read_off, t_lo, t_hi, n_reads,
+                   EaBases{codes, ref_off, ref_len, m2_in, d4_in, EaModel{k, lvl, w, bias, EaState{lvl_bg, w_bg, bias_bg}}, status, score, first_step,
+                           last_step, ev_start, ev_end, ev_sum, ev_sumsq, ev_min, ev_max, fit_sums},
+                   m2, d4};
+    int64_t n_bases = 0;
+    int rc = ea_check_args("rd_eventalign_banded_host", c, &n_bases);
+    if (!rc) rc = eab_check_guide("rd_eventalign_banded_host", c, guide, n_edge, n_bases);
+    if (rc || n_reads == 0) return rc;
+    std::vector<int64_t> cnt;
+    std::vector<int32_t> zq, V, lo_t, ev_status(n_reads);
+    std::vector<EaState> st;
+    std::vector<uint64_t> bp;
+    for (int r = 0; r < n_reads; r++) {
+        const int64_t T = t_hi[r] - t_lo[r], L = ref_len[r], S = L + 2, o = ref_off[r];
+        const int16_t* x = raw + read_off[r] + t_lo[r];
+        int32_t um2 = m2_in[r], ud4 = d4_in[r];
+        ev_status[r] = 1;
+        n_edge[r] = 0;
+        if (T <= 0 || T > EA_MAX_T) {
+            ea_blank(c, r, ea_status(T, L, 1), 0, 0);
+            continue;
+        }
+        if (ud4 == 0) ea_host_scale(x, T, cnt, &um2, &ud4);
+        const int stat = ea_status(T, L, ud4);
+        ea_blank(c, r, stat, um2, ud4);
+        if (stat != EA_OK) continue;
+        zq.resize(T);
+        lo_t.resize(T);
+        int64_t g = 0;
+        for (int64_t t = 0; t < T; t++) {
+            zq[t] = ea_quant(x[t], um2, ud4);
+            while (g < L && guide[o + g] <= t_lo[r] + t) g++;
+            lo_t[t] = eab_lo(g, L);
+        }
+        ea_host_states(c.b, r, st);
+        V.assign(S, EA_INF);   // a state above every window so far still holds this
+        bp.assign((size_t)T, 0);
+        for (int64_t s = 0; s < 2; s++)
+            if (s >= lo_t[0]) V[s] = ea_cost(zq[0], st[s].lvl, st[s].w, st[s].bias);   // (s <= 1 is below the window's top)
+        for (int64_t t = 1; t < T; t++) {
+            const int64_t lo = lo_t[t], hi = std::min<int64_t>(lo + EAB_W - 1, S - 1);
+            for (int64_t s = hi; s >= lo; s--) {
+                int32_t best = V[s];
+                if (s > lo && ea_advance(V[s], V[s - 1])) {
+                    best = V[s - 1];
+                    bp[(size_t)t] |= (uint64_t)1 << (s & (EAB_W - 1));
+                }
+                V[s] = ea_cost(zq[t], st[s].lvl, st[s].w, st[s].bias) + best;
+            }
+        }
+        const int64_t hi = std::min<int64_t>((int64_t)lo_t[T - 1] + EAB_W - 1, S - 1);
+        const int32_t v_trail = L + 1 <= hi ? V[L + 1] : EA_INF, v_last = L <= hi ? V[L] : EA_INF;   // (the window never starts above L)
+        int64_t s = ea_ends_in_trail(v_trail, v_last) ? L + 1 : L;
+        const int32_t end = s == L + 1 ? v_trail : v_last;
+        if (!eab_finite(end)) {
+            status[r] = EA_OFF_BAND;
+            continue;
+        }
+        ev_status[r] = 0;
+        score[r] = end;
+        const int32_t off = (int32_t)t_lo[r];
+        if (s >= 1 && s <= L) last_step[o + s - 1] = (int32_t)(T - 1) + off;
+        for (int64_t t = T - 1; t > 0; t--) {
+            if (!((bp[(size_t)t] >> (s & (EAB_W - 1))) & 1)) continue;
+            if (s <= L) first_step[o + s - 1] = (int32_t)t + off;
+            if (s - 1 >= 1) last_step[o + s - 2] = (int32_t)t - 1 + off;
+            s--;
+        }
+        if (s == 1 && L >= 1) first_step[o] = off;
+        for (int64_t b = 0; b < L; b++)
+            n_edge[r] += eab_on_rim((int32_t)b + 1, lo_t[last_step[o + b] - off], lo_t[first_step[o + b] - off]);
+    }
+    if (n_bases &&
+        (rc = rd_event_stats_host(raw, read_off, n_reads, first_step, last_step, ref_off, ref_len, ev_status.data(), ev_start, ev_end, ev_sum, ev_sumsq,
+                                  ev_min, ev_max)))
+        return rc;
+    for (int r = 0; r < n_reads; r++)
+        if (status[r] == EA_OK) ea_host_sums(c.b, r);
     return RD_OK;
 }
 
@@ -1142,6 +1267,311 @@ extern "C" int rd_eventalign_events(rd_ctx* ctx, int n_reads, const int64_t* n_s
     if (plan.too_large) {
         const int r = (int)plan.first_too_large;
         return ea_too_large("rd_eventalign_events", plan, n_events[r], "events", ref_len[r], ear_read_bytes(n_events[r], ref_len[r]), budget_bytes);
+    }
+    return RD_OK;
+}
+
+// ---- sample rows in a band (rd_eventalign_banded).  An EaSeq of these kernels: zq the quantised samples, bp one
+// 64-bit word a row, col the window's lowest state per row (int32) followed, at the next multiple of 256 bytes, by the state table: lvl,
+// w and bias of n = L + 2 + 128 states, three arrays of n, zeros past the read (a state that costs nothing and is never read out).
+namespace {
+
+constexpr int EAB_WAVES = 4;   // reads of a DP workgroup, one wave each, no barrier
+
+__device__ __forceinline__ const int32_t* eab_tab(const uint8_t* ws, const EaSeq& q) { return (const int32_t*)(ws + q.col + (((int64_t)q.T * 4 + 255) & ~(int64_t)255)); }
+
+// grid (ceil(max(T, L + 130) / 256), reads): zq and the window's lowest state of every row, the constants of every state
+__global__ __launch_bounds__(256) void eab_rows_kernel(const EaSeq* __restrict__ seqs, const int16_t* __restrict__ raw, const uint8_t* __restrict__ codes,
+                                                       const int32_t* __restrict__ guide, const int32_t* __restrict__ lvl_t, const uint32_t* __restrict__ w_t,
+                                                       const int32_t* __restrict__ bias_t, EaState bg, int k, uint8_t* __restrict__ ws,
+                                                       int32_t* __restrict__ fin)
+{
+    const EaSeq q = seqs[blockIdx.y];
+    if (blockIdx.x == 0 && threadIdx.x < 2) fin[2 * (int64_t)blockIdx.y + threadIdx.x] = EA_INF;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t < q.T) {
+        ((int32_t*)(ws + q.zq))[t] = ea_quant(raw[q.raw0 + t], q.m2, q.d4);
+        ((int32_t*)(ws + q.col))[t] = eab_lo(eab_count(guide + q.lab, q.L, (int64_t)q.t_lo + t), q.L);
+    }
+    if (t < (int64_t)q.L + 2 + 2 * EAB_W) {
+        EaState st{0, 0, 0};
+        if (t < q.L + 2) st = ea_state((int32_t)t, q.L, codes + q.codes, k, lvl_t, w_t, bias_t, bg);
+        int32_t* tab = (int32_t*)eab_tab(ws, q);
+        const int64_t n = (int64_t)q.L + 2 + 2 * EAB_W;
+        tab[t] = st.lvl;
+        tab[n + t] = (int32_t)st.w;
+        tab[2 * n + t] = st.bias;
+    }
+}
+
+// lane l receives v of lane l - 1, lane 0 that of lane 63 (DPP wave_ror:1)
+__device__ __forceinline__ int32_t lane_ror1(int32_t v) { return __builtin_amdgcn_update_dpp(v, v, 0x13C, 0xf, 0xf, false); }
+
+// One wave per read.  Lane l holds the window's state s with s & 63 == l: its value and its constants, and, prefetched, the constants of
+// s + 64, which the lane takes when the window's lowest state passes s (the load of the state after that is issued then and is not waited
+// for until the lane recycles again, some thirty rows a state later).  zq and the window's lowest state of 64 rows sit in two registers
+// across the wave, loaded a tile ahead, and reach the row as scalars by v_readlane; the row's back-pointer word is the ballot of "advance
+// taken", kept by lane t & 63 and stored 512 consecutive bytes every 64 rows.
+__global__ __launch_bounds__(64 * EAB_WAVES) void eab_dp_kernel(const EaSeq* __restrict__ seqs, int n_reads, uint8_t* __restrict__ ws, int32_t* __restrict__ fin)
+{
+    const int p = __builtin_amdgcn_readfirstlane(blockIdx.x * EAB_WAVES + ((int)threadIdx.x >> 6)), lane = threadIdx.x & 63;   // (the wave's: a scalar)
+    if (p >= n_reads) return;
+    const EaSeq q = seqs[p];
+    const int T = q.T, L = q.L;
+    const int32_t* __restrict__ zq = (const int32_t*)(ws + q.zq);
+    const int32_t* __restrict__ lo_t = (const int32_t*)(ws + q.col);
+    const int n_tab = L + 2 + 2 * EAB_W;
+    const int32_t* __restrict__ t_lvl = eab_tab(ws, q);
+    const int32_t* __restrict__ t_w = t_lvl + n_tab;
+    const int32_t* __restrict__ t_bias = t_w + n_tab;
+    unsigned long long* __restrict__ bp = (unsigned long long*)(ws + q.bp);
+    int32_t tz = lane < T ? zq[lane] : 0, tl = lane < T ? lo_t[lane] : 0;
+    int lo = __builtin_amdgcn_readfirstlane(tl);
+    int s = lo + ((lane - lo) & (EAB_W - 1));
+    int32_t lv = t_lvl[s], bi = t_bias[s], nlv = t_lvl[s + EAB_W], nbi = t_bias[s + EAB_W];   // the state's constants and, prefetched, those of the state 64 above
+    uint32_t wt = (uint32_t)t_w[s], nwt = (uint32_t)t_w[s + EAB_W];
+    // row 0: states 0 and 1 start the path, every other state of the window is unreachable.  (Lane 0's sample by its number, read before
+    // the lanes part: the first ACTIVE lane of the branch is lane 1 when the window starts at state 1)
+    const int z0 = __builtin_amdgcn_readlane(tz, 0);
+    int32_t v = s <= 1 ? ea_cost(z0, lv, wt, bi) : EA_INF;
+    unsigned long long mine = 0;
+    // every load so far has landed before the first row: a row then waits for no load (the compiler would otherwise let the row wait until
+    // few enough loads are in flight for these to be among the landed, and with them for a recycle's prefetch)
+    __builtin_amdgcn_s_waitcnt(0);
+    for (int tbase = 0; tbase < T; tbase += 64) {
+        int32_t nz = 0, nl = 0;   // the next tile's rows
+        if (tbase + 64 + lane < T) {
+            nz = zq[tbase + 64 + lane];
+            nl = lo_t[tbase + 64 + lane];
+        }
+        const int rows = T - tbase < 64 ? T - tbase : 64;
+        for (int r = __builtin_amdgcn_readfirstlane(tbase == 0 ? 1 : 0); r < rows; r++) {   // (row 0 is done)
+            const int z = __builtin_amdgcn_readlane(tz, r), l = __builtin_amdgcn_readlane(tl, r);
+            if (l != lo) {   // (wave-uniform; about once in thirty rows)
+                lo = l;
+                // A lane whose state fell out takes its state + 64 and the constants it had prefetched.  Every lane loads its next constants
+                // (those it holds already, or the new ones), so the load lands in the registers themselves and nothing here waits for it.
+                // After a jump of more than 64 states in one row the same again, now waiting for each load in turn
+                do {
+                    const bool out = s < lo;
+                    s = out ? s + EAB_W : s;
+                    lv = out ? nlv : lv;
+                    wt = out ? nwt : wt;
+                    bi = out ? nbi : bi;
+                    v = out ? EA_INF : v;
+                    nlv = t_lvl[s + EAB_W];
+                    nwt = (uint32_t)t_w[s + EAB_W];
+                    nbi = t_bias[s + EAB_W];
+                } while (__ballot(s < lo));
+            }
+            const int32_t left = lane_ror1(v), adv = s == lo ? EA_INF : left;
+            const bool take = ea_advance(v, adv);
+            v = ea_cost(z, lv, wt, bi) + (take ? adv : v);
+            const unsigned long long word = __ballot(take);
+            if (lane == r) mine = word;
+        }
+        if (tbase + lane < T) bp[tbase + lane] = mine;
+        tz = nz;
+        tl = nl;
+    }
+    // the two states the path may end in, where the last window holds them
+    if (s == L + 1) fin[2 * (int64_t)p] = v;
+    if (s == L) fin[2 * (int64_t)p + 1] = v;
+}
+
+// one wave per read: ea_tb_kernel's ballot walk on one 64-bit word a row.  A read whose end value is not finite is flagged, its steps blank
+__global__ __launch_bounds__(64) void eab_tb_kernel(const EaSeq* __restrict__ seqs, const uint8_t* __restrict__ ws, const int32_t* __restrict__ fin,
+                                                    EaOut* __restrict__ out, int32_t* __restrict__ lost, int32_t* __restrict__ first,
+                                                    int32_t* __restrict__ last)
+{
+    const int p = blockIdx.x, lane = threadIdx.x;
+    const EaSeq q = seqs[p];
+    const int L = q.L, off = q.t_lo;
+    const int32_t v_trail = fin[2 * (int64_t)p], v_last = fin[2 * (int64_t)p + 1];
+    int s = ea_ends_in_trail(v_trail, v_last) ? L + 1 : L;   // (s, t and r0 below are the same in every lane)
+    const int32_t end = s == L + 1 ? v_trail : v_last;
+    int32_t* fs = first + q.lab;
+    int32_t* ls = last + q.lab;
+    if (!eab_finite(end)) {
+        for (int b = lane; b < L; b += 64) fs[b] = ls[b] = -1;
+        if (lane == 0) {
+            lost[p] = 1;
+            out[p].score = 0;
+        }
+        return;
+    }
+    const unsigned long long* __restrict__ bp = (const unsigned long long*)(ws + q.bp);
+    int t = q.T - 1;
+    if (lane == 0) {
+        lost[p] = 0;
+        out[p].score = end;
+        if (s >= 1 && s <= L) ls[s - 1] = t + off;
+    }
+    while (t > 0) {
+        const int n = t < 64 ? t : 64;
+        const unsigned long long a = lane < n ? bp[t - lane] : 0ull;   // lane r holds the word of row t - r
+        int r0 = 0;   // rows t .. t - r0 + 1 are walked
+        while (r0 < n && s > 0) {
+            const unsigned long long m = __ballot(lane >= r0 && lane < n && ((a >> (s & (EAB_W - 1))) & 1ull));
+            if (m == 0) {   // the path stays in s for the rest of these rows
+                r0 = n;
+                break;
+            }
+            const int r1 = __ffsll((long long)m) - 1, tt = t - r1;   // the nearest row that was entered from s - 1
+            if (lane == 0) {
+                if (s <= L) fs[s - 1] = tt + off;
+                if (s - 1 >= 1) ls[s - 2] = tt - 1 + off;
+            }
+            s--;
+            r0 = r1 + 1;
+        }
+        if (s == 0) break;   // the lead: nothing is left to record
+        t -= r0;
+    }
+    if (lane == 0 && s == 1 && L >= 1) fs[0] = off;
+}
+
+// one wave per read, a lane per base: the bases whose rows touch the window's rim
+__global__ __launch_bounds__(64) void eab_edge_kernel(const EaSeq* __restrict__ seqs, const uint8_t* __restrict__ ws, const int32_t* __restrict__ lost,
+                                                      const int32_t* __restrict__ first, const int32_t* __restrict__ last, int32_t* __restrict__ n_edge)
+{
+    const int p = blockIdx.x, lane = threadIdx.x;
+    const EaSeq q = seqs[p];
+    const int32_t* __restrict__ lo_t = (const int32_t*)(ws + q.col);
+    int cnt = 0;
+    if (!lost[p])
+        for (int b = lane; b < q.L; b += 64) {
+            const int f = min(max(first[q.lab + b] - q.t_lo, 0), q.T - 1), l = min(max(last[q.lab + b] - q.t_lo, 0), q.T - 1);   // (a walked path leaves them inside)
+            cnt += eab_on_rim(b + 1, lo_t[l], lo_t[f]) ? 1 : 0;
+        }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d);
+    if (lane == 0) n_edge[p] = cnt;
+}
+
+}  // namespace
+
+extern "C" int rd_eventalign_banded(rd_ctx* ctx, const int16_t* raw, const int64_t* read_off, int n_reads, const int64_t* t_lo, const int64_t* t_hi,
+                                    const uint8_t* codes, const int64_t* ref_off, const int32_t* ref_len, const int32_t* guide, const int32_t* m2_in,
+                                    const int32_t* d4_in, int k, const int32_t* lvl, const uint32_t* w, const int32_t* bias, int32_t lvl_bg, uint32_t w_bg,
+                                    int32_t bias_bg, int64_t budget_bytes, int32_t* status, int64_t* score, int32_t* m2, int32_t* d4, int32_t* n_edge,
+                                    int32_t* first_step, int32_t* last_step, int32_t* ev_start, int32_t* ev_end, int64_t* ev_sum, int64_t* ev_sumsq,
+                                    int16_t* ev_min, int16_t* ev_max, int64_t* fit_sums)
+{
+    RD_REQUIRE(ctx, "rd_eventalign_banded: null context");
+    RD_REQUIRE(budget_bytes >= 0, "rd_eventalign_banded: negative budget");
+    const EaCall c{raw, read_off, t_lo, t_hi, n_reads,
+                   EaBases{codes, ref_off, ref_len, m2_in, d4_in, EaModel{k, lvl, w, bias, EaState{lvl_bg, w_bg, bias_bg}}, status, score, first_step,
+                           last_step, ev_start, ev_end, ev_sum, ev_sumsq, ev_min, ev_max, fit_sums},
+                   m2, d4};
+    int64_t n_bases = 0;
+    int rc = ea_check_args("rd_eventalign_banded", c, &n_bases);
+    if (!rc) rc = eab_check_guide("rd_eventalign_banded", c, guide, n_edge, n_bases);
+    if (rc || n_reads == 0) return rc;
+    RD_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const int64_t lo = read_off[0], n_samples = read_off[n_reads] - lo;
+    if (ctx->ws_raw.reserve((size_t)n_samples * 2 + 16) || ctx->ws_labels.reserve((size_t)n_bases + 16)) return RD_ERR_NOMEM;
+    const int16_t* d_raw = ctx->ws_raw.as<int16_t>();
+    const uint8_t* d_codes = ctx->ws_labels.as<uint8_t>();
+    if (n_samples) RD_HIP(hipMemcpyAsync(ctx->ws_raw.p, raw + lo, (size_t)n_samples * 2, hipMemcpyHostToDevice, st));
+    if (n_bases) RD_HIP(hipMemcpyAsync(ctx->ws_labels.p, codes, (size_t)n_bases, hipMemcpyHostToDevice, st));
+    KmerTables tab;
+    if ((rc = signal_upload_tables(ctx, st, k, lvl, w, bias, 0, &tab))) return rc;
+    std::vector<int64_t> off(n_reads + 1);
+    for (int r = 0; r <= n_reads; r++) off[r] = read_off[r] - lo;
+    std::vector<SignalScaleIn> scin(n_reads);
+    std::vector<int32_t> scale;
+    for (int r = 0; r < n_reads; r++) scin[r] = signal_scale_in(off[r] + t_lo[r], t_hi[r] - t_lo[r], t_hi[r] - t_lo[r], EA_MAX_T, m2_in[r], d4_in[r]);
+    if ((rc = signal_scales(ctx, st, d_raw, scin, EA_MAX_T, scale))) return rc;
+    for (int r = 0; r < n_reads; r++) {
+        const int stat = ea_status(t_hi[r] - t_lo[r], ref_len[r], scale[2 * (size_t)r + 1]);
+        ea_blank(c, r, stat == EA_OK ? EA_TOO_LARGE : stat, scale[2 * (size_t)r], scale[2 * (size_t)r + 1]);   // OK: until its launch has run
+        n_edge[r] = 0;
+    }
+    if ((rc = rd_resolve_budget(&budget_bytes, ctx->ws_align.cap))) return rc;
+    const BudgetPlan plan = rd_plan_budget(n_reads, nullptr, budget_bytes, 0, false,
+                                           [&](int r, int) { return status[r] == EA_TOO_LARGE ? (int64_t)eab_read_bytes(t_hi[r] - t_lo[r], ref_len[r]) : (int64_t)-1; },
+                                           [](int, int, int64_t count, int64_t) { return count >= EA_MAX_LAUNCH; });
+    if (plan.max_bytes && ctx->ws_align.reserve_exact((size_t)plan.max_bytes, "rd_eventalign_banded")) return RD_ERR_NOMEM;
+    std::vector<EaSeq> desc;
+    EaFetched h;
+    std::vector<int32_t> ev_len, ev_status, p_guide, rim;
+    std::vector<int64_t> ev_lab;
+    for (auto [k0, k1] : plan.launches) {
+        const int nb = (int)(k1 - k0);
+        const int32_t* members = plan.run.data() + k0;
+        const int r_lo = members[0], r_hi = members[nb - 1] + 1;   // the launch's reads lie in [r_lo, r_hi) of the call's
+        desc.resize(nb);
+        ev_len.assign(r_hi - r_lo, 0);
+        ev_lab.assign(r_hi - r_lo, 0);
+        ev_status.assign(r_hi - r_lo, 0);
+        p_guide.clear();
+        Carve ws;   // (dry: the descriptors hold offsets into ws_align)
+        int64_t nlab = 0, max_n = 0;
+        for (int i = 0; i < nb; i++) {
+            const int r = members[i];
+            EaSeq& d = desc[i];
+            d.raw0 = off[r] + t_lo[r];
+            d.codes = ref_off[r];
+            d.lab = nlab;
+            d.T = (int32_t)(t_hi[r] - t_lo[r]);
+            d.L = ref_len[r];
+            d.m2 = m2[r];
+            d.d4 = d4[r];
+            d.t_lo = (int32_t)t_lo[r];
+            d.n_win = 0;
+            ea_place(ws, d, ea_zq_bytes(d.T), eab_bp_bytes(d.T), eab_lo_bytes(d.T) + eab_tab_bytes(d.L));
+            p_guide.insert(p_guide.end(), guide + ref_off[r], guide + ref_off[r] + d.L);   // the launch's guides, the members' back to back
+            ev_len[r - r_lo] = d.L;
+            ev_lab[r - r_lo] = d.lab;
+            nlab += d.L;
+            max_n = std::max<int64_t>(max_n, std::max<int64_t>(d.T, eab_tab_entries(d.L)));
+        }
+        if ((rc = rd_carve_check("rd_eventalign_banded", ws, ctx->ws_align.cap))) return rc;
+        EaIo io;
+        int32_t* d_guide = nullptr;
+        // the io block with two int32 per read in the skip counts' place (rim count, lost flag), and the launch's guides behind it
+        if (rd_carve(ctx->ws_eval, [&](Carve& cv) {
+                ea_io_layout(cv, nb, nlab, 2 * nb, &io);
+                d_guide = cv.take<int32_t>((size_t)nlab);
+            }))
+            return RD_ERR_NOMEM;
+        int32_t *d_edge = io.nskip, *d_lost = io.nskip + nb;
+        uint8_t* dws = ctx->ws_align.as<uint8_t>();
+        RD_HIP(hipMemcpyAsync(io.seqs, desc.data(), (size_t)nb * sizeof(EaSeq), hipMemcpyHostToDevice, st));
+        if (nlab) RD_HIP(hipMemcpyAsync(d_guide, p_guide.data(), (size_t)nlab * 4, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(eab_rows_kernel, dim3((unsigned)((max_n + 255) / 256), nb), dim3(256), 0, st, io.seqs, d_raw, d_codes, d_guide, tab.lvl, tab.w,
+                           tab.bias, c.b.m.bg, k, dws, io.fin);
+        RD_HIP(hipGetLastError());
+        hipLaunchKernelGGL(eab_dp_kernel, dim3((unsigned)((nb + EAB_WAVES - 1) / EAB_WAVES)), dim3(64 * EAB_WAVES), 0, st, io.seqs, nb, dws, io.fin);
+        RD_HIP(hipGetLastError());
+        hipLaunchKernelGGL(eab_tb_kernel, dim3(nb), dim3(64), 0, st, io.seqs, dws, io.fin, io.out, d_lost, io.first, io.last);
+        RD_HIP(hipGetLastError());
+        hipLaunchKernelGGL(eab_edge_kernel, dim3(nb), dim3(64), 0, st, io.seqs, dws, d_lost, io.first, io.last, d_edge);
+        RD_HIP(hipGetLastError());
+        if ((rc = rd_event_stats_dev(ctx, st, d_raw, off.data() + r_lo, r_hi - r_lo, io.first, io.last, ev_lab.data(), ev_len.data(), ev_status.data(),
+                                     io.start, io.end, io.sum, io.sumsq, io.mn, io.mx)))
+            return rc;
+        hipLaunchKernelGGL(ea_sums_kernel, dim3(nb), dim3(256), 0, st, io.seqs, d_codes, tab.lvl, k, io.start, io.end, io.sum, io.out);
+        RD_HIP(hipGetLastError());
+        rim.resize(2 * (size_t)nb);
+        RD_HIP(hipMemcpyAsync(rim.data(), io.nskip, 2 * (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+        if ((rc = ea_fetch(st, io, nb, nlab, false, h))) return rc;
+        for (int i = 0; i < nb; i++) {
+            const int r = members[i];
+            if (rim[(size_t)nb + i]) {   // the window lost the path: the not-OK outputs, the scale as used
+                ea_blank(c, r, EA_OFF_BAND, m2[r], d4[r]);
+                continue;
+            }
+            ea_scatter(c.b, r, desc[i], i, h);
+            n_edge[r] = rim[i];
+        }
+    }
+    if (plan.too_large) {
+        const int r = (int)plan.first_too_large;
+        const int64_t T = t_hi[r] - t_lo[r];
+        return ea_too_large("rd_eventalign_banded", plan, (long long)T, "samples", ref_len[r], eab_read_bytes(T, ref_len[r]), budget_bytes);
     }
     return RD_OK;
 }

@@ -120,3 +120,34 @@ EA_HD inline int32_t ear_best(int32_t stay, int32_t adv, int32_t skp, bool skips
     *code = k ? EAR_SKIP : a ? EAR_ADV : EAR_STAY;
     return k ? skp : b2;
 }
+
+// ---- sample rows in a band round a guide (include/radian_hip.h, rd_eventalign_banded): rd_eventalign's Viterbi over
+// the states of a 64-state window that slides with a per-base guide (the sample each base is expected to start at)
+constexpr int EA_OFF_BAND = 6;            // the chosen end value is not finite: the window lost the path
+constexpr int EAB_W = 64;                 // states of the window: one wave, one back-pointer word of 64 bits a row
+constexpr int32_t EAB_FINITE = 3 << 28;   // a value at or above this started at 2^30 (finite values stay below 0.625 * 2^30)
+
+// the window's lowest state at a row where g bases have guide <= the row's sample; L bases.  Non-decreasing in g
+EA_HD inline int32_t eab_lo(int64_t g, int64_t L)
+{
+    const int64_t a = g - (EAB_W / 2 - 1) > 0 ? g - (EAB_W / 2 - 1) : 0, top = L + 2 - EAB_W > 0 ? L + 2 - EAB_W : 0;
+    return (int32_t)(a < top ? a : top);
+}
+
+// g(t): the bases of guide[0 .. L) (non-decreasing) that are <= x, the row's sample in read coordinates
+EA_HD inline int32_t eab_count(const int32_t* guide, int32_t L, int64_t x)
+{
+    int32_t lo = 0, hi = L;   // guide[lo - 1] <= x < guide[hi]
+    while (lo < hi) {
+        const int32_t mid = lo + (hi - lo) / 2;
+        if (guide[mid] <= x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// the end of a banded pass: `in_win` tells whether states L + 1 and L lie in the last row's window (the other counts as 2^30)
+EA_HD inline bool eab_finite(int32_t v) { return v < EAB_FINITE; }
+
+// does base b (state s = b + 1) touch the window's rim?  lo_last / lo_first: the window's lowest state at the base's last and first row
+EA_HD inline bool eab_on_rim(int32_t s, int32_t lo_last, int32_t lo_first) { return lo_last == s || lo_first + EAB_W - 1 == s; }

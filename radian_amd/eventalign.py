@@ -5,7 +5,7 @@ weights take part.  fast5, `map`'s read_ref.tsv and a pore-model table in, one e
     python -m radian_amd.eventalign fast5_dir read_ref.tsv -o out_dir (--kmer-table T.tsv [--fill-missing] | --model-seed S --kmer 5)
            [--bounds PATH] [--start-slack 32] [--rescale-rounds 2] [--bg-sd 1.0]
            [--summary PATH] [--kmer-table-out PATH] [--device N] [--batch-reads R] [--budget-bytes B]
-           [--events [--w1 4 --t1 2.5 --w2 12 --t2 5.0 --var-floor 1] [--skip-penalty 96 | --no-skips]]
+           [--events [--w1 4 --t1 2.5 --w2 12 --t2 5.0 --var-floor 1] [--skip-penalty 96 | --no-skips] [--refine]]
 
 NO reference behaviour.  The read's span -- column 3 of read_ref.tsv, reversed into decode order, U = T -- is aligned to the samples by a
 Viterbi pass over the states lead, base 1 .. base L, trail (rd_eventalign; the contract is in include/radian_hip.h):
@@ -41,7 +41,16 @@ A read is `ok`, or is counted and left out: `no-reference`, `has-N`, `signal` (e
                     share of bases skipped.  `no-path` then means fewer than (L + 1) / 2 events (L with --no-skips).  THE STAND-IN IS NO
                     PORE AND THE DEFAULTS COME FROM SIMULATED READS: no sequencer's read took part.  Without --events nothing changes.
 
-Out of scope: dwell priors (an HSMM), skips of more than one base, banding (from the events or otherwise), pooling the rescaling across reads,
+--refine            (with --events) after the event rounds every OK read gets ONE pass over SAMPLE rows inside a window of 64 states that
+                    follows the event path (rd_eventalign_banded): the scale is the refit of the last event round's
+                    sums, the guide that round's event starts.  Where the sample path stays inside the window -- on the simulated reads it
+                    strays at most 4 states of the 31 allowed -- the rows are exactly what sample mode writes on that scale: every base
+                    has a row, and the scale columns are the pass's.  A read the window loses (`off-band`) or that does not fit the budget
+                    keeps its event rows and is counted.  --summary gains refined (1 / 0) and edge (the bases whose rows touch the
+                    window's rim) after rows and skipped, which stay the event pass's; the printed summary adds the reads refined, not
+                    refined, and with edge > 0.  THE STAND-IN IS NO PORE: no sequencer's read took part.  Without --refine nothing changes.
+
+Out of scope: dwell priors (an HSMM), skips of more than one base, a run-time band width, pooling the rescaling across reads,
 conversion to pA, adapter and leader models, per-read modification calls against the table, the pipelined route, several GPUs."""
 import argparse
 import math
@@ -62,6 +71,7 @@ from .simulate import read_kmer_table, standin_tables
 STATUSES = ("ok", "no-reference", "has-N", "no-path", "too-long", "too-large", "signal")
 SUMMARY_COLUMNS = RESQUIGGLE_SUMMARY + ("score_per_sample", "m2", "d4", "rounds")
 EVENTS_SUMMARY_COLUMNS = ("rows", "skipped")       # --events: the read's events and the bases its path jumped over
+REFINE_SUMMARY_COLUMNS = ("refined", "edge")       # --refine: did the banded sample pass replace the event rows; the bases on the window's rim
 _EVAL_STATUS = {EVAL_EMPTY: "signal", EVAL_MAD_ZERO: "signal", EVAL_NO_PATH: "no-path", EVAL_TOO_LONG: "too-long", EVAL_TOO_LARGE: "too-large"}
 MAD_UNIT = 1.4826 * 256     # model units (MAD / 256) per z
 SD_FLOOR = 8                # the least model sd, in MAD / 256
@@ -197,21 +207,37 @@ def events_aligner(seg, align, skip_pen):
     return be_align, cut
 
 
+def refine_pass(banded, raws, codes, model, t_lo, res):
+    """--refine: one banded sample pass for the OK reads of the last event round `res` (an EvalRowsResult): the scale is the refit of that
+    round's sums, the guide its event starts.  banded is Backend.eventalign_banded or eventalign_banded_host bound to the budget.
+    -> ({read index: index into the pass's result}, the EvalBandedResult or None)"""
+    ok = [r for r in range(len(raws)) if int(res.status[r]) == EVAL_OK]
+    if not ok:
+        return {}, None
+    scale = [refit(res.fit_sums[r], res.m2[r], res.d4[r]) for r in ok]
+    fine = banded([raws[r] for r in ok], [codes[r] for r in ok], [res.events.start[r] for r in ok], model, t_lo=[t_lo[r] for r in ok],
+                  m2=[m for m, _ in scale], d4=[d for _, d in scale])
+    return {r: j for j, r in enumerate(ok)}, fine
+
+
 def run(args, be, reads, refs, names, bounds, model, sd_m, open_out):
     """reads: iterable of (file stem, read id, raw int16 samples) in input order; refs / names: {read id: span} / {read id: transcript name};
     bounds: {read id: tail_end} or None.  Returns the counters."""
     from .segment import params_of, window_segmenter      # (segment imports this module's bounds)
     events = getattr(args, "events", False)
+    refine = events and getattr(args, "refine", False)
     st = {"reads": 0, "written": 0, "bases": 0, "unbounded": 0, "dwell": {}, "score_per_sample": [], **{s: 0 for s in STATUSES}}
     if events:
         st.update(rows=0, skipped=0, span_bases=0)
+        if refine:
+            st.update(refined=0, not_refined=0, edge_reads=0)
         seg = window_segmenter(be.segment, params_of(args), budget_bytes=args.budget_bytes, allow_too_large=True)
     kt = KmerTable(model.k) if args.kmer_table_out else None
     summ = open(args.summary, "w") if args.summary else None
     if summ:
-        summ.write("\t".join(SUMMARY_COLUMNS + (EVENTS_SUMMARY_COLUMNS if events else ())) + "\n")
+        summ.write("\t".join(SUMMARY_COLUMNS + (EVENTS_SUMMARY_COLUMNS if events else ()) + (REFINE_SUMMARY_COLUMNS if refine else ())) + "\n")
 
-    def done(rid, status, n_samples, ref_len, extra=("-",) * (11 if events else 9)):
+    def done(rid, status, n_samples, ref_len, extra=("-",) * (13 if refine else 11 if events else 9)):
         st[status] += 1
         if summ:
             summ.write("\t".join((rid, status, str(n_samples), str(ref_len)) + tuple(extra)) + "\n")
@@ -221,6 +247,9 @@ def run(args, be, reads, refs, names, bounds, model, sd_m, open_out):
 
     def be_align_rows(*a, **kw):
         return be.eventalign_events(*a, budget_bytes=args.budget_bytes, allow_too_large=True, **kw)
+
+    def be_banded(*a, **kw):
+        return be.eventalign_banded(*a, budget_bytes=args.budget_bytes, allow_too_large=True, **kw)
 
     try:
         for batch in _batches(reads, args.batch_reads):
@@ -240,6 +269,7 @@ def run(args, be, reads, refs, names, bounds, model, sd_m, open_out):
             if events:      # the batch's events are cut once; only the scale changes between rounds
                 be_align, cut = events_aligner(seg, be_align_rows, args.skip_penalty)
             res = align_rounds(be_align, [t[0] for t in todo], [t[1] for t in todo], model, [t[2] for t in todo], args.rescale_rounds) if todo else None
+            where, fine = refine_pass(be_banded, [t[0] for t in todo], [t[1] for t in todo], model, [t[2] for t in todo], res) if refine and todo else ({}, None)
             r = -1
             for stem, rid, raw, status in verdict:
                 ref_len = len(refs[rid]) if rid in refs else 0
@@ -252,7 +282,10 @@ def run(args, be, reads, refs, names, bounds, model, sd_m, open_out):
                     done(rid, _EVAL_STATUS[e_st], len(raw), ref_len)
                     continue
                 span, codes, lo = refs[rid], todo[r][1], todo[r][2]
-                rows, levels, dwells = read_rows(rid, names.get(rid, ""), span, raw, codes, res, r, model, sd_m)
+                # --refine: a read whose banded pass is OK writes that pass's sample rows on that pass's scale; any other keeps its event rows
+                refined = refine and int(fine.status[where[r]]) == EVAL_OK
+                src, at = (fine, where[r]) if refined else (res, r)
+                rows, levels, dwells = read_rows(rid, names.get(rid, ""), span, raw, codes, src, at, model, sd_m)
                 out = open_out(stem)
                 for row in rows:
                     out.write("\t".join(row) + "\n")
@@ -260,7 +293,7 @@ def run(args, be, reads, refs, names, bounds, model, sd_m, open_out):
                 st["bases"] += len(rows)
                 for d in dwells:
                     st["dwell"][d] = st["dwell"].get(d, 0) + 1
-                score = int(res.score[r])
+                score = int(src.score[at])
                 sps = score / (len(raw) - lo)
                 st["score_per_sample"].append(sps)
                 if kt:
@@ -278,10 +311,15 @@ def run(args, be, reads, refs, names, bounds, model, sd_m, open_out):
                     st["skipped"] += n_skip
                     st["span_bases"] += len(codes)
                     more = (str(n_rows), str(n_skip))
+                    if refine:
+                        edge = int(fine.n_edge[where[r]]) if refined else 0
+                        st["refined" if refined else "not_refined"] += 1
+                        st["edge_reads"] += 1 if edge else 0
+                        more += ("1" if refined else "0", str(edge))
                 else:
                     first = int(res.first_step[r][0]) if rows else -1
                     last = int(res.last_step[r][-1]) if rows else -1
-                done(rid, "ok", len(raw), ref_len, (str(score), spb, md, str(first), str(last), f"{sps:.6f}", str(int(res.m2[r])), str(int(res.d4[r])),
+                done(rid, "ok", len(raw), ref_len, (str(score), spb, md, str(first), str(last), f"{sps:.6f}", str(int(src.m2[at])), str(int(src.d4[at])),
                                                     str(args.rescale_rounds)) + more)
     finally:
         if summ:
@@ -300,6 +338,7 @@ def summary(st):
             + (f"median score per sample: {float(np.median(sps)):.4f}\n" if sps else "median score per sample: -\n")
             + ((f"events per base: {st['rows'] / st['span_bases']:.3f}; bases skipped: {100.0 * st['skipped'] / st['span_bases']:.2f} %\n"
                 if st["span_bases"] else "events per base: -; bases skipped: -\n") if "rows" in st else "")
+            + (f"refined: {st['refined']}; not refined: {st['not_refined']}; with bases on the band's rim: {st['edge_reads']}\n" if "refined" in st else "")
             + "status: " + "; ".join(f"{s}: {st[s]}" for s in STATUSES) + "\n")
 
 
@@ -328,6 +367,8 @@ def build_parser():
     add_detector_arguments(ap)
     ap.add_argument("--skip-penalty", default=96, type=int, help="--events: the cost of skipping one base, in 1/32 nat (0..256)")
     ap.add_argument("--no-skips", action="store_true", help="--events: no base is skipped")
+    ap.add_argument("--refine", action="store_true", help="--events: after the event rounds, one pass over sample rows in a band of 64 states round "
+                    "the event path (rd_eventalign_banded); a read whose pass is OK writes sample-mode rows")
     return ap
 
 
@@ -352,6 +393,8 @@ def main(argv=None):
         raise SystemExit("eventalign: --batch-reads at least 1; --budget-bytes and --start-slack at least 0; --rescale-rounds 0..16; --bg-sd 0.01..32")
     if not os.path.isdir(args.fast5_dir):
         raise SystemExit(f"eventalign: {args.fast5_dir}: no such directory")
+    if args.refine and not args.events:
+        raise SystemExit("eventalign: --refine goes with --events")
     if args.events:
         from .segment import check_detector_arguments
         check_detector_arguments(args, "eventalign")
