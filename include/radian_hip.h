@@ -855,6 +855,62 @@ int rd_eventalign_events_host(int n_reads, const int64_t* n_samples, const int64
                               int64_t* fit_sums);
 int64_t rd_eventalign_events_workspace_bytes(int64_t n_rows, int64_t n_bases);
 
+/* ---- modcall: per-read modification calls by local re-alignment under two models (modcall.hip) --------------
+ * NO reference behaviour.  A job is a (read, site) pair.  The rows between two anchors of an alignment the caller already has are
+ * re-aligned to the at most 63 states round the site, under the canonical model (ref) and with the job's entries in place of some states
+ * (alt); per hypothesis the best path (vit) and the sum over all paths (fwd, the forward algorithm) are returned as negative log
+ * likelihoods in 1/32 nat.  Integer arithmetic only; met exactly.  The rules are csrc/modcall_rules.h.
+ *   reads     raw, read_off, n_reads as rd_eventalign (the whole read, no window).  Per read a GIVEN scale (m2[r], d4[r]): d4 == 0 or a value
+ *             outside rd_eventalign's ranges is RD_ERR_ARG.  codes / ref_off / ref_len in pore order, as rd_eventalign.  first / last per
+ *             base at ref_off[r] + b, int32 in READ sample coordinates: what rd_eventalign and rd_eventalign_banded return as first_step
+ *             and last_step, or ev_start and ev_end - 1 of event rows; -1 marks a base without rows
+ *   model     k, lvl, w, bias as rd_eventalign.  No background takes part
+ *   jobs      n_jobs of them: job_read[j]; alt_first[j], the pore-order index of the first base whose state is replaced; the replacing
+ *             entries alt_lvl / alt_w / alt_bias at alt_off[j] .. alt_off[j+1] (alt_off holds n_jobs + 1 offsets).  1 <= n_alt <= 9,
+ *             alt_first >= 0, alt_first + n_alt <= L, every entry within the model's ranges; a flank F for all jobs, 0 <= F <= 27
+ *   window    a0 = max(0, alt_first - F), a1 = min(L - 1, alt_first + n_alt - 1 + F), S = a1 - a0 + 1 <= 63 states; rows r0 = first[a0] ..
+ *             r1 = last[a1], R = r1 - r0 + 1
+ *   status    in this order: either anchor -1 RD_MC_NO_ANCHOR; R < S or rows outside the read RD_MC_NO_PATH; R > 2^15 RD_MC_TOO_LONG;
+ *             the read alone over the budget RD_MC_TOO_LARGE; otherwise RD_MC_OK
+ *   cell      zq = rd_eventalign's sample rule on raw[r0 + t]; c(t, i) = rd_eventalign's cell cost of zq against state i.  ref: state i is
+ *             base a0 + i's k-mer.  alt: the same, the job's entries in place of bases alt_first .. alt_first + n_alt - 1
+ *   path      anchored at both ends: V[0][0] = c(0, 0), every other state starts at 2^30.  Per hypothesis vit = c + min(stay, adv) and
+ *             fwd = c + softmin(stay, adv), softmin(a, b) = min(a, b) - LSE[min(|a - b|, 133)], LSE[d] = floor(32 ln(1 + e^(-d/32)) + 1/2),
+ *             a literal of 134 integers (LSE[0] = 22, LSE[133] = 0); state 0 has no advance (2^30).  No libm on either side
+ *   bounds    finite values lie in (-2^15 * 278, 2^15 * 1280], below 3 * 2^28; a value that started at 2^30 stays in [2^30 - 22 * 2^15, 2^31); the
+ *             two differ by more than 133, so LSE contributes 0 between them and nothing is masked
+ *   outputs   per job status, n_rows = R, n_states = S and the four values at (R - 1, S - 1): vit_ref, vit_alt, fwd_ref, fwd_alt (int32).  A
+ *             job that is not OK returns zeros in all six
+ * fwd <= vit <= fwd + 22 (R - 1).  Alt entries equal to the canonical ones give *_alt == *_ref.  With first / last from rd_eventalign on the
+ * same scale vit_ref is the summed cell cost of that path over rows r0 .. r1 (a sub-path of an optimal path is optimal between its ends);
+ * from any other steps it is at most that sum.  A result does not depend on the batch, the order of reads or jobs, the budget or the
+ * launches.  RD_ERR_ARG before anything is launched: a null pointer, offsets that are not monotone, a code above 3, a scale, a table or alt
+ * entry, a flank or a job outside its range.  n_jobs == 0 is RD_OK.
+ *   rd_modcall        on the GPU; synchronous, uses the context's stream.  budget_bytes and RD_ERR_NOMEM as rd_eventalign (DESIGN.md section
+ *                     19): the reads that have jobs are packed into launches in the caller's order, rd_modcall_workspace_bytes per read,
+ *                     0 = a quarter of the free device memory; a read that alone exceeds it has all its jobs RD_MC_TOO_LARGE, and the call
+ *                     returns RD_ERR_NOMEM naming it after doing the others
+ *   rd_modcall_host   host, no GPU: the same rules in a plain loop (no budget: never RD_MC_TOO_LARGE)
+ *   rd_modcall_workspace_bytes   of a read of n_samples samples and n_bases bases with n_jobs jobs of n_alt entries in all, each term
+ *                     rounded up to 256: 2 n_samples (samples) + 8 n_bases (steps) + 64 n_jobs (descriptors) + 32 n_jobs (results)
+ *                     + 12 n_alt (entries) */
+#define RD_MC_OK 0
+#define RD_MC_NO_ANCHOR 1
+#define RD_MC_NO_PATH 2
+#define RD_MC_TOO_LONG 3
+#define RD_MC_TOO_LARGE 4
+int rd_modcall(rd_ctx* ctx, const int16_t* raw, const int64_t* read_off, int n_reads, const int32_t* m2, const int32_t* d4, const uint8_t* codes,
+               const int64_t* ref_off, const int32_t* ref_len, const int32_t* first, const int32_t* last, int k, const int32_t* lvl,
+               const uint32_t* w, const int32_t* bias, int n_jobs, const int32_t* job_read, const int32_t* alt_first, const int64_t* alt_off,
+               const int32_t* alt_lvl, const uint32_t* alt_w, const int32_t* alt_bias, int flank, int64_t budget_bytes, int32_t* status,
+               int32_t* n_rows, int32_t* n_states, int32_t* vit_ref, int32_t* vit_alt, int32_t* fwd_ref, int32_t* fwd_alt);
+int rd_modcall_host(const int16_t* raw, const int64_t* read_off, int n_reads, const int32_t* m2, const int32_t* d4, const uint8_t* codes,
+                    const int64_t* ref_off, const int32_t* ref_len, const int32_t* first, const int32_t* last, int k, const int32_t* lvl,
+                    const uint32_t* w, const int32_t* bias, int n_jobs, const int32_t* job_read, const int32_t* alt_first, const int64_t* alt_off,
+                    const int32_t* alt_lvl, const uint32_t* alt_w, const int32_t* alt_bias, int flank, int32_t* status, int32_t* n_rows,
+                    int32_t* n_states, int32_t* vit_ref, int32_t* vit_alt, int32_t* fwd_ref, int32_t* fwd_alt);
+int64_t rd_modcall_workspace_bytes(int64_t n_samples, int64_t n_bases, int64_t n_jobs, int64_t n_alt);
+
 /* ---- sigmap: raw samples against a panel of targets, subsequence Viterbi with a free start and end (sigmap.hip)
  * NO reference behaviour.  Which targets of a panel a window of samples fits best, where the fit ends in each and where it began.  No
  * basecall and no neural network take part.  Integer arithmetic only; met exactly.  Sample, cell and the three model tables are

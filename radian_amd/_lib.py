@@ -122,6 +122,9 @@ SIGNATURES = {
     "rd_eventalign_events": (c_i, [c_vp, c_i] + [c_vp] * 14 + [c_i] + [c_vp] * 3 + [ctypes.c_int32, c_u32, ctypes.c_int32, c_i, c_i64] + [c_vp] * 12),
     "rd_eventalign_events_host": (c_i, [c_i] + [c_vp] * 14 + [c_i] + [c_vp] * 3 + [ctypes.c_int32, c_u32, ctypes.c_int32, c_i] + [c_vp] * 12),
     "rd_eventalign_events_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "rd_modcall": (c_i, [c_vp, c_vp, c_vp, c_i] + [c_vp] * 7 + [c_i] + [c_vp] * 3 + [c_i] + [c_vp] * 6 + [c_i, c_i64] + [c_vp] * 7),
+    "rd_modcall_host": (c_i, [c_vp, c_vp, c_i] + [c_vp] * 7 + [c_i] + [c_vp] * 3 + [c_i] + [c_vp] * 6 + [c_i] + [c_vp] * 7),
+    "rd_modcall_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_i64]),
     "rd_sigmap": (c_i, [c_vp, c_vp, c_i64, c_i] + [c_vp] * 10 + [c_i, c_i] + [c_vp] * 3 + [c_i, c_i64] + [c_vp] * 7),
     "rd_sigmap_host": (c_i, [c_vp, c_i64, c_i] + [c_vp] * 10 + [c_i, c_i] + [c_vp] * 3 + [c_i] + [c_vp] * 7),
     "rd_sigmap_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),

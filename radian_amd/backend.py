@@ -570,6 +570,72 @@ def eventalign_banded_workspace_bytes(n_rows, n_bases):
     return int(_lib.load().rd_eventalign_banded_workspace_bytes(int(n_rows), int(n_bases)))
 
 
+# rd_modcall per-job status (include/radian_hip.h RD_MC_*)
+MC_OK, MC_NO_ANCHOR, MC_NO_PATH, MC_TOO_LONG, MC_TOO_LARGE = 0, 1, 2, 3, 4
+MC_STATUS_NAMES = ("ok", "no-anchor", "no-path", "too-long", "too-large")
+MC_MAX_FLANK, MC_MAX_ALT, MC_MAX_ROWS = 27, 9, 1 << 15
+
+
+class ModcallResult:
+    """rd_modcall, per job (int32 arrays): status (MC_*), n_rows, n_states, vit_ref, vit_alt, fwd_ref, fwd_alt -- negative log likelihoods
+    in 1/32 nat of the window's rows under the canonical states and with the job's entries in their place, by the best path and summed
+    over all paths; zeros where status is not MC_OK.  llr() = (fwd_ref - fwd_alt) / 32 in nats (exact in float64)"""
+    __slots__ = ("status", "n_rows", "n_states", "vit_ref", "vit_alt", "fwd_ref", "fwd_alt")
+
+    def __init__(self, *arrays):
+        self.status, self.n_rows, self.n_states, self.vit_ref, self.vit_alt, self.fwd_ref, self.fwd_alt = arrays
+
+    def llr(self):
+        return (self.fwd_ref.astype(np.int64) - self.fwd_alt) / 32.0
+
+
+def _modcall_args(raws, seqs, m2, d4, firsts, lasts, model, job_read, alt_first, alts, flank):
+    """-> (the arrays, kept alive by the caller; the arguments up to the flank; the seven output buffers).  firsts / lasts: per read one
+    int32 per base; alts: per job (lvl, w, bias), each of 1..9 entries"""
+    flat, off = Backend._pack_raw(raws)
+    n, nj = len(raws), len(job_read)
+    if not (len(seqs) == len(firsts) == len(lasts) == n) or any(len(f) != len(q) or len(l) != len(q) for f, l, q in zip(firsts, lasts, seqs)):
+        raise ValueError(f"modcall takes a sequence and one first and last step per base for each of {n} reads")
+    if len(alt_first) != nj or len(alts) != nj:
+        raise ValueError(f"modcall takes alt_first and the alt entries of each of {nj} jobs")
+    codes, coff = _concat_codes(seqs)
+    ref_off = np.ascontiguousarray(coff[:-1] if n else np.zeros(1), dtype=np.int64)
+    ref_len = np.concatenate([np.diff(coff), np.zeros(1)]).astype(np.int32)
+    def cat(xs, dt):      # (thousands of one-entry arrays: those that are already flat arrays of the type go in as they are)
+        return np.concatenate([x if isinstance(x, np.ndarray) and x.dtype == dt and x.ndim == 1 else np.ascontiguousarray(x, dtype=dt).ravel() for x in xs]
+                              + [np.zeros(1, dt)])
+    first, last = cat(firsts, np.int32), cat(lasts, np.int32)
+    m2, d4 = cat([m2], np.int32), cat([d4], np.int32)
+    if m2.size != n + 1 or d4.size != n + 1:
+        raise ValueError(f"modcall takes the scale of each of {n} reads")
+    jr, af = cat([job_read], np.int32), cat([alt_first], np.int32)
+    a_lvl, a_w, a_bias = cat([a[0] for a in alts], np.int32), cat([a[1] for a in alts], np.uint32), cat([a[2] for a in alts], np.int32)
+    lens = [np.fromiter((np.size(a[i]) for a in alts), np.int64, nj) for i in range(3)]
+    if not ((lens[0] == lens[1]).all() and (lens[0] == lens[2]).all()):
+        raise ValueError("a job's alt entries are three arrays of one length")
+    alt_off = np.zeros(nj + 1, np.int64)
+    np.cumsum(lens[0], out=alt_off[1:])
+    outs = [np.zeros(nj + 1, np.int32) for _ in range(7)]
+    keep = (flat, off, m2, d4, codes, ref_off, ref_len, first, last, model, jr, af, alt_off, a_lvl, a_w, a_bias)
+    head = (_p(flat), _p(off), n, _p(m2), _p(d4), _p(codes), _p(ref_off), _p(ref_len), _p(first), _p(last), model.k, _p(model.lvl), _p(model.w),
+            _p(model.bias), nj, _p(jr), _p(af), _p(alt_off), _p(a_lvl), _p(a_w), _p(a_bias), int(flank))
+    return keep, head, outs
+
+
+def modcall_host(raws, seqs, m2, d4, firsts, lasts, model, job_read, alt_first, alts, flank=6):
+    """Backend.modcall on the host (rd_modcall_host: the same rules in a plain loop; no GPU, no context, no budget)"""
+    L = _lib.load()
+    keep, head, outs = _modcall_args(raws, seqs, m2, d4, firsts, lasts, model, job_read, alt_first, alts, flank)
+    if L.rd_modcall_host(*head, *[_p(b) for b in outs]) != 0:
+        raise RadianHipError(L.rd_last_error().decode())
+    return ModcallResult(*[b[:len(job_read)] for b in outs])
+
+
+def modcall_workspace_bytes(n_samples, n_bases, n_jobs, n_alt):
+    """device workspace Backend.modcall needs for one read: its samples, steps, jobs and alt entries (rd_modcall_workspace_bytes)"""
+    return int(_lib.load().rd_modcall_workspace_bytes(int(n_samples), int(n_bases), int(n_jobs), int(n_alt)))
+
+
 class EvalRowsResult:
     """rd_eventalign_events: per read status (int32, EVAL_*), score (int64), n_skipped (int32), m2 / d4 (int32: the scale as given), fit_sums
     (int64 [reads, 5]); per read and base: row_first / row_last (int32 arrays, indices into the read's events; -1 for a skipped base) and
@@ -1906,6 +1972,23 @@ class Backend:
 
     eventalign_banded_host = staticmethod(eventalign_banded_host)
     eventalign_banded_workspace_bytes = staticmethod(eventalign_banded_workspace_bytes)
+
+    # ------------------------------------------------------------------ per-read modification calls
+    def modcall(self, raws, seqs, m2, d4, firsts, lasts, model, job_read, alt_first, alts, flank=6, budget_bytes=0, allow_too_large=False):
+        """Per (read, site) job the likelihood of the rows round the site under the canonical states and under the job's own (rd_modcall,
+        on the GPU): raws, seqs, model -- as eventalign (the background takes no part); m2 / d4 -- the scale of every read, always given;
+        firsts / lasts -- per read one int32 per base, the read samples the base's rows start and end at (an EvalResult's first_step and
+        last_step, or events[r]["start"] and events[r]["end"] - 1; -1: no rows); job_read, alt_first -- per job its read and the first
+        base whose state is replaced; alts -- per job (lvl, w, bias) of the 1..9 replacing entries; flank -- bases either side, 0..27.
+        budget_bytes and allow_too_large as eventalign (status MC_TOO_LARGE).  -> ModcallResult."""
+        keep, head, outs = _modcall_args(raws, seqs, m2, d4, firsts, lasts, model, job_read, alt_first, alts, flank)
+        rc = self._L.rd_modcall(self._h, *head, int(budget_bytes), *[_p(b) for b in outs])
+        if rc != 0 and not (allow_too_large and rc == -4 and (outs[0][:len(job_read)] == MC_TOO_LARGE).any()):
+            self._check(rc)
+        return ModcallResult(*[b[:len(job_read)] for b in outs])
+
+    modcall_host = staticmethod(modcall_host)
+    modcall_workspace_bytes = staticmethod(modcall_workspace_bytes)
 
     # ------------------------------------------------------------------ signal against a panel of targets (DESIGN.md section 25)
     def sigmap(self, raw, targets, model, q_lo, q_hi, sc_lo=None, sc_hi=None, m2=None, d4=None, s_lo=None, s_hi=None, n_best=1,

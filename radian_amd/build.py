@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libradian_hip.so")
-SOURCES = ["api.hip", "context.hip", "model.hip", "rccl.hip", "plan.hip", "pipe_reads.hip", "forward.hip", "decode.hip", "decode_wide.hip", "assemble.hip", "preprocess.hip", "stitch.hip", "lmjson.hip", "fast5.hip", "align.hip", "fit.hip", "tfrecord.hip", "ctc.hip", "ctcalign.hip", "events.hip", "polya.hip", "sitecmp.hip", "sim.hip", "eventalign.hip", "train.hip", "lmbuild.hip", "map.hip", "quant.hip", "scoremath.hip", "pileup.hip", "sigmap.hip", "segment.hip"]
+SOURCES = ["api.hip", "context.hip", "model.hip", "rccl.hip", "plan.hip", "pipe_reads.hip", "forward.hip", "decode.hip", "decode_wide.hip", "assemble.hip", "preprocess.hip", "stitch.hip", "lmjson.hip", "fast5.hip", "align.hip", "fit.hip", "tfrecord.hip", "ctc.hip", "ctcalign.hip", "events.hip", "polya.hip", "sitecmp.hip", "sim.hip", "eventalign.hip", "train.hip", "lmbuild.hip", "map.hip", "quant.hip", "scoremath.hip", "pileup.hip", "sigmap.hip", "segment.hip", "modcall.hip"]
 
 
 def _stale():

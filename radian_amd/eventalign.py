@@ -6,6 +6,8 @@ weights take part.  fast5, `map`'s read_ref.tsv and a pore-model table in, one e
            [--bounds PATH] [--start-slack 32] [--rescale-rounds 2] [--bg-sd 1.0]
            [--summary PATH] [--kmer-table-out PATH] [--device N] [--batch-reads R] [--budget-bytes B]
            [--events [--w1 4 --t1 2.5 --w2 12 --t2 5.0 --var-floor 1] [--skip-penalty 96 | --no-skips] [--refine]]
+           [--call SITES.tsv --paf PATH --calls-out PATH [--alt-table ALT.tsv] [--mod-base A] [--call-flank 6] [--call-threshold 0]
+            [--call-sites-out PATH]]
 
 NO reference behaviour.  The read's span -- column 3 of read_ref.tsv, reversed into decode order, U = T -- is aligned to the samples by a
 Viterbi pass over the states lead, base 1 .. base L, trail (rd_eventalign; the contract is in include/radian_hip.h):
@@ -50,8 +52,29 @@ A read is `ok`, or is counted and left out: `no-reference`, `has-N`, `signal` (e
                     window's rim) after rows and skipped, which stay the event pass's; the printed summary adds the reads refined, not
                     refined, and with edge > 0.  THE STAND-IN IS NO PORE: no sequencer's read took part.  Without --refine nothing changes.
 
+--call SITES.tsv --paf PATH --calls-out PATH
+                    PER-READ MODIFICATION CALLS (rd_modcall).  SITES.tsv: rows ref_name <tab> pos [<tab> level_shift
+                    ...] without a header, pos 0-based on the transcript, further columns ignored -- a `simulate --modify` file is one.
+                    --paf (`map --paf`, truth.paf) gives the start of every read's span on its transcript, as in `compare`; a read it
+                    lacks is counted and gets no jobs, a site outside the read's span makes no job, a ref_name no read maps to is
+                    reported.  After a batch's last alignment every (read, site) pair is re-aligned locally on the read's final rows
+                    (the refined pass where --refine took, otherwise the last round) and scale: the rows between the first row of the
+                    base --call-flank before the replaced states and the last row of the base --call-flank after them, under the
+                    canonical states and under the site's alternative ones, by the FORWARD algorithm (the sum over all paths) and by the
+                    best path.  The alternative: with --alt-table (a --kmer-table file whose k-mers spell the modified base as M,
+                    exactly one each) every base whose k-mer covers the site takes its k-mer's entry with M at the site -- an entry the
+                    table lacks, or a k-mer clipped at the span's end, keeps the canonical one and is counted; a site that is not
+                    --mod-base is refused; without it the site's own state alone, its level moved by level_shift z.  Each site is tested
+                    on its own, the others canonical.  calls.tsv: read_id ref_name pos base status n_states n_rows vit_ref vit_alt fwd_ref
+                    fwd_alt llr call, in input read order and then the sites file's; the four values are negative log likelihoods in
+                    1/32 nat, llr = (fwd_ref - fwd_alt) / 32 nats, call = 1 where llr > --call-threshold; a job that is not `ok`
+                    (`no-anchor`: an anchor base without rows; `no-path`; `too-long`: more than 2^15 rows; `too-large`) carries `-`.
+                    --call-sites-out: ref_name pos base n_reads n_ok n_called frac_called mean_llr per site.  THE STAND-IN IS NO PORE,
+                    THRESHOLD AND FLANK ARE NOT CALIBRATED, AND NO SEQUENCER'S READ TOOK PART.  Without --call nothing changes.
+
 Out of scope: dwell priors (an HSMM), skips of more than one base, a run-time band width, pooling the rescaling across reads,
-conversion to pA, adapter and leader models, per-read modification calls against the table, the pipelined route, several GPUs."""
+conversion to pA, adapter and leader models, the pipelined route, several GPUs; of --call: joint hypotheses over neighbouring sites, dwell
+in the likelihood, learning the alt table (EM), calibrating the threshold, sites in the lead or the trail, `resquiggle` tables."""
 import argparse
 import math
 import os
@@ -82,6 +105,14 @@ def model_tables(k, level_q10, sd_q10, bg_sd=1.0):
     """Q10 tables in z (simulate.read_kmer_table / standin_tables) -> the EvalModel, in fp64: lvl = rint(level 1.4826 / 4) (MAD / 256),
     sd_m = max(rint(sd 1.4826 / 4), 8), w = min(rint(16 2^32 / sd_m^2), 2^32 - 1), bias = clip(rint(32 ln(sd_m / bg)), +-256); the
     background has level 0 and sd bg = bg_sd 1.4826 256.  -> (EvalModel, sd_m)"""
+    bg = float(bg_sd) * MAD_UNIT
+    lvl, sd_m, w, bias = table_entries(level_q10, sd_q10, bg_sd)
+    w_bg = min(float(np.rint(16.0 * 2.0 ** 32 / (bg * bg))), 2.0 ** 32 - 1)
+    return EvalModel(k, lvl.astype(np.int32), w.astype(np.uint32), bias.astype(np.int32), (0, int(w_bg), 0)), sd_m.astype(np.int32)
+
+
+def table_entries(level_q10, sd_q10, bg_sd=1.0):
+    """model_tables' formulas on any number of entries -> (lvl, sd_m, w, bias), fp64 arrays of integers"""
     level = np.asarray(level_q10, dtype=np.float64)
     sd = np.asarray(sd_q10, dtype=np.float64)
     bg = float(bg_sd) * MAD_UNIT
@@ -89,8 +120,7 @@ def model_tables(k, level_q10, sd_q10, bg_sd=1.0):
     sd_m = np.maximum(np.rint(sd * 1.4826 / 4), SD_FLOOR)
     w = np.minimum(np.rint(16.0 * 2.0 ** 32 / (sd_m * sd_m)), 2.0 ** 32 - 1)
     bias = np.clip(np.rint(32.0 * np.log(sd_m / bg)), -256, 256)
-    w_bg = min(float(np.rint(16.0 * 2.0 ** 32 / (bg * bg))), 2.0 ** 32 - 1)
-    return EvalModel(k, lvl.astype(np.int32), w.astype(np.uint32), bias.astype(np.int32), (0, int(w_bg), 0)), sd_m.astype(np.int32)
+    return lvl, sd_m, w, bias
 
 
 def _rnd(q):
@@ -220,9 +250,196 @@ def refine_pass(banded, raws, codes, model, t_lo, res):
     return {r: j for j, r in enumerate(ok)}, fine
 
 
-def run(args, be, reads, refs, names, bounds, model, sd_m, open_out):
+# ------------------------------------------------------------------------------------------------ --call: per-read modification calls
+CALL_COLUMNS = ("read_id", "ref_name", "pos", "base", "status", "n_states", "n_rows", "vit_ref", "vit_alt", "fwd_ref", "fwd_alt", "llr", "call")
+CALL_SITE_COLUMNS = ("ref_name", "pos", "base", "n_reads", "n_ok", "n_called", "frac_called", "mean_llr")
+
+
+def read_sites(path, need_shift):
+    """SITES.tsv: rows ref_name <tab> pos [<tab> level_shift ...], no header -> [(ref_name, pos, level_shift or None)] in the file's order"""
+    out = []
+    with open(path, "r") as f:
+        for n, line in enumerate(f, start=1):
+            if not line.strip():
+                continue
+            cols = line.rstrip("\n").rstrip("\r").split("\t")
+            try:
+                pos = int(cols[1])
+                shift = float(cols[2]) if len(cols) > 2 else None
+            except (IndexError, ValueError):
+                raise SystemExit(f"eventalign: {path}, line {n}: not ref_name <tab> pos [<tab> level_shift]")
+            if pos < 0 or (shift is not None and not math.isfinite(shift)):
+                raise SystemExit(f"eventalign: {path}, line {n}: a negative position or a level_shift that is no number")
+            if need_shift and shift is None:
+                raise SystemExit(f"eventalign: {path}, line {n}: no level_shift column, and no --alt-table to take the modified levels from")
+            out.append((cols[0], pos, shift))
+    if not out:
+        raise SystemExit(f"eventalign: {path} holds no site")
+    return out
+
+
+def read_alt_table(path, k, mod_base):
+    """--alt-table: a `resquiggle --kmer-table` file whose k-mers spell the modified base as M, exactly one M each -> {(the pore-order place
+    of M in the k-mer, the pore-order index of the k-mer with mod_base for M): (level_q10, sd_q10)}"""
+    from .simulate import KMER_COLUMNS, encode
+    out = {}
+    with open(path, "r") as f:
+        for i, line in enumerate(f):
+            if i == 0 or not line.strip():
+                continue
+            cols = line.rstrip("\n").rstrip("\r").split("\t")
+            if len(cols) != len(KMER_COLUMNS):
+                raise SystemExit(f"eventalign: {path}, line {i + 1}: {len(cols)} columns, not {', '.join(KMER_COLUMNS)}")
+            kmer = cols[0]
+            if len(kmer) != k:
+                raise SystemExit(f"eventalign: {path}, line {i + 1}: a k-mer of {len(kmer)} letters beside a model of k = {k}")
+            if kmer.count("M") != 1:
+                raise SystemExit(f"eventalign: {path}, line {i + 1}: {kmer} spells the modified base {kmer.count('M')} times, not once")
+            try:
+                level, sd = float(cols[2]), float(cols[3])
+            except ValueError:
+                raise SystemExit(f"eventalign: {path}, line {i + 1}: a number does not parse")
+            idx = 0
+            for c in encode(kmer.replace("M", mod_base), f"{path}: k-mer {kmer}")[::-1]:
+                idx = idx * 4 + int(c)
+            out[(k - 1 - kmer.index("M"), idx)] = (float(np.clip(np.rint(level * 1024), -(1 << 15), 1 << 15)), float(np.clip(np.rint(sd * 1024), 0, 1 << 15)))
+    return out
+
+
+class Caller:
+    """--call: collects a batch's (read, site) jobs from the reads' final alignments, runs them (Backend.modcall) and writes calls.tsv.
+    tables: (level_q10, sd_q10) of the canonical model; sites: read_sites'; paf: compare.read_paf's; alt: read_alt_table's or None"""
+
+    def __init__(self, args, model, tables, sites, paf, alt, out):
+        from .backend import MC_STATUS_NAMES
+        self.args, self.model, self.level, self.sd = args, model, tables[0], tables[1]
+        self.sites, self.paf, self.alt, self.out = sites, paf, alt, out
+        self.by_name = {}
+        for i, (name, _, _) in enumerate(sites):
+            self.by_name.setdefault(name, []).append(i)
+        self.names = MC_STATUS_NAMES
+        self.st = {"jobs": 0, "no_paf": 0, "canonical": 0, "called": 0, "reads": 0, "seen_names": set(), **{s: 0 for s in MC_STATUS_NAMES}}
+        self.site_st = [dict(base="-", n_reads=0, n_ok=0, n_called=0, llr=0) for _ in sites]
+        self.batch = []     # (rid, raw, codes, m2, d4, first, last, [(site index, base, alt_first, (lvl, w, bias))])
+        if out is not None:
+            out.write("\t".join(CALL_COLUMNS) + "\n")
+
+    def alt_entries(self, codes, s, shift, what):
+        """the replaced states of the site at pore-order base s -> (alt_first, (lvl, w, bias))"""
+        k, L = self.model.k, len(codes)
+        idx = kmer_indices(codes, k)
+        if self.alt is None:
+            level = np.clip(np.rint(self.level[idx[s]] + shift * 1024.0), -(1 << 15), 1 << 15)
+            lvl, _, w, bias = table_entries([level], [self.sd[idx[s]]], self.args.bg_sd)
+            return s, (lvl.astype(np.int32), w.astype(np.uint32), bias.astype(np.int32))
+        if "ACGT"[int(codes[s])] != self.args.mod_base:
+            raise SystemExit(f"eventalign: --call: {what} is {'ACGT'[int(codes[s])]} on its transcript, not the --mod-base {self.args.mod_base}")
+        h = k // 2
+        lo, hi = max(0, s - h), min(L - 1, s + h)
+        level, sd = [], []
+        for b in range(lo, hi + 1):     # base b's k-mer holds the site at pore-order place h - (b - s); a k-mer clipped at the span's end keeps its entry
+            e = self.alt.get((h - (b - s), int(idx[b]))) if b - h >= 0 and b + h <= L - 1 else None
+            if e is None:
+                self.st["canonical"] += 1
+                e = (float(self.level[idx[b]]), float(self.sd[idx[b]]))
+            level.append(e[0])
+            sd.append(e[1])
+        lvl, _, w, bias = table_entries(level, sd, self.args.bg_sd)
+        return lo, (lvl.astype(np.int32), w.astype(np.uint32), bias.astype(np.int32))
+
+    def check_sites(self, refs):
+        """before anything is written: with --alt-table every site a read's span covers must be the --mod-base on it"""
+        if self.alt is None:
+            return
+        for rid, span in refs.items():
+            if rid not in self.paf:
+                continue
+            tname, _, tstart = self.paf[rid]
+            for i in self.by_name.get(tname, ()):
+                at = self.sites[i][1] - tstart
+                if 0 <= at < len(span) and span[at].upper().replace("U", "T") != self.args.mod_base:
+                    raise SystemExit(f"eventalign: --call: {tname}:{self.sites[i][1]} is {span[at]} on its transcript (read {rid}), not the --mod-base "
+                                     f"{self.args.mod_base}")
+
+    def add(self, rid, span, raw, codes, src, at):
+        """an OK read and its final alignment (src, at): an EvalResult, EvalBandedResult or EvalRowsResult"""
+        self.st["reads"] += 1
+        if rid not in self.paf:
+            self.st["no_paf"] += 1
+            return
+        tname, _, tstart = self.paf[rid]
+        self.st["seen_names"].add(tname)
+        L = len(codes)
+        jobs = []
+        for i in self.by_name.get(tname, ()):
+            _, pos, shift = self.sites[i]
+            if not 0 <= pos - tstart < L:
+                continue
+            s = L - 1 - (pos - tstart)
+            base = "ACGT"[int(codes[s])]
+            alt_first, entries = self.alt_entries(codes, s, shift, f"{tname}:{pos}")
+            jobs.append((i, base, alt_first, entries))
+        if not jobs:
+            return
+        ev = src.events
+        start, end = ev.start[at].astype(np.int64), ev.end[at].astype(np.int64)
+        rows = end > start
+        first, last = np.where(rows, start, -1).astype(np.int32), np.where(rows, end - 1, -1).astype(np.int32)
+        self.batch.append((rid, raw, codes, int(src.m2[at]), int(src.d4[at]), first, last, jobs))
+
+    def flush(self, be):
+        """run the batch's jobs and write their rows: input read order, then sites-file order"""
+        from .backend import MC_OK
+        batch, self.batch = self.batch, []
+        if not batch:
+            return
+        job_read = [r for r, b in enumerate(batch) for _ in b[7]]
+        flat = [j for b in batch for j in b[7]]
+        res = be.modcall([b[1] for b in batch], [b[2] for b in batch], [b[3] for b in batch], [b[4] for b in batch], [b[5] for b in batch],
+                         [b[6] for b in batch], self.model, job_read, [j[2] for j in flat], [j[3] for j in flat], flank=self.args.call_flank,
+                         budget_bytes=self.args.budget_bytes, allow_too_large=True)
+        for j, (r, (i, base, _, _)) in enumerate(zip(job_read, flat)):
+            name, pos, _ = self.sites[i]
+            status = int(res.status[j])
+            ss = self.site_st[i]
+            ss["base"] = base
+            ss["n_reads"] += 1
+            self.st["jobs"] += 1
+            self.st[self.names[status]] += 1
+            if status != MC_OK:
+                self.out.write("\t".join((batch[r][0], name, str(pos), base, self.names[status]) + ("-",) * 8) + "\n")
+                continue
+            num = int(res.fwd_ref[j]) - int(res.fwd_alt[j])     # llr = num / 32 nats: exact in fp64, five decimals hold it
+            called = num > 32.0 * self.args.call_threshold
+            ss["n_ok"] += 1
+            ss["n_called"] += int(called)
+            ss["llr"] += num
+            self.st["called"] += int(called)
+            self.out.write("\t".join((batch[r][0], name, str(pos), base, "ok", str(int(res.n_states[j])), str(int(res.n_rows[j])), str(int(res.vit_ref[j])),
+                                      str(int(res.vit_alt[j])), str(int(res.fwd_ref[j])), str(int(res.fwd_alt[j])), f"{num / 32.0:.5f}",
+                                      "1" if called else "0")) + "\n")
+
+    def write_sites(self, path):
+        with open(path, "w") as f:
+            f.write("\t".join(CALL_SITE_COLUMNS) + "\n")
+            for (name, pos, _), s in zip(self.sites, self.site_st):
+                frac = f"{s['n_called'] / s['n_ok']:.6f}" if s["n_ok"] else "nan"
+                mean = f"{s['llr'] / (32.0 * s['n_ok']):.6f}" if s["n_ok"] else "nan"
+                f.write("\t".join((name, str(pos), s["base"], str(s["n_reads"]), str(s["n_ok"]), str(s["n_called"]), frac, mean)) + "\n")
+
+    def summary(self):
+        st = self.st
+        unknown = sorted({name for name, _, _ in self.sites} - st["seen_names"])
+        ok = st["ok"]
+        return (f"calls: {st['jobs']} jobs over {len(self.sites)} sites; " + "; ".join(f"{s}: {st[s]}" for s in self.names) + "\n"
+                + f"calls: reads without a PAF line: {st['no_paf']} of {st['reads']}; alt entries kept canonical: {st['canonical']}\n"
+                + (f"calls: sites on transcripts no read maps to: {', '.join(unknown)}\n" if unknown else "")
+                + (f"calls: called modified: {st['called']} of {ok} ({100.0 * st['called'] / ok:.2f} %)\n" if ok else "calls: called modified: -\n"))
+
+
+def run(args, be, reads, refs, names, bounds, model, sd_m, open_out, caller=None):
     """reads: iterable of (file stem, read id, raw int16 samples) in input order; refs / names: {read id: span} / {read id: transcript name};
-    bounds: {read id: tail_end} or None.  Returns the counters."""
+    bounds: {read id: tail_end} or None; caller: --call's Caller or None.  Returns the counters."""
     from .segment import params_of, window_segmenter      # (segment imports this module's bounds)
     events = getattr(args, "events", False)
     refine = events and getattr(args, "refine", False)
@@ -286,6 +503,8 @@ def run(args, be, reads, refs, names, bounds, model, sd_m, open_out):
                 refined = refine and int(fine.status[where[r]]) == EVAL_OK
                 src, at = (fine, where[r]) if refined else (res, r)
                 rows, levels, dwells = read_rows(rid, names.get(rid, ""), span, raw, codes, src, at, model, sd_m)
+                if caller is not None:
+                    caller.add(rid, span, raw, codes, src, at)
                 out = open_out(stem)
                 for row in rows:
                     out.write("\t".join(row) + "\n")
@@ -321,6 +540,8 @@ def run(args, be, reads, refs, names, bounds, model, sd_m, open_out):
                     last = int(res.last_step[r][-1]) if rows else -1
                 done(rid, "ok", len(raw), ref_len, (str(score), spb, md, str(first), str(last), f"{sps:.6f}", str(int(src.m2[at])), str(int(src.d4[at])),
                                                     str(args.rescale_rounds)) + more)
+            if caller is not None:      # the batch's jobs run after its last alignment, on every read's final source
+                caller.flush(be)
     finally:
         if summ:
             summ.close()
@@ -369,16 +590,50 @@ def build_parser():
     ap.add_argument("--no-skips", action="store_true", help="--events: no base is skipped")
     ap.add_argument("--refine", action="store_true", help="--events: after the event rounds, one pass over sample rows in a band of 64 states round "
                     "the event path (rd_eventalign_banded); a read whose pass is OK writes sample-mode rows")
+    ap.add_argument("--call", default=None, metavar="SITES.tsv", help="per-read modification calls at these sites (rd_modcall): rows ref_name <tab> pos "
+                    "[<tab> level_shift ...] without a header, pos 0-based on the transcript; a `simulate --modify` file is one.  The stand-in is no "
+                    "pore; threshold and flank are not calibrated")
+    ap.add_argument("--paf", default=None, help="--call: the reads' mappings (`map --paf`, truth.paf): where each span starts on its transcript")
+    ap.add_argument("--calls-out", default=None, help="--call: the per-(read, site) TSV")
+    ap.add_argument("--alt-table", default=None, help="--call: the modified k-mers' levels, a --kmer-table file whose k-mers spell the modified base as M "
+                    "(exactly one M each); without it the site's own state moves by the sites file's level_shift (z)")
+    ap.add_argument("--mod-base", default="A", help="--alt-table: the base M stands for")
+    ap.add_argument("--call-flank", default=6, type=int, help="--call: bases either side of the replaced states that are re-aligned (0..27)")
+    ap.add_argument("--call-threshold", default=0.0, type=float, help="--call: call = 1 where llr (nats) is above this")
+    ap.add_argument("--call-sites-out", default=None, help="--call: a per-site TSV of the reads called")
     return ap
 
 
-def build_model(args):
+def build_tables(args):
+    """-> (k, level_q10, sd_q10) of the pore model the options name"""
     if args.kmer_table:
         k, level, sd, _ = read_kmer_table(args.kmer_table, args.fill_missing)
     else:
         k = args.kmer
         level, sd, _ = standin_tables(k, args.model_seed)
-    return model_tables(k, level, sd, args.bg_sd)
+    return k, level, sd
+
+
+def build_model(args):
+    return model_tables(*build_tables(args), args.bg_sd)
+
+
+def check_call_arguments(args):
+    if args.call is None:
+        for opt in ("paf", "calls_out", "alt_table", "call_sites_out"):
+            if getattr(args, opt) is not None:
+                raise SystemExit(f"eventalign: --{opt.replace('_', '-')} goes with --call")
+        return
+    if args.paf is None or args.calls_out is None:
+        raise SystemExit("eventalign: --call takes --paf and --calls-out")
+    if not 0 <= args.call_flank <= 27 or not math.isfinite(args.call_threshold):
+        raise SystemExit("eventalign: --call-flank 0..27; --call-threshold a number")
+    if args.mod_base not in ("A", "C", "G", "T", "U"):
+        raise SystemExit("eventalign: --mod-base is one of A C G T U")
+    args.mod_base = "T" if args.mod_base == "U" else args.mod_base
+    for p in (args.call, args.paf) + ((args.alt_table,) if args.alt_table else ()):
+        if not os.path.isfile(p):
+            raise SystemExit(f"eventalign: {p}: no such file")
 
 
 def main(argv=None):
@@ -402,9 +657,11 @@ def main(argv=None):
             raise SystemExit("eventalign: --skip-penalty must be 0..256")
         if args.no_skips:
             args.skip_penalty = -1
+    check_call_arguments(args)
     refs, names = read_ref_tsv(args.read_ref), read_ref_names(args.read_ref)
     bounds = read_bounds(args.bounds) if args.bounds else None
-    model, sd_m = build_model(args)
+    k, level, sd = build_tables(args)
+    model, sd_m = model_tables(k, level, sd, args.bg_sd)
     os.makedirs(args.out_dir, exist_ok=True)
     files = fast5.list_files(args.fast5_dir)
     stems = {}
@@ -422,15 +679,27 @@ def main(argv=None):
         return outs[stem]
 
     reads = ((os.path.splitext(os.path.basename(p))[0], r.read_id, r.get_raw_data()) for p in files for r in fast5.iter_reads(p))
+    caller = None
+    if args.call is not None:
+        from .compare import read_paf
+        alt = read_alt_table(args.alt_table, k, args.mod_base) if args.alt_table else None
+        sites, paf = read_sites(args.call, alt is None), read_paf(args.paf)
+        Caller(args, model, (level, sd), sites, paf, alt, None).check_sites(refs)
+        calls = open(args.calls_out, "w")
+        caller = Caller(args, model, (level, sd), sites, paf, alt, calls)
     try:
         with Backend(args.device) as be:
             for stem in stems:
                 open_out(stem)   # a file per input file, also when none of its reads is written
-            st = run(args, be, reads, refs, names, bounds, model, sd_m, open_out)
+            st = run(args, be, reads, refs, names, bounds, model, sd_m, open_out, caller)
     finally:
-        for f in outs.values():
+        for f in list(outs.values()) + ([calls] if caller is not None else []):
             f.close()
     sys.stdout.write(summary(st))
+    if caller is not None:
+        if args.call_sites_out:
+            caller.write_sites(args.call_sites_out)
+        sys.stdout.write(caller.summary())
     sys.stdout.flush()
     return st
 
